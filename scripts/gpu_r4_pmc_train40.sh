@@ -3,7 +3,7 @@
 TAG=${1:-r4pmc}
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}; cd $REPO
 OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT
-CMD="python $REPO/bench.py --mode train --kind synth40 --mols 4096 --steps 6 --warmup 3 --no-cpu-baseline --no-graph --no-large-batches"
+CMD="python $REPO/bench.py --full --mode train --kind synth40 --mols 4096 --steps 6 --warmup 3 --no-cpu-baseline --no-graph --no-large-batches"
 cd /tmp && export TMPDIR=/tmp
 timeout 400 rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d $OUT/pmc_fetch -o p -- $CMD > $OUT/pmc_fetch.log 2>&1
 timeout 400 rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE -d $OUT/pmc_write -o p -- $CMD > $OUT/pmc_write.log 2>&1

@@ -8,7 +8,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}; cd $REPO
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 export PYTHONUNBUFFERED=1 HSA_ENABLE_IPC_MODE_LEGACY=0
 DMPNN_FORCE_COLLECTIVE=1 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 \
-  bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-large-batches > $OUT/bench_nccl_world1.json 2> $OUT/bench_nccl_world1.err
+  bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-large-batches > $OUT/bench_nccl_world1.json 2> $OUT/bench_nccl_world1.err
 echo "rc=$?" | tee $OUT/summary.txt
 python - <<PY | tee -a $OUT/summary.txt
 import json

@@ -4,7 +4,7 @@
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}; cd $REPO
 TAG=${1:-r06_wgradr}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 export PYTHONUNBUFFERED=1 TMPDIR=/tmp
-run() { python bench.py --steps 200 --warmup 20 --no-cpu-baseline $2 2>/dev/null | python -c "
+run() { python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline $2 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); oc = d.get('other_configs', {})
 print('$1', 'train', d.get('train_step', {}).get('ms_per_step'), 'model', d.get('model_step', {}).get('fused_ms_per_step'), {k: v.get('train_step_us') for k, v in oc.items() if 'train_step_us' in v})"; }

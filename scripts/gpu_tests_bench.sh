@@ -13,7 +13,7 @@ fi
 echo "pytest rc=$?" | tee $OUT/summary.txt
 grep -v "^  File\|^Extension modules" $OUT/pytest.log | tail -60 | cut -c1-300 | tee -a $OUT/summary.txt
 if [ -z "$NOBENCH" ]; then
-  timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/summary.txt
+  timeout 600 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/summary.txt
   python - <<PY | tee -a $OUT/summary.txt
 import json
 try:

@@ -6,8 +6,8 @@
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}; cd $REPO
 OUT=$REPO/gpurun_out/pmc_l2; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 400 rocprofv3 --kernel-trace --output-format csv --pmc TCP_TCC_READ_REQ_sum TCC_REQ_sum TCC_HIT_sum TCC_MISS_sum -d $OUT/a -o p -- python $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-graph --no-large-batches > $OUT/a.log 2>&1
-timeout 400 rocprofv3 --kernel-trace --output-format csv --pmc TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_LATENCY_sum TCP_PENDING_STALL_CYCLES_sum -d $OUT/b -o p -- python $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-graph --no-large-batches > $OUT/b.log 2>&1
+timeout 400 rocprofv3 --kernel-trace --output-format csv --pmc TCP_TCC_READ_REQ_sum TCC_REQ_sum TCC_HIT_sum TCC_MISS_sum -d $OUT/a -o p -- python $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-graph --no-large-batches > $OUT/a.log 2>&1
+timeout 400 rocprofv3 --kernel-trace --output-format csv --pmc TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_LATENCY_sum TCP_PENDING_STALL_CYCLES_sum -d $OUT/b -o p -- python $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-graph --no-large-batches > $OUT/b.log 2>&1
 python - <<'PY' | tee $OUT/summary.txt
 import csv, glob, collections, os
 out = os.environ.get("GRAFT_REPO_ROOT", os.getcwd()) + "/gpurun_out/pmc_l2"
