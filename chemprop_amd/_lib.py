@@ -131,6 +131,7 @@ class HeadArgs(C.Structure):
         ("bn_num_batches_tracked", C.c_void_p),
         ("n_classes", C.c_int32),
         ("evid_v_kl", C.c_float), ("evid_eps", C.c_float), ("quantile_alpha", C.c_float),
+        ("X_d", C.c_void_p), ("ld_xd", C.c_int64),
     ]
 
 

@@ -499,6 +499,7 @@ __global__ __launch_bounds__(1024) void k_out_all(OutAllArgs q) {
 constexpr int64_t kRowsMaxB = 1024;      // (4 molecules per thread of the column kernels)
 constexpr int64_t kFuseAggMols = 512;    // batches up to this size are aggregated inside k_agg_bn_fwd
 constexpr int kRowsMaxWidth = 320;       // WN <= 5 column tiles per wave
+constexpr int kRowsMaxK = 512;           // with molecule descriptors: the first layer's reduction width d_h + d_xd (k_head_rows<8, 1>)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 using mega16::h4;
 using mega16::h8;
@@ -524,7 +525,9 @@ __device__ __forceinline__ int col_ldi(gemm::rsrc_t r, bool ok, int64_t idx) {
 // One workgroup per 32 rows n (= one reduction chunk of `bwd`, two column tiles of `fwd`): row maxima by the waves (coalesced),
 // then every thread converts 8 consecutive k of a row (fwd) / 8 consecutive n of a column (bwd: lanes along k, coalesced) into one
 // 16-byte store each.  (split_weights_wave with tr = 1 reads a column per wave — 64 cache lines per load instruction: 20 us here.)
-struct HeadSplit { const float* W; int N, K; unsigned char* fwd; unsigned char* bwd; float* inv_scale; int ncf, ncb; };
+// With molecule descriptors W0 is [N, d_h + d_xd]: `fwd` covers every column, `bwd` only the first Kb = d_h (no gradient toward X_d);
+// the row scale s_n is the maximum over the whole row in both.
+struct HeadSplit { const float* W; int N, K; unsigned char* fwd; unsigned char* bwd; float* inv_scale; int ncf, ncb, Kb; };
 __device__ __forceinline__ void head_split_block(const HeadSplit& a, int blk) {
     __shared__ float sc[32];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;   // 1024 threads
@@ -535,7 +538,7 @@ __device__ __forceinline__ void head_split_block(const HeadSplit& a, int blk) {
         const int n = n0 + 2 * wave + rr;
         float mx = 0.f;
 #pragma unroll
-        for (int u = 0; u < kRowsMaxWidth / 64; ++u) {   // (buffer loads: out of range reads 0 — no branch, all in flight together)
+        for (int u = 0; u < kRowsMaxK / 64; ++u) {   // (buffer loads: out of range reads 0 — no branch, all in flight together)
             const int k = lane + 64 * u;
             mx = fmaxf(mx, fabsf(col_ldf(rW, n < a.N && k < a.K, (int64_t)n * a.K + k)));
         }
@@ -566,25 +569,42 @@ __device__ __forceinline__ void head_split_block(const HeadSplit& a, int blk) {
         const float x[8] = {v0.x * sn, v0.y * sn, v0.z * sn, v0.w * sn, v1.x * sn, v1.y * sn, v1.z * sn, v1.w * sn};
         put(a.fwd, n >> 4, a.ncf, k8 >> 2, k8 & 3, n & 15, x);
     }
-    const int Kp = (a.K + 15) & ~15;
+    const int Kp = (a.Kb + 15) & ~15;
     for (int it = tid; it < Kp * 4; it += 1024) {
         const int lg = it / Kp, k = it - lg * Kp;
         float x[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int n = n0 + 8 * lg + j;
-            x[j] = col_ldf(rW, n < a.N && k < a.K, (int64_t)n * a.K + k) * sc[8 * lg + j];
+            x[j] = col_ldf(rW, n < a.N && k < a.Kb, (int64_t)n * a.K + k) * sc[8 * lg + j];
         }
         put(a.bwd, k >> 4, a.ncb, blk, lg, k & 15, x);
     }
 }
 
+// The descriptor columns of the fingerprint Z [B, ldz] = cat(bn(H), X_d, zeros): columns [c0, c0 + w) of every row, X_d [B, nx]
+// (row stride ldx, any alignment) and zeros up to the padded width.  A workgroup takes `per` consecutive elements of the B x w block.
+struct XdFill { const float* X; int64_t ldx; float* Z; int64_t ldz; int64_t B; int c0, w, nx; int64_t per; };
+__device__ __forceinline__ void xd_fill_block(const XdFill& a, int blk) {
+    const int64_t e0 = (int64_t)blk * a.per, n = a.B * a.w;
+    const int64_t e1 = e0 + a.per < n ? e0 + a.per : n;
+    for (int64_t e = e0 + threadIdx.x; e < e1; e += blockDim.x) {
+        const int64_t r = e / a.w; const int c = (int)(e - r * a.w);
+        a.Z[r * a.ldz + a.c0 + c] = c < a.nx ? a.X[r * a.ldx + c] : 0.f;
+    }
+}
+// the chain form's copy (the four-launch form's rides in k_agg_bn_fwd)
+__global__ __launch_bounds__(1024) void k_xd_fill(XdFill a) { xd_fill_block(a, (int)blockIdx.x); }
+inline int xd_fill_blocks(const XdFill& a) { return (int)((a.B * a.w + a.per - 1) / a.per); }
+
 struct AggBnArgs {
     BnArgs b;                              // X = H [B, d] (written here), Y = Z (BN only)
     const float* Hv; int64_t ldhv; int64_t nV; const int* bounds; int agg_mode; float agg_norm;
     int use_done;                          // 1: bounds[2 B + 4 + m] != 0 — X already holds molecule m's aggregate (the forward tile kernel wrote it)
-    int n_col_blocks;                      // workgroups [0, n_col_blocks): columns; the others: the weight split (32 rows of W0 each)
+    int n_col_blocks;                      // workgroups [0, n_col_blocks): columns; then n_split_blocks: the weight split (32 rows of W0
+    int n_split_blocks;                    // each); the rest: the descriptor columns of Z (xd)
     HeadSplit split;
+    XdFill xd;
     long long* dbg;                        // optional cycle stamps: [0..5] column workgroup 1, [6..9] the first split workgroup
 };
 // Geometry of the two column kernels: a workgroup = QPW column QUADS (16-byte loads and stores: a quarter of the memory instructions
@@ -626,6 +646,10 @@ template <int QPW, int RR, bool BN>
 __global__ __launch_bounds__(1024) void k_agg_bn_fwd(AggBnArgs q) {
     constexpr int kQLanes = 1024 / QPW;
     if ((int)blockIdx.x >= q.n_col_blocks) {   // (uniform per workgroup)
+        if ((int)blockIdx.x >= q.n_col_blocks + q.n_split_blocks) {
+            xd_fill_block(q.xd, (int)blockIdx.x - q.n_col_blocks - q.n_split_blocks);
+            return;
+        }
         const bool st = q.dbg && (int)blockIdx.x == q.n_col_blocks && threadIdx.x == 0;
         if (st) q.dbg[6] = (long long)__builtin_readcyclecounter();
         head_split_block(q.split, (int)blockIdx.x - q.n_col_blocks);
@@ -892,10 +916,11 @@ struct RowsArgs {
     float* A1;                             // [B, N] the hidden layer's output tau(Z W0^T + b0): written by PH 1, read by PH 2
     float* preds;                          // [B, t]
     const float* T; const float* w; const float* tw; const unsigned char* lt; const unsigned char* gt; int kind;
-    float* gA1; float* gZ;                 // [B, N], [B, K]
+    float* gA1; float* gZ;                 // [B, N], [B, Kg]
     float* part; int part_stride;          // per row block: gW1 [t][N] | gb1 [t] | loss sum | number of finite targets
     int64_t B; int N, K, t, act; float slope;
     long long* dbg;                        // optional cycle stamps of workgroup (1, 1)
+    int Kg;                                // columns of dl/dZ formed: K, or d_h with molecule descriptors (Z's first d_h columns)
 };
 // The predictor + criterion + their backward as TWO launches over (row block of 16 molecules) x (slice of 64 columns):
 //   PH 1  A1[:, slice] = tau(Z W0^T + b0)                                                          160 workgroups at 512 x 300
@@ -1043,7 +1068,7 @@ __global__ __launch_bounds__(256) void k_head_rows(RowsArgs a) {
         float b1v[kOutMaxTasks];
 #pragma unroll
         for (int j = 0; j < kOutMaxTasks; ++j) b1v[j] = ldf(buf(a.b1, t * 4), j < t, j);
-        request(a.W0b, a.K);
+        request(a.W0b, a.Kg);
         __builtin_amdgcn_sched_barrier(0);   // (requests above, consumers below)
         stamp();  // 1 requests out
 #pragma unroll
@@ -1163,7 +1188,7 @@ __global__ __launch_bounds__(256) void k_head_rows(RowsArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int i = 4 * lg + r;
-            if (col < a.K && i < nrows) a.gZ[(row0 + i) * a.K + col] = acc[r] * inv_s[i];
+            if (col < a.Kg && i < nrows) a.gZ[(row0 + i) * a.Kg + col] = acc[r] * inv_s[i];
         }
         stamp();  // 6 end
     }
@@ -1195,6 +1220,8 @@ __global__ void k_head_act_bwd(float* __restrict__ g, int64_t ldg, const float* 
 
 struct HeadLayout {
     size_t bounds, Hm, Z, mean, invstd, act[DMPNN_MAX_FFN_LAYERS], gP, gA, gB, Wt, wgrad, gHm, total;
+    size_t Zx;                             // with molecule descriptors: the fingerprint cat(bn(H), X_d) [B, Kp] (zero-padded to Kp)
+    int64_t Kp;
     size_t wgrad_bytes;
     int64_t maxd;
     // the four-launch form (rows_shape): the hidden layer's split weight in both orientations, their row scales, the row kernel's partials
@@ -1202,9 +1229,10 @@ struct HeadLayout {
     int part_stride, n_part;
 };
 // the shapes the four-launch form takes (training or not is the caller's business): one hidden layer, a handful of outputs
+// (with molecule descriptors the first layer's reduction may be up to kRowsMaxK wide: d_h + d_xd; its data gradient stays d_h wide)
 bool rows_shape(const dmpnn_head_args& h) {
     return h.n_layers == 2 && h.dims[2] <= kOutMaxTasks && h.dims[2] >= 1 && h.loss <= DMPNN_LOSS_BCE && h.n_mols <= kRowsMaxB &&
-           h.dims[0] <= kRowsMaxWidth && h.dims[1] <= kRowsMaxWidth && h.dims[0] % 4 == 0;
+           h.dims[0] <= (h.X_d ? kRowsMaxK : kRowsMaxWidth) && h.d_h <= kRowsMaxWidth && h.dims[1] <= kRowsMaxWidth && h.dims[0] % 4 == 0;
 }
 HeadLayout head_layout(const dmpnn_head_args& h) {
     HeadLayout L;
@@ -1216,7 +1244,9 @@ HeadLayout head_layout(const dmpnn_head_args& h) {
     L.Z = o; o += al256(h.bn_weight ? (size_t)B * d * 4 : 0);
     L.mean = o; o += al256((size_t)d * 4);
     L.invstd = o; o += al256((size_t)d * 4);
-    int64_t maxd = d;
+    L.Kp = h.X_d ? (h.dims[0] + 3) & ~int64_t(3) : d;
+    L.Zx = o; o += al256(h.X_d ? (size_t)B * L.Kp * 4 : 0);
+    int64_t maxd = h.X_d && L.Kp > d ? L.Kp : d;   // (the chain's scratch for layer 0: its data gradient [B, Kp], its unwanted weight gradient)
     for (int l = 0; l < h.n_layers; ++l) {
         if (h.dims[l + 1] > maxd) maxd = h.dims[l + 1];
         L.act[l] = o;
@@ -1242,7 +1272,7 @@ HeadLayout head_layout(const dmpnn_head_args& h) {
     if (h.n_layers == 2 && rows_shape(h)) {
         const int64_t N = h.dims[1], K = h.dims[0], t = h.dims[2];
         L.W0f = o; o += al256((size_t)((N + 15) / 16) * ((K + 31) / 32) * 2048);
-        L.W0b = o; o += al256((size_t)((K + 15) / 16) * ((N + 31) / 32) * 2048);
+        L.W0b = o; o += al256((size_t)((d + 15) / 16) * ((N + 31) / 32) * 2048);   // (the backward orientation: the first d_h columns)
         L.isf = o; o += al256((size_t)N * 4);
         L.isb = o; o += al256((size_t)K * 4);
         L.n_part = (int)((B + 15) / 16);
@@ -1314,7 +1344,11 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     const int64_t B = h.n_mols, d = h.d_h, nV = h.n_atoms;
     const int Ln = h.n_layers;
     DMPNN_CHECK_ARG(B >= 0 && nV >= 0 && d > 0 && ldhv >= d, "head: bad sizes");
-    DMPNN_CHECK_ARG(Ln >= 1 && Ln <= DMPNN_MAX_FFN_LAYERS && h.dims[0] == d, "head: 1..%d predictor layers, dims[0] == d_h", DMPNN_MAX_FFN_LAYERS);
+    DMPNN_CHECK_ARG(Ln >= 1 && Ln <= DMPNN_MAX_FFN_LAYERS, "head: 1..%d predictor layers", DMPNN_MAX_FFN_LAYERS);
+    // molecule descriptors: the predictor's input is cat(bn(agg(H_v)), X_d), dims[0] = d_h + d_xd
+    const bool xd = h.X_d != nullptr;
+    DMPNN_CHECK_ARG(xd ? h.dims[0] > d : h.dims[0] == d, xd ? "head: with X_d, dims[0] = d_h + d_xd > d_h" : "head: dims[0] == d_h without X_d");
+    DMPNN_CHECK_ARG(!xd || h.ld_xd >= h.dims[0] - d, "head: ld_xd (%lld) < d_xd (%lld)", (long long)h.ld_xd, (long long)(h.dims[0] - d));
     for (int l = 0; l < Ln; ++l) DMPNN_CHECK_ARG(h.W[l] && h.dims[l + 1] > 0, "head: layer %d has no weight / width", l);
     DMPNN_CHECK_ARG(h.act >= DMPNN_ACT_NONE && h.act <= DMPNN_ACT_ELU && h.act != DMPNN_ACT_PRELU, "head: activation %d is not built in", h.act);
     DMPNN_CHECK_ARG(h.loss >= DMPNN_LOSS_MSE && h.loss <= DMPNN_LOSS_QUANTILE, "head: unknown criterion %d", h.loss);
@@ -1338,7 +1372,15 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     DMPNN_CHECK_ARG(aligned16(h.ws), "head: workspace must be 16-byte aligned");
     if (B == 0) return DMPNN_OK;
     unsigned char* ws = static_cast<unsigned char*>(h.ws);
-    float* Hm = reinterpret_cast<float*>(ws + L.Hm);
+    // H = agg(H_v) [B, ldH] and bn(H) [B, ldY]; with descriptors bn(H) — or H itself without batch norm — is written straight into the
+    // first d_h columns of the fingerprint Zx [B, Kp], whose other columns are X_d and zeros (XdFill)
+    float* Zx = xd ? reinterpret_cast<float*>(ws + L.Zx) : nullptr;
+    const int64_t Kp = L.Kp;
+    float* Hm = (xd && !h.bn_weight) ? Zx : reinterpret_cast<float*>(ws + L.Hm);
+    const int64_t ldH = (xd && !h.bn_weight) ? Kp : d;
+    float* Ybn = xd ? Zx : reinterpret_cast<float*>(ws + L.Z);
+    const int64_t ldY = xd ? Kp : d;
+    XdFill xf{h.X_d, h.ld_xd, Zx, Kp, B, (int)d, (int)(Kp - d), (int)(h.dims[0] - d), 4096};
     const int t_out = (int)h.dims[Ln];                                  // width of the output layer
     const int nc = h.loss == DMPNN_LOSS_CE ? h.n_classes : ((h.loss == DMPNN_LOSS_MVE || h.loss == DMPNN_LOSS_QUANTILE) ? 2 : (h.loss == DMPNN_LOSS_EVIDENTIAL ? 4 : 1));   // outputs per task
     const int t = t_out / nc;                                           // tasks (= columns of `targets`)
@@ -1358,6 +1400,7 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     // (DMPNN_HEAD=rows: tests — a training call that does NOT take the four-launch form is an error instead of a silent chain)
     DMPNN_CHECK_ARG(!(head_env && !strcmp(head_env, "rows")) || rows || !want_grad, "head: DMPNN_HEAD=rows, but this shape takes the chain");
     const float* Z = Hm;
+    int64_t ldz = ldH;
     float* mean = reinterpret_cast<float*>(ws + L.mean);
     float* invstd = reinterpret_cast<float*>(ws + L.invstd);
     SplitW W0f{ws + L.W0f, reinterpret_cast<float*>(ws + L.isf), (int)((h.dims[0] + 31) / 32)};
@@ -1365,7 +1408,7 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     if (cols_fused) {
         AggBnArgs q;
         memset(&q, 0, sizeof(q));
-        q.b = BnArgs{Hm, d, reinterpret_cast<float*>(ws + L.Z), d, h.bn_weight, h.bn_bias, h.bn_running_mean, h.bn_running_var, mean, invstd,
+        q.b = BnArgs{Hm, ldH, Ybn, ldY, h.bn_weight, h.bn_bias, h.bn_running_mean, h.bn_running_var, mean, invstd,
                      B, (int)d, h.bn_eps, h.bn_momentum, h.bn_training, h.bn_num_batches_tracked};
         // the aggregation inside this launch up to 512 molecules (one launch less: 159 against 166 us per step at 64 molecules, 221
         // against 220 at 512 — the column workgroups pull H_v at ~55 GB/s each, 5.5 MB over 38 of them); beyond that
@@ -1373,7 +1416,7 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
         const char* agg_env = getenv("DMPNN_HEAD_AGG");
         const bool fuse_agg = agg_rode || (agg_env ? !strcmp(agg_env, "fused") : B <= kFuseAggMols);   // (rode: only what the tile kernel left is summed here)
         q.use_done = agg_rode ? 1 : 0;
-        if (!fuse_agg) DMPNN_TRY(dmpnn_molagg_fwd(Hv, ldhv, nV, d, B, ws + L.bounds, h.agg_mode, h.agg_norm, Hm, d, stream));
+        if (!fuse_agg) DMPNN_TRY(dmpnn_molagg_fwd(Hv, ldhv, nV, d, B, ws + L.bounds, h.agg_mode, h.agg_norm, Hm, ldH, stream));
         q.Hv = fuse_agg ? Hv : nullptr; q.ldhv = ldhv; q.nV = nV; q.bounds = reinterpret_cast<const int*>(ws + L.bounds); q.agg_mode = h.agg_mode; q.agg_norm = h.agg_norm;
         const int qpw = col_quads(B);
         q.n_col_blocks = (int)((d + 4 * qpw - 1) / (4 * qpw));
@@ -1381,57 +1424,64 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
         int split_blocks = 0;
         if (rows) {
             const int N = (int)h.dims[1], K = (int)h.dims[0];
-            q.split = HeadSplit{h.W[0], N, K, ws + L.W0f, ws + L.W0b, reinterpret_cast<float*>(ws + L.isf), W0f.nc, W0b.nc};
+            q.split = HeadSplit{h.W[0], N, K, ws + L.W0f, ws + L.W0b, reinterpret_cast<float*>(ws + L.isf), W0f.nc, W0b.nc, (int)d};
             split_blocks = W0b.nc;
         }
-        const dim3 grid((unsigned)(q.n_col_blocks + split_blocks));
+        q.n_split_blocks = split_blocks;
+        const int xd_blocks = xd ? xd_fill_blocks(xf) : 0;   // (the descriptor columns of Zx: the launch's last workgroups)
+        q.xd = xf;
+        const dim3 grid((unsigned)(q.n_col_blocks + split_blocks + xd_blocks));
         const bool bn = h.bn_weight != nullptr;
-        if (fuse_agg || bn || split_blocks) DMPNN_COL_LAUNCH(k_agg_bn_fwd, qpw, B, bn, grid, s, q);
+        if (fuse_agg || bn || split_blocks || xd_blocks) DMPNN_COL_LAUNCH(k_agg_bn_fwd, qpw, B, bn, grid, s, q);
         DMPNN_CHECK_LAUNCH("k_agg_bn_fwd");
-        if (bn) Z = reinterpret_cast<float*>(ws + L.Z);
-    } else
-        DMPNN_TRY(dmpnn_molagg_fwd(Hv, ldhv, nV, d, B, ws + L.bounds, h.agg_mode, h.agg_norm, Hm, d, stream));
+        if (bn) { Z = Ybn; ldz = ldY; }
+    } else {
+        DMPNN_TRY(dmpnn_molagg_fwd(Hv, ldhv, nV, d, B, ws + L.bounds, h.agg_mode, h.agg_norm, Hm, ldH, stream));
+        if (xd) {
+            hipLaunchKernelGGL(k_xd_fill, dim3((unsigned)xd_fill_blocks(xf)), dim3(1024), 0, s, xf);
+            DMPNN_CHECK_LAUNCH("k_xd_fill");
+        }
+    }
     if (h.bn_weight && !cols_fused) {
-        BnArgs b{Hm, d, reinterpret_cast<float*>(ws + L.Z), d, h.bn_weight, h.bn_bias, h.bn_running_mean, h.bn_running_var, mean, invstd,
+        BnArgs b{Hm, ldH, Ybn, ldY, h.bn_weight, h.bn_bias, h.bn_running_mean, h.bn_running_var, mean, invstd,
                  B, (int)d, h.bn_eps, h.bn_momentum, h.bn_training, h.bn_num_batches_tracked};
         if (B <= kBnRegRows * kBnLanes) hipLaunchKernelGGL(k_bn_fwd<true>, dim3((unsigned)((d + kBnCols - 1) / kBnCols)), dim3(1024), 0, s, b);
         else hipLaunchKernelGGL(k_bn_fwd<false>, dim3((unsigned)((d + kBnCols - 1) / kBnCols)), dim3(1024), 0, s, b);
         DMPNN_CHECK_LAUNCH("k_bn_fwd");
-        Z = reinterpret_cast<float*>(ws + L.Z);
+        Z = Ybn; ldz = ldY;
     }
     if (rows) {
         const int N = (int)h.dims[1], K = (int)h.dims[0];
         float* gA1 = reinterpret_cast<float*>(ws + L.gA);
         float* gZr = reinterpret_cast<float*>(ws + L.gB);
-        RowsArgs r{Z, d, W0f, W0b, h.b[0], h.W[1], h.b[1], reinterpret_cast<float*>(ws + L.act[0]), h.preds, h.targets, h.weights, h.task_weights,
+        const int Kg = (int)d;   // dl/dZ: the first d_h columns (= K without descriptors)
+        RowsArgs r{Z, ldz, W0f, W0b, h.b[0], h.W[1], h.b[1], reinterpret_cast<float*>(ws + L.act[0]), h.preds, h.targets, h.weights, h.task_weights,
                    h.lt_mask, h.gt_mask, h.loss, gA1, gZr, reinterpret_cast<float*>(ws + L.part), L.part_stride, B, N, K, t, h.act, h.act_slope,
-                   g_debug_stamps ? g_debug_stamps + 64 : nullptr};
-        const int widest = N > K ? N : K;
+                   g_debug_stamps ? g_debug_stamps + 64 : nullptr, Kg};
+        // PH 1 reduces over K, PH 2 holds rows of N and forms Kg columns; without descriptors K == Kg and both take the wider of N, K
+        const int widest = N > Kg ? N : Kg, w1 = xd ? K : (N > K ? N : K);
         const dim3 g1((unsigned)L.n_part, (unsigned)((N + 63) / 64)), g2((unsigned)L.n_part, (unsigned)((widest + 63) / 64));
-        if (widest <= 128) {
-            hipLaunchKernelGGL((k_head_rows<2, 1>), g1, dim3(256), 0, s, r);
-            if (r.dbg) r.dbg += 8;
-            hipLaunchKernelGGL((k_head_rows<2, 2>), g2, dim3(256), 0, s, r);
-        } else {
-            hipLaunchKernelGGL((k_head_rows<5, 1>), g1, dim3(256), 0, s, r);
-            if (r.dbg) r.dbg += 8;
-            hipLaunchKernelGGL((k_head_rows<5, 2>), g2, dim3(256), 0, s, r);
-        }
+        if (w1 <= 128) hipLaunchKernelGGL((k_head_rows<2, 1>), g1, dim3(256), 0, s, r);
+        else if (w1 <= kRowsMaxWidth) hipLaunchKernelGGL((k_head_rows<5, 1>), g1, dim3(256), 0, s, r);
+        else hipLaunchKernelGGL((k_head_rows<8, 1>), g1, dim3(256), 0, s, r);
+        if (r.dbg) r.dbg += 8;
+        if (widest <= 128) hipLaunchKernelGGL((k_head_rows<2, 2>), g2, dim3(256), 0, s, r);
+        else hipLaunchKernelGGL((k_head_rows<5, 2>), g2, dim3(256), 0, s, r);
         DMPNN_CHECK_LAUNCH("k_head_rows");
         if (h.gW[0] || h.gb[0]) {   // the hidden layer's weight gradient: in the block's backward launches, or its own product
             if (defer && h.gW[0] && N % 2 == 0 && K % 2 == 0) {
-                *defer = ExtraWgrad{gA1, N, Z, K, B, N, K, h.b[0] ? 1 : 0, h.gW[0], K, h.b[0] ? h.gb[0] : nullptr, reinterpret_cast<float*>(ws + L.wgrad)};
+                *defer = ExtraWgrad{gA1, N, Z, ldz, B, N, K, h.b[0] ? 1 : 0, h.gW[0], K, h.b[0] ? h.gb[0] : nullptr, reinterpret_cast<float*>(ws + L.wgrad)};
             } else {
                 dmpnn_gemm_args g;
                 memset(&g, 0, sizeof(g));
-                g.M = B; g.N = N; g.K1 = K; g.A1 = Z; g.lda1 = K;
+                g.M = B; g.N = N; g.K1 = K; g.A1 = Z; g.lda1 = ldz;
                 float* gw = h.gW[0] ? h.gW[0] : reinterpret_cast<float*>(ws + L.Wt);
                 DMPNN_TRY(dmpnn_linear_wgrad(&g, gA1, N, gw, K, h.b[0] ? h.gb[0] : nullptr, ws + L.wgrad, L.wgrad_bytes, stream));
             }
         }
         BnAggBwdArgs q;
         memset(&q, 0, sizeof(q));
-        q.b = BnBwdArgs{gZr, d, Hm, d, nullptr, d, h.bn_weight, mean, invstd, h.bn_running_mean, h.bn_running_var, h.g_bn_weight, h.g_bn_bias,
+        q.b = BnBwdArgs{gZr, Kg, Hm, ldH, nullptr, d, h.bn_weight, mean, invstd, h.bn_running_mean, h.bn_running_var, h.g_bn_weight, h.g_bn_bias,
                         B, (int)d, h.bn_eps, h.bn_training};
         q.gHv = h.gHv; q.ldg = h.ldg; q.bounds = reinterpret_cast<const int*>(ws + L.bounds); q.nV = nV; q.agg_mode = h.agg_mode; q.agg_norm = h.agg_norm;
         q.part = reinterpret_cast<const float*>(ws + L.part); q.n_part = L.n_part; q.part_stride = L.part_stride; q.tN = t * N; q.t = t;
@@ -1440,13 +1490,15 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
         return launch_bn_agg_bwd(q, h.bn_weight != nullptr, s);
     }
     const float* A[DMPNN_MAX_FFN_LAYERS + 1];
+    int64_t ldA[DMPNN_MAX_FFN_LAYERS + 1];   // row strides of the layers' inputs: the fingerprint's, then the widths
     A[0] = Z;
+    for (int l = 0; l <= Ln; ++l) ldA[l] = l == 0 ? ldz : h.dims[l];
     const bool small_out = h.dims[Ln] <= kOutMaxTasks && Ln >= 1;   // the output layer as dot products (k_out_fwd / k_out_bwd)
     // training on a short batch: the criterion and the output layer's backward are ONE launch further down (k_out_all)
     const bool out_all = small_out && want_grad && h.targets && B <= kOutAllMaxRows && nc == 1;
     for (int l = 0; l < Ln; ++l) {
         if (small_out && l == Ln - 1) {
-            OutFwdArgs q{A[l], h.dims[l], h.W[l], h.b[l], h.preds, B, (int)h.dims[l], (int)h.dims[Ln]};
+            OutFwdArgs q{A[l], ldA[l], h.W[l], h.b[l], h.preds, B, (int)h.dims[l], (int)h.dims[Ln]};
             hipLaunchKernelGGL(k_out_fwd, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, q);
             DMPNN_CHECK_LAUNCH("k_out_fwd");
             A[l + 1] = h.preds;
@@ -1455,7 +1507,7 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
         dmpnn_gemm_args g;
         memset(&g, 0, sizeof(g));
         g.M = B; g.N = h.dims[l + 1]; g.K1 = h.dims[l];
-        g.A1 = A[l]; g.lda1 = h.dims[l];
+        g.A1 = A[l]; g.lda1 = ldA[l];
         g.W = h.W[l]; g.ldw = h.dims[l]; g.bias = h.b[l];
         float* out = l + 1 < Ln ? reinterpret_cast<float*>(ws + L.act[l]) : h.preds;
         g.C = out; g.ldc = h.dims[l + 1];
@@ -1479,47 +1531,51 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     float* bufs[2] = {reinterpret_cast<float*>(ws + L.gA), reinterpret_cast<float*>(ws + L.gB)};
     float* Wt = reinterpret_cast<float*>(ws + L.Wt);
     const float* g_cur = gP;   // gradient w.r.t. the pre-activation of layer l's output
+    int64_t ld_cur = t_out;    // (its row stride)
     int pp = 0;
     for (int l = Ln - 1; l >= 0; --l) {
         const int64_t N = h.dims[l + 1], K = h.dims[l];
+        // the data gradient of layer 0 is wanted for the block's d_h columns only (none flows to the descriptors)
+        const int64_t Kout = l == 0 ? d : K;
         if (small_out && l == Ln - 1) {
             float* out = bufs[pp]; pp ^= 1;
-            // (l == 0: no activation in front of the only layer — the derivative factor is 1)
-            OutBwdArgs q{g_cur, A[l], K, h.W[l], out, K, h.gW[l], h.b[l] ? h.gb[l] : nullptr, B, (int)K, (int)N, l > 0 ? h.act : DMPNN_ACT_NONE, h.act_slope};
+            // (l == 0: no activation in front of the only layer — the derivative factor is 1; every column's gradient is formed, in rows of
+            //  ldA[0] — Kp with descriptors, 16-byte rows for the column kernels)
+            OutBwdArgs q{g_cur, A[l], ldA[l], h.W[l], out, ldA[l], h.gW[l], h.b[l] ? h.gb[l] : nullptr, B, (int)K, (int)N, l > 0 ? h.act : DMPNN_ACT_NONE, h.act_slope};
             if (out_all) {
                 DMPNN_CHECK_ARG(h.loss_out != nullptr, "head: targets without loss_out");
                 OutAllArgs qa{q, LossArgs{h.preds, t, h.targets, t, h.weights, h.task_weights, h.lt_mask, h.gt_mask, nullptr, t, h.loss_out, B, t, h.loss, 1, 0.f, 0.f, 0.f}};
                 qa.o.gP = nullptr;
                 hipLaunchKernelGGL(k_out_all, dim3((unsigned)((K + kBnCols - 1) / kBnCols)), dim3(1024), 0, s, qa);
                 DMPNN_CHECK_LAUNCH("k_out_all");
-                g_cur = out;
+                g_cur = out; ld_cur = ldA[l];
                 continue;
             }
             hipLaunchKernelGGL(k_out_bwd, dim3((unsigned)((K + kBnCols - 1) / kBnCols)), dim3(1024), 0, s, q);
             DMPNN_CHECK_LAUNCH("k_out_bwd");
-            g_cur = out;
+            g_cur = out; ld_cur = ldA[l];
             continue;
         }
         if (h.gW[l] || h.gb[l]) {
             dmpnn_gemm_args g;
             memset(&g, 0, sizeof(g));
-            g.M = B; g.N = N; g.K1 = K; g.A1 = A[l]; g.lda1 = K;
+            g.M = B; g.N = N; g.K1 = K; g.A1 = A[l]; g.lda1 = ldA[l];
             float* gw = h.gW[l] ? h.gW[l] : Wt;  // (the product writes both; an unwanted one lands in scratch)
             if (defer && l == 0 && h.gW[l] && N % 2 == 0 && K % 2 == 0) {
-                *defer = ExtraWgrad{g_cur, N, A[l], K, B, (int)N, (int)K, h.b[l] ? 1 : 0, h.gW[l], K, h.b[l] ? h.gb[l] : nullptr,
+                *defer = ExtraWgrad{g_cur, N, A[l], ldA[l], B, (int)N, (int)K, h.b[l] ? 1 : 0, h.gW[l], K, h.b[l] ? h.gb[l] : nullptr,
                                     reinterpret_cast<float*>(ws + L.wgrad)};
             } else {
                 DMPNN_TRY(dmpnn_linear_wgrad(&g, g_cur, N, gw, K, h.b[l] ? h.gb[l] : nullptr, ws + L.wgrad, L.wgrad_bytes, stream));
             }
         }
-        // data gradient: gA[l] = g . W_l   (the contraction kernel on W_l^T)
-        hipLaunchKernelGGL(k_head_transpose, dim3((unsigned)((K + 31) / 32), (unsigned)((N + 31) / 32)), dim3(32, 8), 0, s, h.W[l], K, Wt, N, (int)N, (int)K);
+        // data gradient: gA[l] = g . W_l   (the contraction kernel on W_l^T; layer 0 with descriptors: its first d_h columns)
+        hipLaunchKernelGGL(k_head_transpose, dim3((unsigned)((Kout + 31) / 32), (unsigned)((N + 31) / 32)), dim3(32, 8), 0, s, h.W[l], K, Wt, N, (int)N, (int)Kout);
         DMPNN_CHECK_LAUNCH("k_head_transpose");
         dmpnn_gemm_args g;
         memset(&g, 0, sizeof(g));
-        g.M = B; g.N = K; g.K1 = N; g.A1 = g_cur; g.lda1 = N; g.W = Wt; g.ldw = N;
+        g.M = B; g.N = Kout; g.K1 = N; g.A1 = g_cur; g.lda1 = ld_cur; g.W = Wt; g.ldw = N;
         float* out = bufs[pp]; pp ^= 1;
-        g.C = out; g.ldc = K; g.act = DMPNN_ACT_NONE;
+        g.C = out; g.ldc = Kout; g.act = DMPNN_ACT_NONE;
         DMPNN_TRY(dmpnn_linear_fwd(&g, stream));
         if (l > 0 && h.act != DMPNN_ACT_NONE) {
             const int64_t n = B * K;
@@ -1527,30 +1583,31 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
             hipLaunchKernelGGL(k_head_act_bwd, dim3((unsigned)blocks), dim3(256), 0, s, out, K, A[l], K, B, (int)K, h.act, h.act_slope);
             DMPNN_CHECK_LAUNCH("k_head_act_bwd");
         }
-        g_cur = out;
+        g_cur = out; ld_cur = Kout;
     }
-    const float* gZ = g_cur;   // [B, d]: gradient w.r.t. the fingerprint
+    const float* gZ = g_cur;   // [B, d] (row stride ldgz): gradient w.r.t. the fingerprint's first d_h columns
+    int64_t ldgz = ld_cur;
     float* gHm = reinterpret_cast<float*>(ws + L.gHm);
     if (cols_fused) {   // batch norm backward + the broadcast to the atoms' rows: one column kernel
         BnAggBwdArgs q;
         memset(&q, 0, sizeof(q));
-        q.b = BnBwdArgs{gZ, d, Hm, d, nullptr, d, h.bn_weight, mean, invstd, h.bn_running_mean, h.bn_running_var, h.g_bn_weight, h.g_bn_bias,
+        q.b = BnBwdArgs{gZ, ldgz, Hm, ldH, nullptr, d, h.bn_weight, mean, invstd, h.bn_running_mean, h.bn_running_var, h.g_bn_weight, h.g_bn_bias,
                         B, (int)d, h.bn_eps, h.bn_training};
         q.gHv = h.gHv; q.ldg = h.ldg; q.bounds = reinterpret_cast<const int*>(ws + L.bounds); q.nV = nV; q.agg_mode = h.agg_mode; q.agg_norm = h.agg_norm;
         return launch_bn_agg_bwd(q, h.bn_weight != nullptr, s);
     }
     if (h.bn_weight) {
-        BnBwdArgs b{gZ, d, Hm, d, gHm, d, h.bn_weight, mean, invstd, h.bn_running_mean, h.bn_running_var, h.g_bn_weight, h.g_bn_bias,
+        BnBwdArgs b{gZ, ldgz, Hm, ldH, gHm, d, h.bn_weight, mean, invstd, h.bn_running_mean, h.bn_running_var, h.g_bn_weight, h.g_bn_bias,
                     B, (int)d, h.bn_eps, h.bn_training};
         if (B <= kBnRegRows * kBnLanes) hipLaunchKernelGGL(k_bn_bwd<true>, dim3((unsigned)((d + kBnCols - 1) / kBnCols)), dim3(1024), 0, s, b);
         else hipLaunchKernelGGL(k_bn_bwd<false>, dim3((unsigned)((d + kBnCols - 1) / kBnCols)), dim3(1024), 0, s, b);
         DMPNN_CHECK_LAUNCH("k_bn_bwd");
-        gZ = gHm;
+        gZ = gHm; ldgz = d;
     }
     // (Running the hidden layers' weight-gradient products and the molecule bounds on a second stream of the library's own was
     //  built and measured: each fork / join pair costs ~6 us of cross-queue synchronisation on this runtime — the step got 12 us
     //  SLOWER, profiles/r03_side_stream_ab.txt.  One stream.)
-    return dmpnn_molagg_bwd(gZ, d, h.batch, nV, d, B, ws + L.bounds, h.agg_mode, h.agg_norm, h.gHv, h.ldg, stream);
+    return dmpnn_molagg_bwd(gZ, ldgz, h.batch, nV, d, B, ws + L.bounds, h.agg_mode, h.agg_norm, h.gHv, h.ldg, stream);
 }
 }  // namespace
 
@@ -1597,7 +1654,9 @@ int dmpnn_train_step(const dmpnn_step_args* a, void* stream) {
             const dmpnn_head_args& h = a->head;
             const char* he = getenv("DMPNN_HEAD");
             const char* ae = getenv("DMPNN_HEAD_AGG");
+            // (with descriptors and no batch norm the aggregate is written into the fingerprint's rows, not into H: no ride there)
             if (bounds_done && h.ws && h.n_mols > 0 && h.n_mols <= kRowsMaxB && h.d_h % 4 == 0 && h.d_h == f.d_h && !f.W_d && !(he && !strcmp(he, "chain")) &&
+                (!h.X_d || h.bn_weight) &&
                 !(ae && strcmp(ae, "tile"))) {
                 const HeadLayout HL = head_layout(h);
                 unsigned char* hws = static_cast<unsigned char*>(h.ws);

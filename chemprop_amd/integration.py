@@ -279,7 +279,8 @@ def hip_mpnn_class():
       scheduler, counts ``trainer.global_step`` through ``LightningOptimizer.step`` (what ``ModelCheckpoint`` keys on,
       ``cli/train.py:1912-1919``), saves ``optimizer.state_dict()`` (``torch.optim.Adam``'s format) in its checkpoints.
     * ``training_step``: where :class:`chemprop_amd.model.FusedTrainer` applies (a bond block with a built-in activation, sum / mean /
-      norm aggregation, batch norm, regression MLP, MSE / MAE, no ``V_d`` / ``X_d``) the whole step — K0, forward, head, backward,
+      norm aggregation, batch norm, regression MLP, MSE / MAE, no ``V_d``; molecule descriptors ``X_d`` through the model's
+      ``X_d_transform``) the whole step — K0, forward, head, backward,
       clip, Adam — is enqueued by that one call with this step's learning rate and ``Trainer(gradient_clip_val)``
       (``cli/train.py:1937``); the hooks Lightning runs afterwards inside ``optimizer.step(closure)`` — ``backward``,
       ``configure_gradient_clipping``, the optimizer's own update — find the work done and return.  Everything else is the MODULE
@@ -393,13 +394,13 @@ def hip_mpnn_class():
             # the last; the block's backward kernels OVERWRITE their gradient views once per exchange (GradSync._written), so the
             # exchange — which re-arms the views — must run on the stepping micro-batch only (backward() below)
             self.__dict__["_hip_accumulating"] = accumulate > 1 and _should_accumulate(tr, batch_idx, accumulate)
-            if fused is not None and V_d is None and X_d is None and self.training and accumulate == 1:
+            if fused is not None and V_d is None and self.training and accumulate == 1:
                 try:
                     clip = (getattr(tr, "gradient_clip_val", None), _clip_algorithm(getattr(tr, "gradient_clip_algorithm", None)))
                     g = opt.param_groups[0]
                     fl = st["opt"]
                     fl.betas, fl.eps, fl.weight_decay = (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"]), float(g["weight_decay"])
-                    out = fused.step(bmg, targets, weights, lt_mask, gt_mask, lr=float(g["lr"]), clip=clip)
+                    out = fused.step(bmg, targets, weights, lt_mask, gt_mask, lr=float(g["lr"]), clip=clip, X_d=X_d)   # (X_d_transform inside)
                     loss = out[0]
                     self.__dict__["_hip_applied"] = True
                     st["route"] = "fused:" + str(fused.last_route)
@@ -408,14 +409,15 @@ def hip_mpnn_class():
             if loss is None:
                 # the module path: a loss with a graph; Lightning's closure runs backward() (below), the clip, HipAdam.step()
                 st["sync"].wait()
-                if X_d is None and self.training:
+                if self.training:
                     # everything behind the block as ONE autograd node on the head kernels where they implement this model
-                    # (chemprop_amd.model.head_loss: aggregation, batch norm, predictor, criterion + their backward in one call)
+                    # (chemprop_amd.model.head_loss: aggregation, batch norm, descriptors, predictor, criterion + their backward in one call)
                     from .model import criterion_kind, head_loss
 
                     bounded = criterion_kind(self.criterion)[1]
                     loss = head_loss(self, self.message_passing(bmg, V_d), bmg.batch, len(bmg), targets, weights,
-                                     lt_mask if bounded else None, gt_mask if bounded else None)
+                                     lt_mask if bounded else None, gt_mask if bounded else None,
+                                     X_d=None if X_d is None else self.X_d_transform(X_d))
                 if loss is None:
                     loss = Ref.training_step(self, batch, batch_idx)   # the reference's own arithmetic AND its own train_loss log
                     logged = True

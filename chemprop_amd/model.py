@@ -284,16 +284,22 @@ class BinaryClassificationFFN(RegressionFFN):
 
 class MPNN(nn.Module):
     """``chemprop.models.MPNN`` (``models/model.py:60-146``) without Lightning: the four sub-modules under the reference's
-    names and ``fingerprint`` / ``forward``; ``loss(batch)`` is the arithmetic of ``training_step`` (``model.py:148-161``)."""
+    names and ``fingerprint`` / ``forward``; ``loss(batch)`` is the arithmetic of ``training_step`` (``model.py:148-161``).
 
-    def __init__(self, message_passing: nn.Module, agg: nn.Module, predictor: nn.Module, batch_norm: bool = False):
+    Molecule descriptors ``X_d`` (``--molecule-featurizers`` / ``--descriptors-path``) are concatenated behind the batch norm,
+    through ``X_d_transform`` (the reference's ``ScaleTransform`` or ``nn.Identity``): the predictor's ``input_dim`` is then
+    ``message_passing.output_dim + d_xd``."""
+
+    def __init__(self, message_passing: nn.Module, agg: nn.Module, predictor: nn.Module, batch_norm: bool = False,
+                 X_d_transform: Optional[nn.Module] = None):
         super().__init__()
-        if message_passing.output_dim != predictor.input_dim:
-            raise ValueError(f"message passing output dim {message_passing.output_dim} != predictor input dim {predictor.input_dim}")
+        if predictor.input_dim < message_passing.output_dim:
+            raise ValueError(f"predictor input dim {predictor.input_dim} < message passing output dim {message_passing.output_dim}")
         self.message_passing = message_passing
         self.agg = agg
         self.bn = nn.BatchNorm1d(message_passing.output_dim) if batch_norm else nn.Identity()
         self.predictor = predictor
+        self.X_d_transform = X_d_transform if X_d_transform is not None else nn.Identity()
 
     @property
     def criterion(self):
@@ -301,17 +307,19 @@ class MPNN(nn.Module):
 
     def fingerprint(self, bmg, V_d: Optional[Tensor] = None, X_d: Optional[Tensor] = None) -> Tensor:
         H = self.bn(self.agg(self.message_passing(bmg, V_d), bmg.batch))
-        return H if X_d is None else torch.cat((H, X_d), dim=1)
+        return H if X_d is None else torch.cat((H, self.X_d_transform(X_d)), dim=1)
 
     def forward(self, bmg, V_d: Optional[Tensor] = None, X_d: Optional[Tensor] = None) -> Tensor:
         return self.predictor(self.fingerprint(bmg, V_d, X_d))
 
     def loss(self, bmg, targets: Tensor, weights: Optional[Tensor] = None, lt_mask: Optional[Tensor] = None,
              gt_mask: Optional[Tensor] = None, V_d: Optional[Tensor] = None, X_d: Optional[Tensor] = None) -> Tensor:
-        if X_d is None and torch.is_grad_enabled() and self.training:
+        if torch.is_grad_enabled() and self.training:
             # the module path of a training step: the block through its own autograd node, everything behind it — aggregation, batch
-            # norm, predictor, criterion AND their backward pass — as ONE more (head_loss); None: the head kernels do not take this model
-            l = head_loss(self, self.message_passing(bmg, V_d), bmg.batch, len(bmg), targets, weights, lt_mask, gt_mask)
+            # norm, the descriptors' concatenation, predictor, criterion AND their backward pass — as ONE more (head_loss); None: the
+            # head kernels do not take this model or these inputs
+            l = head_loss(self, self.message_passing(bmg, V_d), bmg.batch, len(bmg), targets, weights, lt_mask, gt_mask,
+                          X_d=None if X_d is None else self.X_d_transform(X_d))
             if l is not None:
                 return l
         preds = self.predictor.train_step(self.fingerprint(bmg, V_d, X_d))
@@ -367,7 +375,10 @@ class HeadSpec:
     """What ``dmpnn_head`` needs to know of the model around the block — aggregation, batch norm, the predictor's layers and
     activation, the criterion — taken once from the modules; raises ``NotImplementedError`` for what the head kernels do not
     implement.  Shared by :class:`FusedTrainer` (the whole step as one C call) and :func:`head_loss` (the module path's ONE
-    autograd node for everything behind the block)."""
+    autograd node for everything behind the block).
+
+    ``d_xd`` is the width of the molecule descriptors the model expects: the first layer's ``in_features`` less the block's output
+    width (0: none).  ``fill(..., X_d=...)`` hands them over as ``dmpnn_head_args.X_d`` / ``ld_xd`` with ``dims[0] = d_h + d_xd``."""
 
     def __init__(self, model):
         agg, pred = model.agg, model.predictor
@@ -411,6 +422,10 @@ class HeadSpec:
         self.agg_mode, self.agg_norm = MODES[mode], float(getattr(agg, "norm", 1.0))
         self.f_act, self.f_slope, self.kind = f_act, f_slope, kind
         self.layers = [b[-1] for b in blocks]
+        k0 = int(self.layers[0].in_features)
+        self.d_xd = k0 - int(getattr(model.message_passing, "output_dim", k0))
+        if self.d_xd < 0:
+            raise NotImplementedError("a predictor at least as wide as the block's output")
         self.bn = model.bn if isinstance(model.bn, nn.BatchNorm1d) else None
         if self.bn is not None and (self.bn.momentum is None or not self.bn.affine or not self.bn.track_running_stats):
             raise NotImplementedError("nn.BatchNorm1d with a fixed momentum, affine, running statistics")
@@ -435,9 +450,30 @@ class HeadSpec:
                 ps.append(lin.bias)
         return ps
 
-    def fill(self, h, nV: int, n_mols: int, d_out: int, batch: Tensor, T: Tensor, weights, lt_mask, gt_mask, gptr, bn_training: bool = True) -> list:
+    def descriptors(self, X_d: Optional[Tensor], n_mols: int, dev) -> Optional[Tensor]:
+        """``X_d`` (already through ``X_d_transform``) as fp32 rows on ``dev`` with unit column stride — what ``fill`` hands to the
+        kernels; ``ValueError`` when the model expects descriptors and gets none, gets descriptors it has no columns for, or the
+        shape is not ``[n_mols, d_xd]``."""
+        if X_d is None:
+            if self.d_xd:
+                raise ValueError(f"this model's predictor expects {self.d_xd} molecule descriptors per molecule (X_d), got none")
+            return None
+        if not self.d_xd:
+            raise ValueError("X_d given, but this model's predictor takes no molecule descriptors")
+        if X_d.dim() != 2 or tuple(X_d.shape) != (n_mols, self.d_xd):
+            raise ValueError(f"X_d must be [{n_mols}, {self.d_xd}], got {tuple(X_d.shape)}")
+        if X_d.device != dev:
+            raise ValueError(f"X_d must live on {dev}, got {X_d.device}")
+        X = X_d.detach()
+        if X.dtype != torch.float32 or X.stride(1) != 1 or X.stride(0) < self.d_xd:
+            X = X.float().contiguous()
+        return X
+
+    def fill(self, h, nV: int, n_mols: int, d_out: int, batch: Tensor, T: Tensor, weights, lt_mask, gt_mask, gptr, bn_training: bool = True,
+             X_d: Optional[Tensor] = None) -> list:
         """Fill ``h`` (a ``_lib.HeadArgs``) but for ``preds / loss_out / gHv / ws``; ``gptr(param)`` gives the address the gradient of
-        ``param`` goes to (``None``: not wanted).  Returns the tensors that must stay alive until the call has been enqueued."""
+        ``param`` goes to (``None``: not wanted).  ``X_d``: the molecule descriptors as :meth:`descriptors` returns them.  Returns the
+        tensors that must stay alive until the call has been enqueued."""
         dev = T.device
         h.n_atoms, h.n_mols, h.d_h = nV, n_mols, d_out
         h.batch = batch.data_ptr()
@@ -453,6 +489,9 @@ class HeadSpec:
                 h.bn_num_batches_tracked = nbt.data_ptr()  # (counted by the batch-norm kernel: no launch of its own)
         h.n_layers, h.act, h.act_slope = len(self.layers), _lib.ACT[self.f_act], float(self.f_slope)
         h.dims[0] = d_out
+        if X_d is not None:
+            h.X_d, h.ld_xd = X_d.data_ptr(), X_d.stride(0)
+            h.dims[0] = d_out + self.d_xd
         for l, lin in enumerate(self.layers):
             h.W[l], h.b[l] = lin.weight.data_ptr(), (None if lin.bias is None else lin.bias.data_ptr())
             h.dims[l + 1] = lin.out_features
@@ -461,7 +500,7 @@ class HeadSpec:
         h.n_classes = self.n_classes
         h.evid_v_kl, h.evid_eps, h.quantile_alpha = self.v_kl, self.eps, self.q_alpha
         h.targets = T.data_ptr()
-        keep = []
+        keep = [] if X_d is None else [X_d]
         if weights is not None:
             wt = engine._f32c(weights.reshape(-1, 1), "weights").reshape(-1).contiguous()
             h.weights = wt.data_ptr()
@@ -489,7 +528,7 @@ class _HeadLoss(torch.autograd.Function):
     one flat buffer) and hands them to autograd.  Replaces ~40 torch launches and autograd nodes of the module path."""
 
     @staticmethod
-    def forward(ctx, spec, Hv, batch, n_mols, T, weights, lt_mask, gt_mask, *params):
+    def forward(ctx, spec, Hv, batch, n_mols, T, weights, lt_mask, gt_mask, X_d, *params):
         lib = _lib.load()
         dev = Hv.device
         Hv = engine._f32c(Hv, "H_v")
@@ -501,11 +540,12 @@ class _HeadLoss(torch.autograd.Function):
             n += (p.numel() + 3) // 4 * 4
         flat = torch.empty(n + nV * d_out, dtype=torch.float32, device=dev)
         ptr = {id(p): flat.data_ptr() + 4 * o for p, o in zip(params, offs)}
-        want = {id(p) for p, need in zip(params, ctx.needs_input_grad[8:]) if need}
+        want = {id(p) for p, need in zip(params, ctx.needs_input_grad[9:]) if need}
         gH = flat[n:].view(nV, d_out)
         h = _lib.HeadArgs()
         keep = spec.fill(h, nV, n_mols, d_out, batch, T, weights, lt_mask, gt_mask,
-                         lambda p: None if (p is None or id(p) not in want) else ptr[id(p)], bn_training=spec.bn is None or spec.bn.training)
+                         lambda p: None if (p is None or id(p) not in want) else ptr[id(p)], bn_training=spec.bn is None or spec.bn.training,
+                         X_d=X_d)
         preds = torch.empty(n_mols, spec.n_out, dtype=torch.float32, device=dev)
         loss = torch.empty(2, dtype=torch.float32, device=dev)
         h.preds, h.loss_out = preds.data_ptr(), loss.data_ptr()
@@ -527,14 +567,15 @@ class _HeadLoss(torch.autograd.Function):
         n = ctx.n
         gH = flat[n:].view(ctx.hv_shape) if ctx.needs_input_grad[1] else None
         gp = [flat[o:o + math.prod(sh)].view(sh) if w else None for o, sh, w in zip(ctx.offs, ctx.shapes, ctx.want)]
-        return (None, gH, None, None, None, None, None, None, *gp)
+        return (None, gH, None, None, None, None, None, None, None, *gp)
 
 
 def head_loss(model, Hv: Tensor, batch: Tensor, n_mols: int, targets: Tensor, weights: Optional[Tensor] = None,
-              lt_mask: Optional[Tensor] = None, gt_mask: Optional[Tensor] = None) -> Optional[Tensor]:
-    """``criterion(predictor.train_step(bn(agg(H_v, batch))), targets, ...)`` (``models/model.py:152-157``) as ONE autograd node on the
-    head kernels (:class:`_HeadLoss`); ``None`` when the head kernels do not implement this model or these inputs (the caller then
-    runs the torch modules)."""
+              lt_mask: Optional[Tensor] = None, gt_mask: Optional[Tensor] = None, X_d: Optional[Tensor] = None) -> Optional[Tensor]:
+    """``criterion(predictor.train_step(cat(bn(agg(H_v, batch)), X_d)), targets, ...)`` (``models/model.py:152-157``) as ONE autograd
+    node on the head kernels (:class:`_HeadLoss`); ``X_d``: the molecule descriptors already through ``X_d_transform`` (no gradient
+    flows to them).  ``None`` when the head kernels do not implement this model or these inputs — ``X_d`` that needs a gradient
+    included (the caller then runs the torch modules)."""
     # (cached on the identities of what the spec was read from — swapping model.predictor / criterion / bn / agg, or changing a
     #  predictor dropout p, after the first step must not leave the old modules in use: round-4 ADVICE)
     pred = model.predictor
@@ -559,7 +600,13 @@ def head_loss(model, Hv: Tensor, batch: Tensor, n_mols: int, targets: Tensor, we
         return None
     if weights is not None and weights.numel() != n_mols:
         return None
-    return _HeadLoss.apply(spec, Hv, batch, int(n_mols), T, weights, lt_mask, gt_mask, *spec.params())
+    if X_d is not None and X_d.requires_grad:
+        return None
+    try:
+        Xd = spec.descriptors(X_d, n_mols, Hv.device)
+    except ValueError:
+        return None
+    return _HeadLoss.apply(spec, Hv, batch, int(n_mols), T, weights, lt_mask, gt_mask, Xd, *spec.params())
 
 
 class FusedTrainer:
@@ -569,6 +616,8 @@ class FusedTrainer:
     :class:`~chemprop_amd.nn.BondMessagePassing` block with a built-in activation, no ``V_d``, directed, dropout 0 or — with a
     ReLU-class activation — ``nn.Dropout`` inside the tile kernels (hash mask, one seed per step from torch's CPU generator); sum /
     mean / norm aggregation; optional ``nn.BatchNorm1d``; an MLP predictor with a built-in activation and dropout 0; MSE / MAE.
+    A predictor wider than the block's output takes molecule descriptors: ``step(..., X_d=...)`` concatenates
+    ``model.X_d_transform(X_d)`` behind the batch norm inside the same call (no gradient flows to ``X_d``).
     """
 
     def __init__(self, model: MPNN, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, group=None,
@@ -623,11 +672,14 @@ class FusedTrainer:
         return d.get_world_size(self.sync.group) if (d.is_available() and d.is_initialized()) else 1
 
     def step(self, bmg, targets: Tensor, weights: Optional[Tensor] = None, lt_mask: Optional[Tensor] = None,
-             gt_mask: Optional[Tensor] = None, lr: Optional[float] = None, clip: Optional[tuple] = None) -> Tensor:
-        """One optimisation step on ``(bmg, targets, ...)`` (a ``TrainingBatch`` without ``V_d`` / ``X_d``); returns the device
+             gt_mask: Optional[Tensor] = None, lr: Optional[float] = None, clip: Optional[tuple] = None,
+             X_d: Optional[Tensor] = None) -> Tensor:
+        """One optimisation step on ``(bmg, targets, ...)`` (a ``TrainingBatch`` without ``V_d``); returns the device
         tensor ``[loss, number of finite targets]`` of THIS step (no host sync).  ``model.train()`` semantics (batch norm uses
         and updates batch statistics).  ``clip = (value, "norm" | "value")``: Lightning's ``gradient_clip_val`` / ``_algorithm``
-        (``cli/train.py:1937``), applied between the backward pass and the update inside the same call."""
+        (``cli/train.py:1937``), applied between the backward pass and the update inside the same call.  ``X_d``: the batch's
+        molecule descriptors ``[n_mols, d_xd]`` for a model whose predictor takes them (``ValueError`` when they are missing,
+        unexpected or of the wrong shape); ``model.X_d_transform`` is applied to them here."""
         from .nn import _VALIDATE_FIRST_N, _route, _training_plan_kind
 
         lib = _lib.load()
@@ -654,6 +706,11 @@ class FusedTrainer:
                 raise ValueError(f"{name} must have the targets' shape [{n_mols}, {n_tasks}], got {tuple(m.shape)}")
         if self.bn is not None and n_mols == 1:
             raise ValueError("Expected more than 1 value per channel when training (batch norm on a batch of one molecule)")
+        if X_d is not None and self.head.d_xd and tuple(X_d.shape) == (n_mols, self.head.d_xd):
+            xt = getattr(self.model, "X_d_transform", None)
+            with torch.no_grad():
+                X_d = X_d if xt is None else xt(X_d)
+        Xd = self.head.descriptors(X_d, n_mols, dev)
         validate = _lib.opt("DMPNN_VALIDATE", "first") != "never" and self._checked < _VALIDATE_FIRST_N
         world = self._world()
         self.sync.wait()
@@ -719,7 +776,7 @@ class FusedTrainer:
         # ---- the head ----
         h = _lib.HeadArgs()
         keep = [T, gout, keep_b, st, plan]
-        keep += self.head.fill(h, nV, n_mols, d_out, batch, T, weights, lt_mask, gt_mask, self._gv)
+        keep += self.head.fill(h, nV, n_mols, d_out, batch, T, weights, lt_mask, gt_mask, self._gv, X_d=Xd)
         bn = self.bn
         t = int(self.layers[-1].out_features)
         preds = torch.empty(n_mols, t, dtype=torch.float32, device=dev)

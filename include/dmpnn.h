@@ -52,7 +52,8 @@ extern "C" {
  * vector runs over several workgroups and uses the plan's unused arrays as hand-off scratch (nothing for the caller to do).
  * 14 — round 6: DMPNN_LOSS_MVE / DMPNN_LOSS_EVIDENTIAL / DMPNN_LOSS_QUANTILE in dmpnn_head (evid_v_kl / evid_eps / quantile_alpha).
  * 15 — round 6: DMPNN_F_STORE16 also with DMPNN_F_MEGA (the whole-forward tile kernel on f16 operands: one MFMA pass, opt-in, not
- * fp32-class; it was DMPNN_EINVAL there). */
+ * fp32-class; it was DMPNN_EINVAL there).  Grown at its end, same version: dmpnn_head_args.X_d / ld_xd (molecule descriptors behind
+ * the batch norm; the two fields are zero in a caller built before them, which is the NULL they default to). */
 #define DMPNN_ABI_VERSION 15
 
 enum dmpnn_status {
@@ -615,7 +616,7 @@ typedef struct dmpnn_head_args {
     int32_t n_layers; int32_t act; float act_slope;       /* Linear layers of the predictor; enum dmpnn_activation */
     const float* W[DMPNN_MAX_FFN_LAYERS];   /* W[l]: [dims[l+1], dims[l]]  (nn.Linear layout)                       */
     const float* b[DMPNN_MAX_FFN_LAYERS];   /* [dims[l+1]] or NULL                                                  */
-    int64_t dims[DMPNN_MAX_FFN_LAYERS + 1]; /* dims[0] = d_h ... dims[n_layers] = n_tasks                           */
+    int64_t dims[DMPNN_MAX_FFN_LAYERS + 1]; /* dims[0] = d_h (+ d_xd with X_d) ... dims[n_layers] = n_tasks    */
     int32_t loss;                           /* enum dmpnn_loss                                                      */
     const float* targets;                   /* [n_mols, n_tasks], NaN / inf = missing; NULL: predictions only       */
     const float* weights;                   /* [n_mols] or NULL (ones)                                              */
@@ -631,6 +632,9 @@ typedef struct dmpnn_head_args {
     int32_t n_classes;                      /* v12, DMPNN_LOSS_CE: classes per task (>= 2); the last layer's width is n_tasks * n_classes */
     float evid_v_kl, evid_eps;              /* v14, DMPNN_LOSS_EVIDENTIAL: EvidentialLoss.v_kl (0.2) and .eps (1e-8)                   */
     float quantile_alpha;                   /* v14, DMPNN_LOSS_QUANTILE: QuantileLoss.alpha (0.1)                                      */
+    const float* X_d; int64_t ld_xd;        /* v15 growth: [n_mols, d_xd] molecule descriptors, row stride ld_xd >= d_xd, or NULL (none).
+                                               d_xd = dims[0] - d_h: the predictor's input is cat(bn(agg(H_v)), X_d) (models/model.py,
+                                               fingerprint) and W[0] is [dims[1], d_h + d_xd]; no gradient flows to X_d               */
 } dmpnn_head_args;
 size_t dmpnn_head_ws_bytes(const dmpnn_head_args* h);
 int dmpnn_head(const dmpnn_head_args* h, const float* Hv, int64_t ldhv, void* stream);
