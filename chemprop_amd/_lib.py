@@ -109,6 +109,7 @@ class BwdArgs(C.Structure):
 
 
 MAX_FFN_LAYERS = 8
+MAX_COMPONENTS = 8   # (DMPNN_MAX_COMPONENTS: blocks side by side in one fingerprint)
 LOSS = {"mse": 0, "mae": 1, "bce": 2, "ce": 3, "mve": 4, "evidential": 5, "quantile": 6}
 STEP_FORWARD, STEP_BACKWARD, STEP_UPDATE = 1, 2, 4
 
@@ -132,11 +133,19 @@ class HeadArgs(C.Structure):
         ("n_classes", C.c_int32),
         ("evid_v_kl", C.c_float), ("evid_eps", C.c_float), ("quantile_alpha", C.c_float),
         ("X_d", C.c_void_p), ("ld_xd", C.c_int64),
+        ("n_components", C.c_int32),
     ]
 
 
 class TrainRouteInfo(C.Structure):
     _fields_ = [("plan_kind", C.c_int32), ("route", C.c_int32), ("keep_rows", C.c_int32), ("keep_bits", C.c_int32), ("lean", C.c_int32)]
+
+
+class StepComponent(C.Structure):
+    _fields_ = [
+        ("edge_index", C.c_void_p), ("rev_edge_index", C.c_void_p), ("batch", C.c_void_p), ("plan_bytes", C.c_size_t), ("plan_ready", C.c_int32),
+        ("bwd", BwdArgs),
+    ]
 
 
 class StepArgs(C.Structure):
@@ -148,6 +157,7 @@ class StepArgs(C.Structure):
         ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
         ("bias_corr1", C.c_float), ("sqrt_bias_corr2", C.c_float), ("grad_scale", C.c_float), ("dev_scalars", C.c_void_p),
         ("clip_val", C.c_float), ("clip_mode", C.c_int32), ("clip_ws", C.c_void_p),
+        ("n_extra", C.c_int32), ("extra", C.POINTER(StepComponent)),
     ]
 
 

@@ -252,6 +252,12 @@ bool mega16_keeps_rows(const dmpnn_fwd_args& a);   // M^(t) kept as split rows i
 int prepare_tiles_and_bounds(const int64_t* edge_index, const int64_t* rev, const int64_t* batch, int64_t nV, int64_t nE, void* plan,
                              size_t plan_bytes, int* mol_bounds, int64_t n_mols, void* stream, bool* wrote_bounds,
                              const dmpnn_fwd_args* split_for = nullptr, bool* did_split = nullptr);
+// dmpnn_molagg_fwd / _bwd with the aggregate's rows folded (dmpnn_molagg.hip): molecule m is row m % rows, columns [(m / rows) d_h, + d_h)
+// — the multicomponent fingerprint [B, n d_h] of a batch vector that numbers molecule i of component c as c B + i (rows = B)
+int molagg_fwd_rows(const float* H, int64_t ldh, int64_t n_atoms, int64_t d_h, int64_t n_mols, const void* ws, int mode,
+                    float norm, float* out, int64_t ldo, int64_t rows, void* stream);
+int molagg_bwd_rows(const float* gout, int64_t ldg, const int64_t* batch, int64_t n_atoms, int64_t d_h, int64_t n_mols,
+                    const void* ws, int mode, float norm, float* gH, int64_t ldgh, int64_t rows, void* stream);
 // the same tables for batches beyond the single-workgroup plan (dmpnn_tiles_large.hip)
 bool tiles_large_fits(int64_t nV, int64_t nE);
 int launch_prepare_tiles_large(const int64_t* edge_index, const int64_t* batch, int64_t nV, int64_t nE, int* plan, hipStream_t s);

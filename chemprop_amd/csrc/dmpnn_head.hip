@@ -606,6 +606,8 @@ struct AggBnArgs {
     HeadSplit split;
     XdFill xd;
     long long* dbg;                        // optional cycle stamps: [0..5] column workgroup 1, [6..9] the first split workgroup
+    int dh_c; int64_t nBt;                 // a multicomponent fingerprint: column c of X / Y is column c % dh_c of component c / dh_c, whose
+                                           // molecule r is c / dh_c B + r of the bounds table (nBt molecules); one block: dh_c = d, nBt = B
 };
 // Geometry of the two column kernels: a workgroup = QPW column QUADS (16-byte loads and stores: a quarter of the memory instructions
 // of a thread-per-column layout, whose 1 500 four-segment wave loads per CU cost the aggregation 11 us) x 1024 / QPW row lanes; thread
@@ -667,15 +669,19 @@ __global__ __launch_bounds__(1024) void k_agg_bn_fwd(AggBnArgs q) {
     const int tq = threadIdx.x % QPW, ty = threadIdx.x / QPW;
     const int c = (blockIdx.x * QPW + tq) * 4;
     const bool ok = c < a.d;   // (d % 4 == 0: a quad is inside or outside)
-    const gemm::rsrc_t rBd = gemm::make_rsrc(q.bounds, (unsigned)((3 * a.B + 4) * 4));
-    const int flag = col_ldi(rBd, true, 2 * a.B);
+    // (the component of this quad — dh_c % 4 == 0: a quad never straddles two — its column in H_v and its first molecule in the table)
+    const int comp = ok ? c / q.dh_c : 0;
+    const int cv = c - comp * q.dh_c;
+    const int64_t mo = (int64_t)comp * a.B, nBt = q.nBt;
+    const gemm::rsrc_t rBd = gemm::make_rsrc(q.bounds, (unsigned)((3 * nBt + 4) * 4));
+    const int flag = col_ldi(rBd, true, 2 * nBt);
     int v0[RR], nv[RR], dn[RR];
 #pragma unroll
     for (int i = 0; i < RR; ++i) {
         const int64_t r = ty + (int64_t)kQLanes * i;
-        v0[i] = col_ldi(rBd, r < a.B, r);
-        nv[i] = col_ldi(rBd, r < a.B, a.B + r);
-        dn[i] = col_ldi(rBd, q.use_done && r < a.B, 2 * a.B + 4 + r);
+        v0[i] = col_ldi(rBd, r < a.B, mo + r);
+        nv[i] = col_ldi(rBd, r < a.B, nBt + mo + r);
+        dn[i] = col_ldi(rBd, q.use_done && r < a.B, 2 * nBt + 4 + mo + r);
     }
     // (batch norm's per-column constants: requested now, used behind the statistics)
     auto ldq = [&](const float* p) {
@@ -724,7 +730,7 @@ __global__ __launch_bounds__(1024) void k_agg_bn_fwd(AggBnArgs q) {
 #pragma unroll
             for (int i = 0; i < RR; ++i)
                 tv[u][i] = gemm::as_f4(__builtin_amdgcn_raw_buffer_load_b128(
-                    rH, s0 + u < nv[i] ? (unsigned)((int64_t)(v0[i] + s0 + u) * q.ldhv + c) * 4u : gemm::kOOB, 0, 0));
+                    rH, s0 + u < nv[i] ? (unsigned)((int64_t)(v0[i] + s0 + u) * q.ldhv + cv) * 4u : gemm::kOOB, 0, 0));
 #pragma unroll
         for (int u = 0; u < AT; ++u)
 #pragma unroll
@@ -800,6 +806,7 @@ struct BnAggBwdArgs {
     const float* part; int n_part, part_stride, tN, t;
     float* gW1; float* gb1; float* loss_out;
     long long* dbg;                        // optional cycle stamps of column workgroup 1
+    int dh_c; int64_t nBt;                 // the multicomponent map of AggBnArgs (one block: dh_c = d, nBt = B)
 };
 template <int QPW, int RR, bool BN>
 __global__ __launch_bounds__(1024) void k_bn_agg_bwd(BnAggBwdArgs q) {
@@ -838,6 +845,9 @@ __global__ __launch_bounds__(1024) void k_bn_agg_bwd(BnAggBwdArgs q) {
     const int tq = threadIdx.x % QPW, ty = threadIdx.x / QPW;
     const int c = (blockIdx.x * QPW + tq) * 4;
     const bool ok = c < a.d;
+    const int comp = ok ? c / q.dh_c : 0;
+    const int cv = c - comp * q.dh_c;   // (this quad's column in H_v's rows)
+    const int64_t mo = (int64_t)comp * a.B, nBt = q.nBt;
     int n_stamp = 0;
     auto stamp = [&]() {
         if (q.dbg && blockIdx.x == 1 && threadIdx.x == 0 && n_stamp < 6) q.dbg[n_stamp] = (long long)__builtin_readcyclecounter();
@@ -847,7 +857,7 @@ __global__ __launch_bounds__(1024) void k_bn_agg_bwd(BnAggBwdArgs q) {
     // every request of the kernel first (buffer loads: no branch, no wait in between)
     float4 gs[RR], xr[RR];
     int v0[RR], v1[RR];
-    const gemm::rsrc_t rBd = gemm::make_rsrc(q.bounds, (unsigned)((3 * a.B + 4) * 4));
+    const gemm::rsrc_t rBd = gemm::make_rsrc(q.bounds, (unsigned)((3 * nBt + 4) * 4));
     const gemm::rsrc_t rG = gemm::make_rsrc(a.gY, gemm::clamp_bytes(a.B * a.ldgy * 4)), rX = gemm::make_rsrc(a.X, gemm::clamp_bytes(a.B * a.ldx * 4));
 #pragma unroll
     for (int i = 0; i < RR; ++i) {
@@ -855,10 +865,10 @@ __global__ __launch_bounds__(1024) void k_bn_agg_bwd(BnAggBwdArgs q) {
         const bool in = ok && r < a.B;
         gs[i] = gemm::as_f4(__builtin_amdgcn_raw_buffer_load_b128(rG, in ? (unsigned)(r * a.ldgy + c) * 4u : gemm::kOOB, 0, 0));
         xr[i] = BN ? gemm::as_f4(__builtin_amdgcn_raw_buffer_load_b128(rX, in ? (unsigned)(r * a.ldx + c) * 4u : gemm::kOOB, 0, 0)) : make_float4(0.f, 0.f, 0.f, 0.f);
-        v0[i] = col_ldi(rBd, r < a.B, r);
-        v1[i] = col_ldi(rBd, r < a.B, a.B + r);
+        v0[i] = col_ldi(rBd, r < a.B, mo + r);
+        v1[i] = col_ldi(rBd, r < a.B, nBt + mo + r);
     }
-    const int flag = col_ldi(rBd, true, 2 * a.B);
+    const int flag = col_ldi(rBd, true, 2 * nBt);
     auto ldq = [&](const float* p) {
         return gemm::as_f4(__builtin_amdgcn_raw_buffer_load_b128(col_buf(p, (int64_t)a.d * 4, q.bounds), (BN && ok) ? (unsigned)c * 4u : gemm::kOOB, 0, 0));
     };
@@ -894,7 +904,7 @@ __global__ __launch_bounds__(1024) void k_bn_agg_bwd(BnAggBwdArgs q) {
     if (!ok) return;
     const float nanv = __int_as_float(0x7fc00000);
     if (flag) {   // an invalid `batch`: every row NaN (atoms outside every molecule's range included)
-        for (int64_t v = ty; v < q.nV; v += kQLanes) *reinterpret_cast<float4*>(q.gHv + v * q.ldg + c) = make_float4(nanv, nanv, nanv, nanv);
+        for (int64_t v = ty; v < q.nV; v += kQLanes) *reinterpret_cast<float4*>(q.gHv + v * q.ldg + cv) = make_float4(nanv, nanv, nanv, nanv);
         return;
     }
 #pragma unroll
@@ -904,7 +914,7 @@ __global__ __launch_bounds__(1024) void k_bn_agg_bwd(BnAggBwdArgs q) {
         float4 g = gs[i];
         if (q.agg_mode == DMPNN_MOLAGG_MEAN) { const float n = (float)(v1[i] - v0[i]); g = make_float4(g.x / n, g.y / n, g.z / n, g.w / n); }
         if (q.agg_mode == DMPNN_MOLAGG_NORM) g = make_float4(g.x / q.agg_norm, g.y / q.agg_norm, g.z / q.agg_norm, g.w / q.agg_norm);
-        for (int v = v0[i]; v < v1[i]; ++v) *reinterpret_cast<float4*>(q.gHv + (int64_t)v * q.ldg + c) = g;
+        for (int v = v0[i]; v < v1[i]; ++v) *reinterpret_cast<float4*>(q.gHv + (int64_t)v * q.ldg + cv) = g;
     }
     stamp();  // 4 (2 without batch norm) rows issued
 }
@@ -1230,16 +1240,19 @@ struct HeadLayout {
 };
 // the shapes the four-launch form takes (training or not is the caller's business): one hidden layer, a handful of outputs
 // (with molecule descriptors the first layer's reduction may be up to kRowsMaxK wide: d_h + d_xd; its data gradient stays d_h wide)
+// components of a multicomponent fingerprint (dmpnn_head_args.n_components: 0 and 1 are one block)
+inline int64_t head_ncomp(const dmpnn_head_args& h) { return h.n_components > 1 ? h.n_components : 1; }
 bool rows_shape(const dmpnn_head_args& h) {
     return h.n_layers == 2 && h.dims[2] <= kOutMaxTasks && h.dims[2] >= 1 && h.loss <= DMPNN_LOSS_BCE && h.n_mols <= kRowsMaxB &&
-           h.dims[0] <= (h.X_d ? kRowsMaxK : kRowsMaxWidth) && h.d_h <= kRowsMaxWidth && h.dims[1] <= kRowsMaxWidth && h.dims[0] % 4 == 0;
+           h.dims[0] <= (h.X_d ? kRowsMaxK : kRowsMaxWidth) && head_ncomp(h) * h.d_h <= kRowsMaxWidth && h.dims[1] <= kRowsMaxWidth && h.dims[0] % 4 == 0;
 }
 HeadLayout head_layout(const dmpnn_head_args& h) {
     HeadLayout L;
     memset(&L, 0, sizeof(L));
-    const int64_t B = h.n_mols > 0 ? h.n_mols : 0, d = h.d_h;
+    // d: the width of the block part of the fingerprint (n_components d_h); the bounds table covers every component's molecules
+    const int64_t B = h.n_mols > 0 ? h.n_mols : 0, d = head_ncomp(h) * h.d_h;
     size_t o = 0;
-    L.bounds = o; o += al256(dmpnn_molagg_ws_bytes(B));
+    L.bounds = o; o += al256(dmpnn_molagg_ws_bytes(head_ncomp(h) * B));
     L.Hm = o; o += al256((size_t)B * d * 4);
     L.Z = o; o += al256(h.bn_weight ? (size_t)B * d * 4 : 0);
     L.mean = o; o += al256((size_t)d * 4);
@@ -1291,7 +1304,7 @@ using namespace dmpnn;
 extern "C" {
 
 size_t dmpnn_head_ws_bytes(const dmpnn_head_args* h) {
-    if (!h || h->n_layers < 0 || h->n_layers > DMPNN_MAX_FFN_LAYERS || h->d_h <= 0) return 0;
+    if (!h || h->n_layers < 0 || h->n_layers > DMPNN_MAX_FFN_LAYERS || h->d_h <= 0 || h->n_components < 0 || h->n_components > DMPNN_MAX_COMPONENTS) return 0;
     return head_layout(*h).total;
 }
 
@@ -1341,13 +1354,18 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     DMPNN_CHECK_ARG(hp != nullptr, "head: null args");
     const dmpnn_head_args& h = *hp;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t B = h.n_mols, d = h.d_h, nV = h.n_atoms;
+    DMPNN_CHECK_ARG(h.n_components >= 0 && h.n_components <= DMPNN_MAX_COMPONENTS, "head: n_components (%d) outside 0..%d", (int)h.n_components,
+                    DMPNN_MAX_COMPONENTS);
+    // a multicomponent fingerprint: ncomp blocks of dc columns each, side by side (d = ncomp dc); the table of molecule bounds covers nBt
+    const int64_t ncomp = head_ncomp(h), dc = h.d_h;
+    const int64_t B = h.n_mols, d = ncomp * dc, nV = h.n_atoms, nBt = ncomp * B;
     const int Ln = h.n_layers;
-    DMPNN_CHECK_ARG(B >= 0 && nV >= 0 && d > 0 && ldhv >= d, "head: bad sizes");
+    DMPNN_CHECK_ARG(B >= 0 && nV >= 0 && dc > 0 && ldhv >= dc, "head: bad sizes");
     DMPNN_CHECK_ARG(Ln >= 1 && Ln <= DMPNN_MAX_FFN_LAYERS, "head: 1..%d predictor layers", DMPNN_MAX_FFN_LAYERS);
     // molecule descriptors: the predictor's input is cat(bn(agg(H_v)), X_d), dims[0] = d_h + d_xd
     const bool xd = h.X_d != nullptr;
-    DMPNN_CHECK_ARG(xd ? h.dims[0] > d : h.dims[0] == d, xd ? "head: with X_d, dims[0] = d_h + d_xd > d_h" : "head: dims[0] == d_h without X_d");
+    DMPNN_CHECK_ARG(xd ? h.dims[0] > d : h.dims[0] == d, xd ? "head: with X_d, dims[0] = n_components d_h + d_xd > n_components d_h"
+                                                           : "head: dims[0] == d_h (times n_components) without X_d");
     DMPNN_CHECK_ARG(!xd || h.ld_xd >= h.dims[0] - d, "head: ld_xd (%lld) < d_xd (%lld)", (long long)h.ld_xd, (long long)(h.dims[0] - d));
     for (int l = 0; l < Ln; ++l) DMPNN_CHECK_ARG(h.W[l] && h.dims[l + 1] > 0, "head: layer %d has no weight / width", l);
     DMPNN_CHECK_ARG(h.act >= DMPNN_ACT_NONE && h.act <= DMPNN_ACT_ELU && h.act != DMPNN_ACT_PRELU, "head: activation %d is not built in", h.act);
@@ -1363,7 +1381,7 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     //  molecule has no variance, and the output would silently be beta)
     DMPNN_CHECK_ARG(!(h.bn_weight && h.bn_training) || B != 1, "head: batch norm in training mode needs more than 1 molecule per batch");
     const bool want_grad = h.gHv != nullptr;
-    DMPNN_CHECK_ARG(!want_grad || (h.targets && h.loss_out && h.ldg >= d), "head: gradients need targets, loss_out and ldg >= d_h");
+    DMPNN_CHECK_ARG(!want_grad || (h.targets && h.loss_out && h.ldg >= dc), "head: gradients need targets, loss_out and ldg >= d_h");
     const HeadLayout L = head_layout(h);
     if (!h.ws || h.ws_bytes < L.total) {
         set_error("head: workspace missing or too small (%zu < %zu bytes)", h.ws_bytes, L.total);
@@ -1386,13 +1404,14 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     const int t = t_out / nc;                                           // tasks (= columns of `targets`)
 
     // ---- forward ----
-    if (!bounds_done) DMPNN_TRY(dmpnn_molagg_bounds(h.batch, nV, B, ws + L.bounds, dmpnn_molagg_ws_bytes(B), stream));
+    if (!bounds_done) DMPNN_TRY(dmpnn_molagg_bounds(h.batch, nV, nBt, ws + L.bounds, dmpnn_molagg_ws_bytes(nBt), stream));
     // round 5: the four-launch form (see k_agg_bn_fwd) — aggregation + batch norm as ONE column kernel for <= kRowsMaxB molecules
     // (forward, inference included), the whole predictor + criterion + their backward as ONE row kernel when the shape fits
     const char* head_env = getenv("DMPNN_HEAD");
     const bool chain = head_env && !strcmp(head_env, "chain");
     // (the column kernels move 16-byte quads: widths and strides in multiples of 4 floats, 16-byte aligned rows)
-    const bool cols_fused = !chain && B <= kRowsMaxB && nV > 0 && d % 4 == 0 && ldhv % 4 == 0 && aligned16(Hv) &&
+    // (a multicomponent fingerprint: a quad must not straddle two components — dc % 4 == 0 — or the chain takes it)
+    const bool cols_fused = !chain && B <= kRowsMaxB && nV > 0 && dc % 4 == 0 && ldhv % 4 == 0 && aligned16(Hv) &&
                             (!want_grad || (h.ldg % 4 == 0 && aligned16(h.gHv))) && (int64_t)nV * ldhv < (1ll << 29) &&
                             (!h.bn_weight || (aligned16(h.bn_weight) && aligned16(h.bn_bias) && aligned16(h.bn_running_mean) && aligned16(h.bn_running_var) &&
                                               (!h.g_bn_weight || aligned16(h.g_bn_weight)) && (!h.g_bn_bias || aligned16(h.g_bn_bias))));
@@ -1416,11 +1435,12 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
         const char* agg_env = getenv("DMPNN_HEAD_AGG");
         const bool fuse_agg = agg_rode || (agg_env ? !strcmp(agg_env, "fused") : B <= kFuseAggMols);   // (rode: only what the tile kernel left is summed here)
         q.use_done = agg_rode ? 1 : 0;
-        if (!fuse_agg) DMPNN_TRY(dmpnn_molagg_fwd(Hv, ldhv, nV, d, B, ws + L.bounds, h.agg_mode, h.agg_norm, Hm, ldH, stream));
+        if (!fuse_agg) DMPNN_TRY(molagg_fwd_rows(Hv, ldhv, nV, dc, nBt, ws + L.bounds, h.agg_mode, h.agg_norm, Hm, ldH, B, stream));
         q.Hv = fuse_agg ? Hv : nullptr; q.ldhv = ldhv; q.nV = nV; q.bounds = reinterpret_cast<const int*>(ws + L.bounds); q.agg_mode = h.agg_mode; q.agg_norm = h.agg_norm;
         const int qpw = col_quads(B);
         q.n_col_blocks = (int)((d + 4 * qpw - 1) / (4 * qpw));
         q.dbg = g_debug_stamps ? g_debug_stamps + 80 : nullptr;
+        q.dh_c = (int)dc; q.nBt = nBt;
         int split_blocks = 0;
         if (rows) {
             const int N = (int)h.dims[1], K = (int)h.dims[0];
@@ -1436,7 +1456,7 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
         DMPNN_CHECK_LAUNCH("k_agg_bn_fwd");
         if (bn) { Z = Ybn; ldz = ldY; }
     } else {
-        DMPNN_TRY(dmpnn_molagg_fwd(Hv, ldhv, nV, d, B, ws + L.bounds, h.agg_mode, h.agg_norm, Hm, ldH, stream));
+        DMPNN_TRY(molagg_fwd_rows(Hv, ldhv, nV, dc, nBt, ws + L.bounds, h.agg_mode, h.agg_norm, Hm, ldH, B, stream));
         if (xd) {
             hipLaunchKernelGGL(k_xd_fill, dim3((unsigned)xd_fill_blocks(xf)), dim3(1024), 0, s, xf);
             DMPNN_CHECK_LAUNCH("k_xd_fill");
@@ -1487,6 +1507,7 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
         q.part = reinterpret_cast<const float*>(ws + L.part); q.n_part = L.n_part; q.part_stride = L.part_stride; q.tN = t * N; q.t = t;
         q.gW1 = h.gW[1]; q.gb1 = h.b[1] ? h.gb[1] : nullptr; q.loss_out = h.loss_out;
         q.dbg = g_debug_stamps ? g_debug_stamps + 96 : nullptr;
+        q.dh_c = (int)dc; q.nBt = nBt;
         return launch_bn_agg_bwd(q, h.bn_weight != nullptr, s);
     }
     const float* A[DMPNN_MAX_FFN_LAYERS + 1];
@@ -1594,6 +1615,7 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
         q.b = BnBwdArgs{gZ, ldgz, Hm, ldH, nullptr, d, h.bn_weight, mean, invstd, h.bn_running_mean, h.bn_running_var, h.g_bn_weight, h.g_bn_bias,
                         B, (int)d, h.bn_eps, h.bn_training};
         q.gHv = h.gHv; q.ldg = h.ldg; q.bounds = reinterpret_cast<const int*>(ws + L.bounds); q.nV = nV; q.agg_mode = h.agg_mode; q.agg_norm = h.agg_norm;
+        q.dh_c = (int)dc; q.nBt = nBt;
         return launch_bn_agg_bwd(q, h.bn_weight != nullptr, s);
     }
     if (h.bn_weight) {
@@ -1607,7 +1629,7 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     // (Running the hidden layers' weight-gradient products and the molecule bounds on a second stream of the library's own was
     //  built and measured: each fork / join pair costs ~6 us of cross-queue synchronisation on this runtime — the step got 12 us
     //  SLOWER, profiles/r03_side_stream_ab.txt.  One stream.)
-    return dmpnn_molagg_bwd(gZ, ldgz, h.batch, nV, d, B, ws + L.bounds, h.agg_mode, h.agg_norm, h.gHv, h.ldg, stream);
+    return molagg_bwd_rows(gZ, ldgz, h.batch, nV, dc, nBt, ws + L.bounds, h.agg_mode, h.agg_norm, h.gHv, h.ldg, B, stream);
 }
 }  // namespace
 
@@ -1620,24 +1642,43 @@ int dmpnn_train_step(const dmpnn_step_args* a, void* stream) {
     // (round 6: on a tile plan built here from the batch vector, the tile kernels' launches are bounded by the batch's molecule count — a tile
     //  holds at least one molecule — instead of the layout's bound: 512 instead of 745 workgroups at 512 molecules, forward and backward;
     //  a plan that turns out to hold more tiles than that comes back NaN from both kernels)
+    // a multicomponent model: ncomp > 1 components in the head's fingerprint, either ONE shared block over the merged batch (n_extra = 0:
+    // its batch vector numbers ncomp B molecules) or one block per component (n_extra = ncomp - 1: each batch holds B molecules)
+    const int64_t ncomp = a->head.n_components > 1 ? a->head.n_components : 1;
+    const int n_extra = a->n_extra;
+    DMPNN_CHECK_ARG(n_extra >= 0 && (n_extra == 0 || (a->extra && n_extra + 1 == ncomp)), "train_step: n_extra (%d) must be 0 or head.n_components - 1",
+                    n_extra);
     dmpnn_bwd_args bw = a->bwd;
-    if ((bw.f.flags & DMPNN_F_TILE_PLAN) && bw.f.n_tiles_launch == 0 && a->head.n_mols > 0 && a->head.batch == a->batch) bw.f.n_tiles_launch = a->head.n_mols;
+    // (the tile kernels' launches are bounded by the molecules of the block's OWN batch: a shared block over the merged batch holds ncomp B)
+    const int64_t blk_mols = a->head.batch == a->batch ? ncomp * a->head.n_mols : (n_extra > 0 ? a->head.n_mols : 0);
+    if ((bw.f.flags & DMPNN_F_TILE_PLAN) && bw.f.n_tiles_launch == 0 && blk_mols > 0) bw.f.n_tiles_launch = blk_mols;
     const dmpnn_fwd_args& f = bw.f;
     DMPNN_CHECK_ARG((f.flags & DMPNN_F_KEEP) != 0, "train_step: the forward must keep its tensors (DMPNN_F_KEEP)");
     DMPNN_CHECK_ARG(a->head.gHv == a->bwd.gout && a->head.ldg == a->bwd.ldgout, "train_step: head.gHv must be the backward's gout");
-    DMPNN_CHECK_ARG(a->head.n_atoms == f.n_atoms && a->head.d_h == f.d_h + (f.W_d ? f.d_vd : 0), "train_step: head and block sizes differ");
+    DMPNN_CHECK_ARG(a->head.d_h == f.d_h + (f.W_d ? f.d_vd : 0), "train_step: head and block sizes differ");
+    int64_t n_atoms_all = f.n_atoms;
+    for (int e = 0; e < n_extra; ++e) {   // every further block writes the rows behind the previous one's in H_v, reads them in gHv
+        const dmpnn_bwd_args& eb = a->extra[e].bwd;
+        DMPNN_CHECK_ARG((eb.f.flags & DMPNN_F_KEEP) && eb.f.d_h == a->head.d_h && !eb.f.W_d, "train_step: component %d: a keeping forward of d_h %lld, no V_d",
+                        e + 1, (long long)a->head.d_h);
+        DMPNN_CHECK_ARG(eb.f.ldout == f.ldout && eb.f.out == f.out + n_atoms_all * f.ldout && eb.ldgout == bw.ldgout && eb.gout == bw.gout + n_atoms_all * bw.ldgout,
+                        "train_step: component %d: its H_v / gHv rows must follow the previous component's", e + 1);
+        n_atoms_all += eb.f.n_atoms;
+    }
+    DMPNN_CHECK_ARG(a->head.n_atoms == n_atoms_all, "train_step: head and block sizes differ (%lld atoms against %lld)", (long long)a->head.n_atoms,
+                    (long long)n_atoms_all);
     const int stages = a->stages ? a->stages : (DMPNN_STEP_FORWARD | DMPNN_STEP_BACKWARD | DMPNN_STEP_UPDATE);
     ExtraWgrad rider;
     memset(&rider, 0, sizeof(rider));
     if (stages & DMPNN_STEP_FORWARD) {
         bool bounds_done = false, split_done = false;
         if (!a->plan_ready) {
-            DMPNN_CHECK_ARG(a->edge_index && a->rev_edge_index, "train_step: null index arrays");
+            DMPNN_CHECK_ARG(f.n_edges == 0 || (a->edge_index && a->rev_edge_index), "train_step: null index arrays");
             if (f.flags & DMPNN_F_TILE_PLAN) {  // (the tile table alone: the kept tensors stay in the caller's edge order, dmpnn.h)
                 // ... and the planner already holds every molecule's atom range: it writes the aggregation's bounds table on the side
                 const dmpnn_head_args& h = a->head;
                 int* mb = nullptr;
-                if (h.ws && h.n_mols > 0 && h.batch == a->batch && h.n_atoms == f.n_atoms) {
+                if (h.ws && h.n_mols > 0 && h.batch == a->batch && h.n_atoms == f.n_atoms && ncomp == 1) {
                     const HeadLayout HL = head_layout(h);
                     if (h.ws_bytes >= HL.total) mb = reinterpret_cast<int*>(static_cast<unsigned char*>(h.ws) + HL.bounds);
                 }
@@ -1655,7 +1696,7 @@ int dmpnn_train_step(const dmpnn_step_args* a, void* stream) {
             const char* he = getenv("DMPNN_HEAD");
             const char* ae = getenv("DMPNN_HEAD_AGG");
             // (with descriptors and no batch norm the aggregate is written into the fingerprint's rows, not into H: no ride there)
-            if (bounds_done && h.ws && h.n_mols > 0 && h.n_mols <= kRowsMaxB && h.d_h % 4 == 0 && h.d_h == f.d_h && !f.W_d && !(he && !strcmp(he, "chain")) &&
+            if (bounds_done && ncomp == 1 && h.ws && h.n_mols > 0 && h.n_mols <= kRowsMaxB && h.d_h % 4 == 0 && h.d_h == f.d_h && !f.W_d && !(he && !strcmp(he, "chain")) &&
                 (!h.X_d || h.bn_weight) &&
                 !(ae && strcmp(ae, "tile"))) {
                 const HeadLayout HL = head_layout(h);
@@ -1674,13 +1715,35 @@ int dmpnn_train_step(const dmpnn_step_args* a, void* stream) {
         agg_rode = g_agg_ride.taken;
         g_agg_ride = AggRide{nullptr, 0, nullptr, nullptr, 0, 0, 0.f, false};
         if (frc != DMPNN_OK) return frc;
+        for (int e = 0; e < n_extra; ++e) {   // the further blocks: K0 and the keeping forward of each, into its rows of H_v
+            const dmpnn_step_component& c = a->extra[e];
+            dmpnn_fwd_args fe = c.bwd.f;
+            if ((fe.flags & DMPNN_F_TILE_PLAN) && fe.n_tiles_launch == 0 && a->head.n_mols > 0) fe.n_tiles_launch = a->head.n_mols;
+            bool split_e = false;
+            if (!c.plan_ready) {
+                DMPNN_CHECK_ARG(fe.n_edges == 0 || (c.edge_index && c.rev_edge_index), "train_step: component %d: null index arrays", e + 1);
+                if (fe.flags & DMPNN_F_TILE_PLAN)
+                    DMPNN_TRY(prepare_tiles_and_bounds(c.edge_index, c.rev_edge_index, c.batch, fe.n_atoms, fe.n_edges, const_cast<void*>(fe.plan),
+                                                       c.plan_bytes, nullptr, 0, stream, nullptr, &fe, &split_e));
+                else
+                    DMPNN_TRY(dmpnn_prepare_with_batch(c.edge_index, c.rev_edge_index, c.batch, fe.n_atoms, fe.n_edges, const_cast<void*>(fe.plan),
+                                                       c.plan_bytes, stream));
+            }
+            if (split_e) fe.flags |= DMPNN_F_WSPLIT_READY;
+            DMPNN_TRY(dmpnn_forward(&fe, stream));
+        }
         // (a whole step in one call: the first predictor layer's weight gradient rides in the block's backward launches; a staged
         //  step — data parallel — has the head's gradients final after this stage, so nothing is deferred there)
         DMPNN_TRY(head_run(&a->head, f.out, f.ldout, stream, bounds_done, (stages & DMPNN_STEP_BACKWARD) ? &rider : nullptr, agg_rode));
     }
     if (stages & DMPNN_STEP_BACKWARD) {
         bool rode = false;
-        DMPNN_TRY(backward_impl(&bw, stream, rider.Z ? &rider : nullptr, &rode));
+        DMPNN_TRY(backward_impl(&bw, stream, rider.Z ? &rider : nullptr, &rode));   // (the rider: in component 0's launches only)
+        for (int e = 0; e < n_extra; ++e) {
+            dmpnn_bwd_args be = a->extra[e].bwd;
+            if ((be.f.flags & DMPNN_F_TILE_PLAN) && be.f.n_tiles_launch == 0 && a->head.n_mols > 0) be.f.n_tiles_launch = a->head.n_mols;
+            DMPNN_TRY(backward_impl(&be, stream, nullptr, nullptr));
+        }
         if (rider.Z && !rode) {  // (the backward pass did not take the f16 products: the product of its own, as dmpnn_head would have run it)
             dmpnn_gemm_args g;
             memset(&g, 0, sizeof(g));

@@ -67,6 +67,7 @@ struct MolAggArgs {
     int64_t n_mols;
     int h, mode;
     float norm;
+    int64_t rows;   // output rows: molecule m goes to row m % rows, columns from (m / rows) h (a multicomponent fingerprint; rows = n_mols: row m)
 };
 
 template <int VEC>
@@ -80,6 +81,8 @@ __global__ __launch_bounds__(256) void k_mol_reduce(MolAggArgs a) {
     const int flag = a.ws[2 * a.n_mols];
     const int v0 = a.ws[m], v1 = a.ws[a.n_mols + m];
     if (c >= a.h) return;
+    float* out = a.out + m * a.ldo;
+    if (a.rows != a.n_mols) out = a.out + (m % a.rows) * a.ldo + (m / a.rows) * a.h;
     float acc[VEC];
 #pragma unroll
     for (int t = 0; t < VEC; ++t) acc[t] = 0.f;
@@ -101,7 +104,7 @@ __global__ __launch_bounds__(256) void k_mol_reduce(MolAggArgs a) {
         if (a.mode == DMPNN_MOLAGG_MEAN && v1 > v0) y = y / cnt;
         if (a.mode == DMPNN_MOLAGG_NORM) y = y / a.norm;
         if (flag) y = __int_as_float(0x7fc00000);
-        if (c + t < a.h) a.out[m * a.ldo + c + t] = y;
+        if (c + t < a.h) out[c + t] = y;
     }
 }
 
@@ -113,6 +116,7 @@ struct MolBwdArgs {
     int64_t nV, n_mols;
     int h, mode;
     float norm;
+    int64_t rows;   // gout's rows: molecule m reads row m % rows, columns from (m / rows) h (MolAggArgs.rows)
 };
 
 __global__ __launch_bounds__(256) void k_mol_bwd(MolBwdArgs a) {
@@ -124,8 +128,10 @@ __global__ __launch_bounds__(256) void k_mol_bwd(MolBwdArgs a) {
     const bool ok = m >= 0 && m < a.n_mols;
     m = ok ? m : 0;
     const float cnt = (float)(a.ws[a.n_mols + m] - a.ws[m]);
+    const float* gout = a.gout + m * a.ldg;
+    if (a.rows != a.n_mols) gout = a.gout + (m % a.rows) * a.ldg + (m / a.rows) * a.h;
     for (int c = lane; c < a.h; c += 64) {
-        float g = a.gout[m * a.ldg + c];
+        float g = gout[c];
         if (a.mode == DMPNN_MOLAGG_MEAN) g = g / cnt;
         if (a.mode == DMPNN_MOLAGG_NORM) g = g / a.norm;
         if (flag || !ok) g = __int_as_float(0x7fc00000);
@@ -168,11 +174,26 @@ int dmpnn_molagg_bounds(const int64_t* batch, int64_t n_atoms, int64_t n_mols, v
 
 int dmpnn_molagg_fwd(const float* H, int64_t ldh, int64_t n_atoms, int64_t d_h, int64_t n_mols, const void* ws, int mode,
                      float norm, float* out, int64_t ldo, void* stream) {
+    return dmpnn::molagg_fwd_rows(H, ldh, n_atoms, d_h, n_mols, ws, mode, norm, out, ldo, n_mols, stream);
+}
+
+int dmpnn_molagg_bwd(const float* gout, int64_t ldg, const int64_t* batch, int64_t n_atoms, int64_t d_h, int64_t n_mols,
+                     const void* ws, int mode, float norm, float* gH, int64_t ldgh, void* stream) {
+    return dmpnn::molagg_bwd_rows(gout, ldg, batch, n_atoms, d_h, n_mols, ws, mode, norm, gH, ldgh, n_mols, stream);
+}
+
+}  // extern "C"
+
+namespace dmpnn {
+int molagg_fwd_rows(const float* H, int64_t ldh, int64_t n_atoms, int64_t d_h, int64_t n_mols, const void* ws, int mode,
+                    float norm, float* out, int64_t ldo, int64_t rows, void* stream) {
     DMPNN_CHECK_ARG(mode == DMPNN_MOLAGG_SUM || mode == DMPNN_MOLAGG_MEAN || mode == DMPNN_MOLAGG_NORM, "molagg_fwd: unknown mode %d", mode);
-    DMPNN_CHECK_ARG(d_h >= 0 && d_h < (1 << 24) && ldh >= d_h && ldo >= d_h, "molagg_fwd: bad row sizes");
+    if (rows <= 0 || rows > n_mols) rows = n_mols;
+    const int64_t ncol = rows > 0 ? (n_mols + rows - 1) / rows : 1;   // (column blocks of an output row)
+    DMPNN_CHECK_ARG(d_h >= 0 && d_h < (1 << 24) && ldh >= d_h && ldo >= d_h * ncol, "molagg_fwd: bad row sizes");
     if (n_mols == 0 || d_h == 0) return DMPNN_OK;
     DMPNN_CHECK_ARG(ws && out && (n_atoms == 0 || H), "molagg_fwd: NULL pointer");
-    MolAggArgs a{H, ldh, out, ldo, static_cast<const int*>(ws), n_mols, (int)d_h, mode, norm};
+    MolAggArgs a{H, ldh, out, ldo, static_cast<const int*>(ws), n_mols, (int)d_h, mode, norm, rows};
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool vec = d_h % 4 == 0 && ldh % 4 == 0 && aligned16(H);
     const int per_wave = vec ? 256 : 64;
@@ -184,19 +205,20 @@ int dmpnn_molagg_fwd(const float* H, int64_t ldh, int64_t n_atoms, int64_t d_h, 
     return DMPNN_OK;
 }
 
-int dmpnn_molagg_bwd(const float* gout, int64_t ldg, const int64_t* batch, int64_t n_atoms, int64_t d_h, int64_t n_mols,
-                     const void* ws, int mode, float norm, float* gH, int64_t ldgh, void* stream) {
+int molagg_bwd_rows(const float* gout, int64_t ldg, const int64_t* batch, int64_t n_atoms, int64_t d_h, int64_t n_mols,
+                    const void* ws, int mode, float norm, float* gH, int64_t ldgh, int64_t rows, void* stream) {
     DMPNN_CHECK_ARG(mode == DMPNN_MOLAGG_SUM || mode == DMPNN_MOLAGG_MEAN || mode == DMPNN_MOLAGG_NORM, "molagg_bwd: unknown mode %d", mode);
-    DMPNN_CHECK_ARG(d_h >= 0 && ldg >= d_h && ldgh >= d_h, "molagg_bwd: bad row sizes");
+    if (rows <= 0 || rows > n_mols) rows = n_mols;
+    const int64_t ncol = rows > 0 ? (n_mols + rows - 1) / rows : 1;
+    DMPNN_CHECK_ARG(d_h >= 0 && ldg >= d_h * ncol && ldgh >= d_h, "molagg_bwd: bad row sizes");
     if (n_atoms == 0 || d_h == 0) return DMPNN_OK;
     DMPNN_CHECK_ARG(n_mols > 0 && ws && gout && batch && gH, "molagg_bwd: NULL pointer / no molecules");
-    MolBwdArgs a{gout, ldg, batch, gH, ldgh, static_cast<const int*>(ws), n_atoms, n_mols, (int)d_h, mode, norm};
+    MolBwdArgs a{gout, ldg, batch, gH, ldgh, static_cast<const int*>(ws), n_atoms, n_mols, (int)d_h, mode, norm, rows};
     hipLaunchKernelGGL(k_mol_bwd, dim3((unsigned)((n_atoms + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     DMPNN_CHECK_LAUNCH("k_mol_bwd");
     return DMPNN_OK;
 }
-
-}  // extern "C"
+}  // namespace dmpnn
 
 // ---- generic row gather: out[i] = X[idx[i]] (f2, atom messages: M[e] = S[src(e)], mixins.py:30) ----------
 namespace dmpnn {

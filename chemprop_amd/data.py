@@ -222,3 +222,32 @@ class PackedBatch:
         if self.n_tiles >= 0:
             bmg.tiles = (sl("tile_row").view(torch.int32), sl("tile_atom").view(torch.int32), self.n_tiles)
         return bmg
+
+
+def merge_components(bmgs: Sequence["BatchMolGraph"]) -> "BatchMolGraph":
+    """The components of a multicomponent batch (``bmgs[c]`` holds molecule ``i`` of component ``c`` for every target row ``i``) as
+    ONE batch for a block shared by every component: V and E concatenated, ``edge_index`` / ``rev_edge_index`` offset by the atoms /
+    edges of the components in front, and the batch vector numbering molecule ``i`` of component ``c`` as ``c B + i`` (non-decreasing).
+    ``len()`` of the result is ``n B``; the head kernels fold it back into ``[B, n d_h]`` (``dmpnn_head_args.n_components``).
+    Every component must hold the same number of molecules ``B`` (``ValueError``) and share the feature widths."""
+    bmgs = list(bmgs)
+    if not bmgs:
+        raise ValueError("merge_components: no components")
+    B = len(bmgs[0])
+    if any(len(b) != B for b in bmgs):
+        raise ValueError(f"merge_components: every component must hold the same number of molecules, got {[len(b) for b in bmgs]}")
+    if any(b.V.shape[1:] != bmgs[0].V.shape[1:] or b.E.shape[1:] != bmgs[0].E.shape[1:] for b in bmgs):
+        raise ValueError("merge_components: components of one shared block must have the same atom / bond feature widths")
+    ei, rev, bt = [], [], []
+    a_off = e_off = 0
+    for c, b in enumerate(bmgs):
+        ei.append(b.edge_index + a_off)
+        rev.append(b.rev_edge_index + e_off)
+        bt.append(b.batch + c * B)
+        a_off += int(b.V.shape[0])
+        e_off += int(b.E.shape[0])
+    m = BatchMolGraph.from_tensors(torch.cat([b.V for b in bmgs]), torch.cat([b.E for b in bmgs]), torch.cat(ei, dim=1),
+                                   torch.cat(rev), torch.cat(bt).contiguous(), len(bmgs) * B)
+    ov = [getattr(b, "oversize", None) for b in bmgs]
+    m.oversize = True if any(o is True for o in ov) else (False if all(o is False for o in ov) else None)
+    return m

@@ -492,7 +492,7 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
             keep: bool = False, fused: Optional[bool] = None, route: Optional[str] = None,
             max_level: int = 2, mfma: Optional[str] = None, wcache: Optional[dict] = None,
             launch: bool = True, form: int = 0, dropout: Optional[tuple] = None, atom: bool = False,
-            keep_bits: bool = True) -> tuple[Tensor, ForwardState]:
+            keep_bits: bool = True, out: Optional[Tensor] = None) -> tuple[Tensor, ForwardState]:
     """One ``dmpnn_forward`` call.  Routes (``route`` = ``"mega" | "fused" | "general"``, default: the best
     the shapes allow):
 
@@ -514,6 +514,8 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
     the tile kernel with a ReLU-class activation and no ``W_d``; raises :class:`RouteUnavailable` when this batch takes another
     route (the caller then runs its own ``nn.Dropout`` between the row kernels).
     ``launch=False`` prepares the argument block and the workspace without enqueuing anything (``trainer.FusedTrainer``).
+    ``out``: the fp32 rows the output goes to (default: a new ``[n_atoms, d_h]`` tensor) — a multicomponent step hands every block
+    its rows of one ``H_v`` matrix.
     ``route`` is a demand (raises when the shapes do not allow it); ``max_level`` (0 general, 1 fused,
     2 mega) only caps the automatic choice.  ``fused=False`` is shorthand for ``route="general"``;
     ``fused=True`` demands at least ``fused``.
@@ -554,7 +556,12 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
         W_d, b_d = Wc(W_d, "W_d"), Wc(b_d, "b_d")
         a.W_d, a.b_d = _ptr(W_d), _ptr(b_d)
     a.ldh = ldh
-    out = torch.empty(nV, d_h + d_vd, dtype=torch.float32, device=dev)
+    if out is None:
+        out = torch.empty(nV, d_h + d_vd, dtype=torch.float32, device=dev)
+    elif (out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (nV, d_h + d_vd) or out.stride(1) != 1
+          or out.stride(0) % 4 or out.data_ptr() % 16):
+        # (out=: the rows of a bigger buffer — a multicomponent step writes every block's H_v into ONE [sum n_atoms, d_h] matrix)
+        raise ValueError(f"forward: out must be fp32 [{nV}, {d_h + d_vd}] on {dev}, unit column stride, 16-byte aligned rows")
     a.out, a.ldout = out.data_ptr(), out.stride(0)
 
     # ---- route.  The DEFAULT policy is ONE shape rule in the library (dmpnn_forward_route: the measured crossovers are its

@@ -382,8 +382,13 @@ def hip_mpnn_class():
             if opt is None:
                 # no Trainer, or a Trainer with an optimizer that is not ours: the reference's step (a loss with a graph; whoever
                 # drives the loop calls backward and steps) on the HIP kernels of the swapped blocks
-                return Ref.training_step(self, batch, batch_idx)
+                return super(HipMPNN, self).training_step(batch, batch_idx)
             bmg, V_d, X_d, targets, weights, lt_mask, gt_mask = batch
+            # a multicomponent batch (HipMulticomponentMPNN): the components' BatchMolGraphs and V_ds = [None, ...] (no atom descriptors)
+            multi = isinstance(bmg, (list, tuple))
+            if multi and V_d is not None and all(v is None for v in V_d):
+                V_d = None
+            n_batch = len(bmg[0]) if multi else len(bmg)
             st = opt._st()     # (the flat buffers of this device; a state dict loaded before they existed goes in now)
             self._hip_own_the_exchange(tr)
             self.__dict__["_hip_applied"] = False
@@ -415,17 +420,17 @@ def hip_mpnn_class():
                     from .model import criterion_kind, head_loss
 
                     bounded = criterion_kind(self.criterion)[1]
-                    loss = head_loss(self, self.message_passing(bmg, V_d), bmg.batch, len(bmg), targets, weights,
+                    loss = head_loss(self, self.message_passing(bmg, V_d), [b.batch for b in bmg] if multi else bmg.batch, n_batch, targets, weights,
                                      lt_mask if bounded else None, gt_mask if bounded else None,
                                      X_d=None if X_d is None else self.X_d_transform(X_d))
                 if loss is None:
-                    loss = Ref.training_step(self, batch, batch_idx)   # the reference's own arithmetic AND its own train_loss log
+                    loss = super(HipMPNN, self).training_step(batch, batch_idx)   # the reference's own arithmetic AND its own train_loss log
                     logged = True
                 st["route"] = "module"
             if not logged:
                 # (the reference logs the criterion Metric object — epoch value = sum L / sum mask; the batch's scalar weighted by the
                 #  batch size is the same number whenever no target is missing)
-                self.log("train_loss", loss.detach(), batch_size=len(bmg), prog_bar=True, on_epoch=True)
+                self.log("train_loss", loss.detach(), batch_size=n_batch, prog_bar=True, on_epoch=True)
             return loss
 
         def on_train_start(self) -> None:
@@ -470,9 +475,37 @@ def hip_mpnn_class():
     return _mpnn_cache
 
 
+_multi_cache = None
+
+
+def hip_multicomponent_mpnn_class():
+    """Build (once) ``class HipMulticomponentMPNN(HipMPNN, chemprop.models.MulticomponentMPNN)`` (``models/multi.py``): what ``HipMPNN``
+    does for a model of one block — ``training_step`` on the one-call step where :class:`chemprop_amd.model.FusedTrainer` takes the
+    model (a shared block or one bond block per component, all of one ``d_h``, no ``V_d`` per component, no dropout in the blocks),
+    ``configure_optimizers``, the gradient exchange, the hooks — by inheritance from ``HipMPNN`` (nothing restated); ``fingerprint``,
+    ``forward``, ``__init__`` and the checkpoint loaders resolve to the reference's multicomponent class, which follows ``HipMPNN`` in
+    the method order.  A batch is ``(bmgs, V_ds, X_d, targets, weights, lt_mask, gt_mask)``; ``V_ds = [None, ...]`` counts as none."""
+    global _multi_cache
+    if _multi_cache is not None:
+        return _multi_cache
+    try:
+        from chemprop.models.multi import MulticomponentMPNN as Ref  # noqa: WPS433
+    except Exception as e:  # pragma: no cover
+        raise ImportError("chemprop_amd.integration needs an importable `chemprop`") from e
+    HipMPNN = hip_mpnn_class()[1]
+
+    class HipMulticomponentMPNN(HipMPNN, Ref):  # type: ignore[misc, valid-type]
+        pass
+
+    _multi_cache = (Ref, HipMulticomponentMPNN)
+    return _multi_cache
+
+
 def __getattr__(name):
     if name == "HipMPNN":
         return hip_mpnn_class()[1]
+    if name == "HipMulticomponentMPNN":
+        return hip_multicomponent_mpnn_class()[1]
     if name == "HipMLP":
         return hip_mlp_class()[1]
     if name == "HipBondMessagePassing":
@@ -563,14 +596,14 @@ _enabled = None
 # modules of the reference that bind the classes BY NAME at import time (cli/train.py:60-68, :1500, :1598, :1623; models/utils.py:5;
 # cli/predict.py:34-35; cli/fingerprint.py:19) — rebinding the defining module alone would not reach them
 _BINDING_MODULES = ("chemprop.nn", "chemprop.nn.message_passing", "chemprop.nn.message_passing.base", "chemprop.nn.message_passing.mol_atom_bond",
-                    "chemprop.models", "chemprop.models.model", "chemprop.models.utils", "chemprop.cli.train", "chemprop.cli.predict",
+                    "chemprop.models", "chemprop.models.model", "chemprop.models.multi", "chemprop.models.utils", "chemprop.cli.train", "chemprop.cli.predict",
                     "chemprop.cli.fingerprint", "chemprop.cli.hpopt", "chemprop")
 
 
 def enable(fused_step: bool = True, verbose: bool = False) -> dict:
     """Make an installed chemprop build and load its models on the MI355X engine WITHOUT editing it (SURVEY §5 "Engine selection
     must not need a new CLI flag"): every place the reference binds ``BondMessagePassing`` / ``AtomMessagePassing`` /
-    ``MABBondMessagePassing`` / ``MABAtomMessagePassing`` (and, with ``fused_step``, ``MPNN``) by name — ``chemprop.nn``,
+    ``MABBondMessagePassing`` / ``MABAtomMessagePassing`` (and, with ``fused_step``, ``MPNN`` and ``MulticomponentMPNN``) by name — ``chemprop.nn``,
     ``chemprop.models``, ``chemprop.cli.train`` (``cli/train.py:60-68``: ``build_model`` at ``:1500,:1598,:1623``) ... — is rebound to
     the HIP subclass, and ``load_model`` / ``MPNN.load_from_file`` (``models/utils.py:27-35``, ``models/model.py:318-329``: predict /
     fingerprint) accelerate what they load.  Checkpoints keep naming the reference classes (``hparams["cls"]``), so they load in a
@@ -593,6 +626,11 @@ def enable(fused_step: bool = True, verbose: bool = False) -> dict:
     if fused_step:
         RefM, HipM = hip_mpnn_class()
         mapping[RefM] = HipM
+        try:   # (chemprop train --smiles-columns a b / --reaction-columns beside --smiles-columns: cli/train.py's build_model)
+            RefMC, HipMC = hip_multicomponent_mpnn_class()
+            mapping[RefMC] = HipMC
+        except ImportError:
+            pass
     for name in _BINDING_MODULES:           # (the CLI modules exist only in a full install; bind them if they import)
         if name not in sys.modules and name.startswith("chemprop.cli"):
             try:

@@ -25,11 +25,12 @@ from . import _lib, engine
 from .agg import MODES, Aggregation, NormAggregation, note_batch
 from .distributed import GradSync, force_collective
 from .ffn import MLP
-from .nn import BondMessagePassing, classify_activation
+from .nn import BondMessagePassing, MulticomponentMessagePassing, classify_activation
+from .data import merge_components
 from .optim import FlatAdam
 
 __all__ = ["MSE", "MAE", "BCE", "CE", "MVE", "Evidential", "Quantile", "RegressionFFN", "BinaryClassificationFFN", "MulticlassClassificationFFN", "MveFFN", "EvidentialFFN", "QuantileFFN",
-           "MPNN", "FusedTrainer", "masked_loss"]
+           "MPNN", "MulticomponentMPNN", "FusedTrainer", "masked_loss"]
 
 
 def masked_loss(preds: Tensor, targets: Tensor, weights: Optional[Tensor] = None, task_weights: Optional[Tensor] = None,
@@ -328,6 +329,57 @@ class MPNN(nn.Module):
                            float(getattr(c, "v_kl", 0.2)), float(getattr(c, "eps", 1e-8)), float(getattr(c, "alpha", 0.1)))
 
 
+class MulticomponentMPNN(MPNN):
+    """``chemprop.models.MulticomponentMPNN`` (``models/multi.py``): a :class:`~chemprop_amd.nn.MulticomponentMessagePassing` block,
+    the fingerprint ``cat([agg(H_v^c, bmg^c.batch) for c], 1)`` through the batch norm (``BatchNorm1d(sum of the blocks' widths)``),
+    then the descriptors.  ``fingerprint`` / ``forward`` / ``loss`` take a list of batches and a list of ``V_d`` (or ``None``); row
+    ``i`` of every component belongs to target row ``i``."""
+
+    def fingerprint(self, bmgs, V_ds=None, X_d: Optional[Tensor] = None) -> Tensor:
+        H_vs = self.message_passing(bmgs, V_ds)
+        H = self.bn(torch.cat([self.agg(H_v, bmg.batch) for H_v, bmg in zip(H_vs, bmgs)], 1))
+        return H if X_d is None else torch.cat((H, self.X_d_transform(X_d)), dim=1)
+
+    def forward(self, bmgs, V_ds=None, X_d: Optional[Tensor] = None) -> Tensor:
+        return self.predictor(self.fingerprint(bmgs, V_ds, X_d))
+
+    def loss(self, bmgs, targets: Tensor, weights: Optional[Tensor] = None, lt_mask: Optional[Tensor] = None,
+             gt_mask: Optional[Tensor] = None, V_ds=None, X_d: Optional[Tensor] = None) -> Tensor:
+        if torch.is_grad_enabled() and self.training:
+            # the module path: every block through its own autograd node, everything behind them as ONE more (head_loss on the
+            # blocks' outputs side by side)
+            B = len(bmgs[0])
+            if all(len(b) == B for b in bmgs):
+                l = head_loss(self, self.message_passing(bmgs, V_ds), [b.batch for b in bmgs], B, targets, weights, lt_mask, gt_mask,
+                              X_d=None if X_d is None else self.X_d_transform(X_d))
+                if l is not None:
+                    return l
+        preds = self.predictor.train_step(self.fingerprint(bmgs, V_ds, X_d))
+        c = self.criterion
+        return masked_loss(preds, targets, weights, getattr(c, "task_weights", None), lt_mask, gt_mask, getattr(c, "kind", "mse"),
+                           float(getattr(c, "v_kl", 0.2)), float(getattr(c, "eps", 1e-8)), float(getattr(c, "alpha", 0.1)))
+
+
+def fused_block(mp) -> tuple:
+    """``(activation, slope)`` of a block the one-call step takes: a bond block (this package's mirror, or the subclass of the
+    reference's own class, ``integration.HipBondMessagePassing``) with a built-in activation (not PReLU), directed, no ``V_d``, dropout 0
+    or ``nn.Dropout`` with a ReLU-class activation; ``NotImplementedError`` for anything else (it trains through the module path)."""
+    # (W_h is [d_h, d_h] in a bond block: the atom variant's takes d_e + d_h columns, the mol-atom-bond ones have a second read-out)
+    bond = (all(isinstance(getattr(mp, n, None), nn.Linear) for n in ("W_i", "W_h", "W_o"))
+            and mp.W_h.in_features == mp.W_h.out_features and mp.W_o.in_features > mp.W_h.out_features)
+    if not bond:
+        raise NotImplementedError("FusedTrainer: a BondMessagePassing block (W_i / W_h [d_h, d_h] / W_o)")
+    act, slope, slope_t = classify_activation(mp.tau)
+    if act in ("custom", "prelu") or mp.undirected or mp.W_d is not None:
+        raise NotImplementedError("FusedTrainer: built-in activation (not PReLU), directed, no V_d — other blocks train "
+                                  "through the module path (MPNN.loss + autograd)")
+    if mp.dropout.p > 0 and not (type(mp.dropout) is nn.Dropout and act in ("relu", "leakyrelu")):
+        # (active dropout lives inside the tile kernels for ReLU-class activations: dmpnn_fwd_args.dropout_p; a dropout module
+        #  that is not exactly nn.Dropout has its own semantics and stays on the module path)
+        raise NotImplementedError("FusedTrainer: dropout inside the block needs nn.Dropout and a ReLU / LeakyReLU activation")
+    return act, slope
+
+
 def _mro_names(obj) -> set:
     return {c.__name__ for c in type(obj).__mro__}
 
@@ -422,6 +474,18 @@ class HeadSpec:
         self.agg_mode, self.agg_norm = MODES[mode], float(getattr(agg, "norm", 1.0))
         self.f_act, self.f_slope, self.kind = f_act, f_slope, kind
         self.layers = [b[-1] for b in blocks]
+        # a multicomponent model (models/multi.py): the fingerprint is the components' aggregates side by side, ONE width per block
+        self.n_components, self.blocks = 1, None
+        mp = model.message_passing
+        if isinstance(getattr(mp, "blocks", None), nn.ModuleList) and hasattr(mp, "n_components"):
+            comp = list(mp.blocks)
+            for b in comp:
+                fused_block(b)
+            if len({int(b.output_dim) for b in comp}) != 1:
+                raise NotImplementedError("multicomponent blocks of one output width d_h")
+            if len(comp) > _lib.MAX_COMPONENTS:
+                raise NotImplementedError(f"at most {_lib.MAX_COMPONENTS} components")
+            self.n_components, self.blocks = len(comp), comp
         k0 = int(self.layers[0].in_features)
         self.d_xd = k0 - int(getattr(model.message_passing, "output_dim", k0))
         if self.d_xd < 0:
@@ -476,6 +540,8 @@ class HeadSpec:
         tensors that must stay alive until the call has been enqueued."""
         dev = T.device
         h.n_atoms, h.n_mols, h.d_h = nV, n_mols, d_out
+        if self.n_components > 1:   # (d_out: one block's width; `batch` numbers molecule i of component c as c n_mols + i)
+            h.n_components = self.n_components
         h.batch = batch.data_ptr()
         h.agg_mode, h.agg_norm = self.agg_mode, self.agg_norm
         bn = self.bn
@@ -488,10 +554,10 @@ class HeadSpec:
             if bn_training and nbt is not None and nbt.dtype == torch.int64 and nbt.device == dev:
                 h.bn_num_batches_tracked = nbt.data_ptr()  # (counted by the batch-norm kernel: no launch of its own)
         h.n_layers, h.act, h.act_slope = len(self.layers), _lib.ACT[self.f_act], float(self.f_slope)
-        h.dims[0] = d_out
+        h.dims[0] = self.n_components * d_out
         if X_d is not None:
             h.X_d, h.ld_xd = X_d.data_ptr(), X_d.stride(0)
-            h.dims[0] = d_out + self.d_xd
+            h.dims[0] = self.n_components * d_out + self.d_xd
         for l, lin in enumerate(self.layers):
             h.W[l], h.b[l] = lin.weight.data_ptr(), (None if lin.bias is None else lin.bias.data_ptr())
             h.dims[l + 1] = lin.out_features
@@ -532,7 +598,7 @@ class _HeadLoss(torch.autograd.Function):
         lib = _lib.load()
         dev = Hv.device
         Hv = engine._f32c(Hv, "H_v")
-        nV, d_out = int(Hv.shape[0]), int(Hv.shape[1])
+        nV, d_out = int(Hv.shape[0]), int(Hv.shape[1])   # (a multicomponent H_v: every component's rows, one block's width)
         # one flat buffer for the head's parameter gradients (16-byte aligned pieces) + gH_v
         offs, n = [], 0
         for p in params:
@@ -591,7 +657,18 @@ def head_loss(model, Hv: Tensor, batch: Tensor, n_mols: int, targets: Tensor, we
         except NotImplementedError as e:
             spec = str(e)
         model.__dict__["_dmpnn_head_spec"] = (key, spec)
-    if isinstance(spec, str) or Hv.device.type != "cuda" or Hv.dtype != torch.float32:
+    if isinstance(spec, str):
+        return None
+    if isinstance(Hv, (list, tuple)):
+        # a multicomponent model: the blocks' outputs as ONE H_v of every component's rows, the batch vectors as one that numbers
+        # molecule i of component c as c n_mols + i (torch ops: the module path; the fused step writes them in place)
+        if spec.n_components != len(Hv) or len(batch) != len(Hv) or any(b is None for b in batch):
+            return None
+        batch = torch.cat([b + c * n_mols for c, b in enumerate(batch)]) if len(Hv) > 1 else batch[0]
+        Hv = torch.cat(list(Hv)) if len(Hv) > 1 else Hv[0]
+    elif spec.n_components != 1:
+        return None
+    if Hv.device.type != "cuda" or Hv.dtype != torch.float32:
         return None
     if batch is None or batch.dtype != torch.int64 or not batch.is_contiguous() or batch.numel() != Hv.shape[0] or batch.device != Hv.device:
         return None
@@ -623,25 +700,23 @@ class FusedTrainer:
     def __init__(self, model: MPNN, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, group=None,
                  tile_plan: bool = True):
         mp, agg, pred = model.message_passing, model.agg, model.predictor
-        # a bond block: this package's mirror, or the subclass of the reference's own class (integration.HipBondMessagePassing):
-        # W_h is [d_h, d_h] there (the atom variant's takes d_e + d_h columns, the mol-atom-bond ones have a second read-out)
-        bond = (all(isinstance(getattr(mp, n, None), nn.Linear) for n in ("W_i", "W_h", "W_o"))
-                and mp.W_h.in_features == mp.W_h.out_features and mp.W_o.in_features > mp.W_h.out_features)
-        if not bond:
-            raise NotImplementedError("FusedTrainer: a BondMessagePassing block (W_i / W_h [d_h, d_h] / W_o)")
-        act, slope, slope_t = classify_activation(mp.tau)
-        if act in ("custom", "prelu") or mp.undirected or mp.W_d is not None:
-            raise NotImplementedError("FusedTrainer: built-in activation (not PReLU), directed, no V_d — other blocks train "
-                                      "through the module path (MPNN.loss + autograd)")
-        if mp.dropout.p > 0 and not (type(mp.dropout) is nn.Dropout and act in ("relu", "leakyrelu")):
-            # (active dropout lives inside the tile kernels for ReLU-class activations: dmpnn_fwd_args.dropout_p; a dropout module
-            #  that is not exactly nn.Dropout has its own semantics and stays on the module path)
-            raise NotImplementedError("FusedTrainer: dropout inside the block needs nn.Dropout and a ReLU / LeakyReLU activation")
+        # a multicomponent model: ONE block shared by every component (the components' graphs merged into one batch per step), or
+        # one block per component (each block's forward into its rows of one H_v, the head once, each block's backward)
+        multi = isinstance(getattr(mp, "blocks", None), nn.ModuleList) and hasattr(mp, "n_components")
+        self.blocks = list(mp.blocks) if multi else [mp]
+        self.shared = multi and all(b is self.blocks[0] for b in self.blocks)
+        self.n_components = len(self.blocks) if multi else 1
+        acts = [fused_block(b) for b in self.blocks]
+        if multi and any(b.dropout.p > 0 for b in self.blocks):
+            raise NotImplementedError("FusedTrainer: dropout inside the blocks of a multicomponent model")
         try:
             self.head = HeadSpec(model)
         except NotImplementedError as e:
             raise NotImplementedError(f"FusedTrainer: {e}") from None
-        self.model, self.mp = model, mp
+        self.model, self.mp = model, self.blocks[0]
+        self.multi = multi
+        act, slope = acts[0]
+        self.acts = acts
         self.act, self.slope = act, slope
         self.layers, self.bn, self.bounded = self.head.layers, self.head.bn, self.head.bounded
         params = [p for p in model.parameters() if p.requires_grad]
@@ -651,7 +726,7 @@ class FusedTrainer:
         self.dev = params[0].device
         self._views = {id(p): v for p, v in zip(self.sync.params, self.sync.views)}
         # the two slices of the flat gradient buffer a data-parallel step exchanges one after the other (see step())
-        blk = [p for p in mp.parameters() if p.requires_grad]
+        blk = [p for p in mp.parameters() if p.requires_grad]   # (every component's block: one contiguous run)
         blk_ids = {id(p) for p in blk}
         rest = [p for p in params if id(p) not in blk_ids]
         self._block_range = self.sync.range_of(blk) if blk else (0, 0)
@@ -673,32 +748,53 @@ class FusedTrainer:
 
     def step(self, bmg, targets: Tensor, weights: Optional[Tensor] = None, lt_mask: Optional[Tensor] = None,
              gt_mask: Optional[Tensor] = None, lr: Optional[float] = None, clip: Optional[tuple] = None,
-             X_d: Optional[Tensor] = None) -> Tensor:
+             X_d: Optional[Tensor] = None, V_ds=None) -> Tensor:
         """One optimisation step on ``(bmg, targets, ...)`` (a ``TrainingBatch`` without ``V_d``); returns the device
         tensor ``[loss, number of finite targets]`` of THIS step (no host sync).  ``model.train()`` semantics (batch norm uses
         and updates batch statistics).  ``clip = (value, "norm" | "value")``: Lightning's ``gradient_clip_val`` / ``_algorithm``
         (``cli/train.py:1937``), applied between the backward pass and the update inside the same call.  ``X_d``: the batch's
         molecule descriptors ``[n_mols, d_xd]`` for a model whose predictor takes them (``ValueError`` when they are missing,
-        unexpected or of the wrong shape); ``model.X_d_transform`` is applied to them here."""
-        from .nn import _VALIDATE_FIRST_N, _route, _training_plan_kind
+        unexpected or of the wrong shape); ``model.X_d_transform`` is applied to them here.
+
+        A :class:`MulticomponentMPNN`: ``bmg`` is the list of the components' batches, each of the same ``B`` molecules, and ``V_ds``
+        ``None`` or a list of ``None`` (``ValueError`` otherwise)."""
+        from .nn import _VALIDATE_FIRST_N
 
         lib = _lib.load()
-        mp, dev = self.mp, self.dev
-        engine._require_device(bmg.V, "bmg.V")
+        dev = self.dev
+        if self.multi:
+            bmgs = list(bmg)
+            if len(bmgs) != self.n_components:
+                raise ValueError(f"FusedTrainer.step: {self.n_components} component batches expected, got {len(bmgs)}")
+            if V_ds is not None and any(v is not None for v in V_ds):
+                raise ValueError("FusedTrainer.step: atom descriptors (V_ds) per component are not taken by the fused step")
+            if len({len(b) for b in bmgs}) != 1:
+                raise ValueError(f"FusedTrainer.step: every component must hold the same number of molecules, got {[len(b) for b in bmgs]}")
+            for b in bmgs:
+                engine._require_device(b.V, "bmg.V")
+            n_mols = len(bmgs[0])
+            # (shared: ONE batch of n B molecules, numbered c B + i — the head folds it back into [B, n d_h])
+            comps = [merge_components(bmgs)] if self.shared else bmgs
+            blocks = [self.mp] if self.shared else self.blocks
+        else:
+            if V_ds is not None:
+                raise ValueError("FusedTrainer.step: V_ds is for multicomponent models")
+            engine._require_device(bmg.V, "bmg.V")
+            comps, blocks, n_mols = [bmg], [self.mp], len(bmg)
         if not self.model.training:
             # (batch norm would update its running statistics while the block's dropout follows model.training: the two switches
             #  must not disagree — and a training step of a model in eval mode is a bug of the caller, not a mode)
             raise RuntimeError("FusedTrainer.step: the model is in eval mode — call model.train() first")
-        batch = bmg.batch
-        n_mols = len(bmg)
-        nV, nE = int(bmg.V.shape[0]), int(bmg.E.shape[0])
         n_tasks = self.head.n_tasks
         T = engine._f32c(targets, "targets")
         if T.dim() != 2 or T.shape[0] != n_mols or T.shape[1] != n_tasks or not T.is_contiguous():
             raise ValueError(f"targets must be a contiguous [{n_mols}, {n_tasks}] matrix, got {tuple(targets.shape)}")
         # the head kernels read these through raw pointers: a wrong dtype / size would be an out-of-bounds device read, not an error
-        if batch is None or batch.dtype != torch.int64 or not batch.is_contiguous() or batch.device != bmg.V.device or batch.numel() != nV:
-            raise ValueError(f"bmg.batch must be a contiguous int64 vector of {nV} molecule ids on {bmg.V.device}")
+        for cb in comps:
+            nV = int(cb.V.shape[0])
+            batch = cb.batch
+            if batch is None or batch.dtype != torch.int64 or not batch.is_contiguous() or batch.device != cb.V.device or batch.numel() != nV:
+                raise ValueError(f"bmg.batch must be a contiguous int64 vector of {nV} molecule ids on {cb.V.device}")
         if weights is not None and weights.numel() != n_mols:
             raise ValueError(f"weights must hold one value per molecule ({n_mols}), got {tuple(weights.shape)}")
         for name, m in (("lt_mask", lt_mask), ("gt_mask", gt_mask)):
@@ -714,85 +810,58 @@ class FusedTrainer:
         validate = _lib.opt("DMPNN_VALIDATE", "first") != "never" and self._checked < _VALIDATE_FIRST_N
         world = self._world()
         self.sync.wait()
-
-        # ---- K0: a launched plan while the first batches are validated (host read of the verdict), else inside the C call ----
-        # The kind of plan: once the first batches are validated (on full plans: their verdict on the graph invariants is read on
-        # the host), a batch bound for the tile kernels gets the TILE plan — K0 is then the 11 us tile table instead of the 28 us
-        # CSR plan, the kept tensors stay in the caller's edge order and the backward tile kernel reads the batch's own index
-        # arrays (DMPNN_F_TILE_PLAN; every tile checks itself, a molecule beyond the tile takes the kernels' generic path).
-        no_mega = getattr(mp, "_dmpnn_no_mega", False) or (n_mols > 0 and nE > 30 * n_mols)
-        oversize = getattr(bmg, "oversize", None)
-        if oversize is None and mp.dropout.p > 0 and not no_mega:
-            # (dropout lives inside the tile kernels only; their generic path for a molecule beyond the tile has none and answers NaN —
-            #  which this step would feed to Adam.  A foreign batch is counted on the device: nn.batch_oversize)
-            from .nn import batch_oversize
-
-            oversize = batch_oversize(bmg, n_mols)
-        level = 1 if (no_mega or oversize is True) else 2
-        # (ONE rule for "this training forward runs on the tile plan", the module path's: shapes of the tile kernel — d_h <= 320, even
-        #  d_v / d_e —, the environment switches, a plan the library can build; anything else keeps the full plan and the per-step routes)
-        kind = _training_plan_kind(mp, bmg) if (self.tile_plan and not validate and level == 2) else False
-        plan = engine.GraphPlan.from_bmg(bmg, light=kind, launch=validate)
-        plan.oversize = oversize
         if validate:
             self._checked += 1
-            level = _route(mp, plan, n_mols, batch)
-            if plan.oversize is True:
-                level = min(level, 1)
-        self._last_plan_tiles = bool(plan.tiles_only)
-        if plan.tiles_only and level < 2:  # (cannot happen: the tile plan was only asked for at level 2)
-            raise RuntimeError("FusedTrainer: a tile plan without the tile kernels")
-        note_batch(batch, n_mols)
-
-        # ---- argument blocks of the block's forward / backward (workspace allocated, nothing enqueued) ----
-        W = lambda lin, n: getattr(getattr(mp, lin), n)
-        drop = None
-        if mp.dropout.p > 0 and self.model.training:
-            # one seed per step from torch's CPU generator (torch.manual_seed fixes the run), like the module path's fused dropout
-            drop = (float(mp.dropout.p), int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
-            self.last_dropout_seed = drop[1]
-        try:
-            out, st = engine.forward(plan, bmg.V, bmg.E, W("W_i", "weight"), W("W_h", "weight"), W("W_o", "weight"), W("W_o", "bias"),
-                                     W("W_i", "bias"), W("W_h", "bias"), depth=mp.depth, act=self.act, slope=self.slope, keep=True,
-                                     max_level=level, launch=False, dropout=drop)
-        except engine.RouteUnavailable as e:
-            raise NotImplementedError(f"FusedTrainer: this batch does not take the tile kernels ({e}); dropout on the other routes "
-                                      "runs through the module path (MPNN.loss + autograd)") from None
-        self.last_route = st.route
+        # a multicomponent step with a block per component: every block writes its rows of ONE H_v and reads its rows of ONE gHv
+        nV_all = sum(int(cb.V.shape[0]) for cb in comps)
+        H_all = g_all = None
+        if len(comps) > 1:
+            d_blk = int(blocks[0].output_dim)
+            H_all = torch.empty(nV_all, d_blk, dtype=torch.float32, device=dev)
+            g_all = torch.empty(nV_all, d_blk, dtype=torch.float32, device=dev)
+        parts, row = [], 0
+        for ci, (mp, cb) in enumerate(zip(blocks, comps)):
+            nV_c = int(cb.V.shape[0])
+            parts.append(self._block_args(mp, cb, len(cb), self.acts[self.blocks.index(mp)], validate,
+                                          None if H_all is None else H_all[row:row + nV_c], None if g_all is None else g_all[row:row + nV_c]))
+            row += nV_c
+        self.last_route = parts[0]["route"] if len(parts) == 1 else tuple(p["route"] for p in parts)
+        self._last_plan_tiles = all(p["plan"].tiles_only for p in parts)
+        out, gout = (parts[0]["out"], parts[0]["gout"]) if H_all is None else (H_all, g_all)
         d_out = int(out.shape[1])
-        gout = torch.empty(nV, d_out, dtype=torch.float32, device=dev)
-        need, views = {}, {}
-        for k, (lin, n) in dict(W_i=("W_i", "weight"), b_i=("W_i", "bias"), W_h=("W_h", "weight"), b_h=("W_h", "bias"),
-                                W_o=("W_o", "weight"), b_o=("W_o", "bias")).items():
-            p = W(lin, n)
-            need[k] = p is not None and p.requires_grad
-            if need[k]:
-                views[k] = self._views[id(p)]
-        grads, b, keep_b = engine.backward(st, gout, need, out=views, launch=False)
-        for k, g in grads.items():  # (a view the engine did not take would silently drop the gradient)
-            if g is not None and g is not views.get(k):
-                raise RuntimeError(f"FusedTrainer: the gradient view of {k} was not accepted (dtype / layout)")
+        if self.multi and not self.shared:
+            batch = torch.cat([cb.batch + c * n_mols for c, cb in enumerate(comps)])   # (molecule i of component c: c B + i)
+        else:
+            batch = comps[0].batch
+        if self.multi:
+            note_batch(batch, self.n_components * n_mols)
 
         # ---- the head ----
         h = _lib.HeadArgs()
-        keep = [T, gout, keep_b, st, plan]
-        keep += self.head.fill(h, nV, n_mols, d_out, batch, T, weights, lt_mask, gt_mask, self._gv, X_d=Xd)
+        keep = [T, out, gout, batch, parts]
+        keep += self.head.fill(h, nV_all, n_mols, d_out, batch, T, weights, lt_mask, gt_mask, self._gv, X_d=Xd)
         bn = self.bn
         t = int(self.layers[-1].out_features)
         preds = torch.empty(n_mols, t, dtype=torch.float32, device=dev)
         loss = torch.empty(2, dtype=torch.float32, device=dev)
         h.preds, h.loss_out = preds.data_ptr(), loss.data_ptr()
-        h.gHv, h.ldg = gout.data_ptr(), d_out
+        h.gHv, h.ldg = gout.data_ptr(), gout.stride(0)
         nb = int(lib.dmpnn_head_ws_bytes(C.byref(h)))
         ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
         h.ws, h.ws_bytes = ws.data_ptr(), nb
 
         s = _lib.StepArgs()
-        s.edge_index, s.rev_edge_index = plan.edge_index.data_ptr(), plan.rev_edge_index.data_ptr()
-        bt = batch if (batch.dtype == torch.int64 and batch.is_contiguous()) else None
-        s.batch = None if bt is None else bt.data_ptr()
-        s.plan_bytes, s.plan_ready = plan.buf.numel() * 4, (1 if validate else 0)
-        s.bwd, s.head = b, h
+        p0 = parts[0]
+        s.edge_index, s.rev_edge_index, s.batch = p0["edge_index"], p0["rev_edge_index"], p0["batch"]
+        s.plan_bytes, s.plan_ready = p0["plan_bytes"], (1 if validate else 0)
+        s.bwd, s.head = p0["b"], h
+        if len(parts) > 1:
+            extra = (_lib.StepComponent * (len(parts) - 1))()
+            for e, pc in zip(extra, parts[1:]):
+                e.edge_index, e.rev_edge_index, e.batch = pc["edge_index"], pc["rev_edge_index"], pc["batch"]
+                e.plan_bytes, e.plan_ready, e.bwd = pc["plan_bytes"], (1 if validate else 0), pc["b"]
+            s.n_extra, s.extra = len(parts) - 1, C.cast(extra, C.POINTER(_lib.StepComponent))
+            keep.append(extra)
         opt = self.opt
         fused_update = world == 1 and not force_collective()   # (forced: the staged data-parallel step also on one rank)
         if fused_update:
@@ -819,6 +888,7 @@ class FusedTrainer:
                 s.stages = _lib.STEP_BACKWARD
                 _lib.check(lib.dmpnn_train_step(C.byref(s), engine._stream_ptr(dev)), "dmpnn_train_step(backward)")
                 self.sync.allreduce(*self._block_range)
+        del keep
         if bn is not None and not h.bn_num_batches_tracked and bn.num_batches_tracked is not None:
             bn.num_batches_tracked += 1
         self.preds = preds
@@ -829,3 +899,73 @@ class FusedTrainer:
         else:
             opt.step(lr, clip=None if (clip is None or clip[0] is None or not float(clip[0]) > 0) else (float(clip[0]), clip[1] or "norm"))
         return loss
+
+    def _block_args(self, mp, bmg, n_mols: int, act_slope: tuple, validate: bool, out: Optional[Tensor], gout: Optional[Tensor]) -> dict:
+        """K0's plan and the argument blocks of one block's forward / backward on ``bmg`` (workspace allocated, nothing enqueued but —
+        while the first batches are validated — the plan).  ``out`` / ``gout``: the block's rows of a multicomponent step's H_v / gHv
+        (``None``: allocated here)."""
+        from .nn import _route, _training_plan_kind
+
+        act, slope = act_slope
+        batch = bmg.batch
+        nV, nE = int(bmg.V.shape[0]), int(bmg.E.shape[0])
+        # ---- K0: a launched plan while the first batches are validated (host read of the verdict), else inside the C call ----
+        # The kind of plan: once the first batches are validated (on full plans: their verdict on the graph invariants is read on
+        # the host), a batch bound for the tile kernels gets the TILE plan — K0 is then the 11 us tile table instead of the 28 us
+        # CSR plan, the kept tensors stay in the caller's edge order and the backward tile kernel reads the batch's own index
+        # arrays (DMPNN_F_TILE_PLAN; every tile checks itself, a molecule beyond the tile takes the kernels' generic path).
+        no_mega = getattr(mp, "_dmpnn_no_mega", False) or (n_mols > 0 and nE > 30 * n_mols)
+        oversize = getattr(bmg, "oversize", None)
+        if oversize is None and mp.dropout.p > 0 and not no_mega:
+            # (dropout lives inside the tile kernels only; their generic path for a molecule beyond the tile has none and answers NaN —
+            #  which this step would feed to Adam.  A foreign batch is counted on the device: nn.batch_oversize)
+            from .nn import batch_oversize
+
+            oversize = batch_oversize(bmg, n_mols)
+        level = 1 if (no_mega or oversize is True) else 2
+        # (ONE rule for "this training forward runs on the tile plan", the module path's: shapes of the tile kernel — d_h <= 320, even
+        #  d_v / d_e —, the environment switches, a plan the library can build; anything else keeps the full plan and the per-step routes)
+        kind = _training_plan_kind(mp, bmg) if (self.tile_plan and not validate and level == 2) else False
+        plan = engine.GraphPlan.from_bmg(bmg, light=kind, launch=validate)
+        plan.oversize = oversize
+        if validate:
+            level = _route(mp, plan, n_mols, batch)
+            if plan.oversize is True:
+                level = min(level, 1)
+        if plan.tiles_only and level < 2:  # (cannot happen: the tile plan was only asked for at level 2)
+            raise RuntimeError("FusedTrainer: a tile plan without the tile kernels")
+        if not self.multi:
+            note_batch(batch, n_mols)
+
+        # ---- argument blocks of the block's forward / backward (workspace allocated, nothing enqueued) ----
+        W = lambda lin, n: getattr(getattr(mp, lin), n)
+        drop = None
+        if mp.dropout.p > 0 and self.model.training:
+            # one seed per step from torch's CPU generator (torch.manual_seed fixes the run), like the module path's fused dropout
+            drop = (float(mp.dropout.p), int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
+            self.last_dropout_seed = drop[1]
+        try:
+            out, st = engine.forward(plan, bmg.V, bmg.E, W("W_i", "weight"), W("W_h", "weight"), W("W_o", "weight"), W("W_o", "bias"),
+                                     W("W_i", "bias"), W("W_h", "bias"), depth=mp.depth, act=act, slope=slope, keep=True,
+                                     max_level=level, launch=False, dropout=drop, out=out)
+        except engine.RouteUnavailable as e:
+            raise NotImplementedError(f"FusedTrainer: this batch does not take the tile kernels ({e}); dropout on the other routes "
+                                      "runs through the module path (MPNN.loss + autograd)") from None
+        d_out = int(out.shape[1])
+        if gout is None:
+            gout = torch.empty(nV, d_out, dtype=torch.float32, device=self.dev)
+        need, views = {}, {}
+        for k, (lin, n) in dict(W_i=("W_i", "weight"), b_i=("W_i", "bias"), W_h=("W_h", "weight"), b_h=("W_h", "bias"),
+                                W_o=("W_o", "weight"), b_o=("W_o", "bias")).items():
+            p = W(lin, n)
+            need[k] = p is not None and p.requires_grad
+            if need[k]:
+                views[k] = self._views[id(p)]
+        grads, b, keep_b = engine.backward(st, gout, need, out=views, launch=False)
+        for k, g in grads.items():  # (a view the engine did not take would silently drop the gradient)
+            if g is not None and g is not views.get(k):
+                raise RuntimeError(f"FusedTrainer: the gradient view of {k} was not accepted (dtype / layout)")
+        bt = batch if (batch.dtype == torch.int64 and batch.is_contiguous()) else None
+        return dict(plan=plan, st=st, b=b, keep_b=keep_b, out=out, gout=gout, route=st.route, edge_index=plan.edge_index.data_ptr(),
+                    rev_edge_index=plan.rev_edge_index.data_ptr(), batch=None if bt is None else bt.data_ptr(), plan_bytes=plan.buf.numel() * 4,
+                    bmg=bmg)

@@ -657,3 +657,35 @@ def atom_message_passing_forward(mp, bmg, V_d: Optional[Tensor] = None) -> Tenso
     if has_vd:
         Hv = drop(linear_fn(Hv, mp.W_d.weight, mp.W_d.bias, A2=V_d))
     return Hv
+
+
+class MulticomponentMessagePassing(nn.Module):
+    """``chemprop.nn.MulticomponentMessagePassing`` (``nn/message_passing/multi.py``): one block per component, or — ``shared`` —
+    ``blocks[0]`` for every component (the same module ``n_components`` times in ``self.blocks``, so its parameters are listed once).
+    ``forward(bmgs, V_ds)`` is ``[block(bmg[, V_d]) for each component]``; ``output_dim`` the sum of the blocks' widths."""
+
+    def __init__(self, blocks, n_components: int, shared: bool = False):
+        super().__init__()
+        blocks = list(blocks)
+        self.hparams = _HParams(cls=self.__class__, blocks=[getattr(b, "hparams", None) for b in blocks], n_components=n_components,
+                                shared=shared)
+        if len(blocks) == 0:
+            raise ValueError("arg 'blocks' was empty!")
+        if not shared and len(blocks) != n_components:
+            raise ValueError(f"arg 'n_components' must be equal to `len(blocks)` if 'shared' is False! got: {n_components} and {len(blocks)}, "
+                             "respectively.")
+        self.n_components = n_components
+        self.shared = shared
+        self.blocks = nn.ModuleList([blocks[0]] * n_components if shared else blocks)
+
+    def __len__(self) -> int:
+        return len(self.blocks)
+
+    @property
+    def output_dim(self) -> int:
+        return sum(block.output_dim for block in self.blocks)
+
+    def forward(self, bmgs, V_ds=None) -> list:
+        if V_ds is None:
+            return [block(bmg) for block, bmg in zip(self.blocks, bmgs)]
+        return [block(bmg, V_d) for block, bmg, V_d in zip(self.blocks, bmgs, V_ds)]

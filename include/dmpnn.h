@@ -53,7 +53,8 @@ extern "C" {
  * 14 — round 6: DMPNN_LOSS_MVE / DMPNN_LOSS_EVIDENTIAL / DMPNN_LOSS_QUANTILE in dmpnn_head (evid_v_kl / evid_eps / quantile_alpha).
  * 15 — round 6: DMPNN_F_STORE16 also with DMPNN_F_MEGA (the whole-forward tile kernel on f16 operands: one MFMA pass, opt-in, not
  * fp32-class; it was DMPNN_EINVAL there).  Grown at its end, same version: dmpnn_head_args.X_d / ld_xd (molecule descriptors behind
- * the batch norm; the two fields are zero in a caller built before them, which is the NULL they default to). */
+ * the batch norm; the two fields are zero in a caller built before them, which is the NULL they default to); dmpnn_head_args.n_components
+ * and dmpnn_step_args.n_extra / extra (multicomponent models: zero in an older caller, which is one block). */
 #define DMPNN_ABI_VERSION 15
 
 enum dmpnn_status {
@@ -591,6 +592,7 @@ int dmpnn_clip_grad(float* g, int64_t n, float clip_val, int32_t mode, float gra
  * caller's business (an int64 buffer that does not enter the arithmetic with a fixed momentum).
  * ------------------------------------------------------------------------------------------- */
 #define DMPNN_MAX_FFN_LAYERS 8
+#define DMPNN_MAX_COMPONENTS 8             /* dmpnn_head_args.n_components: at most this many blocks side by side in the fingerprint */
 enum dmpnn_loss { DMPNN_LOSS_MSE = 0, DMPNN_LOSS_MAE = 1,
                   DMPNN_LOSS_BCE = 2, /* v12: binary cross entropy with logits (nn/metrics.py:292-295; predictors.py:235-247) */
                   DMPNN_LOSS_CE = 3,  /* v12: cross entropy over dmpnn_head_args.n_classes logits per task (nn/metrics.py:298-304;
@@ -635,6 +637,12 @@ typedef struct dmpnn_head_args {
     const float* X_d; int64_t ld_xd;        /* v15 growth: [n_mols, d_xd] molecule descriptors, row stride ld_xd >= d_xd, or NULL (none).
                                                d_xd = dims[0] - d_h: the predictor's input is cat(bn(agg(H_v)), X_d) (models/model.py,
                                                fingerprint) and W[0] is [dims[1], d_h + d_xd]; no gradient flows to X_d               */
+    int32_t n_components;                   /* v15 growth: 0 or 1 — one block; n > 1 — a multicomponent model (models/multi.py): H_v
+                                               holds the atoms of n B molecules (component 0's first), `batch` numbers molecule i of
+                                               component c as c B + i, n_mols = B (target rows); the fingerprint is
+                                               cat(agg(H_v^0), ..., agg(H_v^(n-1))) [B, n d_h] before batch norm (bn_* are n d_h long),
+                                               dims[0] = n d_h (+ d_xd); d_h stays one block's width and gHv [n_atoms, ldg] holds every
+                                               component's rows */
 } dmpnn_head_args;
 size_t dmpnn_head_ws_bytes(const dmpnn_head_args* h);
 int dmpnn_head(const dmpnn_head_args* h, const float* Hv, int64_t ldhv, void* stream);
@@ -649,6 +657,11 @@ enum dmpnn_step_stage {                     /* dmpnn_step_args.stages: which par
     DMPNN_STEP_BACKWARD = 2,                /* ... the block's backward pass runs                                             */
     DMPNN_STEP_UPDATE = 4                   /* the optimizer step                                                             */
 };
+typedef struct dmpnn_step_component {     /* a further block of a multicomponent model (one block per component): its batch */
+    const int64_t* edge_index; const int64_t* rev_edge_index; const int64_t* batch; size_t plan_bytes; int32_t plan_ready;
+    dmpnn_bwd_args bwd;                     /* bwd.f.out / bwd.gout: this component's rows of head's H_v / gHv (the rows after the
+                                               previous component's, same row stride); every block's d_h is head.d_h             */
+} dmpnn_step_component;
 typedef struct dmpnn_step_args {
     const int64_t* edge_index; const int64_t* rev_edge_index; const int64_t* batch; size_t plan_bytes; int32_t plan_ready;
     int32_t stages;
@@ -657,6 +670,10 @@ typedef struct dmpnn_step_args {
     float* p; const float* g; float* m; float* v; int64_t n_params;   /* flat parameter / gradient / moment buffers */
     float lr, beta1, beta2, eps, weight_decay, bias_corr1, sqrt_bias_corr2, grad_scale; const float* dev_scalars;
     float clip_val; int32_t clip_mode; float* clip_ws;   /* v12: clip_val > 0: dmpnn_clip_grad(g, ...) before the update (g is then written) */
+    int32_t n_extra; const dmpnn_step_component* extra;  /* v15 growth: a multicomponent model with head.n_components = 1 + n_extra blocks
+                                               (component 0 is the fields above); each block's K0 and forward, the head once on the
+                                               merged batch, each block's backward.  n_extra = 0 with head.n_components > 1: ONE shared
+                                               block over the merged batch (the components' graphs as one BatchMolGraph)             */
 } dmpnn_step_args;
 int dmpnn_train_step(const dmpnn_step_args* a, void* stream);
 
