@@ -956,15 +956,16 @@ __device__ __forceinline__ void tiles_bounds_block(const int64_t* __restrict__ e
     const int64_t em64 = i < nE ? batch[d] : 0, ep64 = (i > 0 && i <= nE && nE > 0) ? batch[dp] : -1;
     if (i < nV) {
         if (bm < 0 || bm >= nV) bad |= PLAN_RANGE_ERROR;   // at most one molecule per atom
+        // not non-decreasing: the ranges mean nothing.  On the RAW ids: clamped into [0, batch[nV-1]], [0,0,5,5,1,1] would read as sorted
+        if (bm < bp || bm > last) bad |= PLAN_NO_PIECE_TILES;
         const int m = clampm(bm), pm = i > 0 ? clampm(bp) : -1;
-        if (m < pm) bad |= PLAN_NO_PIECE_TILES;            // not non-decreasing: the ranges mean nothing
         for (int mm = pm + 1; mm <= m; ++mm) st_tagged(aoff, mm, S.tag, i);   // (empty unless i is a boundary; the boundary thread fills a gap of empty molecules)
     } else if (i == nV) {
         st_tagged(aoff, n_mols, S.tag, nV);
     }
     if (i < nE) {
+        if (em64 < ep64) bad |= PLAN_NO_PIECE_TILES;
         const int m = clampm(em64), pm = i > 0 ? clampm(ep64) : -1;
-        if (m < pm) bad |= PLAN_NO_PIECE_TILES;
         for (int mm = pm + 1; mm <= m; ++mm) st_tagged(eoff, mm, S.tag, i);
     } else if (i == nE) {
         const int pm = nE > 0 ? clampm(ep64) : -1;
@@ -1111,7 +1112,8 @@ int launch_prepare_tiles_batch(const int64_t* edge_index, const int64_t* batch, 
     if (did_split) *did_split = false;
     mega16::SplitArgs sp;
     {   // K0 over several workgroups (k_prepare_tiles_batch_multi), with or without the weight pre-split riding in the launch
-        static const bool multi_off = [] { const char* e = getenv("DMPNN_K0_SINGLE"); return e && atoi(e) != 0; }();
+        const char* k0e = getenv("DMPNN_K0_SINGLE");   // (read per launch, as DMPNN_HEAD: a test switches it inside one process)
+        const bool multi_off = k0e && atoi(k0e) != 0;
         MultiScratch S = multi_scratch(L, nV, nE);
         static std::atomic<unsigned> launch_no{0u};
         S.tag = kBoundsTag ^ (launch_no.fetch_add(1u, std::memory_order_relaxed) * 0x9E3779B1u);   // (never 0 twice in a row; a replayed graph node keeps its own)

@@ -16,28 +16,32 @@
 // The same tables as the single-workgroup kernels produce for small batches (blocked greedy packing; restated in
 // oracle/collate_numpy.py: blocked_molecule_tiles).  Scratch lives in the arrays of the plan a tile plan never fills
 // (src ... ident).  A molecule larger than a tile becomes a tile of its own (counted in DMPNN_HDR_NSPILL; the tile kernel
-// runs its generic path on it); more tiles than the launch bound, or a batch vector that is not
-// 0 .. n_mols-1 non-decreasing gives DMPNN_PLAN_NO_PIECE_TILES (the tile kernel then returns NaN); everything else a
-// wrong table could do is caught by the tile kernel's own closure check on the batch's index arrays.
+// runs its generic path on it); more tiles than the launch bound, a batch vector that is not 0 .. n_mols-1 non-decreasing
+// (raw ids: k_large_bounds reports one error word per workgroup, k_large_finish reads them all), or a destination atom
+// out of range gives DMPNN_PLAN_NO_PIECE_TILES (the tile kernel then returns NaN); everything else a wrong table could
+// do is caught by the tile kernel's own closure check on the batch's index arrays.
 #include "dmpnn_common.hpp"
 
 namespace dmpnn {
 namespace {
 
 struct LargeScratch {
-    int64_t aoff, eoff, bcnt, brow, batom, end;  // word offsets inside the plan
-    int nblk_max;
+    int64_t aoff, eoff, bcnt, brow, batom, err, end;  // word offsets inside the plan
+    int nblk_max, n_err;                               // n_err: workgroups of k_large_bounds (one error word each)
 };
 
-LargeScratch large_scratch(const PlanLayout& L, int64_t nV) {
+LargeScratch large_scratch(const PlanLayout& L, int64_t nV, int64_t nE) {
     LargeScratch S;
     S.nblk_max = (int)(nV / 64 + 1);
+    const int64_t nb = ((nV > nE ? nV : nE) + 1 + 255) / 256;   // (one thread per atom / edge)
+    S.n_err = (int)(nb > 2048 ? 2048 : nb);
     int64_t o = L.src;
     S.aoff = o; o += align4(nV + 2);
     S.eoff = o; o += align4(nV + 2);
     S.bcnt = o; o += align4(S.nblk_max + 1);
     S.brow = o; o += (int64_t)S.nblk_max * 64;
     S.batom = o; o += (int64_t)S.nblk_max * 64;
+    S.err = o; o += align4(S.n_err);
     S.end = o;
     return S;
 }
@@ -55,13 +59,20 @@ __device__ __forceinline__ int mol_count(const long long* __restrict__ batch, in
 // molecules, as long as the two kernels behind it together): an atom whose molecule differs from its predecessor's IS that
 // molecule's first atom; the same for an edge through the molecule of its destination atom.  Molecules without atoms / edges in
 // between (a single atom has no edge) take the offset of the next boundary: the boundary thread fills the gap.  For a batch
-// vector that is not non-decreasing some entries stay unwritten or contradict each other — k_large_blocks flags offsets that are
-// not monotone, and whatever table comes out of the rest is checked by the tile kernel itself (closure, ranges).
+// vector that is not non-decreasing some entries stay unwritten or contradict each other: every thread also compares the RAW
+// ids of its atom / edge with its predecessor's (clamped ids can read as sorted: [0,0,5,5,1,1] -> [0,0,1,1,1,1]) and checks the
+// ranges; the workgroup writes what it found to its error word (always written: no clearing between launches), k_large_finish
+// turns any of them into DMPNN_PLAN_NO_PIECE_TILES.
 __global__ __launch_bounds__(256) void k_large_bounds(const long long* __restrict__ batch, const long long* __restrict__ dst, int nV,
                                                       int nE, int* __restrict__ plan, LargeScratch S) {
+    __shared__ int bad_blk;
+    if (threadIdx.x == 0) bad_blk = 0;
+    __syncthreads();
+    const long long last = batch[nV - 1];
     const int n_mols = mol_count(batch, nV);
     int* aoff = plan + S.aoff;
     int* eoff = plan + S.eoff;
+    int bad = 0;
     auto mol_of_atom = [&](int v) -> long long {
         const long long m = batch[v];
         return m < 0 ? 0 : (m >= n_mols ? n_mols - 1 : m);
@@ -74,12 +85,20 @@ __global__ __launch_bounds__(256) void k_large_bounds(const long long* __restric
     const int stride = gridDim.x * blockDim.x;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i <= (nV > nE ? nV : nE); i += stride) {
         if (i < nV) {
+            const long long bm = batch[i];
+            if (bm < 0 || bm >= nV || bm > last || (i > 0 && bm < batch[i - 1])) bad = 1;
             const long long m = mol_of_atom(i), pm = i > 0 ? mol_of_atom(i - 1) : -1;
             for (long long mm = pm + 1; mm <= m; ++mm) aoff[mm] = i;   // (empty unless i is a boundary; one iteration for a dense batch vector)
         } else if (i == nV) {
             aoff[n_mols] = nV;
         }
         if (i < nE) {
+            const long long d = dst[i];
+            if (d < 0 || d >= nV) bad = 1;
+            else if (i > 0) {
+                const long long dp = dst[i - 1];   // (out of range: flagged by the thread of that edge)
+                if (dp >= 0 && dp < nV && batch[d] < batch[dp]) bad = 1;
+            }
             const long long m = mol_of_edge(i), pm = i > 0 ? mol_of_edge(i - 1) : -1;
             for (long long mm = pm + 1; mm <= m; ++mm) eoff[mm] = i;
         } else if (i == nE) {
@@ -87,6 +106,9 @@ __global__ __launch_bounds__(256) void k_large_bounds(const long long* __restric
             for (long long mm = pm + 1; mm <= n_mols; ++mm) eoff[mm] = nE;   // molecules behind the last edge (and the end marker)
         }
     }
+    if (bad) atomicOr(&bad_blk, 1);
+    __syncthreads();
+    if (threadIdx.x == 0) plan[S.err + blockIdx.x] = bad_blk;
 }
 
 __global__ __launch_bounds__(256) void k_large_blocks(const long long* __restrict__ batch, int nV, int* __restrict__ plan, LargeScratch S) {
@@ -143,6 +165,7 @@ __global__ __launch_bounds__(256) void k_large_finish(const long long* __restric
     const int slots = (int)L.max_mtiles + 2;
     // one pass over the block counts: rank of this wave's block, the total, the oversize bits
     int rank = 0, total = 0, nonmono = 0, n_spill = 0;
+    for (int b2 = lane; b2 < S.n_err; b2 += 64) nonmono |= plan[S.err + b2];   // (k_large_bounds: raw ids not sorted / out of range)
     for (int b2 = lane; b2 < nblk; b2 += 64) {
         const int c = bcnt[b2];
         nonmono |= c & kNonMono;
@@ -186,18 +209,16 @@ __global__ __launch_bounds__(256) void k_large_finish(const long long* __restric
 bool tiles_large_fits(int64_t nV, int64_t nE) {
     if (nV <= 0 || nV >= (1ll << 30) || nE >= (1ll << 30)) return false;
     const PlanLayout L = plan_layout(nV, nE);
-    return large_scratch(L, nV).end <= L.tile_row;  // the scratch fits the arrays a tile plan leaves unused
+    return large_scratch(L, nV, nE).end <= L.tile_row;  // the scratch fits the arrays a tile plan leaves unused
 }
 
 int launch_prepare_tiles_large(const int64_t* edge_index, const int64_t* batch, int64_t nV64, int64_t nE64, int* plan, hipStream_t s) {
     const int nV = (int)nV64, nE = (int)nE64;
     const PlanLayout L = plan_layout(nV, nE);
-    const LargeScratch S = large_scratch(L, nV);
+    const LargeScratch S = large_scratch(L, nV, nE);
     const long long* b = reinterpret_cast<const long long*>(batch);
     const long long* dst = reinterpret_cast<const long long*>(edge_index) + nE;
-    int blocks = ((nV > nE ? nV : nE) + 1 + 255) / 256;  // (one thread per atom / edge)
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(k_large_bounds, dim3((unsigned)blocks), dim3(256), 0, s, b, dst, nV, nE, plan, S);
+    hipLaunchKernelGGL(k_large_bounds, dim3((unsigned)S.n_err), dim3(256), 0, s, b, dst, nV, nE, plan, S);
     DMPNN_CHECK_LAUNCH("k_large_bounds");
     const unsigned wgs = (unsigned)((S.nblk_max + 3) / 4);
     hipLaunchKernelGGL(k_large_blocks, dim3(wgs), dim3(256), 0, s, b, nV, plan, S);

@@ -113,3 +113,81 @@ def full_plan_tiles_ok(src, dst, n_atoms: int, tile_row, tile_atom) -> bool:
     t_dst = np.clip(t_dst, 0, len(tile_atom) - 2)
     return bool(((src >= tile_atom[t_dst]) & (src < tile_atom[t_dst + 1])).all())
 
+
+
+# flag bits of the plan header word 0 (include/dmpnn.h, DMPNN_HDR_FLAGS) that the batch-vector planners write
+PLAN_RANGE_ERROR, PLAN_NO_PIECE_TILES, PLAN_TILES_ONLY = 2, 8, 16
+
+
+def batch_tile_plan(batch, dst, n_mols_out: int | None = None, max_mtiles: int | None = None, planner: str = "small"):
+    """What every batch-vector planner (K0: ``k_prepare_tiles_batch[_split]``, ``k_prepare_tiles_batch_multi`` — ``planner="small"``;
+    ``k_large_bounds / _blocks / _finish`` — ``planner="large"``) must produce from the int64 batch vector ``batch [nV]`` and the
+    destination row ``dst [nE]`` (``edge_index[1]``).
+
+    -> dict(valid, flags, flags_mask, n_tiles, n_spill, mtile_row, mtile_atom, bounds, bounds_mask):
+
+    * ``flags`` / ``flags_mask``: the header's flag word compares as ``hdr[0] & flags_mask == flags``.
+    * a VALID batch (ids in [0, nV), ``batch`` and ``batch[dst]`` non-decreasing, ``dst`` in [0, nV)): the flag word is
+      PLAN_TILES_ONLY; ``n_tiles`` (hdr[6]), ``n_spill`` (hdr[8]) and the tables of :func:`blocked_molecule_tiles` over the
+      per-molecule atom / edge counts of molecules 0 .. batch[-1] (ids without atoms in between are molecules without atoms;
+      ids behind batch[-1] are not planned), padded with the (nE, nV) sentinel to ``max_mtiles + 2`` slots when given.  An
+      oversize molecule is a tile of its own and every one of them is counted in ``n_spill`` (it always starts a tile).
+    * an INVALID batch: only the error bits are defined (``flags_mask``; PLAN_TILES_ONLY stays set), nothing else.  Both small planners set
+      PLAN_RANGE_ERROR for an id or a destination out of [0, nV) (PLAN_NO_PIECE_TILES is then undefined: what the clamped ids
+      look like differs between the kernels) and PLAN_NO_PIECE_TILES for ids that are in range but not sorted (``batch``, or
+      ``batch[dst]``: edges not in molecule order).  The large planner reports every one of these as PLAN_NO_PIECE_TILES and
+      never sets PLAN_RANGE_ERROR (its header carries only that bit; a full plan built around it keeps only that bit).
+    * ``bounds`` (``n_mols_out`` given): the per-molecule aggregation's table ``first[n] | end[n] | flag`` of the small planners —
+      empty ranges for ids without atoms and for molecules behind batch[-1]; flag bit 0: an id or destination out of range, or
+      batch[-1] >= n_mols_out; bit 1: not sorted (undefined next to a range error).  ``bounds_mask`` as ``flags_mask`` (an
+      invalid batch defines the flag word only: ``bounds`` and ``bounds_mask`` then have that one entry).
+    """
+    batch = np.asarray(batch, dtype=np.int64).reshape(-1)
+    dst = np.asarray(dst, dtype=np.int64).reshape(-1)
+    nV, nE = len(batch), len(dst)
+    assert nV > 0 and planner in ("small", "large")
+    range_err = bool((batch < 0).any() or (batch >= nV).any() or (dst < 0).any() or (dst >= nV).any())
+    unsorted = False
+    if not range_err:
+        unsorted = bool((np.diff(batch) < 0).any() or (np.diff(batch[dst]) < 0).any())
+    out = dict(valid=not (range_err or unsorted))
+    if planner == "large":
+        out["flags"] = (PLAN_NO_PIECE_TILES if (range_err or unsorted) else 0) | PLAN_TILES_ONLY
+        out["flags_mask"] = PLAN_RANGE_ERROR | PLAN_NO_PIECE_TILES | PLAN_TILES_ONLY
+    elif range_err:
+        out["flags"], out["flags_mask"] = PLAN_RANGE_ERROR, PLAN_RANGE_ERROR
+    else:
+        out["flags"] = (PLAN_NO_PIECE_TILES if unsorted else 0) | PLAN_TILES_ONLY
+        out["flags_mask"] = PLAN_RANGE_ERROR | PLAN_NO_PIECE_TILES | PLAN_TILES_ONLY
+    if n_mols_out is not None:
+        n = int(n_mols_out)
+        if range_err:
+            out["bounds"], out["bounds_mask"] = np.array([1], dtype=np.int32), np.array([1], dtype=np.int32)
+        elif unsorted:
+            out["bounds"] = np.array([2 | (1 if int(batch[-1]) + 1 > n else 0)], dtype=np.int32)
+            out["bounds_mask"] = np.array([3], dtype=np.int32)
+    if not out["valid"]:
+        return out
+    nm = int(batch[-1]) + 1
+    n_atoms = np.bincount(batch, minlength=nm)
+    n_edges = np.bincount(batch[dst], minlength=nm) if nE else np.zeros(nm, dtype=np.int64)
+    tr, ta = blocked_molecule_tiles(n_atoms, n_edges)
+    n_tiles = len(tr) - 1
+    out["n_tiles"] = n_tiles
+    out["n_spill"] = int(((n_atoms > 32) | (n_edges > 48)).sum())
+    if max_mtiles is not None:
+        slots = int(max_mtiles) + 2
+        assert n_tiles <= int(max_mtiles)
+        out["mtile_row"] = np.concatenate([tr, np.full(slots - n_tiles - 1, nE, dtype=np.int32)])
+        out["mtile_atom"] = np.concatenate([ta, np.full(slots - n_tiles - 1, nV, dtype=np.int32)])
+    else:
+        out["mtile_row"], out["mtile_atom"] = tr, ta
+    if n_mols_out is not None:
+        ao = np.concatenate([[0], np.cumsum(n_atoms)])
+        first = np.full(n, nV, dtype=np.int64)
+        end = np.full(n, nV, dtype=np.int64)
+        k = min(n, nm)
+        first[:k], end[:k] = ao[:k], ao[1:k + 1]
+        out["bounds"] = np.concatenate([first, end, [1 if nm > n else 0]]).astype(np.int32)
+        out["bounds_mask"] = np.full(2 * n + 1, -1, dtype=np.int32)
+    return out

@@ -421,6 +421,84 @@ def test_pack_tiles_properties():
     prop()
 
 
+def test_batch_tile_plan_statement_properties():
+    """oracle.collate_numpy.batch_tile_plan (what every batch-vector planner must write) over arbitrary molecule-size sequences —
+    ids without atoms in between and at the end, oversize molecules, lone atoms: the tables are the blocked packing of the
+    molecules' own counts (the greedy one where no block boundary or empty molecule intervenes), every tile boundary is a molecule
+    boundary, and the bounds table is the reference's segment of every molecule (agg_torch's scatter over ``batch``)."""
+    from hypothesis import given, settings
+    from hypothesis import strategies as st
+
+    from oracle import agg_torch, collate_numpy as oc
+
+    sizes = st.lists(st.tuples(st.integers(0, 36), st.integers(0, 56)), min_size=1, max_size=200)
+
+    @settings(max_examples=300, deadline=None)
+    @given(sizes, st.integers(0, 3), st.integers(0, 2 ** 31 - 1))
+    def prop(mols, extra, seed):
+        n_at = [a for a, _ in mols]
+        n_ed = [2 * (e // 2) if a >= 2 else 0 for a, e in mols]
+        if sum(n_at) == 0:
+            return
+        rng = np.random.default_rng(seed)
+        batch = np.repeat(np.arange(len(mols)), n_at).astype(np.int64)
+        ao = np.concatenate([[0], np.cumsum(n_at)]).astype(np.int64)
+        dst = np.concatenate([rng.integers(ao[m], ao[m + 1], n_ed[m]) for m in range(len(mols)) if n_ed[m]] or [np.zeros(0, np.int64)])
+        nm = int(batch[-1]) + 1   # (molecules without atoms behind the last atom are not in the batch vector)
+        n_out = len(mols) + extra
+        L = 2 * (len(dst) // 48 + len(batch) // 32) + 4 + len(batch) // 64 + 1   # (the plan's slot count, dmpnn_common.hpp)
+        got = oc.batch_tile_plan(batch, dst, n_mols_out=n_out, max_mtiles=L)
+        assert got["valid"] and got["flags"] == oc.PLAN_TILES_ONLY
+        tr, ta = oc.blocked_molecule_tiles(n_at[:nm], n_ed[:nm])
+        n = got["n_tiles"]
+        assert n == len(tr) - 1 and len(got["mtile_row"]) == L + 2
+        assert np.array_equal(got["mtile_row"][:n + 1], tr) and np.array_equal(got["mtile_atom"][:n + 1], ta)
+        assert (got["mtile_row"][n:] == len(dst)).all() and (got["mtile_atom"][n:] == len(batch)).all()
+        assert got["n_spill"] == sum(1 for a, e in zip(n_at[:nm], n_ed[:nm]) if a > 32 or e > 48)
+        if nm <= 64 and min(n_at[:nm]) > 0:
+            g = oc.greedy_molecule_tiles(n_at[:nm], n_ed[:nm])
+            assert np.array_equal(g[0], tr) and np.array_equal(g[1], ta)
+        starts = set(ao[:nm + 1].tolist())
+        assert all(int(a) in starts for a in ta)
+        # the bounds table: rows [first[m], end[m]) are exactly the atoms of molecule m; segment sums = the reference's scatter
+        b = got["bounds"]
+        first, end, flag = b[:n_out], b[n_out:2 * n_out], b[2 * n_out]
+        assert flag == 0 and (end >= first).all()
+        for m in range(n_out):
+            assert np.array_equal(np.arange(first[m], end[m]), np.flatnonzero(batch == m)), m
+        H = torch.from_numpy(rng.standard_normal((len(batch), 3)))
+        want = agg_torch.sum_(H, torch.from_numpy(batch))
+        seg = torch.stack([H[first[m]:end[m]].sum(0) for m in range(nm)])
+        assert torch.allclose(seg, want, rtol=1e-12, atol=1e-12)   # (float64; the summation orders differ)
+        # a caller count below the batch vector's: the tables stand, the bounds flag says "range"
+        if nm > 1:
+            assert oc.batch_tile_plan(batch, dst, n_mols_out=nm - 1)["bounds"][-1] == 1
+
+    prop()
+
+
+def test_batch_tile_plan_statement_on_invalid_batches():
+    """Only the error bits of an invalid batch are defined — per planner (the large planner reports everything as 'no tiles')."""
+    from oracle import collate_numpy as oc
+
+    batch = np.array([0, 0, 1, 1, 2, 2], dtype=np.int64)
+    dst = np.array([1, 0, 3, 2, 5, 4], dtype=np.int64)
+    for b, d, small, bflag in (
+        ([0, 0, 5, 5, 1, 1], dst, oc.PLAN_NO_PIECE_TILES, 2),    # the decrease after an id beyond batch[-1]
+        ([0, 0, 2, 2, 1, 1], dst, oc.PLAN_NO_PIECE_TILES, 2),    # a decrease, every id < nV
+        ([0, 0, -1, 1, 2, 2], dst, oc.PLAN_RANGE_ERROR, 1),      # a negative id
+        ([0, 0, 1, 1, 9, 9], dst, oc.PLAN_RANGE_ERROR, 1),       # an id >= nV
+        (batch, [1, 0, 3, 2, 6, 4], oc.PLAN_RANGE_ERROR, 1),     # a destination out of range
+        (batch, [3, 2, 1, 0, 5, 4], oc.PLAN_NO_PIECE_TILES, 2),  # sorted atoms, edges not in molecule order
+    ):
+        s = oc.batch_tile_plan(b, d, n_mols_out=3)
+        assert not s["valid"] and (s["flags"] & (oc.PLAN_RANGE_ERROR | oc.PLAN_NO_PIECE_TILES)) == small and (s["flags_mask"] & small)
+        assert (s["bounds"][0] & s["bounds_mask"][0]) == bflag
+        lg = oc.batch_tile_plan(b, d, planner="large")
+        assert lg["flags"] == oc.PLAN_NO_PIECE_TILES | oc.PLAN_TILES_ONLY and lg["flags_mask"] & oc.PLAN_RANGE_ERROR
+    assert oc.batch_tile_plan(batch, dst)["valid"]
+
+
 def test_packed_batch_roundtrip_properties():
     """Random molecule lists (including empty molecules and lone atoms): wire bytes -> oracle decode == reference batching."""
     from hypothesis import given, settings
