@@ -110,6 +110,7 @@ class BwdArgs(C.Structure):
 
 MAX_FFN_LAYERS = 8
 MAX_COMPONENTS = 8   # (DMPNN_MAX_COMPONENTS: blocks side by side in one fingerprint)
+DROP_SITE_FFN = 0x10000   # (DMPNN_DROP_SITE_FFN: the predictor's dropout sites are DROP_SITE_FFN + layer)
 LOSS = {"mse": 0, "mae": 1, "bce": 2, "ce": 3, "mve": 4, "evidential": 5, "quantile": 6}
 STEP_FORWARD, STEP_BACKWARD, STEP_UPDATE = 1, 2, 4
 
@@ -134,6 +135,7 @@ class HeadArgs(C.Structure):
         ("evid_v_kl", C.c_float), ("evid_eps", C.c_float), ("quantile_alpha", C.c_float),
         ("X_d", C.c_void_p), ("ld_xd", C.c_int64),
         ("n_components", C.c_int32),
+        ("ffn_dropout_p", C.c_float), ("ffn_dropout_seed", C.c_uint64),
     ]
 
 

@@ -21,6 +21,44 @@ namespace {
 
 inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
 
+// ---- the predictor's dropout (dmpnn_head_args.ffn_dropout_p): the mask of layer l's input, regenerated wherever it is needed ----------
+// Element (r, c) of an input N columns wide is kept when drop_hash(seed, DMPNN_DROP_SITE_FFN + l, r nblk + c / 1024, c % 1024) >= thr,
+// nblk = ceil(N / 1024): the hash keys on row * 1024 + col, so a row wider than 1024 takes nblk consecutive hash rows.  on == 0: no mask.
+struct FfnDrop {
+    unsigned lo, hi, site, thr, nblk;
+    float scale, unscale;                  // 1 / (1 - p), 1 - p
+    int on;
+    __device__ __forceinline__ bool keep(int64_t r, int c) const {
+        return drop_hash(lo, hi, site, (unsigned)r * nblk + ((unsigned)c >> 10), (unsigned)c & 1023u) >= thr;
+    }
+    // d(layer input) / d(pre-activation) at an element whose masked value is x = mask tau(pre) scale: scale tau'(pre) where kept, 0 where
+    // dropped.  ReLU class: tau' from the sign of x; tanh / ELU: from tau(pre) = x (1 - p)
+    __device__ __forceinline__ float act_grad(int64_t r, int c, float x, int act, float slope) const {
+        const bool smooth = act == DMPNN_ACT_TANH || act == DMPNN_ACT_ELU;
+        return keep(r, c) ? scale * act_grad_from_out(smooth ? x * unscale : x, act, slope) : 0.f;
+    }
+};
+FfnDrop ffn_drop(const dmpnn_head_args& h, int l) {
+    FfnDrop d;
+    memset(&d, 0, sizeof(d));
+    if (!(h.ffn_dropout_p > 0.f) || l < 1 || l >= h.n_layers) return d;
+    d.lo = (unsigned)(h.ffn_dropout_seed & 0xFFFFFFFFull); d.hi = (unsigned)(h.ffn_dropout_seed >> 32);
+    d.site = (unsigned)(DMPNN_DROP_SITE_FFN + l); d.thr = drop_threshold(h.ffn_dropout_p);
+    d.nblk = (unsigned)((h.dims[l] + 1023) / 1024);
+    d.scale = 1.f / (1.f - h.ffn_dropout_p); d.unscale = 1.f - h.ffn_dropout_p;
+    d.on = 1;
+    return d;
+}
+// the chain form's mask: X [rows, cols] (row stride ldx) *= mask scale in place, behind the contraction whose epilogue applied tau
+// (a product, not a select: a NaN stays NaN where dropped, as under nn.Dropout)
+__global__ void k_ffn_drop(float* __restrict__ X, int64_t ldx, int64_t rows, int cols, FfnDrop d) {
+    const int64_t n = rows * cols;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / cols; const int c = (int)(i - r * cols);
+        X[r * ldx + c] *= d.keep(r, c) ? d.scale : 0.f;
+    }
+}
+
 // ---- BatchNorm1d over the rows of X [B, d] -------------------------------------------------------------------------
 // One workgroup of 1024 threads per 16 columns: 64 row lanes per column, so a thread walks B / 64 rows (8 at 512 molecules;
 // the first version — 4 row lanes, 128 dependent iterations per pass — took 65 us for 0.6 MB).  Two passes over the rows for
@@ -363,6 +401,7 @@ __global__ __launch_bounds__(256) void k_out_fwd(OutFwdArgs a) {
 struct OutBwdArgs {
     const float* gP; const float* A; int64_t lda; const float* W; float* gA; int64_t ldga; float* gW; float* gb;
     int64_t B; int K, t, act; float slope;
+    FfnDrop drop;                          // the mask of A (the layer's input; off for the first layer)
 };
 __global__ __launch_bounds__(1024) void k_out_bwd(OutBwdArgs a) {
     __shared__ float red[kBnLanes][kBnCols];
@@ -378,7 +417,7 @@ __global__ __launch_bounds__(1024) void k_out_bwd(OutBwdArgs a) {
 #pragma unroll
         for (int j = 0; j < kOutMaxTasks; ++j)
             if (j < a.t) { const float gp = a.gP[r * a.t + j]; g += gp * w[j]; gw[j] += gp * x; gbs[j] += gp; }
-        if (ok && a.gA) a.gA[r * a.ldga + k] = g * act_grad_from_out(x, a.act, a.slope);
+        if (ok && a.gA) a.gA[r * a.ldga + k] = g * (a.drop.on ? a.drop.act_grad(r, k, x, a.act, a.slope) : act_grad_from_out(x, a.act, a.slope));
     }
     for (int j = 0; j < a.t; ++j) {
         const float sw = bn_col_sum(red, tx, ty, gw[j]);
@@ -463,7 +502,7 @@ __global__ __launch_bounds__(1024) void k_out_all(OutAllArgs q) {
 #pragma unroll
         for (int j = 0; j < kOutMaxTasks; ++j)
             if (j < t) { const float gp = gPs[r * t + j]; g += gp * w[j]; gw[j] += gp * x; gbs[j] += gp; }
-        if (ok && a.gA) a.gA[r * a.ldga + k] = g * act_grad_from_out(x, a.act, a.slope);
+        if (ok && a.gA) a.gA[r * a.ldga + k] = g * (a.drop.on ? a.drop.act_grad(r, k, x, a.act, a.slope) : act_grad_from_out(x, a.act, a.slope));
     }
     for (int j = 0; j < t; ++j) {
         const float sw = bn_col_sum(red, tx, ty, gw[j]);
@@ -931,6 +970,7 @@ struct RowsArgs {
     int64_t B; int N, K, t, act; float slope;
     long long* dbg;                        // optional cycle stamps of workgroup (1, 1)
     int Kg;                                // columns of dl/dZ formed: K, or d_h with molecule descriptors (Z's first d_h columns)
+    FfnDrop drop;                          // the predictor's dropout on A1 (the output layer's input)
 };
 // The predictor + criterion + their backward as TWO launches over (row block of 16 molecules) x (slice of 64 columns):
 //   PH 1  A1[:, slice] = tau(Z W0^T + b0)                                                          160 workgroups at 512 x 300
@@ -1040,7 +1080,8 @@ __global__ __launch_bounds__(256) void k_head_rows(RowsArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int i = 4 * lg + r;
-            if (col < a.N && i < nrows) a.A1[(row0 + i) * a.N + col] = apply_act_small(acc[r] * (isw * inv_s[i]) + bv, a.act, a.slope);
+            const float y = apply_act_small(acc[r] * (isw * inv_s[i]) + bv, a.act, a.slope);   // (dropout: A1 = mask tau / (1 - p))
+            if (col < a.N && i < nrows) a.A1[(row0 + i) * a.N + col] = a.drop.on ? y * (a.drop.keep(row0 + i, col) ? a.drop.scale : 0.f) : y;
         }
         stamp();  // 3 end
         return;
@@ -1142,6 +1183,7 @@ __global__ __launch_bounds__(256) void k_head_rows(RowsArgs a) {
         stamp();  // 3 criterion
         // ---- the output layer's backward on this row block: thread = column n of A1 (all of them: the operand of the contraction below) ----
         //   dl/dA1[i][n] = (sum_j gP[i][j] W1[j][n]) tau'(A1[i][n]),  partial gW1[j][n] = sum_i gP[i][j] A1[i][n],  partial gb1[j] = sum_i gP[i][j]
+        // (with the predictor's dropout A1 is the masked output and the factor is mask / (1 - p) tau': FfnDrop::act_grad)
         // what leaves for memory is the slice's: columns [64 cs, 64 cs + 64)
         // (the 16 rows of a column in registers, dl/dP as 16-byte rows: straight-line code — a loop with the activation's switch inside
         //  waited for every LDS round trip, 6 us)
@@ -1166,7 +1208,8 @@ __global__ __launch_bounds__(256) void k_head_rows(RowsArgs a) {
                 const float4 gp = gp4[i];   // (columns beyond t are zero)
                 const float g = ((gp.x * w1.x + gp.y * w1.y) + gp.z * w1.z) + gp.w * w1.w;
                 gw.x += gp.x * xv[i]; gw.y += gp.y * xv[i]; gw.z += gp.z * xv[i]; gw.w += gp.w * xv[i];
-                const float dv = simple_act ? (xv[i] > 0.f ? 1.f : neg) : act_grad_from_out(xv[i], a.act, a.slope);
+                float dv = simple_act ? (xv[i] > 0.f ? 1.f : neg) : act_grad_from_out(a.drop.on ? xv[i] * a.drop.unscale : xv[i], a.act, a.slope);
+                if (a.drop.on) dv *= a.drop.keep(row0 + i, n) ? a.drop.scale : 0.f;
                 gv[i] = okn ? g * dv : 0.f;
             }
 #pragma unroll
@@ -1218,13 +1261,15 @@ __global__ void k_head_transpose(const float* __restrict__ in, int64_t ldi, floa
         if (c < cols && r < rows) out[(int64_t)c * ldo + r] = tile[threadIdx.x][j];
     }
 }
-// g[r][c] *= tau'(Y[r][c])   (Y = the activated output the next layer consumed)
+// g[r][c] *= tau'(Y[r][c])   (Y = the activated output the next layer consumed; with the predictor's dropout Y is masked and the factor
+// is FfnDrop::act_grad)
 __global__ void k_head_act_bwd(float* __restrict__ g, int64_t ldg, const float* __restrict__ Y, int64_t ldy, int64_t rows, int cols,
-                               int act, float slope) {
+                               int act, float slope, FfnDrop drop) {
     const int64_t n = rows * cols;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r = i / cols; const int c = (int)(i - r * cols);
-        g[r * ldg + c] *= act_grad_from_out(Y[r * ldy + c], act, slope);
+        const float y = Y[r * ldy + c];
+        g[r * ldg + c] *= drop.on ? drop.act_grad(r, c, y, act, slope) : act_grad_from_out(y, act, slope);
     }
 }
 
@@ -1356,6 +1401,7 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     hipStream_t s = static_cast<hipStream_t>(stream);
     DMPNN_CHECK_ARG(h.n_components >= 0 && h.n_components <= DMPNN_MAX_COMPONENTS, "head: n_components (%d) outside 0..%d", (int)h.n_components,
                     DMPNN_MAX_COMPONENTS);
+    DMPNN_CHECK_ARG(h.ffn_dropout_p >= 0.f && h.ffn_dropout_p < 1.f, "head: ffn_dropout_p (%g) outside [0, 1)", (double)h.ffn_dropout_p);
     // a multicomponent fingerprint: ncomp blocks of dc columns each, side by side (d = ncomp dc); the table of molecule bounds covers nBt
     const int64_t ncomp = head_ncomp(h), dc = h.d_h;
     const int64_t B = h.n_mols, d = ncomp * dc, nV = h.n_atoms, nBt = ncomp * B;
@@ -1477,7 +1523,7 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
         const int Kg = (int)d;   // dl/dZ: the first d_h columns (= K without descriptors)
         RowsArgs r{Z, ldz, W0f, W0b, h.b[0], h.W[1], h.b[1], reinterpret_cast<float*>(ws + L.act[0]), h.preds, h.targets, h.weights, h.task_weights,
                    h.lt_mask, h.gt_mask, h.loss, gA1, gZr, reinterpret_cast<float*>(ws + L.part), L.part_stride, B, N, K, t, h.act, h.act_slope,
-                   g_debug_stamps ? g_debug_stamps + 64 : nullptr, Kg};
+                   g_debug_stamps ? g_debug_stamps + 64 : nullptr, Kg, ffn_drop(h, 1)};
         // PH 1 reduces over K, PH 2 holds rows of N and forms Kg columns; without descriptors K == Kg and both take the wider of N, K
         const int widest = N > Kg ? N : Kg, w1 = xd ? K : (N > K ? N : K);
         const dim3 g1((unsigned)L.n_part, (unsigned)((N + 63) / 64)), g2((unsigned)L.n_part, (unsigned)((widest + 63) / 64));
@@ -1535,6 +1581,13 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
         g.act = l + 1 < Ln ? h.act : DMPNN_ACT_NONE;   // sigma of the NEXT block fused here (ffn.py:49-58)
         g.act_slope = h.act_slope;
         DMPNN_TRY(dmpnn_linear_fwd(&g, stream));
+        const FfnDrop dr = ffn_drop(h, l + 1);   // (the next layer's input: mask behind tau)
+        if (dr.on) {
+            const int64_t n = B * h.dims[l + 1];
+            int64_t blocks = (n + 255) / 256; if (blocks > 1024) blocks = 1024;
+            hipLaunchKernelGGL(k_ffn_drop, dim3((unsigned)blocks), dim3(256), 0, s, out, h.dims[l + 1], B, (int)h.dims[l + 1], dr);
+            DMPNN_CHECK_LAUNCH("k_ffn_drop");
+        }
         A[l + 1] = out;
     }
     if (!h.targets) return DMPNN_OK;
@@ -1562,7 +1615,8 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
             float* out = bufs[pp]; pp ^= 1;
             // (l == 0: no activation in front of the only layer — the derivative factor is 1; every column's gradient is formed, in rows of
             //  ldA[0] — Kp with descriptors, 16-byte rows for the column kernels)
-            OutBwdArgs q{g_cur, A[l], ldA[l], h.W[l], out, ldA[l], h.gW[l], h.b[l] ? h.gb[l] : nullptr, B, (int)K, (int)N, l > 0 ? h.act : DMPNN_ACT_NONE, h.act_slope};
+            OutBwdArgs q{g_cur, A[l], ldA[l], h.W[l], out, ldA[l], h.gW[l], h.b[l] ? h.gb[l] : nullptr, B, (int)K, (int)N, l > 0 ? h.act : DMPNN_ACT_NONE, h.act_slope,
+                         ffn_drop(h, l)};
             if (out_all) {
                 DMPNN_CHECK_ARG(h.loss_out != nullptr, "head: targets without loss_out");
                 OutAllArgs qa{q, LossArgs{h.preds, t, h.targets, t, h.weights, h.task_weights, h.lt_mask, h.gt_mask, nullptr, t, h.loss_out, B, t, h.loss, 1, 0.f, 0.f, 0.f}};
@@ -1598,10 +1652,11 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
         float* out = bufs[pp]; pp ^= 1;
         g.C = out; g.ldc = Kout; g.act = DMPNN_ACT_NONE;
         DMPNN_TRY(dmpnn_linear_fwd(&g, stream));
-        if (l > 0 && h.act != DMPNN_ACT_NONE) {
+        const FfnDrop dr = ffn_drop(h, l);
+        if (l > 0 && (h.act != DMPNN_ACT_NONE || dr.on)) {
             const int64_t n = B * K;
             int64_t blocks = (n + 255) / 256; if (blocks > 1024) blocks = 1024;
-            hipLaunchKernelGGL(k_head_act_bwd, dim3((unsigned)blocks), dim3(256), 0, s, out, K, A[l], K, B, (int)K, h.act, h.act_slope);
+            hipLaunchKernelGGL(k_head_act_bwd, dim3((unsigned)blocks), dim3(256), 0, s, out, K, A[l], K, B, (int)K, h.act, h.act_slope, dr);
             DMPNN_CHECK_LAUNCH("k_head_act_bwd");
         }
         g_cur = out; ld_cur = Kout;

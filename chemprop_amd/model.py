@@ -430,9 +430,13 @@ class HeadSpec:
     autograd node for everything behind the block).
 
     ``d_xd`` is the width of the molecule descriptors the model expects: the first layer's ``in_features`` less the block's output
-    width (0: none).  ``fill(..., X_d=...)`` hands them over as ``dmpnn_head_args.X_d`` / ``ld_xd`` with ``dims[0] = d_h + d_xd``."""
+    width (0: none).  ``fill(..., X_d=...)`` hands them over as ``dmpnn_head_args.X_d`` / ``ld_xd`` with ``dims[0] = d_h + d_xd``.
 
-    def __init__(self, model):
+    ``ffn_dropout=True``: the predictor's dropout may be active — ONE ``nn.Dropout`` shared by its blocks (``MLP.build``), kept as
+    ``drop``; ``fill(..., ffn_dropout=(p, seed))`` hands it to the kernels as their hash mask (``dmpnn_head_args.ffn_dropout_p``).
+    Without it a predictor with dropout is refused (the module path keeps torch's ``nn.Dropout``)."""
+
+    def __init__(self, model, ffn_dropout: bool = False):
         agg, pred = model.agg, model.predictor
         mode = aggregation_mode(agg)
         if mode is None:
@@ -443,9 +447,17 @@ class HeadSpec:
         f_act, f_slope = "none", 0.0
         for b in blocks[1:]:
             code, sl, _ = classify_activation(b[0])
-            if code in ("custom", "prelu") or b[1].p > 0:
+            if code in ("custom", "prelu") or (b[1].p > 0 and not ffn_dropout):
                 raise NotImplementedError("predictor with a built-in activation (not PReLU) and dropout 0")
             f_act, f_slope = code, sl
+        # the predictor's dropout on the kernels: the hash mask has one p for every layer — chemprop's MLP shares one module
+        self.drop = None
+        drops = list({id(b[1]): b[1] for b in blocks[1:]}.values())
+        if ffn_dropout and drops:
+            if len(drops) == 1 and type(drops[0]) is nn.Dropout and 0 <= drops[0].p < 1:
+                self.drop = drops[0]
+            elif any(d.p > 0 for d in drops):
+                raise NotImplementedError("predictor dropout: one nn.Dropout with 0 < p < 1 shared by the predictor's blocks")
         # (the reference's UnscaleTransform IS the identity in training mode, transforms.py:45-50: what a scaled regression run carries)
         if not (isinstance(pred.output_transform, nn.Identity) or "UnscaleTransform" in _mro_names(pred.output_transform)):
             raise NotImplementedError("the output transform is the identity while training (predictors.py:166-169)")
@@ -534,12 +546,15 @@ class HeadSpec:
         return X
 
     def fill(self, h, nV: int, n_mols: int, d_out: int, batch: Tensor, T: Tensor, weights, lt_mask, gt_mask, gptr, bn_training: bool = True,
-             X_d: Optional[Tensor] = None) -> list:
+             X_d: Optional[Tensor] = None, ffn_dropout: Optional[tuple] = None) -> list:
         """Fill ``h`` (a ``_lib.HeadArgs``) but for ``preds / loss_out / gHv / ws``; ``gptr(param)`` gives the address the gradient of
-        ``param`` goes to (``None``: not wanted).  ``X_d``: the molecule descriptors as :meth:`descriptors` returns them.  Returns the
-        tensors that must stay alive until the call has been enqueued."""
+        ``param`` goes to (``None``: not wanted).  ``X_d``: the molecule descriptors as :meth:`descriptors` returns them.
+        ``ffn_dropout``: ``(p, seed)`` of the predictor's dropout mask, or ``None`` (no dropout).  Returns the tensors that must stay
+        alive until the call has been enqueued."""
         dev = T.device
         h.n_atoms, h.n_mols, h.d_h = nV, n_mols, d_out
+        if ffn_dropout is not None:
+            h.ffn_dropout_p, h.ffn_dropout_seed = float(ffn_dropout[0]), int(ffn_dropout[1])
         if self.n_components > 1:   # (d_out: one block's width; `batch` numbers molecule i of component c as c n_mols + i)
             h.n_components = self.n_components
         h.batch = batch.data_ptr()
@@ -695,10 +710,15 @@ class FusedTrainer:
     mean / norm aggregation; optional ``nn.BatchNorm1d``; an MLP predictor with a built-in activation and dropout 0; MSE / MAE.
     A predictor wider than the block's output takes molecule descriptors: ``step(..., X_d=...)`` concatenates
     ``model.X_d_transform(X_d)`` behind the batch norm inside the same call (no gradient flows to ``X_d``).
+
+    ``ffn_dropout=True`` also takes a predictor with dropout (one ``nn.Dropout`` shared by its blocks, as ``MLP.build`` makes it):
+    ``step`` reads its ``p`` at every step and, while the model and that module are in training mode and ``p > 0``, draws one more
+    seed from torch's CPU generator — after the block's — for the head's hash mask (``dmpnn_head_args.ffn_dropout_p``; kept as
+    ``last_head_dropout_seed``); otherwise the head gets ``p = 0``.  The default refuses such a predictor.
     """
 
     def __init__(self, model: MPNN, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, group=None,
-                 tile_plan: bool = True):
+                 tile_plan: bool = True, ffn_dropout: bool = False):
         mp, agg, pred = model.message_passing, model.agg, model.predictor
         # a multicomponent model: ONE block shared by every component (the components' graphs merged into one batch per step), or
         # one block per component (each block's forward into its rows of one H_v, the head once, each block's backward)
@@ -710,7 +730,7 @@ class FusedTrainer:
         if multi and any(b.dropout.p > 0 for b in self.blocks):
             raise NotImplementedError("FusedTrainer: dropout inside the blocks of a multicomponent model")
         try:
-            self.head = HeadSpec(model)
+            self.head = HeadSpec(model, ffn_dropout=ffn_dropout)
         except NotImplementedError as e:
             raise NotImplementedError(f"FusedTrainer: {e}") from None
         self.model, self.mp = model, self.blocks[0]
@@ -837,9 +857,17 @@ class FusedTrainer:
             note_batch(batch, self.n_components * n_mols)
 
         # ---- the head ----
+        hdrop = None
+        drop = self.head.drop
+        if drop is not None and drop.training and float(drop.p) > 0:
+            if not float(drop.p) < 1:
+                raise ValueError(f"FusedTrainer.step: the predictor's dropout needs p < 1, got {drop!r}")
+            # one seed per step from torch's CPU generator, drawn after the block's (model.training: checked above)
+            hdrop = (float(drop.p), int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
+            self.last_head_dropout_seed = hdrop[1]
         h = _lib.HeadArgs()
         keep = [T, out, gout, batch, parts]
-        keep += self.head.fill(h, nV_all, n_mols, d_out, batch, T, weights, lt_mask, gt_mask, self._gv, X_d=Xd)
+        keep += self.head.fill(h, nV_all, n_mols, d_out, batch, T, weights, lt_mask, gt_mask, self._gv, X_d=Xd, ffn_dropout=hdrop)
         bn = self.bn
         t = int(self.layers[-1].out_features)
         preds = torch.empty(n_mols, t, dtype=torch.float32, device=dev)

@@ -54,7 +54,8 @@ extern "C" {
  * 15 — round 6: DMPNN_F_STORE16 also with DMPNN_F_MEGA (the whole-forward tile kernel on f16 operands: one MFMA pass, opt-in, not
  * fp32-class; it was DMPNN_EINVAL there).  Grown at its end, same version: dmpnn_head_args.X_d / ld_xd (molecule descriptors behind
  * the batch norm; the two fields are zero in a caller built before them, which is the NULL they default to); dmpnn_head_args.n_components
- * and dmpnn_step_args.n_extra / extra (multicomponent models: zero in an older caller, which is one block). */
+ * and dmpnn_step_args.n_extra / extra (multicomponent models: zero in an older caller, which is one block); dmpnn_head_args.ffn_dropout_p /
+ * ffn_dropout_seed (the predictor's dropout as a hash mask: zero in an older caller, which is no dropout). */
 #define DMPNN_ABI_VERSION 15
 
 enum dmpnn_status {
@@ -583,7 +584,8 @@ int dmpnn_clip_grad(float* g, int64_t n, float clip_val, int32_t mode, float gra
 /* ---------------------------------------------------------------------------------------------
  * f4, the rest of the model: what chemprop.models.MPNN does after the block in a training step (models/model.py:126-134,
  * 148-161) as ONE call —  H = agg(H_v, batch) (nn/agg.py:66-113);  Z = bn(H) (nn.BatchNorm1d, model.py:94,132);
- * P = ffn(Z) (nn/ffn.py:24-68 under nn/predictors.py:161-169: Linear, then (act, dropout = 0, Linear) blocks);
+ * P = ffn(Z) (nn/ffn.py:24-68 under nn/predictors.py:161-169: Linear, then (act, dropout, Linear) blocks; the dropout is the hash
+ * mask of dmpnn_head_args.ffn_dropout_p);
  * loss = sum(L w_i t_j mask) / sum(mask), mask = isfinite(targets) (model.py:152-156, nn/metrics.py:78-127; L: MSE :137-141,
  * MAE :146-148, with lt_mask / gt_mask the bounded variants :157-163) — and, when gHv != NULL, the gradients of the loss
  * with respect to every parameter and to H_v (the `gout` of dmpnn_backward).  All pointers device pointers, fp32, dense
@@ -593,6 +595,7 @@ int dmpnn_clip_grad(float* g, int64_t n, float clip_val, int32_t mode, float gra
  * ------------------------------------------------------------------------------------------- */
 #define DMPNN_MAX_FFN_LAYERS 8
 #define DMPNN_MAX_COMPONENTS 8             /* dmpnn_head_args.n_components: at most this many blocks side by side in the fingerprint */
+#define DMPNN_DROP_SITE_FFN 0x10000        /* dmpnn_head_args.ffn_dropout_p: the predictor's mask sites start here (the block's are 0 .. depth-1) */
 enum dmpnn_loss { DMPNN_LOSS_MSE = 0, DMPNN_LOSS_MAE = 1,
                   DMPNN_LOSS_BCE = 2, /* v12: binary cross entropy with logits (nn/metrics.py:292-295; predictors.py:235-247) */
                   DMPNN_LOSS_CE = 3,  /* v12: cross entropy over dmpnn_head_args.n_classes logits per task (nn/metrics.py:298-304;
@@ -643,6 +646,14 @@ typedef struct dmpnn_head_args {
                                                cat(agg(H_v^0), ..., agg(H_v^(n-1))) [B, n d_h] before batch norm (bn_* are n d_h long),
                                                dims[0] = n d_h (+ d_xd); d_h stays one block's width and gHv [n_atoms, ldg] holds every
                                                component's rows */
+    float ffn_dropout_p; uint64_t ffn_dropout_seed;  /* v15 growth: the predictor's nn.Dropout (nn/ffn.py:49-58: act, dropout, Linear) as a
+                                               hash mask; 0 (what a caller built before the fields passes): none; outside [0, 1): DMPNN_EINVAL.
+                                               Layer l (1 <= l < n_layers) reads N = dims[l] columns: its input element (r, c) — r the
+                                               target row (the molecule, also of a multicomponent model) — is KEPT, and scaled by 1 / (1 - p),
+                                               when drop_hash(seed, DMPNN_DROP_SITE_FFN + l, r ceil(N / 1024) + c / 1024, c % 1024) >=
+                                               floor(p 2^32) (the hash of dmpnn_fwd_args.dropout_p; dmpnn_dropout_keep).  Applied whenever
+                                               p > 0: the caller decides when training is on.  No mask is stored: the backward pass
+                                               regenerates it */
 } dmpnn_head_args;
 size_t dmpnn_head_ws_bytes(const dmpnn_head_args* h);
 int dmpnn_head(const dmpnn_head_args* h, const float* Hv, int64_t ldhv, void* stream);
