@@ -10,119 +10,8 @@ import torch
 from torch import nn
 
 from chemprop_amd import _lib
-from conftest import parity_err
-
-
-# ---- helpers ---------------------------------------------------------------------------------------------------------------------
-def make_model(d_h, d_xd, hidden, tasks, bn=True, agg="norm", kind="mse", act="relu", n_layers=1, n_classes=3, X_d_transform=None,
-               depth=3):
-    from chemprop_amd import agg as cagg
-    from chemprop_amd.model import (BCE, CE, MAE, MPNN, MSE, MVE, BinaryClassificationFFN, MulticlassClassificationFFN, MveFFN,
-                                    RegressionFFN)
-    from chemprop_amd.nn import BondMessagePassing
-
-    mp = BondMessagePassing(d_h=d_h, depth=depth, activation=act)
-    ag = dict(norm=cagg.NormAggregation, mean=cagg.MeanAggregation, sum=cagg.SumAggregation)[agg]()
-    ffn = dict(n_tasks=tasks, input_dim=d_h + d_xd, hidden_dim=hidden, n_layers=n_layers, activation=act)
-    if kind == "bce":
-        pred = BinaryClassificationFFN(criterion=BCE(1.0), **ffn)
-    elif kind == "ce":
-        pred = MulticlassClassificationFFN(n_classes, criterion=CE(1.0), **ffn)
-    elif kind == "mve":
-        pred = MveFFN(criterion=MVE(1.0), **ffn)
-    else:
-        pred = RegressionFFN(criterion=(MAE if kind.endswith("mae") else MSE)(1.0), **ffn)
-    return MPNN(mp, ag, pred, batch_norm=bn, X_d_transform=X_d_transform)
-
-
-def descriptors(n, d_xd, seed, how="normal"):
-    """``normal``: N(0, 1); ``binary``: 0 / 1 bits (Morgan); ``mixed``: every row spans ~1e-3 .. 1e3 (raw rdkit values beside counts)."""
-    gen = torch.Generator().manual_seed(seed)
-    if how == "binary":
-        return (torch.rand(n, d_xd, generator=gen) < 0.1).float()
-    x = torch.randn(n, d_xd, generator=gen)
-    if how == "mixed":
-        x = x.sign() * 10.0 ** (6.0 * torch.rand(n, d_xd, generator=gen) - 3.0)
-        x[:, 0], x[:, -1] = 1e3, -1e-3   # (both ends in every row)
-    return x
-
-
-def run_head(model, Hv, batch, n_mols, T, w, lt, gt, X):
-    """One ``dmpnn_head`` call (forward + backward, ``bn_training``) with descriptors ``X`` handed over as they are (``ld_xd`` = the
-    view's row stride); returns (loss, preds, {param id: grad}, gH_v)."""
-    from chemprop_amd import engine
-    from chemprop_amd.model import HeadSpec
-
-    lib = _lib.load()
-    spec = HeadSpec(model)
-    dev = Hv.device
-    grads = {id(p): torch.zeros_like(p) for p in spec.params()}
-    h = _lib.HeadArgs()
-    nV, d = int(Hv.shape[0]), int(Hv.shape[1])
-    keep = spec.fill(h, nV, n_mols, d, batch, T, w, lt if spec.bounded else None, gt if spec.bounded else None,
-                     lambda p: None if p is None else grads[id(p)].data_ptr(), X_d=X)
-    preds = torch.full((n_mols, spec.n_out), float("nan"), device=dev)
-    loss = torch.empty(2, device=dev)
-    gH = torch.full((nV, d), float("nan"), device=dev)
-    h.preds, h.loss_out, h.gHv, h.ldg = preds.data_ptr(), loss.data_ptr(), gH.data_ptr(), d
-    nb = int(lib.dmpnn_head_ws_bytes(C.byref(h)))
-    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-    h.ws, h.ws_bytes = ws.data_ptr(), nb
-    with engine._OnDevice(dev):
-        _lib.check(lib.dmpnn_head(C.byref(h), Hv.data_ptr(), Hv.stride(0), engine._stream_ptr(dev)), "dmpnn_head")
-    torch.cuda.synchronize()
-    del keep
-    return float(loss[0]), preds.cpu(), {k: g.cpu() for k, g in grads.items()}, gH.cpu()
-
-
-def restate(model, Hv, batch, n_mols, T, w, lt, gt, X):
-    """The head in float64 on the CPU, op by op: agg, BatchNorm1d (training), cat(., X_d), the MLP, the criterion; returns
-    (loss, raw outputs, {param id: grad}, gH_v, {running_mean, running_var})."""
-    from chemprop_amd.model import MODES, HeadSpec, masked_loss
-
-    spec = HeadSpec(model)
-    f = lambda t: t.detach().cpu().double()
-    Hv64 = f(Hv).requires_grad_()
-    b = batch.cpu()
-    d = Hv64.shape[1]
-    H = torch.zeros(n_mols, d, dtype=torch.float64).index_add(0, b, Hv64)
-    mode = {v: k for k, v in MODES.items()}[spec.agg_mode]
-    if mode == "mean":
-        H = H / torch.bincount(b, minlength=n_mols).clamp(min=1).double().view(-1, 1)
-    elif mode == "norm":
-        H = H / spec.agg_norm
-    leaves, bufs = {}, {}
-    if spec.bn is not None:
-        bw, bb = f(spec.bn.weight).requires_grad_(), f(spec.bn.bias).requires_grad_()
-        rm, rv = f(spec.bn.running_mean).clone(), f(spec.bn.running_var).clone()
-        H = torch.nn.functional.batch_norm(H, rm, rv, bw, bb, training=True, momentum=spec.bn.momentum, eps=spec.bn.eps)
-        leaves[id(spec.bn.weight)], leaves[id(spec.bn.bias)] = bw, bb
-        bufs = dict(running_mean=rm, running_var=rv)
-    Z = torch.cat((H, f(X)), 1)
-    for i, blk in enumerate(model.predictor.ffn):
-        lin = blk[-1]
-        if i > 0:
-            Z = blk[0](Z)
-        W = f(lin.weight).requires_grad_()
-        leaves[id(lin.weight)] = W
-        bias = None
-        if lin.bias is not None:
-            bias = f(lin.bias).requires_grad_()
-            leaves[id(lin.bias)] = bias
-        Z = torch.nn.functional.linear(Z, W, bias)
-    Y = Z
-    if spec.kind == "ce":
-        P = Y.reshape(n_mols, -1, spec.n_classes)
-    elif spec.kind == "mve":
-        mean, var = torch.chunk(Y, 2, 1)
-        P = torch.stack((mean, torch.nn.functional.softplus(var)), 2)
-    else:
-        P = Y
-    T64 = f(T)
-    l = masked_loss(P, T64, None if w is None else f(w), None, f(lt) > 0 if (lt is not None and spec.bounded) else None,
-                    f(gt) > 0 if (gt is not None and spec.bounded) else None, spec.kind)
-    l.backward()
-    return float(l.detach()), Y.detach(), {k: v.grad for k, v in leaves.items()}, Hv64.grad, bufs
+from conftest import parity_err, parity_err_unfloored
+from head_harness import case_inputs, descriptors, make_model, restate, run_head
 
 
 CASES = {
@@ -140,43 +29,6 @@ CASES = {
 }
 
 
-def case_inputs(case, dev, seed=0):
-    from chemprop_amd import synth
-
-    form, n, d_h, d_xd, hidden, tasks, n_layers, bn, agg, kind, act, xk, strided = case
-    torch.manual_seed(seed + 5)
-    model = make_model(d_h, d_xd, hidden, tasks, bn, agg, kind, act, n_layers).to(dev).train()
-    if bn:   # (non-trivial batch-norm parameters and running statistics)
-        with torch.no_grad():
-            model.bn.weight.uniform_(0.5, 1.5), model.bn.bias.uniform_(-0.5, 0.5)
-            model.bn.running_mean.uniform_(-0.1, 0.1), model.bn.running_var.uniform_(0.5, 2.0)
-    bmg = synth.random_batch(n, "qm9", seed=seed + 9)
-    gen = torch.Generator().manual_seed(seed + 2)
-    Hv = torch.randn(int(bmg.V.shape[0]), d_h, generator=gen).to(dev)
-    batch = bmg.batch.to(dev)
-    if kind == "bce":
-        T = torch.rand(n, tasks, generator=gen).round()
-    elif kind == "ce":
-        T = torch.randint(0, 3, (n, tasks), generator=gen).float()
-    else:
-        T = torch.randn(n, tasks, generator=gen)
-    if tasks > 1:
-        T[torch.rand(n, tasks, generator=gen) < 0.2] = float("nan")
-    w = 0.5 + torch.rand(n, 1, generator=gen)
-    lt = (torch.rand(n, tasks, generator=gen) < 0.3) if kind.startswith("bounded") else None
-    gt = (torch.rand(n, tasks, generator=gen) < 0.3) if kind.startswith("bounded") else None
-    X = descriptors(n, d_xd, seed + 4, xk)
-    if strided:   # a view into a wider table: row stride > d_xd, an address that is not 16-byte aligned
-        big = torch.randn(n, d_xd + 7, generator=gen)
-        big[:, 3:3 + d_xd] = X
-        X = big.to(dev)[:, 3:3 + d_xd]
-        assert X.stride(0) == d_xd + 7 and X.data_ptr() % 16 != 0
-    else:
-        X = X.to(dev)
-    to = lambda t: None if t is None else t.to(dev)
-    return model, Hv, batch, n, to(T), to(w), to(lt), to(gt), X
-
-
 # ---- GPU ----------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", list(CASES))
@@ -191,6 +43,7 @@ def test_head_with_descriptors_matches_float64_restatement(name, gpu_device, mon
     loss, P, g, gH = run_head(model, Hv, batch, n, T, w, lt, gt, X)
     assert abs(loss - ref_loss) <= 1e-5 * max(1.0, abs(ref_loss)), (loss, ref_loss)
     assert parity_err(P.numpy(), ref_P.numpy()) <= 2e-5
+    assert parity_err_unfloored(P.numpy(), ref_P.numpy()) <= 2e-5
     from chemprop_amd.model import HeadSpec
 
     spec = HeadSpec(model)
@@ -200,7 +53,14 @@ def test_head_with_descriptors_matches_float64_restatement(name, gpu_device, mon
         assert torch.isfinite(g[id(p)]).all(), names[id(p)]
         e = parity_err(g[id(p)].numpy(), ref_g[id(p)].numpy())
         assert e <= 2e-5, f"{names[id(p)]}: {e:.2e}"
+        # (the loss is a mean over the batch: max|ref| << 1, the floored metric above is an absolute bar there — hold the relative one too)
+        eu = parity_err_unfloored(g[id(p)].numpy(), ref_g[id(p)].numpy())
+        print(f"{name} {names[id(p)]}: floored {e:.2e}, un-floored {eu:.2e}")
+        assert eu <= 2e-5, f"{names[id(p)]}: un-floored {eu:.2e}"
     assert parity_err(gH.numpy(), ref_gH.numpy()) <= 2e-5
+    eu = parity_err_unfloored(gH.numpy(), ref_gH.numpy())
+    print(f"{name} gH_v: un-floored {eu:.2e}")
+    assert eu <= 2e-5, f"gH_v: un-floored {eu:.2e}"
     W0 = spec.layers[0].weight
     assert float(ref_g[id(W0)][:, case[2]:].abs().max()) > 0   # (the descriptor columns of gW[0] carry a gradient)
     for k, v in ref_bufs.items():
@@ -225,7 +85,9 @@ def test_head_rows_form_equals_chain_with_descriptors(name, gpu_device, monkeypa
     for x, y in zip(pa, pb):
         if id(x) in ga:
             assert parity_err(ga[id(x)].numpy(), gb[id(y)].numpy()) <= 1e-5
+            assert parity_err_unfloored(ga[id(x)].numpy(), gb[id(y)].numpy()) <= 1e-5
     assert parity_err(gHa.numpy(), gHb.numpy()) <= 1e-5
+    assert parity_err_unfloored(gHa.numpy(), gHb.numpy()) <= 1e-5
 
 
 @pytest.mark.gpu
@@ -343,6 +205,9 @@ def test_module_path_loss_with_descriptors_is_one_autograd_node(gpu_device):
         assert (pa.grad is None) == (pb.grad is None), k
         if pa.grad is not None:
             assert parity_err(pa.grad.cpu().numpy(), pb.grad.cpu().numpy()) <= 2e-5, k
+            eu = parity_err_unfloored(pa.grad.cpu().numpy(), pb.grad.cpu().numpy())
+            print(f"module path with descriptors {k}: un-floored {eu:.2e}")
+            assert eu <= 2e-5, f"{k}: un-floored {eu:.2e}"
     for k in ("running_mean", "running_var"):
         assert parity_err(getattr(a.bn, k).cpu().numpy(), getattr(b.bn, k).cpu().numpy()) <= 1e-6, k
     Xg = X.clone().requires_grad_()

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN_DIR, adam_comparable, parity_err, parity_err_where
+from conftest import GOLDEN_DIR, adam_comparable, parity_err, parity_err_where, parity_err_unfloored
 from oracle import model_torch as om
 from oracle import ref_shim
 
@@ -651,6 +651,10 @@ def test_module_path_head_is_one_autograd_node(bn, agg, tasks, kind, act, gpu_de
         assert (pa.grad is None) == (pb.grad is None), k
         if pa.grad is not None:
             assert parity_err(pa.grad.cpu().numpy(), pb.grad.cpu().numpy()) <= 2e-5, k
+            # (the loss is a batch mean: max|grad| << 1 and the floored bar an absolute one — the relative one beside it)
+            eu = parity_err_unfloored(pa.grad.cpu().numpy(), pb.grad.cpu().numpy())
+            print(f"module-path head {k}: un-floored {eu:.2e}")
+            assert eu <= 2e-5, f"{k}: un-floored {eu:.2e}"
     if bn:
         for k in ("running_mean", "running_var"):
             assert parity_err(getattr(a.bn, k).cpu().numpy(), getattr(b.bn, k).cpu().numpy()) <= 1e-6, k
@@ -712,6 +716,9 @@ def test_head_in_row_and_column_kernels_equals_the_nine_launch_chain(n_mols, d_h
         if pa.grad is not None:
             assert torch.isfinite(pa.grad).all(), k
             assert parity_err(pa.grad.cpu().numpy(), pb.grad.cpu().numpy()) <= 1e-5, k
+            eu = parity_err_unfloored(pa.grad.cpu().numpy(), pb.grad.cpu().numpy())
+            print(f"rows vs chain {k}: un-floored {eu:.2e}")
+            assert eu <= 1e-5, f"{k}: un-floored {eu:.2e}"
     if bn:
         for k in ("running_mean", "running_var"):
             assert parity_err(getattr(a.bn, k).cpu().numpy(), getattr(b.bn, k).cpu().numpy()) <= 1e-6, k
