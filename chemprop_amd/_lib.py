@@ -21,7 +21,7 @@ INCLUDE = os.path.join(_ROOT, "include")
 # DMPNN_LIB: an alternative build of the same sources (kernel experiments: scripts/build_variant.py), same ABI
 LIB_PATH = os.environ.get("DMPNN_LIB") or os.path.join(_HERE, "libdmpnn_gfx950.so")
 SOURCES = ["dmpnn_abi.hip", "dmpnn_prepare.hip", "dmpnn_segment.hip", "dmpnn_gemm.hip", "dmpnn_gemm_p1.hip",
-           "dmpnn_gemm_p2.hip", "dmpnn_gemm_p3.hip", "dmpnn_gemm_p4.hip", "dmpnn_gemm_s1.hip", "dmpnn_mega.hip", "dmpnn_mega16.hip", "dmpnn_mega16_lp.hip", "dmpnn_mega16_bwd.hip", "dmpnn_rows16.hip", "dmpnn_step16.hip", "dmpnn_bstep16.hip", "dmpnn_backward.hip", "dmpnn_molagg.hip", "dmpnn_collate.hip", "dmpnn_tiles_large.hip", "dmpnn_optim.hip", "dmpnn_wgrad16.hip", "dmpnn_head.hip"]
+           "dmpnn_gemm_p2.hip", "dmpnn_gemm_p3.hip", "dmpnn_gemm_p4.hip", "dmpnn_gemm_s1.hip", "dmpnn_mega.hip", "dmpnn_mega16.hip", "dmpnn_mega16_lp.hip", "dmpnn_mega16_bwd.hip", "dmpnn_rows16.hip", "dmpnn_step16.hip", "dmpnn_bstep16.hip", "dmpnn_backward.hip", "dmpnn_molagg.hip", "dmpnn_collate.hip", "dmpnn_tiles_large.hip", "dmpnn_optim.hip", "dmpnn_wgrad16.hip", "dmpnn_head.hip", "dmpnn_vd.hip"]
 HEADERS = ["dmpnn_common.hpp", "dmpnn_spill_impl.hpp", "dmpnn_gemm_impl.hpp", "dmpnn_mega_impl.hpp", "dmpnn_mega16_impl.hpp", "dmpnn_mega16_bwd_impl.hpp", "dmpnn_rows16_impl.hpp", "dmpnn_seg16.hpp", "dmpnn_step16_impl.hpp"]
 ABI_VERSION = 15
 PLAN_NOFFSETS = 15
@@ -36,6 +36,7 @@ EXPORTS = [
     "dmpnn_prepare_tiles_from_table", "dmpnn_prepare_with_batch", "dmpnn_tile_plan_any_size", "dmpnn_split_row_floats", "dmpnn_forward_can_fuse16", "dmpnn_adam_step",
     "dmpnn_full_plan_keeps_tiles", "dmpnn_head_ws_bytes", "dmpnn_head", "dmpnn_train_step", "dmpnn_forward_tiles", "dmpnn_forward_route", "dmpnn_dropout_keep",
     "dmpnn_clip_grad", "dmpnn_clip_grad_ws_bytes", "dmpnn_train_route", "dmpnn_forward_h0_bytes", "dmpnn_tile_waves", "dmpnn_debug_lds_poison",
+    "dmpnn_vd_ws_bytes", "dmpnn_vd_forward", "dmpnn_vd_backward",
 ]
 
 ACT = {"none": 0, "relu": 1, "leakyrelu": 2, "prelu": 3, "tanh": 4, "elu": 5}
@@ -150,6 +151,23 @@ class StepComponent(C.Structure):
     ]
 
 
+class VdArgs(C.Structure):
+    _fields_ = [
+        ("n_atoms", C.c_int64), ("d_h", C.c_int64), ("d_vd", C.c_int64),
+        ("Hv", C.c_void_p), ("ldhv", C.c_int64),
+        ("V_d", C.c_void_p), ("ldvd", C.c_int64),
+        ("W_d", C.c_void_p), ("b_d", C.c_void_p),
+        ("out", C.c_void_p), ("ldout", C.c_int64),
+        ("gout", C.c_void_p), ("ldgout", C.c_int64),
+        ("gHv", C.c_void_p), ("ldghv", C.c_int64),
+        ("gW_d", C.c_void_p), ("gb_d", C.c_void_p),
+        ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+    ]
+
+
+VD_MAX_WIDTH = 544   # (DMPNN_VD_MAX_WIDTH: the widest d_h + d_vd the atom-descriptor layer takes)
+
+
 class StepArgs(C.Structure):
     _fields_ = [
         ("edge_index", C.c_void_p), ("rev_edge_index", C.c_void_p), ("batch", C.c_void_p), ("plan_bytes", C.c_size_t), ("plan_ready", C.c_int32),
@@ -160,6 +178,7 @@ class StepArgs(C.Structure):
         ("bias_corr1", C.c_float), ("sqrt_bias_corr2", C.c_float), ("grad_scale", C.c_float), ("dev_scalars", C.c_void_p),
         ("clip_val", C.c_float), ("clip_mode", C.c_int32), ("clip_ws", C.c_void_p),
         ("n_extra", C.c_int32), ("extra", C.POINTER(StepComponent)),
+        ("vd", C.POINTER(VdArgs)),
     ]
 
 
@@ -281,7 +300,7 @@ def load() -> C.CDLL:
                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     size_t_fns = ("dmpnn_plan_bytes", "dmpnn_backward_ws_bytes", "dmpnn_linear_wgrad_ws_bytes", "dmpnn_forward_wsplit_bytes", "dmpnn_forward_spill_bytes",
                   "dmpnn_forward_keep_bits_bytes",
-                  "dmpnn_molagg_ws_bytes", "dmpnn_linear16_wsplit_bytes", "dmpnn_head_ws_bytes", "dmpnn_clip_grad_ws_bytes", "dmpnn_forward_h0_bytes")
+                  "dmpnn_molagg_ws_bytes", "dmpnn_linear16_wsplit_bytes", "dmpnn_head_ws_bytes", "dmpnn_clip_grad_ws_bytes", "dmpnn_forward_h0_bytes", "dmpnn_vd_ws_bytes")
     lib.dmpnn_linear16_wsplit_bytes.argtypes = [C.c_int64, C.c_int64]
     lib.dmpnn_linear16_ok.argtypes = [C.POINTER(GemmArgs)]
     lib.dmpnn_linear16_fwd.argtypes = [C.POINTER(GemmArgs), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
@@ -322,6 +341,9 @@ def load() -> C.CDLL:
     lib.dmpnn_head_ws_bytes.argtypes = [C.POINTER(HeadArgs)]
     lib.dmpnn_head.argtypes = [C.POINTER(HeadArgs), C.c_void_p, C.c_int64, C.c_void_p]
     lib.dmpnn_train_step.argtypes = [C.POINTER(StepArgs), C.c_void_p]
+    lib.dmpnn_vd_ws_bytes.argtypes = [C.POINTER(VdArgs)]
+    lib.dmpnn_vd_forward.argtypes = [C.POINTER(VdArgs), C.c_void_p]
+    lib.dmpnn_vd_backward.argtypes = [C.POINTER(VdArgs), C.c_void_p]
     lib.dmpnn_split_row_floats.argtypes = [C.c_int64]
     lib.dmpnn_split_row_floats.restype = C.c_int64
     lib.dmpnn_debug_timestamps.argtypes = [C.c_void_p]

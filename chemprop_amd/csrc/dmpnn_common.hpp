@@ -398,6 +398,11 @@ int launch_mega16_backward(const dmpnn_fwd_args& f, const float* gHO, int64_t ld
                            float* gZs, float* gH0, void* wsplit, float* sp_gM, float* sp_Ta, hipStream_t s, const float* g_edge = nullptr, int64_t ld_gedge = 0,
                            const Mega16BwdRows* rows = nullptr);
 
+// the atom-descriptor layer between a block and the head (dmpnn_vd.hip); split_ready: the workspace holds this step's image of W_d
+int vd_check_args(const dmpnn_vd_args* a, bool bwd);   // every argument check of dmpnn_vd_forward (bwd: of dmpnn_vd_backward), no device work
+int vd_forward_impl(const dmpnn_vd_args* a, void* stream);
+int vd_backward_impl(const dmpnn_vd_args* a, void* stream, bool split_ready);
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace dmpnn

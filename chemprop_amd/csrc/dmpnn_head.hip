@@ -1709,8 +1709,21 @@ int dmpnn_train_step(const dmpnn_step_args* a, void* stream) {
     if ((bw.f.flags & DMPNN_F_TILE_PLAN) && bw.f.n_tiles_launch == 0 && blk_mols > 0) bw.f.n_tiles_launch = blk_mols;
     const dmpnn_fwd_args& f = bw.f;
     DMPNN_CHECK_ARG((f.flags & DMPNN_F_KEEP) != 0, "train_step: the forward must keep its tensors (DMPNN_F_KEEP)");
-    DMPNN_CHECK_ARG(a->head.gHv == a->bwd.gout && a->head.ldg == a->bwd.ldgout, "train_step: head.gHv must be the backward's gout");
-    DMPNN_CHECK_ARG(a->head.d_h == f.d_h + (f.W_d ? f.d_vd : 0), "train_step: head and block sizes differ");
+    const dmpnn_vd_args* vd = a->vd;   // the atom-descriptor layer between the block and the head (dmpnn_vd.hip), or none
+    if (vd) {
+        DMPNN_CHECK_ARG(f.W_d == nullptr, "train_step: with the atom-descriptor stage the block itself carries no W_d");
+        DMPNN_CHECK_ARG(n_extra == 0 && a->head.n_components <= 1, "train_step: the atom-descriptor stage takes one block, one component");
+        DMPNN_CHECK_ARG(f.out == vd->Hv && f.ldout == vd->ldhv && bw.gout == vd->gHv && bw.ldgout == vd->ldghv,
+                        "train_step: the block's out / gout must be the atom-descriptor stage's Hv / gHv");
+        DMPNN_CHECK_ARG(a->head.gHv == vd->gout && a->head.ldg == vd->ldgout, "train_step: head.gHv must be the atom-descriptor stage's gout");
+        DMPNN_CHECK_ARG(a->head.d_h == f.d_h + vd->d_vd && vd->d_h == f.d_h, "train_step: head, block and atom-descriptor widths differ");
+        DMPNN_CHECK_ARG(a->head.n_atoms == vd->n_atoms && vd->n_atoms == f.n_atoms, "train_step: head, block and atom-descriptor atom counts differ");
+        DMPNN_TRY(vd_check_args(vd, false));
+        DMPNN_TRY(vd_check_args(vd, true));
+    } else {
+        DMPNN_CHECK_ARG(a->head.gHv == a->bwd.gout && a->head.ldg == a->bwd.ldgout, "train_step: head.gHv must be the backward's gout");
+        DMPNN_CHECK_ARG(a->head.d_h == f.d_h + (f.W_d ? f.d_vd : 0), "train_step: head and block sizes differ");
+    }
     int64_t n_atoms_all = f.n_atoms;
     for (int e = 0; e < n_extra; ++e) {   // every further block writes the rows behind the previous one's in H_v, reads them in gHv
         const dmpnn_bwd_args& eb = a->extra[e].bwd;
@@ -1751,7 +1764,7 @@ int dmpnn_train_step(const dmpnn_step_args* a, void* stream) {
             const char* he = getenv("DMPNN_HEAD");
             const char* ae = getenv("DMPNN_HEAD_AGG");
             // (with descriptors and no batch norm the aggregate is written into the fingerprint's rows, not into H: no ride there)
-            if (bounds_done && ncomp == 1 && h.ws && h.n_mols > 0 && h.n_mols <= kRowsMaxB && h.d_h % 4 == 0 && h.d_h == f.d_h && !f.W_d && !(he && !strcmp(he, "chain")) &&
+            if (bounds_done && ncomp == 1 && h.ws && h.n_mols > 0 && h.n_mols <= kRowsMaxB && h.d_h % 4 == 0 && h.d_h == f.d_h && !f.W_d && !vd && !(he && !strcmp(he, "chain")) &&
                 (!h.X_d || h.bn_weight) &&
                 !(ae && strcmp(ae, "tile"))) {
                 const HeadLayout HL = head_layout(h);
@@ -1789,10 +1802,13 @@ int dmpnn_train_step(const dmpnn_step_args* a, void* stream) {
         }
         // (a whole step in one call: the first predictor layer's weight gradient rides in the block's backward launches; a staged
         //  step — data parallel — has the head's gradients final after this stage, so nothing is deferred there)
-        DMPNN_TRY(head_run(&a->head, f.out, f.ldout, stream, bounds_done, (stages & DMPNN_STEP_BACKWARD) ? &rider : nullptr, agg_rode));
+        if (vd) DMPNN_TRY(vd_forward_impl(vd, stream));   // H_v' = W_d cat(H_v, V_d) + b_d: what the head reads
+        DMPNN_TRY(head_run(&a->head, vd ? vd->out : f.out, vd ? vd->ldout : f.ldout, stream, bounds_done, (stages & DMPNN_STEP_BACKWARD) ? &rider : nullptr, agg_rode));
     }
     if (stages & DMPNN_STEP_BACKWARD) {
         bool rode = false;
+        // (the layer's gradients lie in the block's slice of the flat buffer: this stage; the image of W_d is the forward's when that ran in this call)
+        if (vd) DMPNN_TRY(vd_backward_impl(vd, stream, (stages & DMPNN_STEP_FORWARD) != 0));
         DMPNN_TRY(backward_impl(&bw, stream, rider.Z ? &rider : nullptr, &rode));   // (the rider: in component 0's launches only)
         for (int e = 0; e < n_extra; ++e) {
             dmpnn_bwd_args be = a->extra[e].bwd;

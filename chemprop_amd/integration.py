@@ -279,7 +279,8 @@ def hip_mpnn_class():
       scheduler, counts ``trainer.global_step`` through ``LightningOptimizer.step`` (what ``ModelCheckpoint`` keys on,
       ``cli/train.py:1912-1919``), saves ``optimizer.state_dict()`` (``torch.optim.Adam``'s format) in its checkpoints.
     * ``training_step``: where :class:`chemprop_amd.model.FusedTrainer` applies (a bond block with a built-in activation, sum / mean /
-      norm aggregation, batch norm, regression MLP, MSE / MAE, no ``V_d``; molecule descriptors ``X_d`` through the model's
+      norm aggregation, batch norm, regression MLP, MSE / MAE; atom descriptors ``V_d`` of a block built with ``d_vd`` through
+      its ``V_d_transform`` and its layer ``W_d`` as a stage of the same call; molecule descriptors ``X_d`` through the model's
       ``X_d_transform``; the predictor's dropout — ``--dropout p`` — as the head kernels' hash mask) the whole step — K0, forward, head, backward,
       clip, Adam — is enqueued by that one call with this step's learning rate and ``Trainer(gradient_clip_val)``
       (``cli/train.py:1937``); the hooks Lightning runs afterwards inside ``optimizer.step(closure)`` — ``backward``,
@@ -399,13 +400,15 @@ def hip_mpnn_class():
             # the last; the block's backward kernels OVERWRITE their gradient views once per exchange (GradSync._written), so the
             # exchange — which re-arms the views — must run on the stepping micro-batch only (backward() below)
             self.__dict__["_hip_accumulating"] = accumulate > 1 and _should_accumulate(tr, batch_idx, accumulate)
-            if fused is not None and V_d is None and self.training and accumulate == 1:
+            # (atom descriptors: the fused step takes them for a block built with d_vd — the layer W_d as a stage of its own; a
+            #  multicomponent model with V_ds stays on the module path)
+            if fused is not None and (V_d is None or not multi) and self.training and accumulate == 1:
                 try:
                     clip = (getattr(tr, "gradient_clip_val", None), _clip_algorithm(getattr(tr, "gradient_clip_algorithm", None)))
                     g = opt.param_groups[0]
                     fl = st["opt"]
                     fl.betas, fl.eps, fl.weight_decay = (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"]), float(g["weight_decay"])
-                    out = fused.step(bmg, targets, weights, lt_mask, gt_mask, lr=float(g["lr"]), clip=clip, X_d=X_d)   # (X_d_transform inside)
+                    out = fused.step(bmg, targets, weights, lt_mask, gt_mask, lr=float(g["lr"]), clip=clip, X_d=X_d, V_d=V_d)   # (X_d_transform / V_d_transform inside)
                     loss = out[0]
                     self.__dict__["_hip_applied"] = True
                     st["route"] = "fused:" + str(fused.last_route)

@@ -362,17 +362,30 @@ class MulticomponentMPNN(MPNN):
 
 def fused_block(mp) -> tuple:
     """``(activation, slope)`` of a block the one-call step takes: a bond block (this package's mirror, or the subclass of the
-    reference's own class, ``integration.HipBondMessagePassing``) with a built-in activation (not PReLU), directed, no ``V_d``, dropout 0
-    or ``nn.Dropout`` with a ReLU-class activation; ``NotImplementedError`` for anything else (it trains through the module path)."""
+    reference's own class, ``integration.HipBondMessagePassing``) with a built-in activation (not PReLU), directed, dropout 0
+    or ``nn.Dropout`` with a ReLU-class activation; ``NotImplementedError`` for anything else (it trains through the module path).
+    A block built with ``d_vd > 0`` is taken — its layer ``W_d`` runs as a stage of its own behind the block (``dmpnn_vd_forward`` /
+    ``dmpnn_vd_backward``) — unless it also has dropout (the reference applies the block's dropout a second time behind ``W_d``: no
+    mask site exists for that) or ``d_h + d_vd`` is beyond ``_lib.VD_MAX_WIDTH``."""
     # (W_h is [d_h, d_h] in a bond block: the atom variant's takes d_e + d_h columns, the mol-atom-bond ones have a second read-out)
     bond = (all(isinstance(getattr(mp, n, None), nn.Linear) for n in ("W_i", "W_h", "W_o"))
             and mp.W_h.in_features == mp.W_h.out_features and mp.W_o.in_features > mp.W_h.out_features)
     if not bond:
         raise NotImplementedError("FusedTrainer: a BondMessagePassing block (W_i / W_h [d_h, d_h] / W_o)")
     act, slope, slope_t = classify_activation(mp.tau)
-    if act in ("custom", "prelu") or mp.undirected or mp.W_d is not None:
-        raise NotImplementedError("FusedTrainer: built-in activation (not PReLU), directed, no V_d — other blocks train "
+    if act in ("custom", "prelu") or mp.undirected:
+        raise NotImplementedError("FusedTrainer: built-in activation (not PReLU), directed — other blocks train "
                                   "through the module path (MPNN.loss + autograd)")
+    if mp.W_d is not None:
+        if mp.dropout.p > 0:
+            raise NotImplementedError("FusedTrainer: atom descriptors (W_d) together with dropout inside the block — the dropout behind "
+                                      "W_d has no mask site; this model trains through the module path")
+        if not (isinstance(mp.W_d, nn.Linear) and mp.W_d.in_features == mp.W_d.out_features and mp.W_d.bias is not None
+                and mp.W_d.in_features > mp.W_o.out_features):
+            raise NotImplementedError("FusedTrainer: W_d must be a square nn.Linear with a bias over cat(H_v, V_d)")
+        if mp.W_d.in_features > _lib.VD_MAX_WIDTH:
+            raise NotImplementedError(f"FusedTrainer: d_h + d_vd = {mp.W_d.in_features} is beyond the {_lib.VD_MAX_WIDTH} columns the "
+                                      "atom-descriptor stage takes")
     if mp.dropout.p > 0 and not (type(mp.dropout) is nn.Dropout and act in ("relu", "leakyrelu")):
         # (active dropout lives inside the tile kernels for ReLU-class activations: dmpnn_fwd_args.dropout_p; a dropout module
         #  that is not exactly nn.Dropout has its own semantics and stays on the module path)
@@ -705,7 +718,8 @@ class FusedTrainer:
     """``training_step`` + ``Adam.step`` of an :class:`MPNN` as one ``dmpnn_train_step`` call per batch.
 
     Takes what the kernels implement and refuses the rest loudly (those models train through the module path): a
-    :class:`~chemprop_amd.nn.BondMessagePassing` block with a built-in activation, no ``V_d``, directed, dropout 0 or — with a
+    :class:`~chemprop_amd.nn.BondMessagePassing` block with a built-in activation, directed, with or without atom descriptors
+    (``d_vd > 0``: ``step(..., V_d=...)``, the layer ``W_d`` as a stage of its own behind the block), dropout 0 or — with a
     ReLU-class activation — ``nn.Dropout`` inside the tile kernels (hash mask, one seed per step from torch's CPU generator); sum /
     mean / norm aggregation; optional ``nn.BatchNorm1d``; an MLP predictor with a built-in activation and dropout 0; MSE / MAE.
     A predictor wider than the block's output takes molecule descriptors: ``step(..., X_d=...)`` concatenates
@@ -729,6 +743,8 @@ class FusedTrainer:
         acts = [fused_block(b) for b in self.blocks]
         if multi and any(b.dropout.p > 0 for b in self.blocks):
             raise NotImplementedError("FusedTrainer: dropout inside the blocks of a multicomponent model")
+        if multi and any(b.W_d is not None for b in self.blocks):
+            raise NotImplementedError("FusedTrainer: atom descriptors (V_ds) in a multicomponent model")
         try:
             self.head = HeadSpec(model, ffn_dropout=ffn_dropout)
         except NotImplementedError as e:
@@ -768,13 +784,16 @@ class FusedTrainer:
 
     def step(self, bmg, targets: Tensor, weights: Optional[Tensor] = None, lt_mask: Optional[Tensor] = None,
              gt_mask: Optional[Tensor] = None, lr: Optional[float] = None, clip: Optional[tuple] = None,
-             X_d: Optional[Tensor] = None, V_ds=None) -> Tensor:
-        """One optimisation step on ``(bmg, targets, ...)`` (a ``TrainingBatch`` without ``V_d``); returns the device
+             X_d: Optional[Tensor] = None, V_ds=None, V_d: Optional[Tensor] = None) -> Tensor:
+        """One optimisation step on ``(bmg, targets, ...)`` (a ``TrainingBatch``); returns the device
         tensor ``[loss, number of finite targets]`` of THIS step (no host sync).  ``model.train()`` semantics (batch norm uses
         and updates batch statistics).  ``clip = (value, "norm" | "value")``: Lightning's ``gradient_clip_val`` / ``_algorithm``
         (``cli/train.py:1937``), applied between the backward pass and the update inside the same call.  ``X_d``: the batch's
         molecule descriptors ``[n_mols, d_xd]`` for a model whose predictor takes them (``ValueError`` when they are missing,
-        unexpected or of the wrong shape); ``model.X_d_transform`` is applied to them here.
+        unexpected or of the wrong shape); ``model.X_d_transform`` is applied to them here.  ``V_d``: the batch's atom descriptors
+        ``[n_atoms, d_vd]`` for a block built with ``d_vd > 0`` (``ValueError`` when missing, unexpected or misshapen); the block's
+        ``V_d_transform`` is applied to them here, no gradient flows to them.  The step is then K0, the block, ``dmpnn_vd_forward``,
+        the head on ``H_v' = W_d cat(H_v, V_d) + b_d``, ``dmpnn_vd_backward``, the block's backward, clip, Adam — still one call.
 
         A :class:`MulticomponentMPNN`: ``bmg`` is the list of the components' batches, each of the same ``B`` molecules, and ``V_ds``
         ``None`` or a list of ``None`` (``ValueError`` otherwise)."""
@@ -805,6 +824,7 @@ class FusedTrainer:
             # (batch norm would update its running statistics while the block's dropout follows model.training: the two switches
             #  must not disagree — and a training step of a model in eval mode is a bug of the caller, not a mode)
             raise RuntimeError("FusedTrainer.step: the model is in eval mode — call model.train() first")
+        Vd = self._atom_descriptors(V_d, comps[0])
         n_tasks = self.head.n_tasks
         T = engine._f32c(targets, "targets")
         if T.dim() != 2 or T.shape[0] != n_mols or T.shape[1] != n_tasks or not T.is_contiguous():
@@ -848,6 +868,10 @@ class FusedTrainer:
         self.last_route = parts[0]["route"] if len(parts) == 1 else tuple(p["route"] for p in parts)
         self._last_plan_tiles = all(p["plan"].tiles_only for p in parts)
         out, gout = (parts[0]["out"], parts[0]["gout"]) if H_all is None else (H_all, g_all)
+        vd = vd_keep = None
+        if Vd is not None:
+            # the atom-descriptor stage between the block and the head: H_v' / gH_v' [n_atoms, d_h + d_vd] are what the head reads / writes
+            vd, out, gout, vd_keep = self._vd_args(self.mp, Vd, out, gout)
         d_out = int(out.shape[1])
         if self.multi and not self.shared:
             batch = torch.cat([cb.batch + c * n_mols for c, cb in enumerate(comps)])   # (molecule i of component c: c B + i)
@@ -866,7 +890,7 @@ class FusedTrainer:
             hdrop = (float(drop.p), int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
             self.last_head_dropout_seed = hdrop[1]
         h = _lib.HeadArgs()
-        keep = [T, out, gout, batch, parts]
+        keep = [T, out, gout, batch, parts, vd, vd_keep]
         keep += self.head.fill(h, nV_all, n_mols, d_out, batch, T, weights, lt_mask, gt_mask, self._gv, X_d=Xd, ffn_dropout=hdrop)
         bn = self.bn
         t = int(self.layers[-1].out_features)
@@ -883,6 +907,8 @@ class FusedTrainer:
         s.edge_index, s.rev_edge_index, s.batch = p0["edge_index"], p0["rev_edge_index"], p0["batch"]
         s.plan_bytes, s.plan_ready = p0["plan_bytes"], (1 if validate else 0)
         s.bwd, s.head = p0["b"], h
+        if vd is not None:
+            s.vd = C.pointer(vd)
         if len(parts) > 1:
             extra = (_lib.StepComponent * (len(parts) - 1))()
             for e, pc in zip(extra, parts[1:]):
@@ -928,6 +954,55 @@ class FusedTrainer:
             opt.step(lr, clip=None if (clip is None or clip[0] is None or not float(clip[0]) > 0) else (float(clip[0]), clip[1] or "norm"))
         return loss
 
+    def _atom_descriptors(self, V_d: Optional[Tensor], bmg) -> Optional[Tensor]:
+        """``V_d`` through the block's ``V_d_transform`` as fp32 rows ``[n_atoms, d_vd]`` on the device (``None``: a block without
+        ``W_d``); ``ValueError`` when they are missing, unexpected or misshapen — the three refusals of ``X_d``."""
+        W_d = None if self.multi else self.mp.W_d
+        if W_d is None:
+            if V_d is not None:
+                raise ValueError("V_d given, but this model's block takes no atom descriptors (it was built without d_vd)")
+            return None
+        d_vd = int(W_d.in_features - self.mp.W_o.out_features)
+        if V_d is None:
+            raise ValueError(f"this model's block expects {d_vd} atom descriptors per atom (V_d), got none")
+        nV = int(bmg.V.shape[0])
+        if V_d.dim() != 2 or tuple(V_d.shape) != (nV, d_vd):
+            raise ValueError(f"V_d must be [{nV}, {d_vd}], got {tuple(V_d.shape)}")
+        if V_d.device != self.dev:
+            raise ValueError(f"V_d must live on {self.dev}, got {V_d.device}")
+        xt = getattr(self.mp, "V_d_transform", None)
+        with torch.no_grad():
+            V = V_d if xt is None else xt(V_d)
+        V = V.detach()
+        if V.dtype != torch.float32 or V.stride(1) != 1 or tuple(V.shape) != (nV, d_vd):
+            V = V.to(torch.float32).contiguous()
+        return V
+
+    def _vd_args(self, mp, Vd: Tensor, Hv: Tensor, gHv: Tensor) -> tuple:
+        """``dmpnn_vd_args`` of the layer ``W_d`` behind the block's output ``Hv`` (its gradient goes to ``gHv``): allocates ``H_v'``,
+        ``gH_v'`` and the workspace, takes the gradient views of ``W_d`` from the flat buffer (``None`` for a frozen parameter)."""
+        lib = _lib.load()
+        nV, d_h = int(Hv.shape[0]), int(Hv.shape[1])
+        D = int(mp.W_d.out_features)
+        Wd, bd = mp.W_d.weight, mp.W_d.bias
+        if Wd.dtype != torch.float32 or not Wd.is_contiguous() or bd.dtype != torch.float32 or not bd.is_contiguous():
+            raise NotImplementedError("FusedTrainer: W_d must be contiguous float32")
+        out2 = torch.empty(nV, D, dtype=torch.float32, device=self.dev)
+        gout2 = torch.empty(nV, D, dtype=torch.float32, device=self.dev)
+        a = _lib.VdArgs()
+        a.n_atoms, a.d_h, a.d_vd = nV, d_h, D - d_h
+        a.Hv, a.ldhv = Hv.data_ptr(), Hv.stride(0)
+        a.V_d, a.ldvd = Vd.data_ptr(), Vd.stride(0)
+        a.W_d, a.b_d = Wd.data_ptr(), bd.data_ptr()
+        a.out, a.ldout = out2.data_ptr(), out2.stride(0)
+        a.gout, a.ldgout = gout2.data_ptr(), gout2.stride(0)
+        a.gHv, a.ldghv = gHv.data_ptr(), gHv.stride(0)
+        a.gW_d, a.gb_d = self._gv(Wd), self._gv(bd)
+        nb = int(lib.dmpnn_vd_ws_bytes(C.byref(a)))
+        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=self.dev)
+        a.ws, a.ws_bytes = ws.data_ptr(), nb
+        return a, out2, gout2, [Vd, Hv, gHv, ws, Wd, bd]
+
     def _block_args(self, mp, bmg, n_mols: int, act_slope: tuple, validate: bool, out: Optional[Tensor], gout: Optional[Tensor]) -> dict:
         """K0's plan and the argument blocks of one block's forward / backward on ``bmg`` (workspace allocated, nothing enqueued but —
         while the first batches are validated — the plan).  ``out`` / ``gout``: the block's rows of a multicomponent step's H_v / gHv
@@ -953,7 +1028,7 @@ class FusedTrainer:
         level = 1 if (no_mega or oversize is True) else 2
         # (ONE rule for "this training forward runs on the tile plan", the module path's: shapes of the tile kernel — d_h <= 320, even
         #  d_v / d_e —, the environment switches, a plan the library can build; anything else keeps the full plan and the per-step routes)
-        kind = _training_plan_kind(mp, bmg) if (self.tile_plan and not validate and level == 2) else False
+        kind = _training_plan_kind(mp, bmg, vd_outside=True) if (self.tile_plan and not validate and level == 2) else False
         plan = engine.GraphPlan.from_bmg(bmg, light=kind, launch=validate)
         plan.oversize = oversize
         if validate:

@@ -133,13 +133,14 @@ class BondMessagePassing(EngineStateMixin, nn.Module):
         return bond_message_passing_forward(self, bmg, V_d)
 
 
-def _training_plan_kind(mp, bmg, atom: bool = False):
+def _training_plan_kind(mp, bmg, atom: bool = False, vd_outside: bool = False):
     """``"tiles"`` when a TRAINING forward of ``mp`` on ``bmg`` runs on the tile plan (K0 = the tile table alone, kept tensors in the
     caller's edge order, ``DMPNN_F_TILE_PLAN``), else ``False`` (the full CSR plan).  The SHAPE rule is the library's
     (``dmpnn_train_route``, include/dmpnn.h: directed, built-in activation, no ``W_d``, the shapes of the tile kernel, a plan the
     library can build from what the batch carries, at most 30 directed edges per molecule); the host adds only what it alone knows:
     the environment switches, an activation / dropout MODULE the kernels cannot stand in for, the validation window of the module's
-    first batches, whether a gradient of ``W_i`` or ``W_h`` is wanted at all."""
+    first batches, whether a gradient of ``W_i`` or ``W_h`` is wanted at all.  ``vd_outside``: the answer for the block with its
+    ``W_d`` taken out (``FusedTrainer`` runs that layer as a stage of its own behind the block: ``dmpnn_vd_forward``)."""
     if _lib.opt("DMPNN_GENERAL", "0") == "1" or _lib.opt("DMPNN_TRAIN_PLAN", "tiles") == "full":
         return False
     act = classify_activation(mp.tau)[0]
@@ -155,7 +156,7 @@ def _training_plan_kind(mp, bmg, atom: bool = False):
     d_e = int(bmg.E.shape[1]) if atom else d_in - d_v
     batch = getattr(bmg, "batch", None)
     info = engine.train_route(int(bmg.V.shape[0]), int(bmg.E.shape[0]), d_v, d_e, d_h, mp.depth, act,
-                              len(bmg) if hasattr(bmg, "__len__") else 0, undirected=bool(mp.undirected), has_vd=mp.W_d is not None,
+                              len(bmg) if hasattr(bmg, "__len__") else 0, undirected=bool(mp.undirected), has_vd=mp.W_d is not None and not vd_outside,
                               dropout_p=float(mp.dropout.p) if mp.training else 0.0, atom=atom,
                               have_batch=batch is not None and batch.dtype == torch.int64 and batch.is_contiguous(),
                               have_table=getattr(bmg, "tiles", None) is not None, oversize=getattr(bmg, "oversize", None),

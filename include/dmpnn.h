@@ -673,6 +673,32 @@ typedef struct dmpnn_step_component {     /* a further block of a multicomponent
     dmpnn_bwd_args bwd;                     /* bwd.f.out / bwd.gout: this component's rows of head's H_v / gHv (the rows after the
                                                previous component's, same row stride); every block's d_h is head.d_h             */
 } dmpnn_step_component;
+
+/* The atom-descriptor layer behind a block's finalize step (message_passing/base.py: H_v' = W_d cat(H_v, V_d) + b_d, no activation)
+ * as a stage of its own (dmpnn_vd.hip): the block in front of it is then the plain W_d-free block.  The forward and the data
+ * gradient: f16 matrix pipe, exact 3-term operand split, fp32 accumulation, at every shape.  The weight gradient gW_d / gb_d is
+ * dmpnn_linear_wgrad's product: on the f16 pipe (operand split, product, reduce) from 1 024 atoms on when d_h + d_vd, ldhv, ldvd and
+ * ldgout are even and the operands 8-byte aligned; otherwise its fp32 kernel plus the reduce (fp32-class either way).  Any d_vd >= 1 and any leading dimension >= its width (operands are read element by element and
+ * zero-padded inside the split: odd widths and unaligned row strides included); d_h + d_vd <= DMPNN_VD_MAX_WIDTH, else DMPNN_EINVAL.
+ * No gradient flows to V_d.  forward reads Hv V_d W_d b_d, writes out; backward reads gout Hv V_d W_d, writes gHv and (when not
+ * NULL) gW_d [d_h+d_vd, d_h+d_vd] dense and gb_d.  n_atoms == 0: the requested gradients are zeroed.  Every argument check runs
+ * before any device work. */
+#define DMPNN_VD_MAX_WIDTH 544
+typedef struct dmpnn_vd_args {
+    int64_t n_atoms, d_h, d_vd;            /* rows; width of H_v; width of V_d (>= 1)                    */
+    const float* Hv;  int64_t ldhv;        /* [n_atoms, d_h]   the block's output                        */
+    const float* V_d; int64_t ldvd;        /* [n_atoms, d_vd]  already through V_d_transform             */
+    const float* W_d; const float* b_d;    /* [d_h+d_vd, d_h+d_vd] nn.Linear layout; [d_h+d_vd]          */
+    float* out; int64_t ldout;             /* [n_atoms, d_h+d_vd]  = cat(Hv, V_d) . W_d^T + b_d (no act) */
+    const float* gout; int64_t ldgout;     /* backward: dL/dout                                          */
+    float* gHv; int64_t ldghv;             /* backward: dL/dHv [n_atoms, d_h] = gout . W_d[:, :d_h]      */
+    float* gW_d; float* gb_d;              /* backward: out, or NULL (not wanted)                        */
+    void* ws; size_t ws_bytes;             /* >= dmpnn_vd_ws_bytes()                                     */
+} dmpnn_vd_args;
+size_t dmpnn_vd_ws_bytes(const dmpnn_vd_args* a);
+int dmpnn_vd_forward(const dmpnn_vd_args* a, void* stream);
+int dmpnn_vd_backward(const dmpnn_vd_args* a, void* stream);
+
 typedef struct dmpnn_step_args {
     const int64_t* edge_index; const int64_t* rev_edge_index; const int64_t* batch; size_t plan_bytes; int32_t plan_ready;
     int32_t stages;
@@ -685,6 +711,13 @@ typedef struct dmpnn_step_args {
                                                (component 0 is the fields above); each block's K0 and forward, the head once on the
                                                merged batch, each block's backward.  n_extra = 0 with head.n_components > 1: ONE shared
                                                block over the merged batch (the components' graphs as one BatchMolGraph)             */
+    const dmpnn_vd_args* vd;                /* v15 growth: NULL (what an older caller passes): none.  Else the atom-descriptor layer between
+                                               the block and the head: K0 -> block forward into vd->Hv -> dmpnn_vd_forward -> the head on
+                                               vd->out -> dmpnn_vd_backward into bwd.gout -> block backward -> update.  Requires
+                                               bwd.f.W_d == NULL, bwd.f.out == vd->Hv, bwd.gout == vd->gHv, head.gHv == vd->gout,
+                                               head.d_h == bwd.f.d_h + vd->d_vd, equal atom counts, n_extra == 0, head.n_components <= 1.
+                                               Staged: the layer's forward belongs to DMPNN_STEP_FORWARD, its backward to
+                                               DMPNN_STEP_BACKWARD (its gradients lie in the block's slice of the flat buffer) */
 } dmpnn_step_args;
 int dmpnn_train_step(const dmpnn_step_args* a, void* stream);
 
