@@ -234,6 +234,18 @@ int dmpnn_update_fwd(const void* plan, int64_t n_atoms, int64_t n_edges, int64_t
     DMPNN_CHECK_ARG(n_edges == 0 || (M && H0 && W_h), "update_fwd: null tensor");
     DMPNN_CHECK_ARG(M_next || Mv || H_out, "update_fwd: no output");
     DMPNN_CHECK_ARG(act != DMPNN_ACT_PRELU || act_slope_ptr, "update_fwd: PReLU needs act_slope_ptr");
+    // the documented shapes, before anything is written: the contraction behind it would take some of the others on a narrower
+    // operand path (8-byte rows of M) and read a leading dimension below d_h as it is
+    DMPNN_CHECK_ARG(d_h % 4 == 0 && d_h <= 320, "update_fwd: d_h must be a multiple of 4 and <= 320 (got %lld)", (long long)d_h);
+    {
+        const struct { const void* p; int64_t ld; const char* name; } t[] = {
+            {M, ld_m, "M"}, {H0, ld_h0, "H0"}, {H_out, ld_hout, "H_out"}, {M_next, ld_mnext, "M_next"}, {Mv, ld_mv, "Mv"}};
+        for (const auto& x : t)
+            DMPNN_CHECK_ARG(!x.p || (x.ld >= d_h && x.ld % 4 == 0 && aligned16(x.p)),
+                            "update_fwd: %s must be 16-byte aligned with a leading dimension >= d_h that is a multiple of 4 (ld %lld)", x.name,
+                            (long long)x.ld);
+        DMPNN_CHECK_ARG(!W_h || aligned16(W_h), "update_fwd: W_h must be 16-byte aligned");
+    }
     if (n_edges == 0) {
         if (Mv && n_atoms > 0) {
             for (int64_t v = 0; v < n_atoms; ++v)

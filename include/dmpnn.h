@@ -284,7 +284,8 @@ int dmpnn_linear16_fwd(const dmpnn_gemm_args* a, void* wsplit, size_t wsplit_byt
  *     Mv[v]   = S[v]                                                        base.py:208-211   (if Mv)
  * Rows are the plan's CSR-row order (row i = edge perm[i]); the segment sums are formed from the
  * LDS-resident output tile in the epilogue of the fp32-MFMA contraction.  H_out may be NULL
- * (inference).  Needs d_h % 4 == 0, d_h <= 320, 16-byte aligned tensors, ld % 4 == 0.            */
+ * (inference).  Needs d_h % 4 == 0, d_h <= 320, 16-byte aligned tensors, ld % 4 == 0, ld >= d_h;
+ * anything else is DMPNN_EINVAL before a byte is written.                                        */
 int dmpnn_update_fwd(const void* plan, int64_t n_atoms, int64_t n_edges, int64_t d_h,
                      const float* M, int64_t ld_m, const float* H0, int64_t ld_h0,
                      const float* W_h, const float* b_h,

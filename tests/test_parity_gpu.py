@@ -997,6 +997,48 @@ def test_custom_activation_and_dropout_rows_route(gpu_device):
     assert parity_err(out.cpu().numpy(), ref.numpy()) <= TOL
 
 
+@pytest.mark.parametrize("n_mols,d_h,depth,bias", [(8, 64, 3, True), (8, 30, 2, False), (64, 64, 3, False)],
+                         ids=["qm9x8-h64-bias", "qm9x8-h30-scalar-paths", "qm9x64-h64-wgrad-f16"])
+def test_custom_activation_rows_route_gradients(n_mols, d_h, depth, bias, gpu_device):
+    """An ``nn.Module`` activation in training mode: the block runs on the row-level autograd functions of
+    ``chemprop_amd/backward.py`` (``dmpnn_linear_wgrad``, ``dmpnn_message_bwd``, ``dmpnn_aggregate_bwd`` and the forward kernels'
+    transposes).  Every parameter gradient of ``(out * G).sum()`` against autograd through the oracle in float64, unfloored, with the
+    float32 run of the same oracle as the yardstick (``rows_harness.compare``).  ``d_h = 30``: every row kernel on its scalar path;
+    64 molecules: more than 1 024 edge rows, the weight gradients of ``W_i`` and ``W_h`` on the f16 pipe."""
+    import rows_harness as rh
+    from chemprop_amd import synth
+    from chemprop_amd.nn import BondMessagePassing
+
+    bmg = synth.random_batch(n_mols, "qm9", seed=5)
+    assert (int(bmg.E.shape[0]) > 1024) == (n_mols == 64)
+    torch.manual_seed(5)
+    mp = BondMessagePassing(d_h=d_h, depth=depth, bias=bias, activation=torch.nn.Softplus(), dropout=0.0).train()
+    G = torch.randn(int(bmg.V.shape[0]), d_h, generator=torch.Generator().manual_seed(6))
+    names = [k for k, _ in mp.named_parameters()]
+
+    def oracle(dtype):
+        p = {k: v.detach().to(dtype).requires_grad_() for k, v in mp.named_parameters()}
+        w = ot.MPWeights(p["W_i.weight"], p["W_h.weight"], p["W_o.weight"], p["W_o.bias"], p.get("W_i.bias"), p.get("W_h.bias"))
+        out = ot.forward(bmg.V.to(dtype), bmg.E.to(dtype), bmg.edge_index, bmg.rev_edge_index, w, depth=depth,
+                         activation=torch.nn.functional.softplus)
+        (out * G.to(dtype)).sum().backward()
+        return out.detach(), {k: v.grad for k, v in p.items()}
+
+    out64, g64 = oracle(torch.float64)
+    out32, g32 = oracle(torch.float32)
+    mp = mp.to(gpu_device)
+    bmg.to(gpu_device)
+    out = mp(bmg)
+    (out * G.to(gpu_device)).sum().backward()
+    assert all(p.grad is not None for p in mp.parameters())
+    got = {k: p.grad.cpu() for k, p in mp.named_parameters()}
+    assert sorted(got) == sorted(names) and (("W_h.bias" in got) == bias)
+    cid = f"softplus-rows-route-{n_mols}x-h{d_h}"
+    fails = rh.compare(cid, dict(out=out.detach().cpu()), dict(out=out64), rh.yardstick(dict(out=out64), dict(out=out32)), "fwd")
+    fails += rh.compare(cid, got, g64, rh.yardstick(g64, g32), "grad")
+    assert not fails, "; ".join(fails)
+
+
 # ------------------------------------------------------------------------------------------------
 # K6: gradients
 # ------------------------------------------------------------------------------------------------
