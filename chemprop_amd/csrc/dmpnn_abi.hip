@@ -222,6 +222,7 @@ int dmpnn_aggregate_fwd(const void* plan, int64_t n_atoms, int64_t n_edges, int6
 int dmpnn_linear_fwd(const dmpnn_gemm_args* a, void* stream) {
     DMPNN_CHECK_ARG(a != nullptr, "linear_fwd: null args");
     DMPNN_CHECK_ARG(a->act != DMPNN_ACT_PRELU || a->act_slope_ptr, "linear_fwd: PReLU needs act_slope_ptr");
+    if (a->M > 0 && a->N > 0 && a->K1 >= 0 && a->K2 >= 0) DMPNN_TRY(check_linear_lds(*a, "linear_fwd"));
     return launch_linear(*a, static_cast<hipStream_t>(stream));
 }
 

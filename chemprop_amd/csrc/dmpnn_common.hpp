@@ -405,4 +405,16 @@ int vd_backward_impl(const dmpnn_vd_args* a, void* stream, bool split_ready);
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// The leading dimensions of a contraction call against the widths they carry (the C entries dmpnn_linear_fwd / dmpnn_linear16_fwd,
+// before anything is launched): a row stride below its width makes rows overlap — reads of the wrong entries, stores over other rows.
+inline int check_linear_lds(const dmpnn_gemm_args& a, const char* who) {
+    const struct { bool live; int64_t ld, width; const char* name; } t[] = {
+        {a.K1 > 0, a.lda1, a.K1, "lda1 < K1"},       {a.K2 > 0, a.lda2, a.K2, "lda2 < K2"},   {true, a.ldw, a.K1 + a.K2, "ldw < K1 + K2"},
+        {a.Cadd != nullptr, a.ldcadd, a.N, "ldcadd < N"}, {a.C != nullptr, a.ldc, a.N, "ldc < N"}, {a.Zpre != nullptr, a.ldz, a.N, "ldz < N"}};
+    for (const auto& x : t)
+        DMPNN_CHECK_ARG(!x.live || x.ld >= x.width, "%s: leading dimension below its width (%s: %lld < %lld)", who, x.name, (long long)x.ld,
+                        (long long)x.width);
+    return DMPNN_OK;
+}
+
 }  // namespace dmpnn

@@ -49,6 +49,7 @@ bool linear16_ok(const dmpnn_gemm_args& a) {
     auto ok8 = [](const void* p, int64_t ld) { return p == nullptr || ((reinterpret_cast<uintptr_t>(p) & 7u) == 0 && ld % 2 == 0); };
     if (!ok8(a.A1, a.lda1) || !ok8(a.A2, a.lda2)) return false;
     if (a.K1 == 0) return false;  // (single operand in the A2 slot: the caller swaps it into A1)
+    if (!a.A1 || (a.K2 > 0 && !a.A2)) return false;  // a live width needs its operand (dmpnn_linear_fwd refuses the same call)
     if (a.M >= (int64_t(1) << 31) / 64 * 48) return false;
     if (a.gather1 && a.gather1_rows * a.lda1 * 4 > 0x7FFFFFFF) return false;
     return true;
@@ -61,7 +62,8 @@ int launch_linear16(const dmpnn_gemm_args& a, const mega16::SplitW& W, const int
     memset(&g, 0, sizeof(g));
     g.M = (int)a.M; g.N = (int)a.N; g.K1 = (int)a.K1; g.K2 = (int)a.K2;
     g.A1 = a.A1; g.lda1 = (int)a.lda1; g.gather1 = a.gather1;
-    g.a1_bytes = a.gather1 ? (unsigned)(a.gather1_rows * a.lda1 * 4) : 0u;
+    // gather1_rows <= 0: the rows of the source are unknown, no index is out of range (as launch_linear_ex has it)
+    g.a1_bytes = a.gather1 ? (a.gather1_rows > 0 ? (unsigned)(a.gather1_rows * a.lda1 * 4) : 0x7FFFFFFFu) : 0u;
     g.A2 = a.K2 ? a.A2 : nullptr; g.lda2 = (int)a.lda2;
     g.W = W; g.bias = a.bias; g.Cadd = a.Cadd; g.ldcadd = (int)a.ldcadd;
     g.C = a.C; g.ldc = (int)a.ldc; g.Zpre = a.Zpre; g.ldz = (int)a.ldz;
@@ -180,6 +182,14 @@ int dmpnn_linear16_fwd(const dmpnn_gemm_args* a, void* wsplit, size_t wsplit_byt
     }
     const int64_t K = g.K1 + g.K2;
     DMPNN_CHECK_ARG(wsplit && wsplit_bytes >= linear16_wsplit_bytes(g.N, K), "linear16: wsplit workspace missing or too small");
+    // everything that can refuse the call, before the weight split writes into wsplit
+    if (g.M > 0) {
+        DMPNN_CHECK_ARG(g.C || g.Zpre, "linear16: no output");
+        DMPNN_CHECK_ARG(g.A1, a->K1 > 0 ? "linear16: null A1 with K1 > 0" : "linear16: null A2 with K2 > 0");
+        DMPNN_CHECK_ARG(g.K2 == 0 || g.A2, "linear16: null A2 with K2 > 0");
+        DMPNN_TRY(check_linear_lds(g, "linear16"));
+        DMPNN_CHECK_ARG(linear16_ok(g), "linear16: shapes / alignment not supported by the split kernel");
+    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     mega16::SplitW W;
     if (!wsplit_ready) {

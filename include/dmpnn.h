@@ -254,7 +254,15 @@ int dmpnn_aggregate_fwd(const void* plan, int64_t n_atoms, int64_t n_edges, int6
  *   K3  base.py:135-141   A1 = M, W = W_h, Cadd = H0                        act = tau
  *   K5  base.py:180-183   A1 = V, A2 = Mv, W = W_o, bias = b_o              act = tau
  *       base.py:185-188   A1 = H_v, A2 = V_d, W = W_d, bias = b_d           act = none
- * Zpre (optional) receives the pre-activation (needed by the backward of PReLU / custom tau).   */
+ * Zpre (optional) receives the pre-activation (needed by the backward of PReLU / custom tau).
+ * Leading dimensions count floats and are at least the width they carry: lda1 >= K1 (when K1 > 0), lda2 >= K2 (when
+ * K2 > 0), ldw >= K1 + K2, and ldcadd / ldc / ldz >= N for each of Cadd / C / Zpre that is given; a smaller one is
+ * DMPNN_EINVAL before anything is launched or written (dmpnn_linear_fwd and dmpnn_linear16_fwd, its wsplit included).
+ * M == 0 is DMPNN_OK and writes no output; at least one of C and Zpre must be given.
+ * gather1: int32 row indices into A1, one per output row.  An index >= gather1_rows reads a row of ZEROS (the hardware
+ * range check of the operand's buffer descriptor; nothing behind the gather1_rows x lda1 floats of A1 is touched), so
+ * the output row is that of A1's part absent; with gather1_rows == 0 (unknown) no index is out of range and every
+ * index must be valid.  Indices are not negative.                                                                */
 typedef struct dmpnn_gemm_args {
     int64_t M, N, K1, K2;
     const float* A1; int64_t lda1; const int32_t* gather1; /* gather1 may be NULL                */
@@ -272,8 +280,9 @@ int dmpnn_linear_fwd(const dmpnn_gemm_args* a, void* stream);
 /* The same contraction on the f16 matrix pipe with the exact 3-term operand split (x s = hi + lo, fp32 accumulate:
  * fp32-class accuracy, see DMPNN_F_SPLIT16).  `wsplit` (>= dmpnn_linear16_wsplit_bytes(N, K1 + K2) bytes, caller-owned)
  * receives the pre-split weights; wsplit_ready != 0: it still holds them from an earlier call with the same W.
- * dmpnn_linear16_ok: 1 when the shapes / alignments are taken (even K1, K2 and row strides, 8-byte aligned operands),
- * else the caller stays on dmpnn_linear_fwd.                                                                    */
+ * dmpnn_linear16_ok: 1 when the shapes / alignments are taken (even K1, K2 and row strides, 8-byte aligned operands,
+ * a non-NULL operand for every live width, a gathered A1 below 2 GiB), else the caller stays on dmpnn_linear_fwd;
+ * dmpnn_linear16_fwd refuses what it refuses (DMPNN_EINVAL) before the weight split writes into wsplit.          */
 size_t dmpnn_linear16_wsplit_bytes(int64_t N, int64_t K);
 int dmpnn_linear16_ok(const dmpnn_gemm_args* a);
 int dmpnn_linear16_fwd(const dmpnn_gemm_args* a, void* wsplit, size_t wsplit_bytes, int wsplit_ready, void* stream);

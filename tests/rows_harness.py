@@ -10,9 +10,12 @@ Three layers:
   0: 16-byte).  The padding columns of an input hold NaN (whatever reads them into a sum shows); an output lives in a buffer
   prefilled with one NaN bit pattern, and ``Mat.read`` fails unless every word outside ``[rows, width]`` — padding columns, the
   words before the pointer, a guard region behind the last row — still holds it bit for bit.
+* ``run_linear`` / ``run_segment_fwd``: the forward counterparts — ``dmpnn_linear_fwd``, ``dmpnn_linear16_fwd`` (+ ``_ok``,
+  ``_wsplit_bytes``), ``dmpnn_message_fwd``, ``dmpnn_aggregate_fwd`` — the same way (``tests/test_forward_rows_boundaries.py``), with
+  ``linear_build`` / ``linear16_build``: the dispatch rules restated, to label a case by the kernel build it runs.
 * ``degree_graph`` / ``chain_graph`` / ``csr_tables``: small symmetric molecular graphs (``BatchMolGraph.from_tensors``) with
   prescribed in-degrees, and the stable incoming-edge CSR the plan builds (``GraphPlan.arrays()`` on the device).
-* ``wgrad_ref`` / ``message_bwd_ref`` / ``update_ref`` / ``compare``: the references in float64 — each runnable in float32 as the
+* ``wgrad_ref`` / ``message_bwd_ref`` / ``update_ref`` / ``linear_ref`` / ``segment_fwd_ref`` / ``compare``: the references in float64 — each runnable in float32 as the
   yardstick, what plain fp32 PyTorch gives on the very same inputs — and the rule of ``head_harness.compare`` restated for named
   tensors: unfloored error within ``min(MARGIN max(e32, 2**-23), cap)``.
 """
@@ -307,6 +310,216 @@ def run_update(dev, plan, inp, act, outputs=("H_out", "M_next", "Mv"), d_h=None,
                        outs["M_next"].ld, p("Mv"), outs["Mv"].ld, _lib.ACT[act], LEAKY_SLOPE if act == "leakyrelu" else 0.0,
                        slope_t.data_ptr() if slope_t is not None else None)
     return rc, msg, outs
+
+
+# ---- dmpnn_linear_fwd / dmpnn_linear16_fwd -------------------------------------------------------------------------------------------
+LINEAR_ACTS = ("none", "relu", "leakyrelu", "prelu", "tanh", "elu")
+SIMPLE_ACTS = ("none", "relu", "leakyrelu", "prelu")   # one branch-free formula in the fp32 kernel's epilogue; exact on load in k_segment
+LINEAR_TENSORS = ("A1", "A2", "W", "Cadd", "C", "Zpre")
+DECOY_SLOPE = 0.7   # what ``act_slope`` holds when the slope travels through ``act_slope_ptr``: the pointer has to win
+
+
+def act_slope(act):
+    return {"leakyrelu": LEAKY_SLOPE, "prelu": PRELU_SLOPE, "relu": 0.0, "none": 1.0}.get(act)
+
+
+def linear_inputs(M, N, K1, K2, n_src=None, seed=0, graded=None, bias=True, cadd=True):
+    """float32 CPU operands of ``C = tau([A1[g] || A2] W^T + bias + Cadd)``: row ``n`` of ``W`` (``nn.Linear``'s range) scaled by
+    ``1 + n / N``, column ``k`` of ``[A1 || A2]`` by ``1 + k / K`` (a transposed, shifted or swapped tile cannot pass); ``K1 == 0``:
+    the single operand sits in the ``A2`` slot; ``n_src``: ``A1`` has that many rows and ``gather`` (int32, repeating) picks ``M`` of
+    them.  ``graded``: ``"rows"`` scales row ``r`` of the operands by ``2**-(r % 16)``; ``("groups", width, exps)`` scales the columns
+    ``[g width, (g + 1) width)`` of ``[A1 || A2]`` by ``2**exps[g]`` (``None``: that group is all zero)."""
+    gen = torch.Generator().manual_seed(4242 + seed)
+    K = K1 + K2
+    k = 1.0 / math.sqrt(K)
+    W = (2 * torch.rand(N, K, generator=gen) - 1) * k * (1 + torch.arange(N).float() / N).view(-1, 1)
+    col = 1 + torch.arange(K).float() / K
+    if isinstance(graded, tuple):
+        _, width, exps = graded
+        assert len(exps) == -(-K // width), (K, width, exps)
+        col = col * torch.tensor([0.0 if e is None else 2.0 ** e for e in exps]).repeat_interleave(width)[:K]
+    rows = (lambda n: (2.0 ** -(torch.arange(n) % 16).float()).view(-1, 1)) if graded == "rows" else (lambda n: 1.0)
+    A1 = A2 = gather = None
+    if n_src is not None:
+        assert K1 > 0
+        A1 = torch.randn(n_src, K1, generator=gen) * col[:K1] * rows(n_src)
+        gather = torch.randint(0, n_src, (M,), generator=gen, dtype=torch.int32)
+    elif K1:
+        A1 = torch.randn(M, K1, generator=gen) * col[:K1] * rows(M)
+    if K2:
+        A2 = torch.randn(M, K2, generator=gen) * col[K1:] * rows(M)
+    return dict(M=M, N=N, K1=K1, K2=K2, A1=A1, A2=A2, gather=gather, W=W, bias=(2 * torch.rand(N, generator=gen) - 1) * k if bias else None,
+                Cadd=torch.randn(M, N, generator=gen) if cadd else None)
+
+
+def linear_ref(inp, act, dtype=torch.float64):
+    """``Zpre = [A1[g] || A2] W^T + bias + Cadd`` and ``C = tau(Zpre)`` in ``dtype`` on the CPU.  A gather index equal to the number
+    of source rows stands for a row of zeros (``include/dmpnn.h``: an index beyond ``gather1_rows`` reads zeros)."""
+    f = lambda t: None if t is None else t.to(dtype)
+    parts = []
+    if inp["A1"] is not None:
+        a = f(inp["A1"])
+        if inp["gather"] is not None:
+            a = torch.cat((a, torch.zeros(1, a.shape[1], dtype=dtype)))[inp["gather"].long()]
+        parts.append(a)
+    if inp["A2"] is not None:
+        parts.append(f(inp["A2"]))
+    Z = torch.nn.functional.linear(torch.cat(parts, 1), f(inp["W"]), f(inp["bias"]))
+    if inp["Cadd"] is not None:
+        Z = Z + f(inp["Cadd"])
+    return dict(C=ot.activation_fn(act, torch.tensor([PRELU_SLOPE], dtype=dtype))(Z), Zpre=Z)
+
+
+def linear_layout(inp, ld=None, off=None):
+    """(ld, off) of the six tensors of a contraction call, the defaults (dense, aligned) filled in."""
+    K = inp["K1"] + inp["K2"]
+    width = dict(A1=inp["K1"], A2=inp["K2"], W=K, Cadd=inp["N"], C=inp["N"], Zpre=inp["N"])
+    ld, off = dict(ld or {}), dict(off or {})
+    assert set(ld) <= set(width) and set(off) <= set(width), (ld, off)
+    return {k: ld.get(k, width[k]) for k in width}, {k: off.get(k, 0) for k in width}
+
+
+def run_linear(dev, inp, act="none", pipe="f32", want=("C", "Zpre"), ld=None, off=None, slope_ptr=False, gather_rows=None, a1_tail=0,
+               wsplit_ready=0, ws=None, ws_short=0, override=None):
+    """One ``dmpnn_linear_fwd`` (``pipe == "f32"``) or ``dmpnn_linear16_fwd`` (``"f16"``) call.  ``ld`` / ``off``: per tensor of
+    ``LINEAR_TENSORS``; ``slope_ptr``: the slope travels through ``act_slope_ptr`` (``act_slope`` holds a decoy; PReLU always does);
+    ``gather_rows``: what ``gather1_rows`` says (default: the rows of ``A1``); ``a1_tail``: NaN rows stored behind the source rows;
+    ``ws``: the workspace of an earlier call (else exactly ``dmpnn_linear16_wsplit_bytes`` bytes, less ``ws_short``, at the front of
+    a larger ``0xA5`` allocation); ``override``: fields of ``dmpnn_gemm_args`` set after everything else (argument-error cases)."""
+    lib = _lib.load()
+    M, N, K1, K2 = inp["M"], inp["N"], inp["K1"], inp["K2"]
+    lds, offs = linear_layout(inp, ld, off)
+    mk = lambda k, rows, width, data=None: Mat(dev, rows, width, lds[k], offs[k], data)
+    m1 = m2 = mc = None
+    if K1:
+        a1 = inp["A1"] if not a1_tail else torch.cat((inp["A1"], torch.full((a1_tail, K1), float("nan"))))
+        m1 = mk("A1", int(a1.shape[0]), K1, a1)
+    if K2:
+        m2 = mk("A2", M, K2, inp["A2"])
+    mw = mk("W", N, K1 + K2, inp["W"])
+    if inp["Cadd"] is not None:
+        mc = mk("Cadd", M, N, inp["Cadd"])
+    outs = dict(C=mk("C", M, N), Zpre=mk("Zpre", M, N))
+    gi = inp["gather"].to(dev) if inp["gather"] is not None else None
+    b = inp["bias"].to(dev) if inp["bias"] is not None else None
+    use_ptr = slope_ptr or act == "prelu"
+    st = torch.tensor([act_slope(act) or 0.0], device=dev) if use_ptr else None
+    g = _lib.GemmArgs()
+    g.M, g.N, g.K1, g.K2 = M, N, K1, K2
+    if m1 is not None:
+        g.A1, g.lda1 = m1.ptr, m1.ld
+    if gi is not None:
+        g.gather1, g.gather1_rows = gi.data_ptr(), int(inp["A1"].shape[0]) if gather_rows is None else gather_rows
+    if m2 is not None:
+        g.A2, g.lda2 = m2.ptr, m2.ld
+    g.W, g.ldw = mw.ptr, mw.ld
+    g.bias = b.data_ptr() if b is not None else None
+    if mc is not None:
+        g.Cadd, g.ldcadd = mc.ptr, mc.ld
+    if "C" in want:
+        g.C, g.ldc = outs["C"].ptr, outs["C"].ld
+    if "Zpre" in want:
+        g.Zpre, g.ldz = outs["Zpre"].ptr, outs["Zpre"].ld
+    g.act = _lib.ACT[act]
+    g.act_slope = DECOY_SLOPE if use_ptr else (act_slope(act) or 0.0)
+    g.act_slope_ptr = st.data_ptr() if st is not None else None
+    for k, v in (override or {}).items():
+        setattr(g, k, v)
+    res = dict(outs=outs, ws=None, ws_bytes=0, ws_tail_ok=True, ws_pristine=True, keep=(m1, m2, mw, mc, gi, b, st))
+    if pipe == "f16":
+        nb = int(lib.dmpnn_linear16_wsplit_bytes(N, K1 + K2))
+        if ws is None:
+            ws = torch.full((nb + 4096,), 0xA5, dtype=torch.uint8, device=dev)
+        assert ws.numel() == nb + 4096
+        rc, msg, launches = _call(dev, lib.dmpnn_linear16_fwd, C.byref(g), ws.data_ptr(), nb - ws_short, wsplit_ready)
+        res.update(ws=ws, ws_bytes=nb, ws_tail_ok=bool((ws[nb - ws_short:] == 0xA5).all()), ws_pristine=bool((ws == 0xA5).all()))
+    else:
+        rc, msg, launches = _call(dev, lib.dmpnn_linear_fwd, C.byref(g))
+    res.update(rc=rc, msg=msg, launches=launches)
+    return res
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def linear_g(inp, ld=None, off=None, want=("C", "Zpre")):
+    """``pick_g`` and the ``vec_c`` rule of ``launch_linear_ex`` restated -> (G, has_a2) of a call (labels and the coverage check
+    only).  An element offset of 0 / 2 / 1 is a 16- / 8- / 4-byte aligned pointer."""
+    lds, offs = linear_layout(inp, ld, off)
+    N, K1, K2 = inp["N"], inp["K1"], inp["K2"]
+    al = lambda k, B: (4 * offs[k]) % B == 0
+    a1, a2 = ("A1", "A2") if K1 else ("A2", "A1")   # K1 == 0: the single operand is moved into the A1 slot
+    if not K1:
+        K1, K2 = K2, 0
+    has_a2 = K2 > 0
+    if not (N % 4 == 0 and all(lds[k] % 4 == 0 and al(k, 16) for k in want)):
+        return 1, has_a2
+    for G in (4, 2):
+        ok = K1 % G == 0 and K2 % G == 0 and lds["W"] % G == 0 and al("W", 4 * G) and lds[a1] % G == 0 and al(a1, 4 * G)
+        if has_a2:
+            ok = ok and lds[a2] % G == 0 and al(a2, 4 * G)
+        if inp["Cadd"] is not None:
+            ok = ok and lds["Cadd"] % G == 0 and al("Cadd", 4 * G) and N % G == 0
+        if ok:
+            return G, has_a2
+    return 1, has_a2
+
+
+def linear_build(M, N, G, has_a2):
+    """``pick_wn`` / ``pick_rt`` of ``csrc/dmpnn_gemm.hip`` restated -> ``(RT, WN, variant)`` of ``k_gemm<RT, WN, G, HAS_A2, EPI_PLAIN>``;
+    variant: ``G4`` (one operand), ``G4+A2``, ``G2``, ``G1`` (the last two are two-operand builds whatever ``has_a2``)."""
+    cost = {wn: _cdiv(N, 64 * wn) * wn for wn in (5, 4, 2, 1)}
+    wn = min((5, 4, 2, 1), key=lambda w: (cost[w], -w))          # the first of 5, 4, 2, 1 with the least padded width
+    row_tiles = _cdiv(M, 16)
+    if row_tiles * _cdiv(N, 64 * wn) <= 128:                     # a short matrix: one workgroup per 64-column slice
+        wn = next((w for w in (1, 2, 4) if w < wn and cost[w] == cost[wn] and row_tiles * _cdiv(N, 64 * w) <= 512), wn)
+    ncb = _cdiv(N, 64 * wn)
+    rt, best = 3, float("inf")
+    for r in (3, 2, 1):
+        c = _cdiv(_cdiv(M, 16 * r) * ncb, 256) * (r + 0.3)
+        if c < best - 1e-9:
+            rt, best = r, c
+    if rt == 2 and G != 4:
+        rt = 3
+    return rt, wn, ("G4+A2" if has_a2 else "G4") if G == 4 else f"G{G}"
+
+
+def linear16_build(M, N):
+    """The ``WN`` / ``one_group`` rule of ``launch_linear16`` restated -> ``(WN, GC)`` of ``k_rows16<WN, GC>``."""
+    col_blocks = _cdiv(N, 320)
+    return _cdiv(N, 64 * col_blocks), 12 if _cdiv(M, 48) * col_blocks <= 512 else 4
+
+
+# ---- dmpnn_message_fwd / dmpnn_aggregate_fwd -------------------------------------------------------------------------------------------
+def segment_fwd_ref(bmg, Hin, which, act="none", undirected=False, dtype=torch.float64):
+    """``M = message(H')`` (``which == "message"``) or ``Mv = segment_sum_dst(H')`` (``"aggregate"``) of ``H' = tau(Hin)``, averaged
+    with its reverse row when ``undirected`` — ``oracle.dmpnn_torch`` in ``dtype``, incoming rows added in increasing edge id."""
+    src, dst = bmg.edge_index
+    nV = int(bmg.V.shape[0])
+    H = ot.activation_fn(act, torch.tensor([PRELU_SLOPE], dtype=dtype))(Hin.to(dtype))
+    if undirected:
+        H = (H + H[bmg.rev_edge_index]) / 2
+    return ot.message(H, src, dst, bmg.rev_edge_index, nV) if which == "message" else ot.segment_sum_dst(H, dst, nV)
+
+
+def run_segment_fwd(dev, plan, which, Hin, act="none", slope=0.0, slope_ptr=None, undirected=False, ld_in=None, ld_out=None, off_in=0,
+                    off_out=0):
+    """``dmpnn_message_fwd`` (``which == "message"`` -> ``M [E, h]``) or ``dmpnn_aggregate_fwd`` (``"aggregate"`` -> ``Mv [V, h]``) on
+    ``Hin [E, h]`` -> (rc, msg, the output ``Mat``).  ``slope_ptr``: a value placed on the device for ``act_slope_ptr``."""
+    lib = _lib.load()
+    h = int(Hin.shape[1])
+    mi = Mat(dev, int(Hin.shape[0]), h, ld_in, off_in, Hin)
+    mo = Mat(dev, plan.n_edges if which == "message" else plan.n_atoms, h, ld_out, off_out)
+    st = torch.tensor([slope_ptr], device=dev) if slope_ptr is not None else None
+    sp = st.data_ptr() if st is not None else None
+    head = (plan.buf.data_ptr(), plan.n_atoms, plan.n_edges, h, mi.ptr, mi.ld, mo.ptr, mo.ld, _lib.ACT[act], slope, sp)
+    if which == "message":
+        rc, msg, _ = _call(dev, lib.dmpnn_message_fwd, *head, _lib.F_UNDIRECTED if undirected else 0)
+    else:
+        assert not undirected, "dmpnn_aggregate_fwd has no flags"
+        rc, msg, _ = _call(dev, lib.dmpnn_aggregate_fwd, *head)
+    return rc, msg, mo
 
 
 # ---- the comparison ------------------------------------------------------------------------------------------------------------------
