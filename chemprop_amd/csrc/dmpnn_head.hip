@@ -1686,6 +1686,42 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     //  SLOWER, profiles/r03_side_stream_ab.txt.  One stream.)
     return molagg_bwd_rows(gZ, ldgz, h.batch, nV, dc, nBt, ws + L.bounds, h.agg_mode, h.agg_norm, h.gHv, h.ldg, B, stream);
 }
+
+constexpr AggRide kNoAggRide = {nullptr, 0, nullptr, nullptr, 0, 0, 0.f, false};
+
+// (round 6: on a tile plan built in the step from the batch vector, the tile kernels' launches are bounded by the batch's molecule count — a
+//  tile holds at least one molecule — instead of the layout's bound: 512 instead of 745 workgroups at 512 molecules, forward and backward;
+//  a plan that turns out to hold more tiles than that comes back NaN from both kernels)
+void bound_tile_launch(dmpnn_fwd_args& f, int64_t n_mols) {
+    if ((f.flags & DMPNN_F_TILE_PLAN) && f.n_tiles_launch == 0 && n_mols > 0) f.n_tiles_launch = n_mols;
+}
+
+// One component of a training step (`c`: dmpnn_step_args for component 0, a dmpnn_step_component for `comp` > 0): K0 unless its plan is
+// ready, then the keeping forward `f` — with DMPNN_F_WSPLIT_READY when the weight pre-split rode in K0's launch.  `mb` / `mb_mols`: the
+// aggregation's bounds table for the planner to fill on the side (*bounds_done: it did); `ride` then goes with the forward (*agg_rode: taken).
+template <class Comp>
+int plan_and_forward(const Comp& c, dmpnn_fwd_args f, int comp, int* mb, int64_t mb_mols, const AggRide& ride, bool* bounds_done, bool* agg_rode,
+                     void* stream) {
+    bool wrote = false, split = false;
+    if (!c.plan_ready) {
+        char who[32] = "";
+        if (comp > 0) snprintf(who, sizeof(who), "component %d: ", comp);
+        DMPNN_CHECK_ARG(f.n_edges == 0 || (c.edge_index && c.rev_edge_index), "train_step: %snull index arrays", who);
+        if (f.flags & DMPNN_F_TILE_PLAN)   // (the tile table alone: the kept tensors stay in the caller's edge order, dmpnn.h)
+            DMPNN_TRY(prepare_tiles_and_bounds(c.edge_index, c.rev_edge_index, c.batch, f.n_atoms, f.n_edges, const_cast<void*>(f.plan), c.plan_bytes,
+                                               mb, mb_mols, stream, &wrote, &f, &split));
+        else
+            DMPNN_TRY(dmpnn_prepare_with_batch(c.edge_index, c.rev_edge_index, c.batch, f.n_atoms, f.n_edges, const_cast<void*>(f.plan), c.plan_bytes,
+                                               stream));
+    }
+    if (split) f.flags |= DMPNN_F_WSPLIT_READY;
+    if (wrote) g_agg_ride = ride;   // (K0 wrote the bounds table and zeroed its done[])
+    const int rc = dmpnn_forward(&f, stream);
+    if (bounds_done) *bounds_done = wrote;
+    if (agg_rode) *agg_rode = g_agg_ride.taken;
+    g_agg_ride = kNoAggRide;
+    return rc;
+}
 }  // namespace
 
 extern "C" {
@@ -1694,9 +1730,6 @@ extern "C" {
 // torch.optim.Adam (model.py:208-231), every kernel enqueued by this one call.
 int dmpnn_train_step(const dmpnn_step_args* a, void* stream) {
     DMPNN_CHECK_ARG(a != nullptr, "train_step: null args");
-    // (round 6: on a tile plan built here from the batch vector, the tile kernels' launches are bounded by the batch's molecule count — a tile
-    //  holds at least one molecule — instead of the layout's bound: 512 instead of 745 workgroups at 512 molecules, forward and backward;
-    //  a plan that turns out to hold more tiles than that comes back NaN from both kernels)
     // a multicomponent model: ncomp > 1 components in the head's fingerprint, either ONE shared block over the merged batch (n_extra = 0:
     // its batch vector numbers ncomp B molecules) or one block per component (n_extra = ncomp - 1: each batch holds B molecules)
     const int64_t ncomp = a->head.n_components > 1 ? a->head.n_components : 1;
@@ -1706,7 +1739,7 @@ int dmpnn_train_step(const dmpnn_step_args* a, void* stream) {
     dmpnn_bwd_args bw = a->bwd;
     // (the tile kernels' launches are bounded by the molecules of the block's OWN batch: a shared block over the merged batch holds ncomp B)
     const int64_t blk_mols = a->head.batch == a->batch ? ncomp * a->head.n_mols : (n_extra > 0 ? a->head.n_mols : 0);
-    if ((bw.f.flags & DMPNN_F_TILE_PLAN) && bw.f.n_tiles_launch == 0 && blk_mols > 0) bw.f.n_tiles_launch = blk_mols;
+    bound_tile_launch(bw.f, blk_mols);
     const dmpnn_fwd_args& f = bw.f;
     DMPNN_CHECK_ARG((f.flags & DMPNN_F_KEEP) != 0, "train_step: the forward must keep its tensors (DMPNN_F_KEEP)");
     const dmpnn_vd_args* vd = a->vd;   // the atom-descriptor layer between the block and the head (dmpnn_vd.hip), or none
@@ -1736,69 +1769,29 @@ int dmpnn_train_step(const dmpnn_step_args* a, void* stream) {
     DMPNN_CHECK_ARG(a->head.n_atoms == n_atoms_all, "train_step: head and block sizes differ (%lld atoms against %lld)", (long long)a->head.n_atoms,
                     (long long)n_atoms_all);
     const int stages = a->stages ? a->stages : (DMPNN_STEP_FORWARD | DMPNN_STEP_BACKWARD | DMPNN_STEP_UPDATE);
-    ExtraWgrad rider;
-    memset(&rider, 0, sizeof(rider));
+    ExtraWgrad rider{};
     if (stages & DMPNN_STEP_FORWARD) {
-        bool bounds_done = false, split_done = false;
-        if (!a->plan_ready) {
-            DMPNN_CHECK_ARG(f.n_edges == 0 || (a->edge_index && a->rev_edge_index), "train_step: null index arrays");
-            if (f.flags & DMPNN_F_TILE_PLAN) {  // (the tile table alone: the kept tensors stay in the caller's edge order, dmpnn.h)
-                // ... and the planner already holds every molecule's atom range: it writes the aggregation's bounds table on the side
-                const dmpnn_head_args& h = a->head;
-                int* mb = nullptr;
-                if (h.ws && h.n_mols > 0 && h.batch == a->batch && h.n_atoms == f.n_atoms && ncomp == 1) {
-                    const HeadLayout HL = head_layout(h);
-                    if (h.ws_bytes >= HL.total) mb = reinterpret_cast<int*>(static_cast<unsigned char*>(h.ws) + HL.bounds);
-                }
-                DMPNN_TRY(prepare_tiles_and_bounds(a->edge_index, a->rev_edge_index, a->batch, f.n_atoms, f.n_edges, const_cast<void*>(f.plan),
-                                                   a->plan_bytes, mb, h.n_mols, stream, &bounds_done, &f, &split_done));
-            } else
-                DMPNN_TRY(dmpnn_prepare_with_batch(a->edge_index, a->rev_edge_index, a->batch, f.n_atoms, f.n_edges, const_cast<void*>(f.plan),
-                                                   a->plan_bytes, stream));
-        }
-        // the aggregate of the block's output leaves with the tile kernel's tiles (AggRide) when K0 wrote the bounds table (and zeroed
-        // its done[]) and the head is going to take its column kernels on this shape; DMPNN_HEAD_AGG=fused | split switches it off
-        bool agg_rode = false;
-        {
-            const dmpnn_head_args& h = a->head;
-            const char* he = getenv("DMPNN_HEAD");
-            const char* ae = getenv("DMPNN_HEAD_AGG");
+        // component 0: the planner already holds every molecule's atom range — it writes the aggregation's bounds table on the side (bounds_done);
+        // the block's aggregate then leaves with the tile kernel's tiles (AggRide) when the head is going to take its column kernels on this shape
+        bool bounds_done = false, agg_rode = false;
+        int* mb = nullptr;
+        AggRide ride = kNoAggRide;
+        const dmpnn_head_args& h = a->head;
+        if (!a->plan_ready && (f.flags & DMPNN_F_TILE_PLAN) && h.ws && h.n_mols > 0 && h.batch == a->batch && h.n_atoms == f.n_atoms && ncomp == 1) {
+            const HeadLayout HL = head_layout(h);
+            unsigned char* hws = static_cast<unsigned char*>(h.ws);
+            if (h.ws_bytes >= HL.total) mb = reinterpret_cast<int*>(hws + HL.bounds);
+            const char *he = getenv("DMPNN_HEAD"), *ae = getenv("DMPNN_HEAD_AGG");   // (DMPNN_HEAD_AGG=fused | split switches the ride off)
             // (with descriptors and no batch norm the aggregate is written into the fingerprint's rows, not into H: no ride there)
-            if (bounds_done && ncomp == 1 && h.ws && h.n_mols > 0 && h.n_mols <= kRowsMaxB && h.d_h % 4 == 0 && h.d_h == f.d_h && !f.W_d && !vd && !(he && !strcmp(he, "chain")) &&
-                (!h.X_d || h.bn_weight) &&
-                !(ae && strcmp(ae, "tile"))) {
-                const HeadLayout HL = head_layout(h);
-                unsigned char* hws = static_cast<unsigned char*>(h.ws);
-                g_agg_ride = AggRide{reinterpret_cast<float*>(hws + HL.Hm), (int)h.d_h, a->batch, reinterpret_cast<int*>(hws + HL.bounds), (int)h.n_mols,
-                                     h.agg_mode, h.agg_norm, false};
-            }
+            if (mb && h.n_mols <= kRowsMaxB && h.d_h % 4 == 0 && h.d_h == f.d_h && !f.W_d && !vd && !(he && !strcmp(he, "chain")) &&
+                (!h.X_d || h.bn_weight) && !(ae && strcmp(ae, "tile")))
+                ride = AggRide{reinterpret_cast<float*>(hws + HL.Hm), (int)h.d_h, a->batch, mb, (int)h.n_mols, h.agg_mode, h.agg_norm, false};
         }
-        int frc;
-        if (split_done) {   // (the weight pre-split rode in K0's launch)
-            dmpnn_fwd_args f2 = f;
-            f2.flags |= DMPNN_F_WSPLIT_READY;
-            frc = dmpnn_forward(&f2, stream);
-        } else
-            frc = dmpnn_forward(&f, stream);
-        agg_rode = g_agg_ride.taken;
-        g_agg_ride = AggRide{nullptr, 0, nullptr, nullptr, 0, 0, 0.f, false};
-        if (frc != DMPNN_OK) return frc;
-        for (int e = 0; e < n_extra; ++e) {   // the further blocks: K0 and the keeping forward of each, into its rows of H_v
-            const dmpnn_step_component& c = a->extra[e];
-            dmpnn_fwd_args fe = c.bwd.f;
-            if ((fe.flags & DMPNN_F_TILE_PLAN) && fe.n_tiles_launch == 0 && a->head.n_mols > 0) fe.n_tiles_launch = a->head.n_mols;
-            bool split_e = false;
-            if (!c.plan_ready) {
-                DMPNN_CHECK_ARG(fe.n_edges == 0 || (c.edge_index && c.rev_edge_index), "train_step: component %d: null index arrays", e + 1);
-                if (fe.flags & DMPNN_F_TILE_PLAN)
-                    DMPNN_TRY(prepare_tiles_and_bounds(c.edge_index, c.rev_edge_index, c.batch, fe.n_atoms, fe.n_edges, const_cast<void*>(fe.plan),
-                                                       c.plan_bytes, nullptr, 0, stream, nullptr, &fe, &split_e));
-                else
-                    DMPNN_TRY(dmpnn_prepare_with_batch(c.edge_index, c.rev_edge_index, c.batch, fe.n_atoms, fe.n_edges, const_cast<void*>(fe.plan),
-                                                       c.plan_bytes, stream));
-            }
-            if (split_e) fe.flags |= DMPNN_F_WSPLIT_READY;
-            DMPNN_TRY(dmpnn_forward(&fe, stream));
+        DMPNN_TRY(plan_and_forward(*a, f, 0, mb, h.n_mols, ride, &bounds_done, &agg_rode, stream));
+        for (int e = 0; e < n_extra; ++e) {   // the further blocks, each into its rows of H_v
+            dmpnn_fwd_args fe = a->extra[e].bwd.f;
+            bound_tile_launch(fe, h.n_mols);
+            DMPNN_TRY(plan_and_forward(a->extra[e], fe, e + 1, nullptr, 0, kNoAggRide, nullptr, nullptr, stream));
         }
         // (a whole step in one call: the first predictor layer's weight gradient rides in the block's backward launches; a staged
         //  step — data parallel — has the head's gradients final after this stage, so nothing is deferred there)
@@ -1812,12 +1805,11 @@ int dmpnn_train_step(const dmpnn_step_args* a, void* stream) {
         DMPNN_TRY(backward_impl(&bw, stream, rider.Z ? &rider : nullptr, &rode));   // (the rider: in component 0's launches only)
         for (int e = 0; e < n_extra; ++e) {
             dmpnn_bwd_args be = a->extra[e].bwd;
-            if ((be.f.flags & DMPNN_F_TILE_PLAN) && be.f.n_tiles_launch == 0 && a->head.n_mols > 0) be.f.n_tiles_launch = a->head.n_mols;
+            bound_tile_launch(be.f, a->head.n_mols);
             DMPNN_TRY(backward_impl(&be, stream, nullptr, nullptr));
         }
         if (rider.Z && !rode) {  // (the backward pass did not take the f16 products: the product of its own, as dmpnn_head would have run it)
-            dmpnn_gemm_args g;
-            memset(&g, 0, sizeof(g));
+            dmpnn_gemm_args g{};
             g.M = rider.M; g.N = rider.N; g.K1 = rider.K; g.A1 = rider.A; g.lda1 = rider.lda;
             const HeadLayout HL = head_layout(a->head);
             DMPNN_TRY(dmpnn_linear_wgrad(&g, rider.Z, rider.ldz, rider.gW, rider.ldgw, rider.gb, rider.ws, HL.wgrad_bytes, stream));

@@ -27,7 +27,7 @@ from .distributed import GradSync, force_collective
 from .ffn import MLP
 from .nn import BondMessagePassing, MulticomponentMessagePassing, classify_activation
 from .data import merge_components
-from .optim import FlatAdam
+from .optim import CLIP_MODES, FlatAdam
 
 __all__ = ["MSE", "MAE", "BCE", "CE", "MVE", "Evidential", "Quantile", "RegressionFFN", "BinaryClassificationFFN", "MulticlassClassificationFFN", "MveFFN", "EvidentialFFN", "QuantileFFN",
            "MPNN", "MulticomponentMPNN", "FusedTrainer", "masked_loss"]
@@ -40,6 +40,8 @@ def masked_loss(preds: Tensor, targets: Tensor, weights: Optional[Tensor] = None
     ``MPNN.training_step`` (``models/model.py:152-156``): torch ops, differentiable — the module path's criterion."""
     mask = targets.isfinite()
     targets = targets.nan_to_num(nan=0.0)
+    w = torch.ones(targets.shape[0], dtype=torch.float, device=targets.device) if weights is None else weights
+    tw = 1.0 if task_weights is None else task_weights.view(1, -1)
     if kind in ("bce", "ce", "mve", "evidential", "quantile"):
         lt_mask = gt_mask = None     # (only the Bounded* criteria apply the masks: metrics.py:157-177)
     if kind in ("mve", "evidential", "quantile"):   # preds [b, t, 2 | 4]: what MveFFN / EvidentialFFN / QuantileFFN.train_step stack (predictors.py:173-232)
@@ -58,13 +60,9 @@ def masked_loss(preds: Tensor, targets: Tensor, weights: Optional[Tensor] = None
             L_nll = (0.5 * (torch.pi / v).log() - alpha * two_b_lambda.log() + (alpha + 0.5) * torch.log(v * residuals**2 + two_b_lambda)
                      + torch.lgamma(alpha) - torch.lgamma(alpha + 0.5))
             L = L_nll + v_kl * ((2 * v + alpha) * residuals.abs() - eps)
-        w = torch.ones(targets.shape[0], dtype=torch.float, device=targets.device) if weights is None else weights
-        tw = 1.0 if task_weights is None else task_weights.view(1, -1)
         return (L * w.view(-1, 1) * tw * mask).sum() / mask.sum()
     if kind == "ce":                 # preds [b, t, c] logits, targets [b, t] class indices (metrics.py:298-304)
         L = torch.nn.functional.cross_entropy(preds.transpose(1, 2), targets.long(), reduction="none")
-        w = torch.ones(targets.shape[0], dtype=torch.float, device=targets.device) if weights is None else weights
-        tw = 1.0 if task_weights is None else task_weights.view(1, -1)
         return (L * w.view(-1, 1) * tw * mask).sum() / mask.sum()
     if lt_mask is not None:
         preds = torch.where((preds < targets) & lt_mask, targets, preds)
@@ -74,14 +72,18 @@ def masked_loss(preds: Tensor, targets: Tensor, weights: Optional[Tensor] = None
         L = torch.nn.functional.binary_cross_entropy_with_logits(preds, targets, reduction="none")
     else:
         L = (preds - targets).abs() if kind == "mae" else torch.nn.functional.mse_loss(preds, targets, reduction="none")
-    w = torch.ones(targets.shape[0], dtype=torch.float, device=targets.device) if weights is None else weights
-    tw = 1.0 if task_weights is None else task_weights.view(1, -1)
-    L = L * w.view(-1, 1) * tw * mask
-    return L.sum() / mask.sum()
+    return (L * w.view(-1, 1) * tw * mask).sum() / mask.sum()
+
+
+def criterion_loss(c, preds: Tensor, targets: Tensor, weights=None, lt_mask=None, gt_mask=None) -> Tensor:
+    """:func:`masked_loss` with what the criterion ``c`` carries — this package's or the reference's (``task_weights``, ``v_kl``, ...)."""
+    return masked_loss(preds, targets, weights, getattr(c, "task_weights", None), lt_mask, gt_mask, getattr(c, "kind", "mse"),
+                       float(getattr(c, "v_kl", 0.2)), float(getattr(c, "eps", 1e-8)), float(getattr(c, "alpha", 0.1)))
 
 
 class MSE(nn.Module):
-    """The criterion's state (``nn/metrics.py:60-76``: a ``task_weights`` buffer of shape ``[1, t]``) and its batch value."""
+    """The criterion's state (``nn/metrics.py:60-76``: a ``task_weights`` buffer of shape ``[1, t]``) and its batch value; only the
+    kinds ``mse`` / ``mae`` apply ``lt_mask`` / ``gt_mask`` (:func:`masked_loss`)."""
 
     kind = "mse"
 
@@ -91,7 +93,7 @@ class MSE(nn.Module):
 
     def forward(self, preds, targets, mask=None, weights=None, lt_mask=None, gt_mask=None):
         t = targets if mask is None else torch.where(mask, targets, torch.full_like(targets, float("nan")))
-        return masked_loss(preds, t, weights, self.task_weights, lt_mask, gt_mask, self.kind)
+        return criterion_loss(self, preds, t, weights, lt_mask, gt_mask)
 
 
 class MAE(MSE):
@@ -103,15 +105,13 @@ class BCE(MSE):
 
     kind = "bce"
 
-    def forward(self, preds, targets, mask=None, weights=None, lt_mask=None, gt_mask=None):
-        return super().forward(preds, targets, mask, weights, None, None)
-
 
 class RegressionFFN(nn.Module):
     """``chemprop.nn.predictors.RegressionFFN`` (``predictors.py:101-169``): ``ffn = MLP.build(input_dim, n_tasks, hidden_dim,
     n_layers, dropout, activation)``, criterion MSE, identity output transform while training."""
 
-    n_targets = 1
+    n_targets = 1   # (values per task, ``predictors.py:132``: the MLP is ``n_tasks * n_targets`` wide)
+    _default_criterion = MSE
 
     def __init__(self, n_tasks: int = 1, input_dim: int = 300, hidden_dim: int = 300, n_layers: int = 1, dropout: float = 0.0,
                  activation="relu", criterion: Optional[nn.Module] = None, task_weights: Optional[Tensor] = None):
@@ -119,7 +119,7 @@ class RegressionFFN(nn.Module):
         self.hparams = dict(n_tasks=n_tasks, input_dim=input_dim, hidden_dim=hidden_dim, n_layers=n_layers, dropout=dropout,
                             activation=activation, cls=self.__class__)
         self.ffn = MLP.build(input_dim, n_tasks * self.n_targets, hidden_dim, n_layers, dropout, activation)
-        self.criterion = criterion if criterion is not None else MSE(torch.ones(n_tasks) if task_weights is None else task_weights)
+        self.criterion = criterion if criterion is not None else self._default_criterion(torch.ones(n_tasks) if task_weights is None else task_weights)
         self.output_transform = nn.Identity()
 
     @property
@@ -145,17 +145,11 @@ class CE(MSE):
 
     kind = "ce"
 
-    def forward(self, preds, targets, mask=None, weights=None, lt_mask=None, gt_mask=None):
-        return super().forward(preds, targets, mask, weights, None, None)
-
 
 class MVE(MSE):
     """``chemprop.nn.metrics.MVELoss`` (``metrics.py:203-219``): ``preds [b, t, 2]`` = (mean, variance); no bounds."""
 
     kind = "mve"
-
-    def forward(self, preds, targets, mask=None, weights=None, lt_mask=None, gt_mask=None):
-        return super().forward(preds, targets, mask, weights, None, None)
 
 
 class Evidential(MSE):
@@ -166,10 +160,6 @@ class Evidential(MSE):
     def __init__(self, task_weights=1.0, v_kl: float = 0.2, eps: float = 1e-8):
         super().__init__(task_weights)
         self.v_kl, self.eps = v_kl, eps
-
-    def forward(self, preds, targets, mask=None, weights=None, lt_mask=None, gt_mask=None):
-        t = targets if mask is None else torch.where(mask, targets, torch.full_like(targets, float("nan")))
-        return masked_loss(preds, t, weights, self.task_weights, None, None, self.kind, self.v_kl, self.eps)
 
 
 class Quantile(MSE):
@@ -184,23 +174,8 @@ class Quantile(MSE):
         self.register_buffer("bounds", torch.tensor([-1 / 2, 1 / 2]).view(-1, 1, 1))
         self.register_buffer("tau", torch.tensor([[alpha / 2, 1 - alpha / 2], [alpha / 2 - 1, -alpha / 2]]).view(2, 2, 1, 1))
 
-    def forward(self, preds, targets, mask=None, weights=None, lt_mask=None, gt_mask=None):
-        t = targets if mask is None else torch.where(mask, targets, torch.full_like(targets, float("nan")))
-        return masked_loss(preds, t, weights, self.task_weights, None, None, self.kind, alpha=self.alpha)
 
-
-class _MultiTargetFFN(RegressionFFN):
-    """A regression predictor with ``n_targets`` values per task (``predictors.py:132``: the MLP is ``n_tasks * n_targets`` wide)."""
-
-    _default_criterion = MSE
-
-    def __init__(self, n_tasks: int = 1, input_dim: int = 300, hidden_dim: int = 300, n_layers: int = 1, dropout: float = 0.0,
-                 activation="relu", criterion: Optional[nn.Module] = None, task_weights: Optional[Tensor] = None):
-        super().__init__(n_tasks, input_dim, hidden_dim, n_layers, dropout, activation,
-                         criterion if criterion is not None else self._default_criterion(torch.ones(n_tasks) if task_weights is None else task_weights))
-
-
-class MveFFN(_MultiTargetFFN):
+class MveFFN(RegressionFFN):
     """``chemprop.nn.predictors.MveFFN`` (``predictors.py:173-190``): an MLP ``2 n_tasks`` wide, chunked into means and raw variances
     (``softplus``), stacked ``[b, t, 2]``; ``train_step`` is ``forward``.  (The output transform is the identity here, as the
     reference's ``UnscaleTransform`` is while training.)"""
@@ -215,7 +190,7 @@ class MveFFN(_MultiTargetFFN):
     train_step = forward
 
 
-class EvidentialFFN(_MultiTargetFFN):
+class EvidentialFFN(RegressionFFN):
     """``chemprop.nn.predictors.EvidentialFFN`` (``predictors.py:193-212``): ``4 n_tasks`` wide — mean | v | alpha | beta,
     ``v = softplus``, ``alpha = softplus + 1``, ``beta = softplus``, stacked ``[b, t, 4]``."""
 
@@ -230,7 +205,7 @@ class EvidentialFFN(_MultiTargetFFN):
     train_step = forward
 
 
-class QuantileFFN(_MultiTargetFFN):
+class QuantileFFN(RegressionFFN):
     """``chemprop.nn.predictors.QuantileFFN`` (``predictors.py:215-232``): ``2 n_tasks`` wide — lower | upper bounds, stacked as
     ``(mean, interval) [b, t, 2]``."""
 
@@ -271,10 +246,7 @@ class BinaryClassificationFFN(RegressionFFN):
     """``chemprop.nn.predictors.BinaryClassificationFFN`` (``predictors.py:235-247``): the same MLP; ``forward`` predicts
     probabilities (``sigmoid``), ``train_step`` hands the raw logits to ``BCELoss``."""
 
-    def __init__(self, n_tasks: int = 1, input_dim: int = 300, hidden_dim: int = 300, n_layers: int = 1, dropout: float = 0.0,
-                 activation="relu", criterion: Optional[nn.Module] = None, task_weights: Optional[Tensor] = None):
-        super().__init__(n_tasks, input_dim, hidden_dim, n_layers, dropout, activation,
-                         criterion if criterion is not None else BCE(torch.ones(n_tasks) if task_weights is None else task_weights))
+    _default_criterion = BCE
 
     def forward(self, Z: Tensor) -> Tensor:
         return self.ffn(Z).sigmoid()
@@ -323,10 +295,11 @@ class MPNN(nn.Module):
                           X_d=None if X_d is None else self.X_d_transform(X_d))
             if l is not None:
                 return l
-        preds = self.predictor.train_step(self.fingerprint(bmg, V_d, X_d))
-        c = self.criterion
-        return masked_loss(preds, targets, weights, getattr(c, "task_weights", None), lt_mask, gt_mask, getattr(c, "kind", "mse"),
-                           float(getattr(c, "v_kl", 0.2)), float(getattr(c, "eps", 1e-8)), float(getattr(c, "alpha", 0.1)))
+        return self._torch_loss(self.fingerprint(bmg, V_d, X_d), targets, weights, lt_mask, gt_mask)
+
+    def _torch_loss(self, Z: Tensor, targets: Tensor, weights, lt_mask, gt_mask) -> Tensor:
+        """The tail of ``loss`` on torch ops: the criterion on ``predictor.train_step`` of the fingerprint ``Z``."""
+        return criterion_loss(self.criterion, self.predictor.train_step(Z), targets, weights, lt_mask, gt_mask)
 
 
 class MulticomponentMPNN(MPNN):
@@ -354,10 +327,7 @@ class MulticomponentMPNN(MPNN):
                               X_d=None if X_d is None else self.X_d_transform(X_d))
                 if l is not None:
                     return l
-        preds = self.predictor.train_step(self.fingerprint(bmgs, V_ds, X_d))
-        c = self.criterion
-        return masked_loss(preds, targets, weights, getattr(c, "task_weights", None), lt_mask, gt_mask, getattr(c, "kind", "mse"),
-                           float(getattr(c, "v_kl", 0.2)), float(getattr(c, "eps", 1e-8)), float(getattr(c, "alpha", 0.1)))
+        return self._torch_loss(self.fingerprint(bmgs, V_ds, X_d), targets, weights, lt_mask, gt_mask)
 
 
 def fused_block(mp) -> tuple:
@@ -434,6 +404,16 @@ def criterion_kind(crit) -> tuple[Optional[str], bool]:
         if cls in names:
             return k, "BoundedMixin" in names
     return None, False
+
+
+def _batch_vector_ok(batch: Optional[Tensor], n_atoms: int, dev) -> bool:
+    """The head kernels read ``batch`` through a raw pointer: a wrong dtype / size would be an out-of-bounds device read, not an error."""
+    return batch is not None and batch.dtype == torch.int64 and batch.is_contiguous() and batch.device == dev and batch.numel() == n_atoms
+
+
+def _component_batch(batches: list, n_mols: int) -> Tensor:
+    """ONE batch vector over every component's rows: molecule ``i`` of component ``c`` is ``c n_mols + i`` (torch ops)."""
+    return torch.cat([b + c * n_mols for c, b in enumerate(batches)]) if len(batches) > 1 else batches[0]
 
 
 class HeadSpec:
@@ -614,6 +594,23 @@ class HeadSpec:
                 keep.append(m8)
         return keep
 
+    def call_args(self, nV: int, n_mols: int, batch: Tensor, T: Tensor, weights, lt_mask, gt_mask, gptr, gHv: Tensor, **fill_kw) -> tuple:
+        """A ``_lib.HeadArgs`` ready to launch: :meth:`fill` (``fill_kw``: its ``bn_training / X_d / ffn_dropout``), fresh ``preds
+        [n_mols, n_out]`` and ``loss [2]``, the gradient of ``H_v`` into ``gHv`` (``[nV, d_out]``, any row stride) and the workspace
+        the library asks for.  Returns ``(h, preds, loss, keep)``; ``keep`` must stay alive until the call is enqueued."""
+        dev = T.device
+        h = _lib.HeadArgs()
+        keep = self.fill(h, nV, n_mols, int(gHv.shape[1]), batch, T, weights, lt_mask, gt_mask, gptr, **fill_kw)
+        preds = torch.empty(n_mols, self.n_out, dtype=torch.float32, device=dev)
+        loss = torch.empty(2, dtype=torch.float32, device=dev)
+        h.preds, h.loss_out = preds.data_ptr(), loss.data_ptr()
+        h.gHv, h.ldg = gHv.data_ptr(), gHv.stride(0)
+        nb = int(_lib.load().dmpnn_head_ws_bytes(C.byref(h)))
+        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
+        h.ws, h.ws_bytes = ws.data_ptr(), nb
+        keep.append(ws)
+        return h, preds, loss, keep
+
 
 class _HeadLoss(torch.autograd.Function):
     """Everything behind the block — aggregation, batch norm, the predictor's layers, the criterion — AND its backward pass as ONE
@@ -623,7 +620,6 @@ class _HeadLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, spec, Hv, batch, n_mols, T, weights, lt_mask, gt_mask, X_d, *params):
-        lib = _lib.load()
         dev = Hv.device
         Hv = engine._f32c(Hv, "H_v")
         nV, d_out = int(Hv.shape[0]), int(Hv.shape[1])   # (a multicomponent H_v: every component's rows, one block's width)
@@ -636,19 +632,11 @@ class _HeadLoss(torch.autograd.Function):
         ptr = {id(p): flat.data_ptr() + 4 * o for p, o in zip(params, offs)}
         want = {id(p) for p, need in zip(params, ctx.needs_input_grad[9:]) if need}
         gH = flat[n:].view(nV, d_out)
-        h = _lib.HeadArgs()
-        keep = spec.fill(h, nV, n_mols, d_out, batch, T, weights, lt_mask, gt_mask,
-                         lambda p: None if (p is None or id(p) not in want) else ptr[id(p)], bn_training=spec.bn is None or spec.bn.training,
-                         X_d=X_d)
-        preds = torch.empty(n_mols, spec.n_out, dtype=torch.float32, device=dev)
-        loss = torch.empty(2, dtype=torch.float32, device=dev)
-        h.preds, h.loss_out = preds.data_ptr(), loss.data_ptr()
-        h.gHv, h.ldg = gH.data_ptr(), d_out
-        nb = int(lib.dmpnn_head_ws_bytes(C.byref(h)))
-        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
-        h.ws, h.ws_bytes = ws.data_ptr(), nb
+        h, preds, loss, keep = spec.call_args(nV, n_mols, batch, T, weights, lt_mask, gt_mask,
+                                              lambda p: None if (p is None or id(p) not in want) else ptr[id(p)], gH,
+                                              bn_training=spec.bn is None or spec.bn.training, X_d=X_d)
         with engine._OnDevice(dev):
-            _lib.check(lib.dmpnn_head(C.byref(h), Hv.data_ptr(), Hv.stride(0), engine._stream_ptr(dev)), "dmpnn_head")
+            _lib.check(_lib.load().dmpnn_head(C.byref(h), Hv.data_ptr(), Hv.stride(0), engine._stream_ptr(dev)), "dmpnn_head")
         del keep
         ctx.flat, ctx.n, ctx.offs, ctx.shapes, ctx.want = flat, n, offs, [tuple(p.shape) for p in params], [id(p) in want for p in params]
         ctx.hv_shape = (nV, d_out)
@@ -688,17 +676,16 @@ def head_loss(model, Hv: Tensor, batch: Tensor, n_mols: int, targets: Tensor, we
     if isinstance(spec, str):
         return None
     if isinstance(Hv, (list, tuple)):
-        # a multicomponent model: the blocks' outputs as ONE H_v of every component's rows, the batch vectors as one that numbers
-        # molecule i of component c as c n_mols + i (torch ops: the module path; the fused step writes them in place)
+        # a multicomponent model: the blocks' outputs as ONE H_v of every component's rows (the fused step writes them in place)
         if spec.n_components != len(Hv) or len(batch) != len(Hv) or any(b is None for b in batch):
             return None
-        batch = torch.cat([b + c * n_mols for c, b in enumerate(batch)]) if len(Hv) > 1 else batch[0]
+        batch = _component_batch(list(batch), n_mols)
         Hv = torch.cat(list(Hv)) if len(Hv) > 1 else Hv[0]
     elif spec.n_components != 1:
         return None
     if Hv.device.type != "cuda" or Hv.dtype != torch.float32:
         return None
-    if batch is None or batch.dtype != torch.int64 or not batch.is_contiguous() or batch.numel() != Hv.shape[0] or batch.device != Hv.device:
+    if not _batch_vector_ok(batch, Hv.shape[0], Hv.device):
         return None
     T = targets if (targets.dtype == torch.float32 and targets.is_contiguous()) else targets.float().contiguous()
     if T.dim() != 2 or T.shape[0] != n_mols or T.shape[1] != spec.n_tasks or (spec.bn is not None and spec.bn.training and n_mols < 2):
@@ -712,6 +699,18 @@ def head_loss(model, Hv: Tensor, batch: Tensor, n_mols: int, targets: Tensor, we
     except ValueError:
         return None
     return _HeadLoss.apply(spec, Hv, batch, int(n_mols), T, weights, lt_mask, gt_mask, Xd, *spec.params())
+
+
+class _BlockPart:
+    """One block's share of a step (``FusedTrainer._block_args``): plan, kept forward state, the backward's argument block, what they
+    point into, the block's rows of ``H_v`` / ``gH_v``, the route — and what K0 reads, named as ``dmpnn_step_args`` names it."""
+
+    __slots__ = ("plan", "st", "bwd", "keep_b", "out", "gout", "route", "bmg", "edge_index", "rev_edge_index", "batch", "plan_bytes")
+
+    def set_on(self, c, plan_ready: int) -> None:
+        """Fill the fields ``_lib.StepArgs`` and ``_lib.StepComponent`` share."""
+        c.edge_index, c.rev_edge_index, c.batch = self.edge_index, self.rev_edge_index, self.batch
+        c.plan_bytes, c.plan_ready, c.bwd = self.plan_bytes, plan_ready, self.bwd
 
 
 class FusedTrainer:
@@ -749,11 +748,7 @@ class FusedTrainer:
             self.head = HeadSpec(model, ffn_dropout=ffn_dropout)
         except NotImplementedError as e:
             raise NotImplementedError(f"FusedTrainer: {e}") from None
-        self.model, self.mp = model, self.blocks[0]
-        self.multi = multi
-        act, slope = acts[0]
-        self.acts = acts
-        self.act, self.slope = act, slope
+        self.model, self.mp, self.multi, self.acts = model, self.blocks[0], multi, acts
         self.layers, self.bn, self.bounded = self.head.layers, self.head.bn, self.head.bounded
         params = [p for p in model.parameters() if p.requires_grad]
         engine._require_device(params[0], "model parameters")
@@ -768,7 +763,6 @@ class FusedTrainer:
         self._block_range = self.sync.range_of(blk) if blk else (0, 0)
         self._head_range = self.sync.range_of(rest) if rest else (0, 0)
         self._checked = 0
-        self._level = None
         self.tile_plan = bool(tile_plan)   # False: always the full (CSR) plan — what every round before used; tests keep both alive
         self.last_route = None
 
@@ -799,27 +793,47 @@ class FusedTrainer:
         ``None`` or a list of ``None`` (``ValueError`` otherwise)."""
         from .nn import _VALIDATE_FIRST_N
 
-        lib = _lib.load()
-        dev = self.dev
-        if self.multi:
-            bmgs = list(bmg)
-            if len(bmgs) != self.n_components:
-                raise ValueError(f"FusedTrainer.step: {self.n_components} component batches expected, got {len(bmgs)}")
-            if V_ds is not None and any(v is not None for v in V_ds):
-                raise ValueError("FusedTrainer.step: atom descriptors (V_ds) per component are not taken by the fused step")
-            if len({len(b) for b in bmgs}) != 1:
-                raise ValueError(f"FusedTrainer.step: every component must hold the same number of molecules, got {[len(b) for b in bmgs]}")
-            for b in bmgs:
-                engine._require_device(b.V, "bmg.V")
-            n_mols = len(bmgs[0])
-            # (shared: ONE batch of n B molecules, numbered c B + i — the head folds it back into [B, n d_h])
-            comps = [merge_components(bmgs)] if self.shared else bmgs
-            blocks = [self.mp] if self.shared else self.blocks
-        else:
+        comps, blocks, n_mols = self._components(bmg, V_ds)
+        T, Vd, Xd = self._check_inputs(comps, n_mols, targets, weights, lt_mask, gt_mask, X_d, V_d)
+        validate = _lib.opt("DMPNN_VALIDATE", "first") != "never" and self._checked < _VALIDATE_FIRST_N
+        world = self._world()
+        self.sync.wait()
+        if validate:
+            self._checked += 1
+        # (everything the argument blocks point into lives in these locals until the call has been enqueued)
+        parts, out, gout, vd, vd_keep = self._blocks(comps, blocks, validate, Vd)
+        h, preds, loss, keep = self._head_args(comps, n_mols, T, weights, lt_mask, gt_mask, Xd, gout)
+        s, extra = self._step_args(parts, h, vd, validate)
+        if clip is not None:   # (normalised: None, or a positive value and its mode)
+            clip = (float(clip[0]), clip[1] or "norm") if (clip[0] is not None and float(clip[0]) > 0) else None
+        # (None: the staged data-parallel step — the update is opt.step's; DMPNN_FORCE_COLLECTIVE takes it on one rank too)
+        k = self._optimizer_args(s, lr, clip) if (world == 1 and not force_collective()) else None
+        self._launch(s, staged=k is None)
+        self._commit(h, preds, k, lr, clip)
+        return loss
+
+    def _components(self, bmg, V_ds) -> tuple:
+        """``(comps, blocks, n_mols)``: the batches the blocks run on and the block of each; a shared block takes the components merged
+        into ONE batch of ``n B`` molecules, numbered ``c B + i`` (the head folds it back into ``[B, n d_h]``)."""
+        if not self.multi:
             if V_ds is not None:
                 raise ValueError("FusedTrainer.step: V_ds is for multicomponent models")
             engine._require_device(bmg.V, "bmg.V")
-            comps, blocks, n_mols = [bmg], [self.mp], len(bmg)
+            return [bmg], [self.mp], len(bmg)
+        bmgs = list(bmg)
+        if len(bmgs) != self.n_components:
+            raise ValueError(f"FusedTrainer.step: {self.n_components} component batches expected, got {len(bmgs)}")
+        if V_ds is not None and any(v is not None for v in V_ds):
+            raise ValueError("FusedTrainer.step: atom descriptors (V_ds) per component are not taken by the fused step")
+        if len({len(b) for b in bmgs}) != 1:
+            raise ValueError(f"FusedTrainer.step: every component must hold the same number of molecules, got {[len(b) for b in bmgs]}")
+        for b in bmgs:
+            engine._require_device(b.V, "bmg.V")
+        return ([merge_components(bmgs)], [self.mp], len(bmgs[0])) if self.shared else (bmgs, self.blocks, len(bmgs[0]))
+
+    def _check_inputs(self, comps, n_mols: int, targets, weights, lt_mask, gt_mask, X_d, V_d) -> tuple:
+        """Everything that refuses a step for its inputs — before anything is counted, drawn or enqueued.  Returns the targets, the
+        atom descriptors and the molecule descriptors as the kernels read them (the two through their transforms; ``None``: none)."""
         if not self.model.training:
             # (batch norm would update its running statistics while the block's dropout follows model.training: the two switches
             #  must not disagree — and a training step of a model in eval mode is a bug of the caller, not a mode)
@@ -829,12 +843,9 @@ class FusedTrainer:
         T = engine._f32c(targets, "targets")
         if T.dim() != 2 or T.shape[0] != n_mols or T.shape[1] != n_tasks or not T.is_contiguous():
             raise ValueError(f"targets must be a contiguous [{n_mols}, {n_tasks}] matrix, got {tuple(targets.shape)}")
-        # the head kernels read these through raw pointers: a wrong dtype / size would be an out-of-bounds device read, not an error
         for cb in comps:
-            nV = int(cb.V.shape[0])
-            batch = cb.batch
-            if batch is None or batch.dtype != torch.int64 or not batch.is_contiguous() or batch.device != cb.V.device or batch.numel() != nV:
-                raise ValueError(f"bmg.batch must be a contiguous int64 vector of {nV} molecule ids on {cb.V.device}")
+            if not _batch_vector_ok(cb.batch, int(cb.V.shape[0]), cb.V.device):
+                raise ValueError(f"bmg.batch must be a contiguous int64 vector of {int(cb.V.shape[0])} molecule ids on {cb.V.device}")
         if weights is not None and weights.numel() != n_mols:
             raise ValueError(f"weights must hold one value per molecule ({n_mols}), got {tuple(weights.shape)}")
         for name, m in (("lt_mask", lt_mask), ("gt_mask", gt_mask)):
@@ -846,113 +857,107 @@ class FusedTrainer:
             xt = getattr(self.model, "X_d_transform", None)
             with torch.no_grad():
                 X_d = X_d if xt is None else xt(X_d)
-        Xd = self.head.descriptors(X_d, n_mols, dev)
-        validate = _lib.opt("DMPNN_VALIDATE", "first") != "never" and self._checked < _VALIDATE_FIRST_N
-        world = self._world()
-        self.sync.wait()
-        if validate:
-            self._checked += 1
-        # a multicomponent step with a block per component: every block writes its rows of ONE H_v and reads its rows of ONE gHv
-        nV_all = sum(int(cb.V.shape[0]) for cb in comps)
+        return T, Vd, self.head.descriptors(X_d, n_mols, self.dev)
+
+    def _blocks(self, comps, blocks, validate: bool, Vd: Optional[Tensor]) -> tuple:
+        """Every block's argument blocks (:meth:`_block_args`) and the atom-descriptor stage's (:meth:`_vd_args`).  ``out`` / ``gout``
+        are what the head reads / writes: with a block per component ONE ``H_v`` / ``gH_v`` that every block takes its rows of, with
+        atom descriptors ``H_v'`` / ``gH_v'`` ``[n_atoms, d_h + d_vd]``."""
         H_all = g_all = None
         if len(comps) > 1:
-            d_blk = int(blocks[0].output_dim)
-            H_all = torch.empty(nV_all, d_blk, dtype=torch.float32, device=dev)
-            g_all = torch.empty(nV_all, d_blk, dtype=torch.float32, device=dev)
+            nV_all, d_blk = sum(int(cb.V.shape[0]) for cb in comps), int(blocks[0].output_dim)
+            H_all = torch.empty(nV_all, d_blk, dtype=torch.float32, device=self.dev)
+            g_all = torch.empty(nV_all, d_blk, dtype=torch.float32, device=self.dev)
         parts, row = [], 0
-        for ci, (mp, cb) in enumerate(zip(blocks, comps)):
+        for mp, cb in zip(blocks, comps):
             nV_c = int(cb.V.shape[0])
             parts.append(self._block_args(mp, cb, len(cb), self.acts[self.blocks.index(mp)], validate,
                                           None if H_all is None else H_all[row:row + nV_c], None if g_all is None else g_all[row:row + nV_c]))
             row += nV_c
-        self.last_route = parts[0]["route"] if len(parts) == 1 else tuple(p["route"] for p in parts)
-        self._last_plan_tiles = all(p["plan"].tiles_only for p in parts)
-        out, gout = (parts[0]["out"], parts[0]["gout"]) if H_all is None else (H_all, g_all)
-        vd = vd_keep = None
-        if Vd is not None:
-            # the atom-descriptor stage between the block and the head: H_v' / gH_v' [n_atoms, d_h + d_vd] are what the head reads / writes
-            vd, out, gout, vd_keep = self._vd_args(self.mp, Vd, out, gout)
-        d_out = int(out.shape[1])
-        if self.multi and not self.shared:
-            batch = torch.cat([cb.batch + c * n_mols for c, cb in enumerate(comps)])   # (molecule i of component c: c B + i)
-        else:
-            batch = comps[0].batch
+        self.last_route = parts[0].route if len(parts) == 1 else tuple(p.route for p in parts)
+        self._last_plan_tiles = all(p.plan.tiles_only for p in parts)
+        out, gout = (parts[0].out, parts[0].gout) if H_all is None else (H_all, g_all)
+        return (parts, out, gout, None, None) if Vd is None else (parts, *self._vd_args(self.mp, Vd, out, gout))
+
+    def _head_args(self, comps, n_mols: int, T: Tensor, weights, lt_mask, gt_mask, Xd, gout: Tensor) -> tuple:
+        """The head's argument block (:meth:`HeadSpec.call_args`) over every component's rows, its gradients into the flat buffer's
+        views and ``gout``; with an active predictor dropout one seed from torch's CPU generator first — drawn after the block's."""
+        batch = _component_batch([cb.batch for cb in comps], n_mols)
         if self.multi:
             note_batch(batch, self.n_components * n_mols)
-
-        # ---- the head ----
         hdrop = None
         drop = self.head.drop
         if drop is not None and drop.training and float(drop.p) > 0:
             if not float(drop.p) < 1:
                 raise ValueError(f"FusedTrainer.step: the predictor's dropout needs p < 1, got {drop!r}")
-            # one seed per step from torch's CPU generator, drawn after the block's (model.training: checked above)
             hdrop = (float(drop.p), int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
             self.last_head_dropout_seed = hdrop[1]
-        h = _lib.HeadArgs()
-        keep = [T, out, gout, batch, parts, vd, vd_keep]
-        keep += self.head.fill(h, nV_all, n_mols, d_out, batch, T, weights, lt_mask, gt_mask, self._gv, X_d=Xd, ffn_dropout=hdrop)
-        bn = self.bn
-        t = int(self.layers[-1].out_features)
-        preds = torch.empty(n_mols, t, dtype=torch.float32, device=dev)
-        loss = torch.empty(2, dtype=torch.float32, device=dev)
-        h.preds, h.loss_out = preds.data_ptr(), loss.data_ptr()
-        h.gHv, h.ldg = gout.data_ptr(), gout.stride(0)
-        nb = int(lib.dmpnn_head_ws_bytes(C.byref(h)))
-        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
-        h.ws, h.ws_bytes = ws.data_ptr(), nb
+        h, preds, loss, keep = self.head.call_args(int(gout.shape[0]), n_mols, batch, T, weights, lt_mask, gt_mask, self._gv, gout,
+                                                   X_d=Xd, ffn_dropout=hdrop)
+        keep.append(batch)
+        return h, preds, loss, keep
 
+    @staticmethod
+    def _step_args(parts: list, h, vd, validate: bool) -> tuple:
+        """``dmpnn_step_args`` from the parts: component 0 inline, the further ones as an array (returned: it must stay alive)."""
         s = _lib.StepArgs()
-        p0 = parts[0]
-        s.edge_index, s.rev_edge_index, s.batch = p0["edge_index"], p0["rev_edge_index"], p0["batch"]
-        s.plan_bytes, s.plan_ready = p0["plan_bytes"], (1 if validate else 0)
-        s.bwd, s.head = p0["b"], h
+        ready = 1 if validate else 0   # (while the first batches are validated, K0 was launched with the plan: _block_args)
+        parts[0].set_on(s, ready)
+        s.head = h
         if vd is not None:
             s.vd = C.pointer(vd)
+        extra = None
         if len(parts) > 1:
             extra = (_lib.StepComponent * (len(parts) - 1))()
             for e, pc in zip(extra, parts[1:]):
-                e.edge_index, e.rev_edge_index, e.batch = pc["edge_index"], pc["rev_edge_index"], pc["batch"]
-                e.plan_bytes, e.plan_ready, e.bwd = pc["plan_bytes"], (1 if validate else 0), pc["b"]
+                pc.set_on(e, ready)
             s.n_extra, s.extra = len(parts) - 1, C.cast(extra, C.POINTER(_lib.StepComponent))
-            keep.append(extra)
-        opt = self.opt
-        fused_update = world == 1 and not force_collective()   # (forced: the staged data-parallel step also on one rank)
-        if fused_update:
-            k = opt.steps + 1  # (committed below, once the call has returned OK: a refused step must not advance Adam's bias correction)
-            b1, b2 = opt.betas
-            s.p, s.g, s.m, s.v, s.n_params = opt.flat.data_ptr(), self.sync.flat.data_ptr(), opt.m.data_ptr(), opt.v.data_ptr(), opt.flat.numel()
-            s.lr, s.beta1, s.beta2, s.eps, s.weight_decay = float(opt.lr if lr is None else lr), b1, b2, opt.eps, opt.weight_decay
-            s.bias_corr1, s.sqrt_bias_corr2, s.grad_scale = 1.0 - b1 ** k, math.sqrt(1.0 - b2 ** k), 1.0
-            if clip is not None and clip[0] is not None and float(clip[0]) > 0:
-                from .optim import CLIP_MODES
+        return s, extra
 
-                s.clip_val, s.clip_mode, s.clip_ws = float(clip[0]), CLIP_MODES[clip[1] or "norm"], opt.clip_ws.data_ptr()
-        with engine._OnDevice(dev):
-            if fused_update:
-                _lib.check(lib.dmpnn_train_step(C.byref(s), engine._stream_ptr(dev)), "dmpnn_train_step")
-                opt.steps = k
-            else:
-                # data parallel: the head's gradients (predictor, batch norm) are final before the block's backward pass starts —
-                # their slice of the flat buffer goes out on the communication stream while that pass runs; the block's slice
-                # follows it; the update waits (stream dependency) for both
-                s.stages = _lib.STEP_FORWARD
-                _lib.check(lib.dmpnn_train_step(C.byref(s), engine._stream_ptr(dev)), "dmpnn_train_step(forward)")
-                self.sync.allreduce(*self._head_range)
-                s.stages = _lib.STEP_BACKWARD
-                _lib.check(lib.dmpnn_train_step(C.byref(s), engine._stream_ptr(dev)), "dmpnn_train_step(backward)")
-                self.sync.allreduce(*self._block_range)
-        del keep
+    def _optimizer_args(self, s, lr: Optional[float], clip: Optional[tuple]) -> int:
+        """Adam's scalars and the clip for an update inside the call; returns the step count to commit once the call has returned OK
+        (a refused step must not advance Adam's bias correction)."""
+        opt = self.opt
+        k = opt.steps + 1
+        b1, b2 = opt.betas
+        s.p, s.g, s.m, s.v, s.n_params = opt.flat.data_ptr(), self.sync.flat.data_ptr(), opt.m.data_ptr(), opt.v.data_ptr(), opt.flat.numel()
+        s.lr, s.beta1, s.beta2, s.eps, s.weight_decay = float(opt.lr if lr is None else lr), b1, b2, opt.eps, opt.weight_decay
+        s.bias_corr1, s.sqrt_bias_corr2, s.grad_scale = 1.0 - b1 ** k, math.sqrt(1.0 - b2 ** k), 1.0
+        if clip is not None:
+            s.clip_val, s.clip_mode, s.clip_ws = clip[0], CLIP_MODES[clip[1]], opt.clip_ws.data_ptr()
+        return k
+
+    def _launch(self, s, staged: bool) -> None:
+        """The step as one call — or, data parallel, as two: the head's gradients (predictor, batch norm) are final before the block's
+        backward pass starts, so their slice of the flat buffer goes out on the communication stream while that pass runs; the
+        block's slice follows it; the update waits (stream dependency) for both."""
+        lib = _lib.load()
+        with engine._OnDevice(self.dev):
+            stream = engine._stream_ptr(self.dev)
+            if not staged:
+                _lib.check(lib.dmpnn_train_step(C.byref(s), stream), "dmpnn_train_step")
+                return
+            s.stages = _lib.STEP_FORWARD
+            _lib.check(lib.dmpnn_train_step(C.byref(s), stream), "dmpnn_train_step(forward)")
+            self.sync.allreduce(*self._head_range)
+            s.stages = _lib.STEP_BACKWARD
+            _lib.check(lib.dmpnn_train_step(C.byref(s), stream), "dmpnn_train_step(backward)")
+            self.sync.allreduce(*self._block_range)
+
+    def _commit(self, h, preds: Tensor, k: Optional[int], lr, clip) -> None:
+        """The bookkeeping of a step that was taken: the batch norm's count where the kernel did not keep it, ``preds``, and either
+        Adam's step count and the parameters' versions (``k``: the update ran inside the call) or the update itself (``opt.step``)."""
+        bn = self.bn
         if bn is not None and not h.bn_num_batches_tracked and bn.num_batches_tracked is not None:
             bn.num_batches_tracked += 1
         self.preds = preds
-        if fused_update:
-            for p in self.sync.params:  # (the engine's weight caches key on the autograd version)
-                torch.autograd.graph.increment_version(p)
-            self.sync.new_step()
-        else:
-            opt.step(lr, clip=None if (clip is None or clip[0] is None or not float(clip[0]) > 0) else (float(clip[0]), clip[1] or "norm"))
-        return loss
+        if k is None:
+            self.opt.step(lr, clip=clip)
+            return
+        self.opt.steps = k
+        for p in self.sync.params:  # (the engine's weight caches key on the autograd version)
+            torch.autograd.graph.increment_version(p)
+        self.sync.new_step()
 
     def _atom_descriptors(self, V_d: Optional[Tensor], bmg) -> Optional[Tensor]:
         """``V_d`` through the block's ``V_d_transform`` as fp32 rows ``[n_atoms, d_vd]`` on the device (``None``: a block without
@@ -1001,9 +1006,9 @@ class FusedTrainer:
         nb = int(lib.dmpnn_vd_ws_bytes(C.byref(a)))
         ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=self.dev)
         a.ws, a.ws_bytes = ws.data_ptr(), nb
-        return a, out2, gout2, [Vd, Hv, gHv, ws, Wd, bd]
+        return out2, gout2, a, [Vd, Hv, gHv, ws, Wd, bd]
 
-    def _block_args(self, mp, bmg, n_mols: int, act_slope: tuple, validate: bool, out: Optional[Tensor], gout: Optional[Tensor]) -> dict:
+    def _block_args(self, mp, bmg, n_mols: int, act_slope: tuple, validate: bool, out: Optional[Tensor], gout: Optional[Tensor]) -> "_BlockPart":
         """K0's plan and the argument blocks of one block's forward / backward on ``bmg`` (workspace allocated, nothing enqueued but —
         while the first batches are validated — the plan).  ``out`` / ``gout``: the block's rows of a multicomponent step's H_v / gHv
         (``None``: allocated here)."""
@@ -1068,7 +1073,9 @@ class FusedTrainer:
         for k, g in grads.items():  # (a view the engine did not take would silently drop the gradient)
             if g is not None and g is not views.get(k):
                 raise RuntimeError(f"FusedTrainer: the gradient view of {k} was not accepted (dtype / layout)")
-        bt = batch if (batch.dtype == torch.int64 and batch.is_contiguous()) else None
-        return dict(plan=plan, st=st, b=b, keep_b=keep_b, out=out, gout=gout, route=st.route, edge_index=plan.edge_index.data_ptr(),
-                    rev_edge_index=plan.rev_edge_index.data_ptr(), batch=None if bt is None else bt.data_ptr(), plan_bytes=plan.buf.numel() * 4,
-                    bmg=bmg)
+        part = _BlockPart()
+        part.plan, part.st, part.bwd, part.keep_b, part.out, part.gout, part.route, part.bmg = plan, st, b, keep_b, out, gout, st.route, bmg
+        part.edge_index, part.rev_edge_index = plan.edge_index.data_ptr(), plan.rev_edge_index.data_ptr()
+        part.batch = batch.data_ptr()   # (int64, contiguous: _check_inputs)
+        part.plan_bytes = plan.buf.numel() * 4
+        return part
