@@ -472,9 +472,13 @@ int dmpnn_forward(const dmpnn_fwd_args* a, void* stream) {
     if (a->dropout_p != 0.f) {
         DMPNN_CHECK_ARG(a->dropout_p > 0.f && a->dropout_p < 1.f, "forward: dropout_p must lie in [0, 1)");
         const bool tile_train = (a->flags & DMPNN_F_MEGA) && (a->flags & DMPNN_F_SPLIT16) && (a->flags & DMPNN_F_KEEP);
-        DMPNN_CHECK_ARG(tile_train && !has_vd && (a->act == DMPNN_ACT_RELU || a->act == DMPNN_ACT_LEAKYRELU),
+        // ... or the LEAN training forward of the per-step fused route, asked for by the caller (flags + keep_bits), under its own conditions
+        const bool lean_train = lean16 && fused16_lean_shapes(*a, true);
+        DMPNN_CHECK_ARG(lean_train || (tile_train && !has_vd && (a->act == DMPNN_ACT_RELU || a->act == DMPNN_ACT_LEAKYRELU)),
                         "forward: dropout inside the kernels needs the training forward of the tile kernel (DMPNN_F_MEGA | DMPNN_F_SPLIT16 | "
-                        "DMPNN_F_KEEP), a ReLU-class activation and no W_d — run dropout between the row kernels otherwise");
+                        "DMPNN_F_KEEP) or the lean training forward of the per-step fused route (DMPNN_F_FUSED | DMPNN_F_SPLIT16 | DMPNN_F_KEEP "
+                        "with keep_bits; d_h <= 320, d_h %% 4 == 0, even d_v / d_e, depth 2 .. %d, a full plan), a ReLU-class activation and "
+                        "no W_d — run dropout between the row kernels otherwise", kWProdMaxJobs);
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const PlanView pv = plan_view(a->plan, nV, nE);

@@ -222,11 +222,18 @@ int launch_edge_bwd(EdgeBwdArgs a, hipStream_t s, const char* name) {
 }
 
 // elementwise: gZ = g * tau'(Y)      (finalize: atoms x h)
+// drop_scale != 0 (the lean forward ran with dropout inside the kernels; ReLU class): Y = dropout(tau(z)) is exactly 0 where dropped (or
+// inactive), else tau(z) / (1 - p) with the sign of z — the factor is its sign's tau' times 1 / (1 - p), as in the backward tile kernel
 template <int VEC>
 __global__ void k_act_bwd(const float* __restrict__ g, int64_t ldg, const float* __restrict__ Y, int64_t ldy,
                           float* __restrict__ out, int64_t ldo, int64_t rows, int h, int act, float slope,
-                          const float* slope_ptr) {
+                          const float* slope_ptr, float drop_scale) {
     const float sl = slope_ptr ? *slope_ptr : slope;
+    const float neg = act == DMPNN_ACT_RELU ? 0.f : sl;
+    auto grad = [&](float y) -> float {
+        if (drop_scale != 0.f) return y > 0.f ? drop_scale : (y < 0.f ? neg * drop_scale : 0.f);
+        return act_grad_from_out(y, act, sl);
+    };
     const int q = h / VEC;  // column groups per row
     const int64_t n = rows * q;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -236,10 +243,9 @@ __global__ void k_act_bwd(const float* __restrict__ g, int64_t ldg, const float*
             const float4 gv = *reinterpret_cast<const float4*>(g + r * ldg + c);
             const float4 yv = *reinterpret_cast<const float4*>(Y + r * ldy + c);
             *reinterpret_cast<float4*>(out + r * ldo + c) =
-                make_float4(gv.x * act_grad_from_out(yv.x, act, sl), gv.y * act_grad_from_out(yv.y, act, sl),
-                            gv.z * act_grad_from_out(yv.z, act, sl), gv.w * act_grad_from_out(yv.w, act, sl));
+                make_float4(gv.x * grad(yv.x), gv.y * grad(yv.y), gv.z * grad(yv.z), gv.w * grad(yv.w));
         } else {
-            out[r * ldo + c] = g[r * ldg + c] * act_grad_from_out(Y[r * ldy + c], act, sl);
+            out[r * ldo + c] = g[r * ldg + c] * grad(Y[r * ldy + c]);
         }
     }
 }
@@ -914,10 +920,12 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
             const int64_t n = nV * (vec ? h / 4 : h);
             int64_t blocks = (n + 255) / 256;
             if (blocks > 4096) blocks = 4096;
+            // (dropout inside the lean forward: out is post-dropout, its sign carries the mask — the factor gets the 1 / (1 - p))
+            const float dsc = (f.dropout_p > 0.f && f.dropout_p < 1.f && drop_threshold(f.dropout_p) > 0u) ? 1.f / (1.f - f.dropout_p) : 0.f;
             if (vec) hipLaunchKernelGGL(k_act_bwd<4>, dim3((unsigned)blocks), dim3(256), 0, s, gHO_p, ld_gHO, HO, ldHO, gZO, ldh, nV, (int)h,
-                                        f.act, f.act_slope, f.act_slope_ptr);
+                                        f.act, f.act_slope, f.act_slope_ptr, dsc);
             else hipLaunchKernelGGL(k_act_bwd<1>, dim3((unsigned)blocks), dim3(256), 0, s, gHO_p, ld_gHO, HO, ldHO, gZO, ldh, nV, (int)h,
-                                    f.act, f.act_slope, f.act_slope_ptr);
+                                    f.act, f.act_slope, f.act_slope_ptr, dsc);
             DMPNN_CHECK_LAUNCH("k_act_bwd");
         }
         if (b->gW_o || b->gb_o) {
@@ -1009,8 +1017,8 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
     DMPNN_CHECK_ARG(!atom || (tile_bwd && L.w16 && !has_vd && (T < 2 || nE == 0 || f.msplit)),
                     "backward: DMPNN_F_ATOM needs the tile-kernel forward (FUSED | MEGA | SPLIT16 | KEEP with `msplit`), even d_v / d_e / d_h and "
                     "16-byte aligned gout / out (leading dimensions multiples of 4)");
-    // in-kernel dropout (dmpnn_fwd_args.dropout_p): its 1 / (1 - p) lives in the backward TILE kernel alone — every other branch below
-    // would return gradients without it, silently
+    // in-kernel dropout (dmpnn_fwd_args.dropout_p): its 1 / (1 - p) lives in the backward TILE kernel and in the lean branch above (the
+    // backward step kernels regenerate the mask) — every other branch below would return gradients without it, silently
     DMPNN_CHECK_ARG(!(f.dropout_p > 0.f) || tile_bwd,
                     "backward: the forward ran with dropout inside the kernels; only the backward tile kernel carries its scale — it needs a "
                     "gradient of W_i or W_h to be wanted and 16-byte aligned gout / out (leading dimensions multiples of 4)");
@@ -1240,9 +1248,9 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
         int64_t blocks = (n + 255) / 256;
         if (blocks > 4096) blocks = 4096;
         if (vec) hipLaunchKernelGGL(k_act_bwd<4>, dim3((unsigned)blocks), dim3(256), 0, s, gHO_p, ld_gHO, HO, ldHO, gZO, ldh, nV, (int)h,
-                                    f.act, f.act_slope, f.act_slope_ptr);
+                                    f.act, f.act_slope, f.act_slope_ptr, 0.f);
         else hipLaunchKernelGGL(k_act_bwd<1>, dim3((unsigned)blocks), dim3(256), 0, s, gHO_p, ld_gHO, HO, ldHO, gZO, ldh, nV, (int)h,
-                                f.act, f.act_slope, f.act_slope_ptr);
+                                f.act, f.act_slope, f.act_slope_ptr, 0.f);
         DMPNN_CHECK_LAUNCH("k_act_bwd");
     }
     if (b->gW_o || b->gb_o) {

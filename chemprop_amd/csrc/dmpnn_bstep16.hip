@@ -45,6 +45,9 @@ struct BStepK {
     const float* gMv; int ldg;                 // [V][ldg] fp32: gH[r] = gMv[dst r]      (gather mode: the first launch)
     const unsigned char* bits; int bstride;    // [tau(z) > 0] of this site's rows, [M][bstride] bytes (null: tau' = 1)
     float neg;                                 // tau' where the bit is 0: 0 (ReLU), the slope (LeakyReLU)
+    // active dropout of this site's forward step (sites t >= 1; all zero: off): the bit is the sign of tau(z) BEFORE dropout, the mask is
+    // regenerated from the hash — gZ = keep ? scale * tau'(z) gH : 0 — keyed like the forward: hash site t - 1, row id perm[row]
+    unsigned drop_thr; float drop_scale; unsigned seed_lo, seed_hi, drop_site; const int* perm;
     unsigned char* Zrows; int tsz;             // gZ as a product operand (k_wgrad16r): split ROWS [M][tsz] — the contraction's own A tile, row by row, the tile's scale in the tails
     SplitW W;                                  // pre-split W_h^T (fragment-major); p null: no contraction (the last site: gZ^(0) only)
     float* Tout; int ldo;                      // Tout[revp[r]] = gM[r]
@@ -66,6 +69,7 @@ __global__ __launch_bounds__(256, 2) void k_bstep16(BStepK g) {
     int* meta = reinterpret_cast<int*>(Bt + BM * (BN / 8));        // [BM] reverse rows | [kAtomCache + 1] row pointers
     int* rp = meta + BM;
     unsigned* maxbits = reinterpret_cast<unsigned*>(rp + kAtomCache + 1);
+    unsigned* erow = maxbits + 16;                                 // [BM] the caller's edge ids of the tile's rows (dropout only)
 
     int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int li = lane & 15, lg = lane >> 4;
@@ -82,6 +86,7 @@ __global__ __launch_bounds__(256, 2) void k_bstep16(BStepK g) {
     if (tid == 0) maxbits[0] = 0u;
     // ---- metadata ----
     if (tid < nrows) meta[tid] = gather ? g.dstp[rs + tid] : (g.Tout ? g.revp[rs + tid] : 0);
+    if (g.drop_thr && tid < nrows) erow[tid] = (unsigned)g.perm[rs + tid];   // (read behind the barriers below)
     {   // sign bytes of the tile's rows (rows are contiguous: nrows * bstride bytes)
         constexpr int BB = BN / 8;
         for (int it = tid; it < nrows * BB; it += NT) Bt[it] = g.bits ? g.bits[(long long)rs * g.bstride + it] : (unsigned char)0xFF;
@@ -126,6 +131,13 @@ __global__ __launch_bounds__(256, 2) void k_bstep16(BStepK g) {
         z.y = (b & 2u) ? gh.y : g.neg * gh.y;
         z.z = (b & 4u) ? gh.z : g.neg * gh.z;
         z.w = (b & 8u) ? gh.w : g.neg * gh.w;
+        if (g.drop_thr) {  // (uniform)
+            const unsigned row = erow[r], c0 = 4u * (unsigned)q;
+            z.x = drop_hash(g.seed_lo, g.seed_hi, g.drop_site, row, c0) >= g.drop_thr ? z.x * g.drop_scale : 0.f;
+            z.y = drop_hash(g.seed_lo, g.seed_hi, g.drop_site, row, c0 + 1u) >= g.drop_thr ? z.y * g.drop_scale : 0.f;
+            z.z = drop_hash(g.seed_lo, g.seed_hi, g.drop_site, row, c0 + 2u) >= g.drop_thr ? z.z * g.drop_scale : 0.f;
+            z.w = drop_hash(g.seed_lo, g.seed_hi, g.drop_site, row, c0 + 3u) >= g.drop_thr ? z.w * g.drop_scale : 0.f;
+        }
         if (poison) z = make_float4(nanv, nanv, nanv, nanv);
         mx = fmaxf(mx, fmaxf(fmaxf(fabsf(z.x), fabsf(z.y)), fmaxf(fabsf(z.z), fabsf(z.w))));
         return z;
@@ -318,7 +330,7 @@ static int launch_bstep(const BStepK& g0, int n_tiles, hipStream_t s) {
     BStepK g = g0;
     constexpr int BN = 64 * WN;
     g.tile_bytes = BM * (BN * 4 + 16);
-    const size_t lds = (size_t)g.tile_bytes + (size_t)BM * (BN / 8) + (size_t)(BM + kAtomCache + 1) * sizeof(int) + 64;
+    const size_t lds = (size_t)g.tile_bytes + (size_t)BM * (BN / 8) + (size_t)(BM + kAtomCache + 1) * sizeof(int) + 64 + (size_t)BM * sizeof(unsigned);
     static size_t attr_set = 0;
     if (attr_set < lds) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bstep16<WN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -355,6 +367,11 @@ int launch_bstep16(const dmpnn_fwd_args& f, int site, const float* Tin, const fl
     g.bstride = bn / 8;
     g.bits = f.act == DMPNN_ACT_NONE ? nullptr : static_cast<const unsigned char*>(f.keep_bits) + (size_t)site * (size_t)nE * (size_t)g.bstride;
     g.neg = f.act == DMPNN_ACT_RELU ? 0.f : (f.act == DMPNN_ACT_LEAKYRELU ? f.act_slope : 1.f);
+    if (site >= 1 && f.dropout_p > 0.f && f.dropout_p < 1.f) {   // (H0, bit site 0, has no dropout: base.py:200)
+        g.drop_thr = drop_threshold(f.dropout_p); g.drop_scale = 1.f / (1.f - f.dropout_p);
+        g.seed_lo = (unsigned)(f.dropout_seed & 0xFFFFFFFFull); g.seed_hi = (unsigned)(f.dropout_seed >> 32);
+        g.drop_site = (unsigned)(site - 1); g.perm = plan_i + L.perm;
+    }
     g.Zrows = Zrows; g.tsz = step16::split_row_bytes((int)h);   // (split rows [n_edges][split_row_bytes(d_h)] for k_wgrad16r)
     if (W) { g.W.p = W->p; g.W.inv_scale = W->inv_scale; g.W.nc = W->nc; }
     g.Tout = W ? Tout : nullptr; g.ldo = (int)f.ldh;

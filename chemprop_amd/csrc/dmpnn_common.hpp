@@ -312,7 +312,8 @@ int tile_waves(const dmpnn_fwd_args& a, int n_tiles);
 // per-step fused route on the f16 pipe (dmpnn_step16.hip): inference forward, any molecule size, d_h <= 320
 bool fused16_shapes_ok(const dmpnn_fwd_args& a);
 // its LEAN training forward (dmpnn_step16.hip) and the backward that reads what it keeps (dmpnn_bstep16.hip)
-bool fused16_lean_shapes(const dmpnn_fwd_args& a);     // shapes / options only (the route rule)
+// shapes / options only.  on_demand false: the route rule (no dropout); true: what a caller may ask for itself — also with active dropout
+bool fused16_lean_shapes(const dmpnn_fwd_args& a, bool on_demand = false);
 size_t fused16_lean_bits_bytes(const dmpnn_fwd_args& a);
 bool fused16_lean(const dmpnn_fwd_args& a);            // ... and the workspace is there (DMPNN_F_KEEP, keep_bits, msplit, H0)
 int64_t split_row_floats(int64_t d_h);

@@ -38,21 +38,28 @@ static inline int msg_row_bytes(const dmpnn_fwd_args& a) { return half_store(a) 
 static bool x_path_shapes(const dmpnn_fwd_args& a) {
     return a.d_h <= 320 && (a.d_v + a.d_e + 31) / 32 <= step16::kXChunks;
 }
-bool fused16_lean_shapes(const dmpnn_fwd_args& a) {
+// `on_demand`: the shapes a caller may ASK the lean form for (flags + keep_bits set by itself) — the route rule's shapes plus active
+// dropout inside the step kernels (ReLU-class activation: the mask is regenerated from the hash, the kept bit stays the sign of
+// tau(z)).  The route RULE (dmpnn_forward_route / dmpnn_train_route, on_demand false) keeps refusing dropout: lean implies p == 0.
+bool fused16_lean_shapes(const dmpnn_fwd_args& a, bool on_demand) {
     const unsigned need = DMPNN_F_FUSED | DMPNN_F_SPLIT16;
     if ((a.flags & need) != need || (a.flags & (DMPNN_F_MEGA | DMPNN_F_UNDIRECTED | DMPNN_F_STORE16 | DMPNN_F_ATOM))) return false;
     if (!(a.act == DMPNN_ACT_NONE || a.act == DMPNN_ACT_RELU || a.act == DMPNN_ACT_LEAKYRELU)) return false;
     // (depth <= kWProdMaxJobs: the backward pass of this route forms every weight gradient as ONE launch of at most that many product
     //  jobs per matrix, dmpnn_backward.hip — a deeper block keeps the fp32 tensors and trains on the fused16 route as before)
-    if (a.W_d || a.dropout_p > 0.f || a.depth < 2 || a.depth > kWProdMaxJobs || a.n_edges <= 0 || a.n_atoms <= 0) return false;
+    if (a.dropout_p != 0.f) {
+        if (!on_demand || !(a.dropout_p > 0.f && a.dropout_p < 1.f)) return false;
+        if (!(a.act == DMPNN_ACT_RELU || a.act == DMPNN_ACT_LEAKYRELU)) return false;
+    }
+    if (a.W_d || a.depth < 2 || a.depth > kWProdMaxJobs || a.n_edges <= 0 || a.n_atoms <= 0) return false;
     if (a.d_h <= 0 || a.d_h % 4 != 0 || a.ldh % 4 != 0 || a.d_v % 2 || a.d_e % 2 || a.ldv % 2 || a.lde % 2) return false;
     return x_path_shapes(a);
 }
 size_t fused16_lean_bits_bytes(const dmpnn_fwd_args& a) {
-    return fused16_lean_shapes(a) ? (size_t)a.depth * (size_t)a.n_edges * (size_t)(step16::block_cols((int)a.d_h) / 8) : 0;
+    return fused16_lean_shapes(a, true) ? (size_t)a.depth * (size_t)a.n_edges * (size_t)(step16::block_cols((int)a.d_h) / 8) : 0;
 }
 bool fused16_lean(const dmpnn_fwd_args& a) {
-    if (!(a.flags & DMPNN_F_KEEP) || !a.keep_bits || !fused16_lean_shapes(a)) return false;
+    if (!(a.flags & DMPNN_F_KEEP) || !a.keep_bits || !fused16_lean_shapes(a, true)) return false;
     if (a.keep_bits_bytes < fused16_lean_bits_bytes(a)) return false;
     if (!a.msplit || a.msplit_bytes < (size_t)(a.depth - 1) * (size_t)a.n_edges * step16::split_row_bytes((int)a.d_h)) return false;
     return !(reinterpret_cast<uintptr_t>(a.msplit) & 15u) && a.H0 && !(reinterpret_cast<uintptr_t>(a.H0) & 15u);
@@ -154,9 +161,14 @@ static step16::Step16K step_args(const dmpnn_fwd_args& a, const PlanLayout& L) {
 // then recomputed inside the step instead of read back (x_path_ok)
 static int launch_update(const dmpnn_fwd_args& a, const PlanLayout& L, const SplitWView& W, const SplitWView* Wi, const unsigned char* xrows,
                          const unsigned char* Min, unsigned char* Mout, float* Sout, unsigned char* SoutS, float* Hout, float* M32, hipStream_t s,
-                         unsigned char* bits = nullptr, const float* h0q = nullptr) {
+                         unsigned char* bits = nullptr, const float* h0q = nullptr, int drop_site = -1) {
     step16::Step16K g = step_args(a, L);
     g.bits = bits; g.bstride = step16::block_cols((int)a.d_h) / 8;
+    if (drop_site >= 0 && bits && a.dropout_p > 0.f && a.dropout_p < 1.f) {   // (lean training forward with active dropout: validated by dmpnn_forward)
+        g.drop_thr = drop_threshold(a.dropout_p); g.drop_scale = 1.f / (1.f - a.dropout_p);
+        g.seed_lo = (unsigned)(a.dropout_seed & 0xFFFFFFFFull); g.seed_hi = (unsigned)(a.dropout_seed >> 32);
+        g.drop_site = (unsigned)drop_site; g.perm = static_cast<const int*>(a.plan) + L.perm;
+    }
     g.A = Min; g.ts = msg_row_bytes(a);
     g.W.p = W.p; g.W.inv_scale = W.inv_scale; g.W.nc = W.nc;
     g.bias = a.b_h;
@@ -307,7 +319,7 @@ int launch_fused16_forward(const dmpnn_fwd_args& a, const SplitWView* w16, float
         for (int t = 1; t < T; ++t) {
             const bool last = t == T - 1;
             DMPNN_TRY(launch_update(a, L, w16[1], &w16[0], xrows, Mk + (size_t)(t - 1) * slot_bytes, last ? nullptr : Mk + (size_t)t * slot_bytes,
-                                    last ? a.Mv : nullptr, nullptr, nullptr, nullptr, s, bits + (size_t)t * bslot));
+                                    last ? a.Mv : nullptr, nullptr, nullptr, nullptr, s, bits + (size_t)t * bslot, nullptr, t - 1));
         }
     } else if (nE > 0 && h0q) {
         // ---- inference with H0 kept as row quads: K1 on the step kernel over the split K1 operand (scratch: the second message slot,
@@ -345,11 +357,26 @@ int launch_fused16_forward(const dmpnn_fwd_args& a, const SplitWView* w16, float
     g.C = out; g.ldc = ldout;
     g.act = a.act; g.act_slope = a.act_slope; g.act_slope_ptr = a.act_slope_ptr;
     const int* plan_i = static_cast<const int*>(a.plan);
-    if (linear16_ok(g)) return launch_linear16_view(g, w16[2], plan_i + DMPNN_HDR_FLAGS, kPlanNoFuse, s);
-    GemmExtra xf;
-    memset(&xf, 0, sizeof(xf));
-    xf.poison_flags = plan_i + DMPNN_HDR_FLAGS; xf.poison_mask = kPlanNoFuse;
-    return launch_linear_ex(g, xf, s);
+    if (linear16_ok(g)) DMPNN_TRY(launch_linear16_view(g, w16[2], plan_i + DMPNN_HDR_FLAGS, kPlanNoFuse, s));
+    else {
+        GemmExtra xf;
+        memset(&xf, 0, sizeof(xf));
+        xf.poison_flags = plan_i + DMPNN_HDR_FLAGS; xf.poison_mask = kPlanNoFuse;
+        DMPNN_TRY(launch_linear_ex(g, xf, s));
+    }
+    // (p below 2^-32 has threshold 0: dropout is OFF in every kernel of this route, forward and backward — no mask, no scale)
+    if (a.dropout_p > 0.f && a.dropout_p < 1.f && drop_threshold(a.dropout_p) > 0u && nE > 0 && fused16_lean(a) && nV > 0) {
+        // dropout(tau(W_o [V || Mv] + b_o)), base.py:182: hash site depth - 1, row = atom id.  One elementwise launch over out
+        // [n_atoms, d_h] behind the finalize — that contraction is the row kernel every route shares, its output a fraction of one
+        // step's edge traffic
+        const int64_t n = nV * (h / 4);
+        int64_t blocks = (n + 255) / 256;
+        if (blocks > 4096) blocks = 4096;
+        hipLaunchKernelGGL(step16::k_row_dropout, dim3((unsigned)blocks), dim3(256), 0, s, out, ldout, nV, (int)h, drop_threshold(a.dropout_p),
+                           1.f / (1.f - a.dropout_p), (unsigned)(a.dropout_seed & 0xFFFFFFFFull), (unsigned)(a.dropout_seed >> 32), (unsigned)(T - 1));
+        DMPNN_CHECK_LAUNCH("k_row_dropout");
+    }
+    return DMPNN_OK;
 }
 
 }  // namespace dmpnn

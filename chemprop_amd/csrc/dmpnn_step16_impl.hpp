@@ -92,6 +92,10 @@ struct Step16K {
     float* M32; int ldm32;                // training: the next message also as fp32 rows (the weight gradients' operand) (or null)
     unsigned char* bits; int bstride;     // lean training (ReLU-class activation): [tau(z) > 0] of every element, one bit each, rows [M][bstride]
                                           // bytes (bit c & 7 of byte c >> 3) — all the backward step kernel needs of H' (or null)
+    // active dropout of a lean training update (dmpnn_fwd_args.dropout_p; all zero: off): threshold floor(p 2^32), 1 / (1 - p), the seed's
+    // halves, the hash site (update step t: t - 1) and the plan's perm — the mask is keyed on the CALLER's edge id perm[row], as in the
+    // tile kernels (dmpnn_mega16_impl.hpp: dropout_frags).  Applied in the pass that writes `bits`, which keep the sign of tau(z) BEFORE it.
+    unsigned drop_thr; float drop_scale; unsigned seed_lo, seed_hi, drop_site; const int* perm;
     int act; float slope; const float* slope_ptr;
     const int* poison_flags; int poison_mask;
     unsigned qmagic;
@@ -471,6 +475,18 @@ __global__ __launch_bounds__(64 * NW, 2) void k_step16(Step16K g) {
             const unsigned b = (m0.x > 0.f ? 1u : 0u) | (m0.y > 0.f ? 2u : 0u) | (m0.z > 0.f ? 4u : 0u) | (m0.w > 0.f ? 8u : 0u) |
                                (m1.x > 0.f ? 16u : 0u) | (m1.y > 0.f ? 32u : 0u) | (m1.z > 0.f ? 64u : 0u) | (m1.w > 0.f ? 128u : 0u);
             g.bits[(long long)(rs + r) * g.bstride + g8] = (unsigned char)b;
+            if (g.drop_thr) {  // (uniform) H' = dropout(tau(z)), base.py:139: the segment pass below forms the message from the masked tile
+                const unsigned row = (unsigned)g.perm[rs + r];
+                float v[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const unsigned col = (unsigned)(8 * g8 + i);
+                    const bool keep = drop_hash(g.seed_lo, g.seed_hi, g.drop_site, row, col) >= g.drop_thr;
+                    if ((int)col < g.N) v[i] = keep ? v[i] * g.drop_scale : 0.f;   // (padding columns stay as they are: zeros)
+                }
+                *reinterpret_cast<float4*>(T + r * LDC + 8 * g8) = make_float4(v[0], v[1], v[2], v[3]);
+                *reinterpret_cast<float4*>(T + r * LDC + 8 * g8 + 4) = make_float4(v[4], v[5], v[6], v[7]);
+            }
         }
     }
     int scale_phase = 0;
@@ -495,6 +511,21 @@ __global__ __launch_bounds__(64 * NW, 2) void k_step16(Step16K g) {
     o.N = g.N; o.half = g.half_out; o.SoutS = g.SoutS; o.tss = TSO; o.M32 = g.M32; o.ldm32 = g.ldm32;
     seg_epilogue<LDC, BN / 4, NT>(o, T, meta, rs, nrows, va, vb, seg_rp, poison, g.qmagic, tile_scale);
     stamp();  // 8 (7 without a message) end
+}
+
+// ---- active dropout on fp32 rows [rows][ld] (the lean training forward's finalize output): X[r][c] kept iff its hash clears the
+// threshold, then scaled by 1 / (1 - p); row id r (the atom).  A product, not a select: a poisoned (NaN) output stays NaN everywhere ----
+static __global__ __launch_bounds__(256) void k_row_dropout(float* __restrict__ X, int64_t ld, int64_t rows, int cols, unsigned thr, float scale,
+                                                            unsigned seed_lo, unsigned seed_hi, unsigned site) {
+    const int q = cols / 4;   // (d_h % 4 == 0 on this route)
+    const int64_t n = rows * q;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / q;
+        const int c = (int)(i - r * q) * 4;
+        float* x = X + r * ld + c;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) x[j] *= drop_hash(seed_lo, seed_hi, site, (unsigned)r, (unsigned)(c + j)) >= thr ? scale : 0.f;
+    }
 }
 
 // ---- the K1 operand [A1[g1[r]] || A2[g2[r]]] (fp32, gathered) as split rows: one workgroup per row tile of the plan ----

@@ -308,6 +308,28 @@ def lean_sign_bits(st: "ForwardState") -> Tensor:
     return ((b.unsqueeze(-1) >> sh) & 1).bool().reshape(depth, st.plan.n_edges, bn)[:, :, :d_h]
 
 
+def lean_dropout_refusal(d_v: int, d_e: int, d_h: int, depth: int, act: str, has_vd: bool = False) -> Optional[str]:
+    """Why the lean step kernels (``route="fused16"``, ``keep``, ``keep_bits``) cannot carry block dropout for these shapes — the
+    condition of ``fused16_lean_shapes`` (csrc/dmpnn_step16.hip) that fails, in words — or ``None`` when they can."""
+    if act not in ("relu", "leakyrelu"):
+        return f"activation {act!r} (relu / leakyrelu: the mask rides on a sign bit)"
+    if has_vd:
+        return "a W_d layer (d_vd > 0)"
+    if depth < 2:
+        return "depth 1 (no update step)"
+    if depth > 8:
+        return f"depth {depth} > 8 (the weight-gradient launch holds 8 product jobs per matrix)"
+    if d_h > 320:
+        return f"d_h {d_h} > 320"
+    if d_h % 4:
+        return f"d_h {d_h} is no multiple of 4"
+    if d_v % 2 or d_e % 2:
+        return f"odd d_v / d_e ({d_v}, {d_e})"
+    if (d_v + d_e + 31) // 32 > 8:
+        return f"d_v + d_e = {d_v + d_e} > 256"
+    return None
+
+
 KEEP_ROWS_MIN = 4096   # (= DMPNN_KEEP_ROWS_MIN of include/dmpnn.h: the rule itself is the library's, dmpnn_train_route)
 
 
@@ -511,7 +533,9 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
     ``atom=True``: ``AtomMessagePassing`` semantics (``DMPNN_F_ATOM``: ``W_i [d_h, d_v]``, ``W_h [d_h, d_h + d_e]``) — the tile
     kernel, inference or (round 4) training; raises :class:`RouteUnavailable` when this batch takes another route.
     ``dropout = (p, seed)``: ACTIVE dropout inside the kernels (``dmpnn_fwd_args.dropout_p``) — a training forward (``keep``) of
-    the tile kernel with a ReLU-class activation and no ``W_d``; raises :class:`RouteUnavailable` when this batch takes another
+    the tile kernel with a ReLU-class activation and no ``W_d``, or, on demand (``route="fused16"``, ``keep``, ``keep_bits``), the
+    lean training forward of the per-step fused route under its own shapes (molecules beyond the tile; ``st.route`` stays
+    ``"fused16/lean"``, the same mask for the same seed); raises :class:`RouteUnavailable` when this batch takes another
     route (the caller then runs its own ``nn.Dropout`` between the row kernels).
     ``launch=False`` prepares the argument block and the workspace without enqueuing anything (``trainer.FusedTrainer``).
     ``out``: the fp32 rows the output goes to (default: a new ``[n_atoms, d_h]`` tensor) — a multicomponent step hands every block
@@ -620,9 +644,17 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
             raise RouteUnavailable("atom messages inside the kernels: the tile kernel, 1 <= d_e <= 16, no W_d (training: even d_v / d_e / d_h)")
         a.flags |= _lib.F_ATOM
     if dropout is not None and float(dropout[0]) > 0.0:
-        if not (use_mega and want16 and keep and not d_vd and act in ("relu", "leakyrelu")):
-            raise RouteUnavailable("dropout inside the kernels: training forward of the tile kernel, ReLU-class activation, no W_d")
-        a.dropout_p, a.dropout_seed = float(dropout[0]), int(dropout[1]) & 0xFFFFFFFFFFFFFFFF
+        # its two homes: the tile kernels, or — on demand (route="fused16", keep, keep_bits) — the lean step kernels beyond the tile
+        tile_home = bool(use_mega and want16 and keep and not d_vd and act in ("relu", "leakyrelu"))
+        # (a DEMAND: the default rule may pick the lean form itself — it saw p = 0 — and must then refuse, as before)
+        lean_home = bool(route == "fused16" and use_fused16 and keep and keep_bits and not d_vd and act in ("relu", "leakyrelu"))
+        if tile_home or lean_home:
+            a.dropout_p, a.dropout_seed = float(dropout[0]), int(dropout[1]) & 0xFFFFFFFFFFFFFFFF
+        if not tile_home and not (lean_home and _lean16_bits(lib, a) > 0):
+            why = lean_dropout_refusal(d_v, d_e, d_h, depth, act, bool(d_vd)) if route == "fused16" else None
+            raise RouteUnavailable("dropout inside the kernels: a training forward of the tile kernel, or the lean training forward of the "
+                                   "per-step fused route (route='fused16', keep, keep_bits); ReLU-class activation, no W_d"
+                                   + (f" — the lean step kernels refuse: {why}" if why else ""))
     bits = None
     lean16 = False
     st = ForwardState()

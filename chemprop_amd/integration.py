@@ -412,7 +412,7 @@ def hip_mpnn_class():
                     loss = out[0]
                     self.__dict__["_hip_applied"] = True
                     st["route"] = "fused:" + str(fused.last_route)
-                except NotImplementedError as e:   # (a batch the fused step refuses, e.g. dropout on a batch beyond the tile kernels)
+                except NotImplementedError as e:   # (a batch the fused step refuses, e.g. block dropout beyond the tile kernels where the lean step kernels' shapes do not hold: d_h > 320, depth 1)
                     st["why"] = str(e)
             if loss is None:
                 # the module path: a loss with a graph; Lightning's closure runs backward() (below), the clip, HipAdam.step()

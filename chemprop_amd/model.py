@@ -357,7 +357,7 @@ def fused_block(mp) -> tuple:
             raise NotImplementedError(f"FusedTrainer: d_h + d_vd = {mp.W_d.in_features} is beyond the {_lib.VD_MAX_WIDTH} columns the "
                                       "atom-descriptor stage takes")
     if mp.dropout.p > 0 and not (type(mp.dropout) is nn.Dropout and act in ("relu", "leakyrelu")):
-        # (active dropout lives inside the tile kernels for ReLU-class activations: dmpnn_fwd_args.dropout_p; a dropout module
+        # (active dropout lives inside the tile kernels and the lean step kernels, for ReLU-class activations: dmpnn_fwd_args.dropout_p; a dropout module
         #  that is not exactly nn.Dropout has its own semantics and stays on the module path)
         raise NotImplementedError("FusedTrainer: dropout inside the block needs nn.Dropout and a ReLU / LeakyReLU activation")
     return act, slope
@@ -719,7 +719,8 @@ class FusedTrainer:
     Takes what the kernels implement and refuses the rest loudly (those models train through the module path): a
     :class:`~chemprop_amd.nn.BondMessagePassing` block with a built-in activation, directed, with or without atom descriptors
     (``d_vd > 0``: ``step(..., V_d=...)``, the layer ``W_d`` as a stage of its own behind the block), dropout 0 or — with a
-    ReLU-class activation — ``nn.Dropout`` inside the tile kernels (hash mask, one seed per step from torch's CPU generator); sum /
+    ReLU-class activation — ``nn.Dropout`` inside the tile kernels or, for molecules beyond the tile, inside the lean step kernels
+    (d_h <= 320, depth 2 .. 8, even d_v / d_e; the same hash mask, one seed per step from torch's CPU generator); sum /
     mean / norm aggregation; optional ``nn.BatchNorm1d``; an MLP predictor with a built-in activation and dropout 0; MSE / MAE.
     A predictor wider than the block's output takes molecule descriptors: ``step(..., X_d=...)`` concatenates
     ``model.X_d_transform(X_d)`` behind the batch norm inside the same call (no gradient flows to ``X_d``).
@@ -1025,8 +1026,8 @@ class FusedTrainer:
         no_mega = getattr(mp, "_dmpnn_no_mega", False) or (n_mols > 0 and nE > 30 * n_mols)
         oversize = getattr(bmg, "oversize", None)
         if oversize is None and mp.dropout.p > 0 and not no_mega:
-            # (dropout lives inside the tile kernels only; their generic path for a molecule beyond the tile has none and answers NaN —
-            #  which this step would feed to Adam.  A foreign batch is counted on the device: nn.batch_oversize)
+            # (the tile kernels' generic path for a molecule beyond the tile has no dropout and answers NaN — which this step would feed
+            #  to Adam; such a batch goes to the lean step kernels instead.  A foreign batch is counted on the device: nn.batch_oversize)
             from .nn import batch_oversize
 
             oversize = batch_oversize(bmg, n_mols)
@@ -1052,13 +1053,35 @@ class FusedTrainer:
             # one seed per step from torch's CPU generator (torch.manual_seed fixes the run), like the module path's fused dropout
             drop = (float(mp.dropout.p), int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
             self.last_dropout_seed = drop[1]
-        try:
-            out, st = engine.forward(plan, bmg.V, bmg.E, W("W_i", "weight"), W("W_h", "weight"), W("W_o", "weight"), W("W_o", "bias"),
-                                     W("W_i", "bias"), W("W_h", "bias"), depth=mp.depth, act=act, slope=slope, keep=True,
-                                     max_level=level, launch=False, dropout=drop, out=out)
-        except engine.RouteUnavailable as e:
-            raise NotImplementedError(f"FusedTrainer: this batch does not take the tile kernels ({e}); dropout on the other routes "
-                                      "runs through the module path (MPNN.loss + autograd)") from None
+        fwd = lambda **kw: engine.forward(plan, bmg.V, bmg.E, W("W_i", "weight"), W("W_h", "weight"), W("W_o", "weight"), W("W_o", "bias"),
+                                          W("W_i", "bias"), W("W_h", "bias"), depth=mp.depth, act=act, slope=slope, keep=True,
+                                          launch=False, dropout=drop, out=out, **kw)
+        # block dropout lives in the tile kernels or — molecules beyond the tile, at any edge count — in the lean step kernels, which
+        # the route rule never picks for p > 0: the step asks for them (route="fused16") on the full plan
+        st, tile_why = None, "molecules beyond the tile"
+        if drop is None or level == 2 or plan.tiles_only:
+            try:
+                out, st = fwd(max_level=level)
+            except engine.RouteUnavailable as e:
+                tile_why = str(e)
+                if drop is None or plan.tiles_only or getattr(plan, "light", False):
+                    raise NotImplementedError(f"FusedTrainer: this batch does not take the tile kernels ({e}); dropout on the other routes "
+                                              "runs through the module path (MPNN.loss + autograd)") from None
+        if st is None:
+            why = engine.lean_dropout_refusal(int(bmg.V.shape[1]), int(bmg.E.shape[1]), int(mp.W_h.weight.shape[0]), int(mp.depth), act)
+            if why is None:
+                try:
+                    out, st = fwd(route="fused16")
+                except engine.RouteUnavailable as e:
+                    why = str(e)
+                except RuntimeError as e:   # (only the refusal of the demanded route is this step's to translate)
+                    if "route 'fused16' requested but not available" not in str(e):
+                        raise
+                    why = str(e)
+            if why is not None:
+                raise NotImplementedError(f"FusedTrainer: this batch does not take the tile kernels ({tile_why}) and the lean step kernels "
+                                          f"refuse it ({why}); dropout on the other routes runs through the module path (MPNN.loss + "
+                                          "autograd)") from None
         d_out = int(out.shape[1])
         if gout is None:
             gout = torch.empty(nV, d_out, dtype=torch.float32, device=self.dev)

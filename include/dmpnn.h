@@ -371,6 +371,11 @@ typedef struct dmpnn_fwd_args {
      * (dropout_seed, site, row, column) — site = t - 1 for the update steps, depth - 1 for the finalize; row = the CALLER's
      * edge id (edge sites: the same mask on a CSR plan and on a tile plan) / the atom (finalize) — restated in oracle/dropout_hash.py; dmpnn_backward regenerates nothing: the
      * kept tensors are post-dropout, and for a ReLU-class activation their sign carries the mask.  0: no dropout.
+     * The second home of the same mask: the LEAN training forward of the per-step fused route (DMPNN_F_FUSED | DMPNN_F_SPLIT16 |
+     * DMPNN_F_KEEP with `keep_bits`, below) — molecules beyond the tile — with relu / leakyrelu and that form's own conditions.
+     * There the kept bit stays the sign of tau(z) BEFORE dropout (one bit cannot also say "dropped") and the backward step kernels
+     * regenerate the mask from the hash; the finalize output is post-dropout and carries it in its sign.  The route rules
+     * (dmpnn_forward_route / dmpnn_train_route) never choose this form for dropout_p > 0: the caller asks for it.
      * Any other route / activation with dropout_p != 0: DMPNN_EINVAL (the caller runs its own dropout between the row kernels). */
     float dropout_p; uint64_t dropout_seed;
     /* DMPNN_F_TILE_PLAN with a ReLU-class activation (none / relu / leakyrelu) and dropout_p == 0: what the backward tile kernel
@@ -384,7 +389,9 @@ typedef struct dmpnn_fwd_args {
      * — rows of ceil((d_v + d_e) / 32) * 128 + 16 bytes, so the buffer must span n_edges * max(4 ldh, that) bytes — (no H0
      * tensor: the residual is recomputed per step), `keep_bits` one bit per element of H0 and of
      * every H^(t) as rows of block_cols(d_h) / 8 bytes per site (site 0: H0), `Mv` the fp32 per-atom sums; Hs / Ms are not used.
-     * dmpnn_backward then runs the backward STEP kernels over the plan's tiles (csrc/dmpnn_bstep16.hip). */
+     * dmpnn_backward then runs the backward STEP kernels over the plan's tiles (csrc/dmpnn_bstep16.hip).
+     * With dropout_p in (0, 1) (relu / leakyrelu only; on request — the route rules keep "lean implies no dropout") the same sizes
+     * hold and the bits mean the same: [tau(z) > 0] before the mask, which both step kernels compute from the hash. */
     void* keep_bits; size_t keep_bits_bytes;
     /* ABI 12, DMPNN_F_FUSED | DMPNN_F_SPLIT16 without DMPNN_F_KEEP (inference on the per-step fused route): the size of the buffer
      * behind `H0`.  With >= dmpnn_forward_h0_bytes() bytes there the route keeps H0 = W_i x + b_i in the layout of the step kernel's
