@@ -32,7 +32,7 @@ EXPORTS = [
     "dmpnn_plan_layout", "dmpnn_prepare", "dmpnn_prepare_light", "dmpnn_prepare_tiles", "dmpnn_message_fwd", "dmpnn_aggregate_fwd",
     "dmpnn_linear_fwd", "dmpnn_linear16_wsplit_bytes", "dmpnn_linear16_ok", "dmpnn_linear16_fwd", "dmpnn_update_fwd", "dmpnn_forward", "dmpnn_forward_can_fuse", "dmpnn_forward_wsplit_bytes", "dmpnn_forward_keep_bits_bytes", "dmpnn_forward_spill_bytes", "dmpnn_backward_ws_bytes", "dmpnn_backward", "dmpnn_message_bwd",
     "dmpnn_aggregate_bwd", "dmpnn_linear_wgrad_ws_bytes", "dmpnn_linear_wgrad",
-    "dmpnn_molagg_ws_bytes", "dmpnn_molagg_bounds", "dmpnn_molagg_fwd", "dmpnn_molagg_bwd", "dmpnn_gather_rows", "dmpnn_collate", "dmpnn_pack_tiles", "dmpnn_max_tiles",
+    "dmpnn_molagg_ws_bytes", "dmpnn_molagg_bounds", "dmpnn_molagg_fwd", "dmpnn_molagg_bwd", "dmpnn_gather_rows", "dmpnn_collate", "dmpnn_pack_tiles", "dmpnn_pack_tiles_blocked", "dmpnn_max_tiles",
     "dmpnn_prepare_tiles_from_table", "dmpnn_prepare_with_batch", "dmpnn_tile_plan_any_size", "dmpnn_split_row_floats", "dmpnn_forward_can_fuse16", "dmpnn_adam_step",
     "dmpnn_full_plan_keeps_tiles", "dmpnn_head_ws_bytes", "dmpnn_head", "dmpnn_train_step", "dmpnn_forward_tiles", "dmpnn_forward_route", "dmpnn_dropout_keep",
     "dmpnn_clip_grad", "dmpnn_clip_grad_ws_bytes", "dmpnn_train_route", "dmpnn_forward_h0_bytes", "dmpnn_tile_waves", "dmpnn_debug_lds_poison",
@@ -308,6 +308,8 @@ def load() -> C.CDLL:
                                       C.c_void_p]
     lib.dmpnn_pack_tiles.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
     lib.dmpnn_pack_tiles.restype = C.c_int64
+    lib.dmpnn_pack_tiles_blocked.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.dmpnn_pack_tiles_blocked.restype = C.c_int64
     lib.dmpnn_max_tiles.argtypes = [C.c_int64, C.c_int64]
     lib.dmpnn_prepare_with_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.dmpnn_prepare_with_batch.restype = C.c_int
@@ -350,7 +352,7 @@ def load() -> C.CDLL:
     for name in size_t_fns:
         getattr(lib, name).restype = C.c_size_t
     for name in EXPORTS:
-        if name != "dmpnn_last_error_string" and name not in size_t_fns and name not in ("dmpnn_pack_tiles", "dmpnn_max_tiles", "dmpnn_split_row_floats"):
+        if name != "dmpnn_last_error_string" and name not in size_t_fns and name not in ("dmpnn_pack_tiles", "dmpnn_pack_tiles_blocked", "dmpnn_max_tiles", "dmpnn_split_row_floats"):
             getattr(lib, name).restype = C.c_int
     if lib.dmpnn_version() != ABI_VERSION:
         raise RuntimeError(f"libdmpnn ABI version {lib.dmpnn_version()} != {ABI_VERSION} (stale build?)")

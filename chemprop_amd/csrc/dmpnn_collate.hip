@@ -88,6 +88,35 @@ extern "C" int64_t dmpnn_pack_tiles(const int* atom_off, const int* edge_off, in
     return n;
 }
 
+// HOST function (no device work): the packing of the DEVICE planners (pack_pieces in dmpnn_prepare.hip, dmpnn_tiles_large.hip;
+// oracle/collate_numpy.py: blocked_molecule_tiles) from the same two running offsets — greedy as above, except that a tile also
+// starts at every block of 64 consecutive molecules and that a molecule without atoms or edges still starts a tile where the
+// walk meets it (an empty slot for the tile kernel).  A batch that carries this table gets the tiles, and with them the tile
+// scales and every bit of the output, that K0 from its batch vector would have given it.  Same outputs and errors as
+// dmpnn_pack_tiles.
+extern "C" int64_t dmpnn_pack_tiles_blocked(const int* atom_off, const int* edge_off, int64_t n_mols, int* tile_row, int* tile_atom,
+                                            int64_t cap) {
+    if (n_mols < 0 || cap < 1 || !tile_row || !tile_atom || (n_mols > 0 && (!atom_off || !edge_off))) return -2;
+    int64_t n = 0;
+    for (int64_t base = 0; base < n_mols; base += 64) {
+        const int64_t lim = base + 64 < n_mols ? base + 64 : n_mols;
+        int64_t p = base;
+        while (p < lim) {
+            const int a0 = atom_off[p], e0 = edge_off[p];
+            if (n + 1 >= cap) return -2;
+            tile_row[n] = e0; tile_atom[n] = a0;
+            ++n;
+            int64_t q = p + 1;
+            if (atom_off[q] - a0 <= dmpnn::kMegaBA && edge_off[q] - e0 <= dmpnn::kMegaBM)   // (else: a tile of its own, the generic path)
+                while (q < n_mols && atom_off[q + 1] - a0 <= dmpnn::kMegaBA && edge_off[q + 1] - e0 <= dmpnn::kMegaBM) ++q;
+            p = q;   // (may lie beyond the block: the next block's first tile then simply ends this one, as on the device)
+        }
+    }
+    tile_row[n] = n_mols ? edge_off[n_mols] : 0;
+    tile_atom[n] = n_mols ? atom_off[n_mols] : 0;
+    return n;
+}
+
 extern "C" int64_t dmpnn_max_tiles(int64_t n_atoms, int64_t n_edges) { return dmpnn::mega_max_tiles(n_atoms, n_edges); }
 
 extern "C" int dmpnn_prepare_tiles_from_table(const int* tile_row, const int* tile_atom, int64_t n_tiles, int64_t n_atoms,

@@ -89,7 +89,11 @@ inline PlanLayout plan_layout(int64_t nV, int64_t nE) {
 }
 
 enum : int { PLAN_ASYMMETRIC = 1, PLAN_RANGE_ERROR = 2, PLAN_HUGE_DEGREE = 4, PLAN_NO_PIECE_TILES = 8,
-             PLAN_TILES_ONLY = 16 };  // tile plan (dmpnn_prepare_tiles): no CSR arrays, only the piece-tile tables
+             PLAN_TILES_ONLY = 16,    // tile plan (dmpnn_prepare_tiles): no CSR arrays, only the piece-tile tables
+             // the table came from the host and the batch vector was checked beside it (k_tiles_checked_split): the kPlanCheckWords
+             // words behind the header hold what the validation workgroups found (0: nothing) — the tile kernel reads them
+             PLAN_CHECK_WORDS = 32 };
+constexpr int kPlanCheckWords = 16;
 // graphs the fused (row-tiled) forward cannot represent: its kernels poison their output with NaN
 constexpr int kPlanNoFuse = PLAN_ASYMMETRIC | PLAN_RANGE_ERROR | PLAN_HUGE_DEGREE | PLAN_TILES_ONLY;
 // what the whole-forward tile kernel cannot take when it reads a tile plan (its own per-tile checks do the rest)
@@ -197,7 +201,8 @@ bool prepare_can_keep_mtiles(int64_t nV, int64_t nE);
 // The piece-tile tables of a tile plan from a table the LOADER made: the body of k_tiles_from_table (dmpnn_collate.hip), shared with
 // the launch that also carries the forward's weight pre-split (k_tiles_from_table_split, dmpnn_prepare.hip).
 __device__ __forceinline__ void tiles_from_table_body(const int* __restrict__ tile_row, const int* __restrict__ tile_atom,
-                                                          int n_tiles, int nV, int nE, int* __restrict__ plan, PlanLayout L) {
+                                                          int n_tiles, int nV, int nE, int* __restrict__ plan, PlanLayout L,
+                                                          int extra_flags = 0) {
     __shared__ int bad_s, spill_s;
     if (threadIdx.x == 0) { bad_s = 0; spill_s = 0; }
     __syncthreads();
@@ -224,7 +229,7 @@ __device__ __forceinline__ void tiles_from_table_body(const int* __restrict__ ti
     if (threadIdx.x < DMPNN_HDR_WORDS) {
         int v = 0;
         const int h = threadIdx.x;
-        if (h == DMPNN_HDR_FLAGS) v = (bad_s ? PLAN_NO_PIECE_TILES : 0) | PLAN_TILES_ONLY;
+        if (h == DMPNN_HDR_FLAGS) v = (bad_s ? PLAN_NO_PIECE_TILES : 0) | PLAN_TILES_ONLY | extra_flags;
         if (h == DMPNN_HDR_NMTILES) v = bad_s ? 0 : n_tiles;
         if (h == DMPNN_HDR_NSPILL) v = bad_s ? 0 : spill_s;
         if (h == DMPNN_HDR_LIGHT) v = 2;
@@ -239,6 +244,12 @@ __device__ __forceinline__ void tiles_from_table_body(const int* __restrict__ ti
 // batch vector does: the loader-tiles path pays no launch for the split either.  *did_split says whether it did.
 int launch_tiles_from_table_split(const int* tile_row, const int* tile_atom, int64_t n_tiles, int64_t nV, int64_t nE, int* plan, hipStream_t s,
                                   const dmpnn_fwd_args* split_for, bool* did_split);
+// ... for a batch that carries BOTH the host's table and its batch vector (dmpnn_forward_tiles with both): table workgroup, validation
+// workgroups (batch and batch[dst] non-decreasing, ids and destinations in range, every tile start a molecule boundary: one check
+// word each, PLAN_CHECK_WORDS) and the weight pre-split in one launch, no workgroup waiting for another.  *did_split false: nothing
+// launched (no split to carry, or more validation workgroups than check words) — the caller plans from the batch vector.
+int launch_tiles_checked_split(const int64_t* edge_index, const int64_t* batch, const int* tile_row, const int* tile_atom, int64_t n_tiles,
+                               int64_t nV, int64_t nE, int* plan, hipStream_t s, const dmpnn_fwd_args* split_for, bool* did_split);
 // mol_bounds (optional): the molecule ranges also as the table dmpnn_molagg_* read (first[n_mols] | end[n_mols] | flag)
 // split_for / did_split: the pre-split of that forward's weights (tile kernel on the f16 pipe) rides in the same launch — workgroup 0
 // plans, the others split; *did_split tells the caller to pass DMPNN_F_WSPLIT_READY to the forward

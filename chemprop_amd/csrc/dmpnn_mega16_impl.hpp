@@ -152,16 +152,50 @@ __device__ __forceinline__ void split_weights_wave(const SplitArgs& a, int wave,
     const bool live = n < NJ;
     const long long rs = J.tr ? 1 : J.ldw, ks = J.tr ? J.ldw : 1;  // strides of the output index n and of the reduction index k
     const float* row = J.W + (long long)(live ? n : 0) * rs;
+    // Fragment-major layout: the 16 B a lane of the tile kernel loads for (column tile T = n / 16, chunk c,
+    // part hi|lo) are contiguous per wave instruction: [T][c][part][lg][li][8 halfs]  (1 KiB per instruction).
+    _Float16* out = reinterpret_cast<_Float16*>(J.out);
+    const int T = n >> 4, li = n & 15;
+    if (J.nc <= 16 && J.scale_K <= 512) {
+        // ONE pass (rows of up to 512 columns: every forward shape of the tile kernels): the row sits in registers — lane l holds the
+        // eight columns 8 l .. 8 l + 7, one 16-byte group of the layout — every load is issued before the first use (one round trip
+        // where the two-pass loops below took up to twelve), one reduction, one conversion, two 16-byte stores per lane.  The
+        // arithmetic per element is the loops': x s -> hi -> x s - hi -> lo under scale_for of the same maximum.
+        float v[8], sv[8];
+        const int k0 = lane * 8;
+        const bool own_scale = J.scale_col0 == J.col0 && J.scale_K == J.K;   // (the scale is taken over the very columns held)
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = (k0 + q < J.K && live) ? row[(J.col0 + k0 + q) * ks] : 0.f;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) sv[q] = (!own_scale && live && lane + 64 * q < J.scale_K) ? row[(J.scale_col0 + lane + 64 * q) * ks] : 0.f;
+        float mx = 0.f;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) mx = fmaxf(mx, fabsf(own_scale ? v[q] : sv[q]));
+        for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+        const float s = live ? scale_for(mx) : 0.f;
+        if (lane == 0 && J.inv_scale && live) J.inv_scale[n] = 1.f / s;
+        if (k0 < J.nc * 32) {
+            h8 hv, lv;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const float x = (k0 + q < J.K && live) ? v[q] * s : 0.f;
+                const _Float16 hi = (_Float16)x;
+                const _Float16 lo = (_Float16)(x - (float)hi);
+                hv[q] = hi; lv[q] = lo;
+            }
+            const int c = k0 >> 5, lg = (k0 & 31) >> 3;
+            const long long base = (((long long)T * J.nc + c) * 2) * 512 + (lg * 16 + li) * 8;
+            *reinterpret_cast<h8*>(out + base) = hv;
+            *reinterpret_cast<h8*>(out + base + 512) = lv;
+        }
+        return;
+    }
     float mx = 0.f;
     for (int k = lane; k < J.scale_K; k += 64) mx = fmaxf(mx, fabsf(row[(J.scale_col0 + k) * ks]));
     for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
     const float s = live ? scale_for(mx) : 0.f;
     if (lane == 0 && J.inv_scale && live) J.inv_scale[n] = 1.f / s;
-    // Fragment-major layout: the 16 B a lane of the tile kernel loads for (column tile T = n / 16, chunk c,
-    // part hi|lo) are contiguous per wave instruction: [T][c][part][lg][li][8 halfs]  (1 KiB per instruction).
-    _Float16* out = reinterpret_cast<_Float16*>(J.out);
-    const int T = n >> 4, li = n & 15;
-    for (int k = lane; k < J.nc * 32; k += 64) {
+    for (int k = lane; k < J.nc * 32; k += 64) {   // (wider rows: two passes, single halfs)
         const float x = (k < J.K && live) ? row[(J.col0 + k) * ks] * s : 0.f;
         const _Float16 hi = (_Float16)x;
         const _Float16 lo = (_Float16)(x - (float)hi);
@@ -293,7 +327,10 @@ __global__ __launch_bounds__(64 * NW, 2) void k_mpnn_tile16(Mega16K G) {
     int rs = g.mtile_row[t], re = g.mtile_row[t + 1];
     int va = g.mtile_atom[t], vb = g.mtile_atom[t + 1];
     int hdr_light = g.flags[DMPNN_HDR_LIGHT], hdr_flags = g.flags[0], hdr_tiles = g.flags[DMPNN_HDR_NMTILES];   // (flags = the header's address)
-    asm volatile("" : "+v"(rs), "+v"(re), "+v"(va), "+v"(vb), "+v"(hdr_light), "+v"(hdr_flags), "+v"(hdr_tiles));
+    // ... and the check words of a K0 that took its table from the host (k_tiles_checked_split: one word per validation workgroup,
+    // right behind the header — the same 128 bytes): lane l looks at word l mod 16; they count only where the header says they were written
+    int chk = g.flags[DMPNN_HDR_WORDS + (lane & (kPlanCheckWords - 1))];
+    asm volatile("" : "+v"(rs), "+v"(re), "+v"(va), "+v"(vb), "+v"(hdr_light), "+v"(hdr_flags), "+v"(hdr_tiles), "+v"(chk));
     rs = __builtin_amdgcn_readfirstlane(rs); re = __builtin_amdgcn_readfirstlane(re);
     va = __builtin_amdgcn_readfirstlane(va); vb = __builtin_amdgcn_readfirstlane(vb);
     hdr_light = __builtin_amdgcn_readfirstlane(hdr_light); hdr_flags = __builtin_amdgcn_readfirstlane(hdr_flags);
@@ -314,7 +351,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_mpnn_tile16(Mega16K G) {
     //  an ESTIMATE of the tile count — 277 instead of 512 workgroups.  Correct on every grid down to one workgroup, but the back edge cost the
     //  allocation 1 .. 7 registers and the schedule 0.8 us at 64 molecules, 2 us at 512: more than the 0.5 us the idle workgroups take)
     const bool poison = (hdr_flags & (lean ? kPlanNoMegaLean : g.poison_mask)) != 0 || (lean && g.nE > 0 && (!g.edge_index || !g.rev64)) ||
-                        hdr_tiles > (int)gridDim.x;
+                        hdr_tiles > (int)gridDim.x || ((hdr_flags & PLAN_CHECK_WORDS) != 0 && __ballot(chk != 0) != 0ull);
     if (poison) {
         const float nanv = __int_as_float(0x7fc00000);
         const long long total = (long long)g.nV * N;

@@ -1082,7 +1082,101 @@ __global__ __launch_bounds__(256) void k_tiles_from_table_split(const int* __res
     else mega16::split_weights_wave(sp, ((int)blockIdx.x - 1) * 4 + (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63));
 }
 
+// The HOST's table (dmpnn_pack_tiles_blocked: a batch made by this package's own batching code) with the batch vector still in play:
+//     block 0                      copies / pads / checks the table and writes the header, as above (+ PLAN_CHECK_WORDS, + zeros in the
+//                                  check words no validation block owns);
+//     blocks [1, 1 + n_check)      validate the batch vector against it, kCheckPerBlock atoms / edges / tiles each: the per-atom and
+//                                  per-edge tests of the bounds blocks above (ids and destinations in range, batch and batch[dst]
+//                                  non-decreasing) without publishing offsets, and every tile start a molecule boundary of the batch
+//                                  vector.  Each block writes ITS check word (plain store, always written: 0 or the error bits);
+//     the other blocks             split the weights.
+// Nobody waits for anybody: the tile kernel reads the check words next to the header and poisons the batch on any bit set, exactly
+// as it does on PLAN_NO_PIECE_TILES / PLAN_RANGE_ERROR in the header.  What is not checked here — that a tile's rows are the edges
+// of its atoms and nothing else — is what the tile kernel checks for every tile it runs, whoever made the table.
+constexpr int kCheckThreads = 256, kCheckItems = 4, kCheckPerBlock = kCheckThreads * kCheckItems;
+__device__ __forceinline__ void tiles_check_block(const int64_t* __restrict__ edge_index, const int64_t* __restrict__ batch,
+                                                  const int* __restrict__ tile_atom, int n_tiles, int nV, int nE, int* __restrict__ plan, int b) {
+    __shared__ int bad_blk;
+    if (threadIdx.x == 0) bad_blk = 0;
+    __syncthreads();
+    const int64_t* dst = edge_index + nE;
+    int64_t bm[kCheckItems], bp[kCheckItems], d[kCheckItems], dp[kCheckItems];
+    int ta[kCheckItems];
+    // every independent read of a thread in flight together ...
+#pragma unroll
+    for (int j = 0; j < kCheckItems; ++j) {
+        const int i = (b * kCheckItems + j) * kCheckThreads + (int)threadIdx.x;
+        bm[j] = i < nV ? batch[i] : 0;
+        bp[j] = (i > 0 && i < nV) ? batch[i - 1] : 0;
+        d[j] = i < nE ? dst[i] : 0;
+        dp[j] = (i > 0 && i < nE) ? dst[i - 1] : 0;
+        ta[j] = i < n_tiles ? tile_atom[i] : 0;
+    }
+    int bad = 0;
+    int64_t em[kCheckItems], ep[kCheckItems], tb[kCheckItems], tp[kCheckItems];
+    // ... then the dependent ones: the molecule of an edge's destination, the ids on both sides of a tile start
+#pragma unroll
+    for (int j = 0; j < kCheckItems; ++j) {
+        const int i = (b * kCheckItems + j) * kCheckThreads + (int)threadIdx.x;
+        if (i < nE && (d[j] < 0 || d[j] >= nV)) { bad |= PLAN_RANGE_ERROR; d[j] = 0; }
+        if (dp[j] < 0 || dp[j] >= nV) dp[j] = 0;   // (flagged by the thread that owns that edge)
+        em[j] = i < nE ? batch[d[j]] : 0;
+        ep[j] = (i > 0 && i < nE) ? batch[dp[j]] : 0;
+        const bool inner = i < n_tiles && ta[j] > 0 && ta[j] < nV;   // (a table out of [0, nV] or out of order: block 0's verdict)
+        tb[j] = inner ? batch[ta[j]] : 1;
+        tp[j] = inner ? batch[ta[j] - 1] : 0;
+    }
+#pragma unroll
+    for (int j = 0; j < kCheckItems; ++j) {
+        const int i = (b * kCheckItems + j) * kCheckThreads + (int)threadIdx.x;
+        if (i < nV) {
+            if (bm[j] < 0 || bm[j] >= nV) bad |= PLAN_RANGE_ERROR;   // at most one molecule per atom
+            if (i > 0 && bm[j] < bp[j]) bad |= PLAN_NO_PIECE_TILES;
+        }
+        if (i > 0 && i < nE && em[j] < ep[j]) bad |= PLAN_NO_PIECE_TILES;   // edges not in molecule order
+        if (tb[j] <= tp[j]) bad |= PLAN_NO_PIECE_TILES;                    // a tile that starts inside a molecule of the batch vector
+    }
+    if (bad) atomicOr(&bad_blk, bad);
+    __syncthreads();
+    if (threadIdx.x == 0) plan[DMPNN_HDR_WORDS + b] = bad_blk;
+}
+
+__global__ __launch_bounds__(kCheckThreads) void k_tiles_checked_split(const int64_t* __restrict__ edge_index, const int64_t* __restrict__ batch,
+                                                                      const int* __restrict__ tile_row, const int* __restrict__ tile_atom, int n_tiles,
+                                                                      int nV, int nE, int n_check, int* __restrict__ plan, PlanLayout L, mega16::SplitArgs sp) {
+    const int b = (int)blockIdx.x;
+    if (b == 0) {
+        tiles_from_table_body(tile_row, tile_atom, n_tiles, nV, nE, plan, L, PLAN_CHECK_WORDS);
+        if ((int)threadIdx.x >= n_check && (int)threadIdx.x < kPlanCheckWords) plan[DMPNN_HDR_WORDS + threadIdx.x] = 0;
+    } else if (b <= n_check) {
+        tiles_check_block(edge_index, batch, tile_atom, n_tiles, nV, nE, plan, b - 1);
+    } else {
+        mega16::split_weights_wave(sp, (b - 1 - n_check) * (kCheckThreads / 64) + (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63));
+    }
+}
+
 }  // namespace
+
+int launch_tiles_checked_split(const int64_t* edge_index, const int64_t* batch, const int* tile_row, const int* tile_atom, int64_t n_tiles,
+                               int64_t nV, int64_t nE, int* plan, hipStream_t s, const dmpnn_fwd_args* split_for, bool* did_split) {
+    *did_split = false;
+    mega16::SplitArgs sp;
+    const PlanLayout L = plan_layout(nV, nE);
+    const int64_t n_items = nV > nE ? nV : nE;
+    const int n_check = (int)((n_items + kCheckPerBlock - 1) / kCheckPerBlock);
+    // (the check words sit in the plan's unused `src` array behind the header: a tile plan never writes it)
+    if (!split_for || !batch || !edge_index || nV <= 0 || nE <= 0 || n_tiles <= 0 || n_tiles > nV || n_check > kPlanCheckWords ||
+        L.words < DMPNN_HDR_WORDS + kPlanCheckWords || L.mtile_row < DMPNN_HDR_WORDS + kPlanCheckWords ||
+        !(split_for->flags & DMPNN_F_FUSED) || !(split_for->flags & DMPNN_F_MEGA) || !(split_for->flags & DMPNN_F_SPLIT16) ||
+        (split_for->flags & (DMPNN_F_WSPLIT_READY | DMPNN_F_KEEP)) || !mega16_split_args(*split_for, &sp))
+        return DMPNN_OK;
+    const int waves = ((sp.N + 15) & ~15) * sp.n_jobs, wpb = kCheckThreads / 64;
+    hipLaunchKernelGGL(k_tiles_checked_split, dim3((unsigned)(1 + n_check + (waves + wpb - 1) / wpb)), dim3(kCheckThreads), 0, s, edge_index, batch,
+                       tile_row, tile_atom, (int)n_tiles, (int)nV, (int)nE, n_check, plan, L, sp);
+    DMPNN_CHECK_LAUNCH("k_tiles_checked_split");
+    *did_split = true;
+    return DMPNN_OK;
+}
 
 int launch_tiles_from_table_split(const int* tile_row, const int* tile_atom, int64_t n_tiles, int64_t nV, int64_t nE, int* plan, hipStream_t s,
                                   const dmpnn_fwd_args* split_for, bool* did_split) {

@@ -40,10 +40,55 @@ def molecules_oversize(n_atoms, n_edges) -> bool:
     return bool(n_atoms.size and (int(n_atoms.max()) > TILE_MAX_ATOMS or int(n_edges.max()) > TILE_MAX_EDGES))
 
 
-class BatchMolGraph:
-    """A batch of :class:`MolGraph` as five tensors.  ``len()`` is the number of molecules."""
+SMALL_PLAN_MAX_ATOMS, SMALL_PLAN_MAX_EDGES = 6144, 10240  # kSmallMaxAtoms / kSmallMaxEdges of csrc/dmpnn_prepare.hip
+_FIVE = frozenset(("V", "E", "edge_index", "rev_edge_index", "batch"))
 
-    __slots__ = ("V", "E", "edge_index", "rev_edge_index", "batch", "_size", "tiles", "oversize")
+
+def host_tile_plan(n_atoms, n_edges):
+    """The tile table of the device planners (``dmpnn_pack_tiles_blocked``: ``oracle.collate_numpy.blocked_molecule_tiles``) from the
+    per-molecule counts a batch is built from -> ``(tile_row, tile_atom, n_tiles)`` as int32 numpy arrays of ``n_tiles + 1`` entries, or
+    ``None``: an empty batch, a molecule beyond the tile, counts beyond the single-workgroup plan (those batches keep K0 on the
+    device).  Molecules without atoms behind the last atom are not planned — as the planners that read ``batch[-1]`` do not."""
+    n_atoms, n_edges = np.asarray(n_atoms, dtype=np.int64), np.asarray(n_edges, dtype=np.int64)
+    with_atoms = np.flatnonzero(n_atoms)
+    if not with_atoms.size or molecules_oversize(n_atoms, n_edges):
+        return None
+    n = int(with_atoms[-1]) + 1
+    nV, nE = int(n_atoms[:n].sum()), int(n_edges.sum())
+    if nE == 0 or nV > SMALL_PLAN_MAX_ATOMS or nE > SMALL_PLAN_MAX_EDGES or int(n_edges[:n].sum()) != nE:
+        return None
+    try:
+        from . import _lib
+
+        lib = _lib.load()
+    except (OSError, RuntimeError):
+        return None  # (no library on this host: the batch is still a batch)
+    atom_off, edge_off = np.zeros(n + 1, dtype=np.int32), np.zeros(n + 1, dtype=np.int32)
+    atom_off[1:] = np.cumsum(n_atoms[:n])
+    edge_off[1:] = np.cumsum(n_edges[:n])
+    cap = int(lib.dmpnn_max_tiles(nV, nE)) + 1
+    trow, tatom = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32)
+    nt = int(lib.dmpnn_pack_tiles_blocked(atom_off.ctypes.data, edge_off.ctypes.data, n, trow.ctypes.data, tatom.ctypes.data, cap))
+    if nt <= 0:
+        return None
+    return trow[:nt + 1], tatom[:nt + 1], nt
+
+
+class BatchMolGraph:
+    """A batch of :class:`MolGraph` as five tensors.  ``len()`` is the number of molecules.
+
+    ``plan_table``: ``(tile_row, tile_atom, n_tiles)`` — the tile plan of the whole-forward tile kernel, made HERE from the atom / edge
+    counts the batching has in hand anyway (:func:`host_tile_plan`), so that K0 need not rebuild the molecule boundaries from
+    ``batch`` on the device; it lives in the tail of the int64 buffer ``batch`` is a view of and moves with it (``to``: still five
+    copies).  The forward validates ``batch`` / ``edge_index`` against it on the device.  Rebinding any of the five tensors drops it."""
+
+    __slots__ = ("V", "E", "edge_index", "rev_edge_index", "batch", "_size", "tiles", "oversize", "plan_table", "_bt")
+
+    def __setattr__(self, name, value):
+        object.__setattr__(self, name, value)
+        if name in _FIVE:  # (the table describes the tensors it was made with)
+            object.__setattr__(self, "plan_table", None)
+            object.__setattr__(self, "_bt", None)
 
     def __init__(self, mgs: Sequence[MolGraph]):
         self._size = len(mgs)
@@ -63,18 +108,46 @@ class BatchMolGraph:
         self.edge_index = torch.from_numpy(ei).long()
         rev = np.concatenate([mg.rev_edge_index + o for mg, o in zip(mgs, edge_off)])
         self.rev_edge_index = torch.from_numpy(rev).long()
-        self.batch = torch.from_numpy(np.repeat(np.arange(len(mgs), dtype=np.int64), n_atoms))
+        bt = np.repeat(np.arange(len(mgs), dtype=np.int64), n_atoms)
+        plan = None if self.oversize else host_tile_plan(n_atoms, n_edges)
+        if plan is None:
+            self.batch = torch.from_numpy(bt)
+        else:  # batch | tile_row | tile_atom in ONE int64 buffer: the table travels with the batch vector
+            nV, nt = len(bt), plan[2]
+            buf = np.zeros(nV + nt + 1, dtype=np.int64)
+            buf[:nV] = bt
+            tab = buf[nV:].view(np.int32)
+            tab[:nt + 1], tab[nt + 1:] = plan[0], plan[1]
+            self._set_packed(torch.from_numpy(buf), nV, nt)
+
+    def _set_packed(self, buf: Tensor, nV: int, nt: int) -> None:
+        tab = buf[nV:].view(torch.int32)
+        self.batch = buf[:nV]
+        self.plan_table, self._bt = (tab[:nt + 1], tab[nt + 1:], nt), buf
+
+    def __getstate__(self):
+        return {k: getattr(self, k) for k in self.__slots__ if hasattr(self, k)}
+
+    def __setstate__(self, state):
+        for k, v in state.items():
+            object.__setattr__(self, k, v)
+        if state.get("_bt") is not None and state.get("plan_table") is not None:  # (the views of one buffer again, whatever the pickler made of them)
+            self._set_packed(state["_bt"], int(state["batch"].numel()), state["plan_table"][2])
 
     def __len__(self) -> int:
         return self._size
 
     def to(self, device) -> None:
         """In-place device move, returns ``None`` exactly like collate.py:68-73."""
+        table, bt = self.plan_table, self._bt
         self.V = self.V.to(device)
         self.E = self.E.to(device)
         self.edge_index = self.edge_index.to(device)
         self.rev_edge_index = self.rev_edge_index.to(device)
-        self.batch = self.batch.to(device)
+        if table is not None and bt is not None:
+            self._set_packed(bt.to(device), int(self.batch.numel()), table[2])  # (one copy: the batch vector with the table behind it)
+        else:
+            self.batch = self.batch.to(device)
         self.tiles = None  # (views of the packed buffer on its own device)
 
     @classmethod
@@ -87,12 +160,14 @@ class BatchMolGraph:
         self._size = int(size) if size is not None else (int(batch[-1]) + 1 if batch.numel() else 0)
         self.tiles = None
         self.oversize = None
+        self.plan_table, self._bt = None, None  # (bare tensors carry no table: K0 plans from the batch vector on the device)
         return self
 
     def __copy__(self):
         b = BatchMolGraph.from_tensors(self.V, self.E, self.edge_index, self.rev_edge_index, self.batch, self._size)
         b.tiles = self.tiles  # (a graph_transform scales V / E of a shallow copy: the connectivity is the same)
         b.oversize = self.oversize
+        b.plan_table, b._bt = self.plan_table, self._bt
         return b
 
 

@@ -103,7 +103,7 @@ class GraphPlan:
     """K0: int32 indices + stable incoming-edge CSR of one batch, built on device (no host sync)."""
 
     __slots__ = ("buf", "n_atoms", "n_edges", "device", "light", "tiles_only", "edge_index", "rev_edge_index", "loader_tiles",
-                 "any_size", "oversize", "pending", "_job")
+                 "any_size", "oversize", "pending", "_job", "host_tiles")
 
     def __init__(self, edge_index: Tensor, rev_edge_index: Tensor, n_atoms: int, light=False, batch: Optional[Tensor] = None,
                  tiles: Optional[tuple] = None, launch: bool = True):
@@ -146,6 +146,9 @@ class GraphPlan:
         self.any_size = (self.tiles_only and not small) or full_tiles  # (the forward's DMPNN_F_LOADER_TILES)
         self.edge_index, self.rev_edge_index = ei, rev
         self.pending, self._job = None, None
+        # (tile_row, tile_atom, n_tiles) of a batch that carries the HOST's table beside its batch vector (data.BatchMolGraph.plan_table):
+        # set by the caller on a deferred plan, taken by the inference forward that runs the deferred K0
+        self.host_tiles = None
         if launch == "defer":
             # K0 NOT launched yet: a tile plan from the batch vector within the single-workgroup plan — the forward that follows
             # runs K0, the pre-split of its weights (in K0's launch) and the tile kernel as ONE foreign call (dmpnn_forward_tiles);
@@ -815,7 +818,13 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
             if pend is not None and use_mega and want16 and tiles_only:
                 # K0 was deferred to this call: tile table + weight pre-split (ONE launch) + tile kernel as one foreign call
                 plan.pending = None
-                _lib.check(lib.dmpnn_forward_tiles(C.byref(a), pend.data_ptr(), None, None, 0, plan.buf.numel() * 4, _stream_ptr(dev)), "dmpnn_forward_tiles")
+                ht = getattr(plan, "host_tiles", None) if not keep else None
+                if ht is not None:  # (the exact grid: the table's tile count)
+                    a.n_tiles_launch = ht[2]
+                    _lib.check(lib.dmpnn_forward_tiles(C.byref(a), pend.data_ptr(), ht[0].data_ptr(), ht[1].data_ptr(), ht[2],
+                                                       plan.buf.numel() * 4, _stream_ptr(dev)), "dmpnn_forward_tiles")
+                else:
+                    _lib.check(lib.dmpnn_forward_tiles(C.byref(a), pend.data_ptr(), None, None, 0, plan.buf.numel() * 4, _stream_ptr(dev)), "dmpnn_forward_tiles")
             else:
                 if pend is not None:
                     plan.ensure_launched()

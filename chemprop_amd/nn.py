@@ -249,6 +249,10 @@ def _replay_forward(mp, r: "_Replay", bmg):
     tiles = getattr(bmg, "tiles", None)
     if tiles is not None and (tiles[0].device != dev or tiles[2] <= 0):
         tiles = None
+    # (our own batch: the table its constructor made from the molecule sizes, validated against `batch` inside K0's launch)
+    own = getattr(bmg, "plan_table", None) if tiles is None else None
+    if own is not None and own[0].device != dev:
+        own = None
     small = engine.small_plan_fits(nV, nE)
     lib = _lib.load()
     if (n_mols <= 0 or nE > 30 * n_mols or nE == 0 or (tiles is None and not small and not lib.dmpnn_tile_plan_any_size(nV, nE))
@@ -283,6 +287,10 @@ def _replay_forward(mp, r: "_Replay", bmg):
             a.flags = r.flags | _lib.F_LOADER_TILES
             a.n_tiles_launch = tiles[2]
             rc = lib.dmpnn_forward_tiles(_ctypes.byref(a), None, tiles[0].data_ptr(), tiles[1].data_ptr(), tiles[2], nbytes, stream)
+        elif own is not None:  # the host's table AND the batch vector: the exact grid, K0 without a planner
+            a.flags = r.flags if small else (r.flags | _lib.F_LOADER_TILES)
+            a.n_tiles_launch = own[2]
+            rc = lib.dmpnn_forward_tiles(_ctypes.byref(a), batch.data_ptr(), own[0].data_ptr(), own[1].data_ptr(), own[2], nbytes, stream)
         else:
             a.flags = r.flags if small else (r.flags | _lib.F_LOADER_TILES)
             # (the tile count is on the device only; a tile holds at least one molecule, so the batch's molecule count bounds it — a third
@@ -386,6 +394,9 @@ def bond_message_passing_forward(mp, bmg, V_d: Optional[Tensor] = None) -> Tenso
         light = _training_plan_kind(mp, bmg) if oversize is not True else False
     # (a tile plan: K0 is deferred into the forward's own call where the library can run it with the weight pre-split in ONE launch)
     plan = engine.GraphPlan.from_bmg(bmg, light=light, launch="defer" if light == "tiles" else True)
+    own = getattr(bmg, "plan_table", None)
+    if own is not None and plan.pending is not None and not torch.is_grad_enabled() and own[0].device == plan.device:
+        plan.host_tiles = own  # (an inference forward of our own batch: the deferred K0 takes the table the batch carries)
     if n_mols and getattr(bmg, "batch", None) is not None:
         from .agg import note_batch
 

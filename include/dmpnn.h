@@ -206,7 +206,9 @@ enum dmpnn_plan_hdr {
                               batch vector was given, or the batch vector / the edge order is not the one collate
                               produces): DMPNN_F_MEGA returns NaN.  A piece (molecule) of more than 48 rows / 32 atoms
                               is NOT an error: it becomes a tile of its own, counted in DMPNN_HDR_NSPILL, and the tile
-                              kernels carry it through their generic fp32 path (csrc/dmpnn_spill_impl.hpp)          */
+                              kernels carry it through their generic fp32 path (csrc/dmpnn_spill_impl.hpp);
+                              bit4: tile plan; bit5: the 16 words behind the header are check words of K0's validation
+                              workgroups (dmpnn_forward_tiles with a host table AND the batch vector)                    */
     DMPNN_HDR_MAXDEG = 1,
     DMPNN_HDR_NATOMS = 2,
     DMPNN_HDR_NEDGES = 3,
@@ -427,7 +429,11 @@ int dmpnn_forward(const dmpnn_fwd_args* a, void* stream);
 /* K0 + forward of the steady inference path in ONE call (one foreign-function transition instead of two on a path whose host
  * side is as long as its device side): the tile plan of `a->plan` — from the loader's table when tile_row / tile_atom (n_tiles
  * entries + 1) are given (dmpnn_prepare_tiles_from_table), else from the batch vector / connectivity (dmpnn_prepare_tiles with
- * a->edge_index, a->rev_edge_index, `batch`) — then dmpnn_forward(a).  `a` as for an inference dmpnn_forward on a tile plan. */
+ * a->edge_index, a->rev_edge_index, `batch`) — then dmpnn_forward(a).  `a` as for an inference dmpnn_forward on a tile plan.
+ * BOTH `batch` and a table (of dmpnn_pack_tiles_blocked, made where the batch was made): K0 copies the table and validates the
+ * batch vector beside it in the same launch — ids and destinations in range, batch and batch[dst] non-decreasing, every tile start
+ * a molecule boundary — one check word per validation workgroup behind the header (header flag bit5), which the tile kernel reads:
+ * any bit set and the output is NaN, as for bits 1 / 3 of the header.  a->n_tiles_launch may then be n_tiles. */
 int dmpnn_forward_tiles(const dmpnn_fwd_args* a, const int64_t* batch, const int* tile_row, const int* tile_atom, int64_t n_tiles,
                         size_t plan_bytes, void* stream);
 /* 1 when the shapes / alignment of `a` allow DMPNN_F_FUSED (d_h % 4 == 0, d_h <= 320, even d_v and
@@ -567,6 +573,11 @@ int dmpnn_collate(const int* atom_off, const int* edge_off, int64_t n_mols, cons
  * A forward on such a plan passes DMPNN_F_LOADER_TILES (no batch-size limit from the single-workgroup plan) and may give
  * n_tiles_launch = n_tiles so that only that many workgroups are launched.                                          */
 int64_t dmpnn_pack_tiles(const int* atom_off, const int* edge_off, int64_t n_mols, int* tile_row, int* tile_atom, int64_t cap);
+/* HOST function: the packing of the DEVICE planners (K0 from the batch vector) — greedy as dmpnn_pack_tiles, except that a tile also
+ * starts at every block of 64 consecutive molecules and that a molecule without atoms or edges starts a tile where the walk meets
+ * it.  A batch that carries THIS table (with its batch vector: dmpnn_forward_tiles given both) gets the tiles, the tile scales and
+ * every output bit K0 would have given it from the batch vector.  Arguments, outputs and errors as dmpnn_pack_tiles. */
+int64_t dmpnn_pack_tiles_blocked(const int* atom_off, const int* edge_off, int64_t n_mols, int* tile_row, int* tile_atom, int64_t cap);
 int64_t dmpnn_max_tiles(int64_t n_atoms, int64_t n_edges);
 int dmpnn_prepare_tiles_from_table(const int* tile_row, const int* tile_atom, int64_t n_tiles, int64_t n_atoms,
                                    int64_t n_edges, void* plan, size_t plan_bytes, void* stream);
