@@ -443,6 +443,54 @@ int dmpnn_forward_tiles(const dmpnn_fwd_args* a, const int64_t* batch, const int
     return dmpnn_forward(&f, stream);
 }
 
+}  // extern "C"
+namespace dmpnn {
+// the update (t >= 1) and the finalize contraction of the per-step general route, as dmpnn_forward launches them
+static dmpnn_gemm_args general_update_gemm(const dmpnn_fwd_args& a, const float* Mt, float* Ht) {
+    dmpnn_gemm_args g;
+    memset(&g, 0, sizeof(g));
+    g.M = a.n_edges; g.N = a.d_h; g.K1 = a.d_h; g.K2 = 0;
+    g.A1 = Mt; g.lda1 = a.ldh;
+    g.W = a.W_h; g.ldw = a.d_h; g.bias = a.b_h;
+    g.Cadd = a.H0; g.ldcadd = a.ldh;
+    g.C = Ht; g.ldc = a.ldh;
+    g.act = a.act; g.act_slope = a.act_slope; g.act_slope_ptr = a.act_slope_ptr;
+    return g;
+}
+static dmpnn_gemm_args general_finalize_gemm(const dmpnn_fwd_args& a) {
+    const bool has_vd = a.W_d != nullptr;
+    dmpnn_gemm_args g;
+    memset(&g, 0, sizeof(g));
+    g.M = a.n_atoms; g.N = a.d_h; g.K1 = a.d_v; g.K2 = a.d_h;
+    g.A1 = a.V; g.lda1 = a.ldv;
+    g.A2 = a.Mv; g.lda2 = a.ldh;
+    g.W = a.W_o; g.ldw = a.d_v + a.d_h; g.bias = a.b_o;
+    g.C = has_vd ? a.Hv : a.out; g.ldc = has_vd ? a.ldh : a.ldout;
+    g.act = a.act; g.act_slope = a.act_slope; g.act_slope_ptr = a.act_slope_ptr;
+    return g;
+}
+// dropout_p in (0, 1) on the training forward of the per-step general route on the f16 pipe (DMPNN_F_SPLIT16 | DMPNN_F_KEEP without
+// DMPNN_F_FUSED): the mask lives in the epilogue of the row kernel k_rows16, so both masked contractions must really run there
+static int rows_dropout_check(const dmpnn_fwd_args& a) {
+    const char* who = "forward: dropout inside the row kernels (DMPNN_F_SPLIT16 | DMPNN_F_KEEP on the per-step general route)";
+    DMPNN_CHECK_ARG(!(a.flags & (DMPNN_F_MEGA | DMPNN_F_ATOM | DMPNN_F_TILE_PLAN)), "%s does not go with DMPNN_F_MEGA / DMPNN_F_ATOM / DMPNN_F_TILE_PLAN", who);
+    DMPNN_CHECK_ARG(!(a.flags & DMPNN_F_UNDIRECTED), "%s: directed messages only (no DMPNN_F_UNDIRECTED)", who);
+    DMPNN_CHECK_ARG(!a.W_d, "%s: no W_d (the reference's second dropout behind W_d has no mask site)", who);
+    DMPNN_CHECK_ARG(a.act != DMPNN_ACT_PRELU, "%s: activation none / relu / leakyrelu / tanh / elu (not PReLU)", who);
+    DMPNN_CHECK_ARG(a.d_h <= 1024, "%s: d_h <= 1024 (the hash key is row * 1024 + col; got %lld)", who, (long long)a.d_h);
+    if (a.depth > 1 && a.n_edges > 0) {
+        DMPNN_CHECK_ARG(a.Ms && a.Hs, "%s: missing Ms / Hs workspace", who);
+        DMPNN_CHECK_ARG(linear16_ok(general_update_gemm(a, a.Ms, a.Hs)),
+                        "%s: the update contraction would fall to the fp32-MFMA kernel (even d_h and ldh, 8-byte aligned Ms)", who);
+    }
+    if (a.n_atoms > 0)
+        DMPNN_CHECK_ARG(linear16_ok(general_finalize_gemm(a)),
+                        "%s: the finalize contraction would fall to the fp32-MFMA kernel (even d_v, d_h, ldv and ldh, 8-byte aligned V / Mv)", who);
+    return DMPNN_OK;
+}
+}  // namespace dmpnn
+extern "C" {
+
 int dmpnn_forward(const dmpnn_fwd_args* a, void* stream) {
     g_launches = 0;
     DMPNN_CHECK_ARG(a != nullptr, "forward: null args");
@@ -485,11 +533,15 @@ int dmpnn_forward(const dmpnn_fwd_args* a, void* stream) {
         const bool tile_train = (a->flags & DMPNN_F_MEGA) && (a->flags & DMPNN_F_SPLIT16) && (a->flags & DMPNN_F_KEEP);
         // ... or the LEAN training forward of the per-step fused route, asked for by the caller (flags + keep_bits), under its own conditions
         const bool lean_train = lean16 && fused16_lean_shapes(*a, true);
-        DMPNN_CHECK_ARG(lean_train || (tile_train && !has_vd && (a->act == DMPNN_ACT_RELU || a->act == DMPNN_ACT_LEAKYRELU)),
+        // ... or the training forward of the per-step general route on the f16 pipe: the mask in the row kernels' epilogue
+        const bool rows_train = !fused && (a->flags & DMPNN_F_SPLIT16) && (a->flags & DMPNN_F_KEEP);
+        if (rows_train) DMPNN_TRY(rows_dropout_check(*a));
+        DMPNN_CHECK_ARG(rows_train || lean_train || (tile_train && !has_vd && (a->act == DMPNN_ACT_RELU || a->act == DMPNN_ACT_LEAKYRELU)),
                         "forward: dropout inside the kernels needs the training forward of the tile kernel (DMPNN_F_MEGA | DMPNN_F_SPLIT16 | "
                         "DMPNN_F_KEEP) or the lean training forward of the per-step fused route (DMPNN_F_FUSED | DMPNN_F_SPLIT16 | DMPNN_F_KEEP "
                         "with keep_bits; d_h <= 320, d_h %% 4 == 0, even d_v / d_e, depth 2 .. %d, a full plan), a ReLU-class activation and "
-                        "no W_d — run dropout between the row kernels otherwise", kWProdMaxJobs);
+                        "no W_d — or the training forward of the per-step general route on the f16 pipe (DMPNN_F_SPLIT16 | DMPNN_F_KEEP "
+                        "without DMPNN_F_FUSED) — run dropout between the row kernels otherwise", kWProdMaxJobs);
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const PlanView pv = plan_view(a->plan, nV, nE);
@@ -659,7 +711,14 @@ int dmpnn_forward(const dmpnn_fwd_args* a, void* stream) {
         DMPNN_TRY(split_weights_views(jobs, nj, views, s));   // (one launch for all of them)
         for (int k = 0; k < nj; ++k) w16[idx[k]] = views[k];
     }
-    auto lin = [&](const dmpnn_gemm_args& g, int slot) -> int {
+    // (site >= 0: the dropout mask of that site on the contraction's output — rows_dropout_check has made sure it runs on k_rows16)
+    const bool drop = a->dropout_p > 0.f;
+    auto lin = [&](const dmpnn_gemm_args& g, int slot, int site = -1) -> int {
+        if (drop && site >= 0) {
+            DMPNN_CHECK_ARG(use16 && linear16_ok(g), "forward: dropout inside the row kernels needs the f16-pipe contraction");
+            const RowsDrop d{a->dropout_p, a->dropout_seed, site};
+            return launch_linear16_view(g, w16[slot], nullptr, 0, s, &d);
+        }
         if (use16 && linear16_ok(g)) return launch_linear16_view(g, w16[slot], nullptr, 0, s);
         return launch_linear(g, s);
     };
@@ -683,15 +742,8 @@ int dmpnn_forward(const dmpnn_fwd_args* a, void* stream) {
         DMPNN_TRY(launch_message(pv, nV, nE, h, Hprev, a->ldh, Mt, a->ldh, act_on_load, a->act_slope,
                                  a->act_slope_ptr, a->flags, s));
         // K3  H = tau(H0 + W_h(M))                                 base.py:135-141
-        dmpnn_gemm_args g;
-        memset(&g, 0, sizeof(g));
-        g.M = nE; g.N = h; g.K1 = h; g.K2 = 0;
-        g.A1 = Mt; g.lda1 = a->ldh;
-        g.W = a->W_h; g.ldw = h; g.bias = a->b_h;
-        g.Cadd = a->H0; g.ldcadd = a->ldh;
-        g.C = Ht; g.ldc = a->ldh;
-        g.act = a->act; g.act_slope = a->act_slope; g.act_slope_ptr = a->act_slope_ptr;
-        DMPNN_TRY(lin(g, 1));
+        const dmpnn_gemm_args g = general_update_gemm(*a, Mt, Ht);
+        DMPNN_TRY(lin(g, 1, t - 1));   // (base.py:139: H^(t) = dropout(tau(.)), site t - 1)
         Hprev = Ht;
         act_on_load = DMPNN_ACT_NONE;
     }
@@ -700,15 +752,8 @@ int dmpnn_forward(const dmpnn_fwd_args* a, void* stream) {
                                a->act_slope_ptr, s));
     // K5  finalize                                                 base.py:180-194
     {
-        dmpnn_gemm_args g;
-        memset(&g, 0, sizeof(g));
-        g.M = nV; g.N = h; g.K1 = dv; g.K2 = h;
-        g.A1 = a->V; g.lda1 = a->ldv;
-        g.A2 = a->Mv; g.lda2 = a->ldh;
-        g.W = a->W_o; g.ldw = dv + h; g.bias = a->b_o;
-        g.C = has_vd ? a->Hv : a->out; g.ldc = has_vd ? a->ldh : a->ldout;
-        g.act = a->act; g.act_slope = a->act_slope; g.act_slope_ptr = a->act_slope_ptr;
-        DMPNN_TRY(lin(g, 2));
+        const dmpnn_gemm_args g = general_finalize_gemm(*a);
+        DMPNN_TRY(lin(g, 2, a->depth - 1));   // (base.py:182: dropout behind the finalize's tau, site depth - 1)
     }
     if (has_vd) {
         dmpnn_gemm_args g;

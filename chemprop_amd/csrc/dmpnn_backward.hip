@@ -46,6 +46,11 @@ struct EdgeBwdArgs {
     float slope;
     const float* slope_ptr;
     int poison_mask;   // plan flags that make the message backward write NaN
+    // DROP builds only (the forward ran with the dropout mask in the row kernels, dmpnn_fwd_args.dropout_p on the per-step general
+    // route): Y = m tau(z) / (1 - p) is post-dropout, the factor is m / (1 - p) tau'(Y (1 - p)) with m regenerated from the hash of
+    // (seed, site, target row, column) — for every activation: a zero of tanh / elu / none does not say "dropped"
+    unsigned drop_thr, seed_lo, seed_hi, drop_site;
+    float drop_scale, drop_unscale;   // 1 / (1 - p), 1 - p
 };
 
 template <int ACT>
@@ -57,18 +62,33 @@ __device__ __forceinline__ float mask1(float g, float y, int act_rt, float slope
     return g * act_grad_from_out(y, act_rt, slope);
 }
 
+// the DROP builds' factor on one element: m / (1 - p) tau'(y (1 - p))
+__device__ __forceinline__ float mask1_drop(const EdgeBwdArgs& a, float g, float y, float slope, unsigned row, unsigned col) {
+    const bool keep = drop_hash(a.seed_lo, a.seed_hi, a.drop_site, row, col) >= a.drop_thr;
+    return keep ? g * a.drop_scale * act_grad_from_out(y * a.drop_unscale, a.act, slope) : 0.f;
+}
+
 // finish one float4 (or float) of target row `row`: mask, store gZ, accumulate gH0
-template <int VEC, int ACT>
+template <int VEC, int ACT, bool DROP = false>
 __device__ __forceinline__ void finish(const EdgeBwdArgs& a, int row, int c, bool ok, float slope,
                                        float gx, float gy, float gz, float gw,
                                        float yx, float yy, float yz, float yw,
                                        float ax, float ay, float az, float aw) {
-    float o0 = mask1<ACT>(gx, yx, a.act, slope, a.y_preact);
-    float o1 = 0.f, o2 = 0.f, o3 = 0.f;
-    if (VEC == 4) {
-        o1 = mask1<ACT>(gy, yy, a.act, slope, a.y_preact);
-        o2 = mask1<ACT>(gz, yz, a.act, slope, a.y_preact);
-        o3 = mask1<ACT>(gw, yw, a.act, slope, a.y_preact);
+    float o0, o1 = 0.f, o2 = 0.f, o3 = 0.f;
+    if constexpr (DROP) {
+        o0 = mask1_drop(a, gx, yx, slope, (unsigned)row, (unsigned)c);
+        if (VEC == 4) {
+            o1 = mask1_drop(a, gy, yy, slope, (unsigned)row, (unsigned)c + 1u);
+            o2 = mask1_drop(a, gz, yz, slope, (unsigned)row, (unsigned)c + 2u);
+            o3 = mask1_drop(a, gw, yw, slope, (unsigned)row, (unsigned)c + 3u);
+        }
+    } else {
+        o0 = mask1<ACT>(gx, yx, a.act, slope, a.y_preact);
+        if (VEC == 4) {
+            o1 = mask1<ACT>(gy, yy, a.act, slope, a.y_preact);
+            o2 = mask1<ACT>(gz, yz, a.act, slope, a.y_preact);
+            o3 = mask1<ACT>(gw, yw, a.act, slope, a.y_preact);
+        }
     }
     if (!ok) return;
     if (a.gZ) {
@@ -93,7 +113,7 @@ __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(
 __device__ __forceinline__ float4 sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 
 // MESSAGE mode, atom with in-degree exactly D: D rows of gM, D rows of Y, D rows of acc in flight.
-template <int VEC, int ACT, int D>
+template <int VEC, int ACT, int D, bool DROP = false>
 __device__ __forceinline__ void msg_bwd_body(const EdgeBwdArgs& a, int beg, int lane, int n_cols, float slope,
                                              const float* Yp, int64_t ldy, const float* Ap, int64_t lda) {
     int eid[D], erev[D];
@@ -118,13 +138,13 @@ __device__ __forceinline__ void msg_bwd_body(const EdgeBwdArgs& a, int beg, int 
 #pragma unroll
         for (int i = 0; i < D; ++i) {
             const float4 g = sub4(S, r[i]);
-            finish<VEC, ACT>(a, eid[i], c, ok, slope, g.x, g.y, g.z, g.w, y[i].x, y[i].y, y[i].z, y[i].w,
-                             ac[i].x, ac[i].y, ac[i].z, ac[i].w);
+            finish<VEC, ACT, DROP>(a, eid[i], c, ok, slope, g.x, g.y, g.z, g.w, y[i].x, y[i].y, y[i].z, y[i].w,
+                                   ac[i].x, ac[i].y, ac[i].z, ac[i].w);
         }
     }
 }
 
-template <int VEC, int ACT>
+template <int VEC, int ACT, bool DROP = false>
 __device__ __forceinline__ void msg_bwd_any(const EdgeBwdArgs& a, int beg, int d, int lane, int n_cols, float slope,
                                             const float* Yp, int64_t ldy, const float* Ap, int64_t lda) {
     for (int cg = lane; cg < n_cols; cg += 64) {
@@ -136,12 +156,12 @@ __device__ __forceinline__ void msg_bwd_any(const EdgeBwdArgs& a, int beg, int d
             const float4 g = sub4(S, ld<VEC>(a.gin + (int64_t)a.pv.rev[e] * a.ld_gin + c));
             const float4 y = ld<VEC>(Yp + (int64_t)e * ldy + c);
             const float4 ac = ld<VEC>(Ap + (int64_t)e * lda + c);
-            finish<VEC, ACT>(a, e, c, true, slope, g.x, g.y, g.z, g.w, y.x, y.y, y.z, y.w, ac.x, ac.y, ac.z, ac.w);
+            finish<VEC, ACT, DROP>(a, e, c, true, slope, g.x, g.y, g.z, g.w, y.x, y.y, y.z, y.w, ac.x, ac.y, ac.z, ac.w);
         }
     }
 }
 
-template <int VEC, int MODE, int ACT>
+template <int VEC, int MODE, int ACT, bool DROP = false>
 __global__ __launch_bounds__(256) void k_edge_bwd(EdgeBwdArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -169,16 +189,16 @@ __global__ __launch_bounds__(256) void k_edge_bwd(EdgeBwdArgs a) {
             const int beg = a.pv.row_ptr[v];
             const int d = a.pv.row_ptr[v + 1] - beg;
             if (ACT == -1) {
-                msg_bwd_any<VEC, ACT>(a, beg, d, lane, n_cols, slope, Yp, ldy, Ap, lda);
+                msg_bwd_any<VEC, ACT, DROP>(a, beg, d, lane, n_cols, slope, Yp, ldy, Ap, lda);
                 continue;
             }
             switch (d) {
                 case 0: break;
-                case 1: msg_bwd_body<VEC, ACT, 1>(a, beg, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
-                case 2: msg_bwd_body<VEC, ACT, 2>(a, beg, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
-                case 3: msg_bwd_body<VEC, ACT, 3>(a, beg, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
-                case 4: msg_bwd_body<VEC, ACT, 4>(a, beg, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
-                default: msg_bwd_any<VEC, ACT>(a, beg, d, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
+                case 1: msg_bwd_body<VEC, ACT, 1, DROP>(a, beg, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
+                case 2: msg_bwd_body<VEC, ACT, 2, DROP>(a, beg, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
+                case 3: msg_bwd_body<VEC, ACT, 3, DROP>(a, beg, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
+                case 4: msg_bwd_body<VEC, ACT, 4, DROP>(a, beg, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
+                default: msg_bwd_any<VEC, ACT, DROP>(a, beg, d, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
             }
         }
     } else {
@@ -193,7 +213,7 @@ __global__ __launch_bounds__(256) void k_edge_bwd(EdgeBwdArgs a) {
                 const float4 y = ld<VEC>(Yp + (int64_t)e * ldy + c);
                 const float4 ac = ld<VEC>(Ap + (int64_t)e * lda + c);
                 if (MODE == EB_AVG) g = make_float4((g.x + g1.x) / 2.f, (g.y + g1.y) / 2.f, (g.z + g1.z) / 2.f, (g.w + g1.w) / 2.f);
-                finish<VEC, ACT>(a, e, c, true, slope, g.x, g.y, g.z, g.w, y.x, y.y, y.z, y.w, ac.x, ac.y, ac.z, ac.w);
+                finish<VEC, ACT, DROP>(a, e, c, true, slope, g.x, g.y, g.z, g.w, y.x, y.y, y.z, y.w, ac.x, ac.y, ac.z, ac.w);
             }
         }
     }
@@ -213,6 +233,13 @@ int launch_edge_bwd(EdgeBwdArgs a, hipStream_t s, const char* name) {
     if (a.gZ) vec = vec && (a.ldgz % 4 == 0) && aligned16(a.gZ);
     if (a.acc) vec = vec && (a.ldacc % 4 == 0) && aligned16(a.acc);
     const dim3 grid((unsigned)blocks), block(256);
+    if (a.drop_scale != 0.f) {   // (the mask is regenerated for every activation: the generic builds)
+        if (MODE == EB_AVG || !a.Y || a.y_preact) { set_error("backward: the dropout mask goes with a kept post-dropout H^(t), directed"); return DMPNN_EINVAL; }
+        if (vec) hipLaunchKernelGGL((k_edge_bwd<4, MODE, -1, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((k_edge_bwd<1, MODE, -1, true>), grid, block, 0, s, a);
+        DMPNN_CHECK_LAUNCH(name);
+        return DMPNN_OK;
+    }
     if (vec && a.act == DMPNN_ACT_NONE) hipLaunchKernelGGL((k_edge_bwd<4, MODE, DMPNN_ACT_NONE>), grid, block, 0, s, a);
     else if (vec && a.act == DMPNN_ACT_RELU) hipLaunchKernelGGL((k_edge_bwd<4, MODE, DMPNN_ACT_RELU>), grid, block, 0, s, a);
     else if (vec) hipLaunchKernelGGL((k_edge_bwd<4, MODE, -1>), grid, block, 0, s, a);
@@ -246,6 +273,35 @@ __global__ void k_act_bwd(const float* __restrict__ g, int64_t ldg, const float*
                 make_float4(gv.x * grad(yv.x), gv.y * grad(yv.y), gv.z * grad(yv.z), gv.w * grad(yv.w));
         } else {
             out[r * ldo + c] = g[r * ldg + c] * grad(Y[r * ldy + c]);
+        }
+    }
+}
+
+// the same where the forward applied the dropout mask in the row kernels (the per-step general route on the f16 pipe): Y = m tau(z) / (1 - p),
+// gZ = g m / (1 - p) tau'(Y (1 - p)) with m regenerated from the hash of (seed, site, row, column) — any activation
+struct ActDrop { unsigned thr, seed_lo, seed_hi, site; float scale, unscale; };
+template <int VEC>
+__global__ void k_act_bwd_hash(const float* __restrict__ g, int64_t ldg, const float* __restrict__ Y, int64_t ldy,
+                               float* __restrict__ out, int64_t ldo, int64_t rows, int h, int act, float slope,
+                               const float* slope_ptr, ActDrop d) {
+    const float sl = slope_ptr ? *slope_ptr : slope;
+    auto grad = [&](float y, unsigned r, unsigned c) -> float {
+        const bool keep = drop_hash(d.seed_lo, d.seed_hi, d.site, r, c) >= d.thr;
+        return keep ? d.scale * act_grad_from_out(y * d.unscale, act, sl) : 0.f;
+    };
+    const int q = h / VEC;  // column groups per row
+    const int64_t n = rows * q;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = n < (int64_t(1) << 31) ? (int64_t)((unsigned)i / (unsigned)q) : i / q;
+        const int c = (int)(i - r * q) * VEC;
+        const unsigned ur = (unsigned)r, uc = (unsigned)c;
+        if (VEC == 4) {
+            const float4 gv = *reinterpret_cast<const float4*>(g + r * ldg + c);
+            const float4 yv = *reinterpret_cast<const float4*>(Y + r * ldy + c);
+            *reinterpret_cast<float4*>(out + r * ldo + c) =
+                make_float4(gv.x * grad(yv.x, ur, uc), gv.y * grad(yv.y, ur, uc + 1u), gv.z * grad(yv.z, ur, uc + 2u), gv.w * grad(yv.w, ur, uc + 3u));
+        } else {
+            out[r * ldo + c] = g[r * ldg + c] * grad(Y[r * ldy + c], ur, uc);
         }
     }
 }
@@ -1019,9 +1075,20 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
                     "16-byte aligned gout / out (leading dimensions multiples of 4)");
     // in-kernel dropout (dmpnn_fwd_args.dropout_p): its 1 / (1 - p) lives in the backward TILE kernel and in the lean branch above (the
     // backward step kernels regenerate the mask) — every other branch below would return gradients without it, silently
-    DMPNN_CHECK_ARG(!(f.dropout_p > 0.f) || tile_bwd,
+    // ... or, for the per-step general route on the f16 pipe (the mask in the row kernels' epilogue), in k_act_bwd_hash / the DROP
+    // builds of k_edge_bwd below, which regenerate the mask from the hash
+    const bool rows_drop = f.dropout_p > 0.f && f.dropout_p < 1.f && !fused && (f.flags & DMPNN_F_SPLIT16) && (f.flags & DMPNN_F_KEEP) &&
+                           !(f.flags & (DMPNN_F_MEGA | DMPNN_F_UNDIRECTED | DMPNN_F_ATOM)) && !has_vd && h <= 1024;
+    DMPNN_CHECK_ARG(!(f.dropout_p > 0.f) || tile_bwd || rows_drop,
                     "backward: the forward ran with dropout inside the kernels; only the backward tile kernel carries its scale — it needs a "
-                    "gradient of W_i or W_h to be wanted and 16-byte aligned gout / out (leading dimensions multiples of 4)");
+                    "gradient of W_i or W_h to be wanted and 16-byte aligned gout / out (leading dimensions multiples of 4) — or the per-step "
+                    "general route on the f16 pipe (DMPNN_F_SPLIT16 | DMPNN_F_KEEP, directed, no W_d, d_h <= 1024)");
+    const unsigned d_thr = rows_drop ? drop_threshold(f.dropout_p) : 0u, d_lo = (unsigned)(f.dropout_seed & 0xFFFFFFFFull), d_hi = (unsigned)(f.dropout_seed >> 32);
+    const float d_scale = rows_drop ? 1.f / (1.f - f.dropout_p) : 0.f, d_unscale = 1.f - f.dropout_p;
+    auto set_drop = [&](EdgeBwdArgs& x, int site) {   // Y of this launch is the post-dropout H of mask site `site`
+        if (!rows_drop) return;
+        x.drop_thr = d_thr; x.seed_lo = d_lo; x.seed_hi = d_hi; x.drop_site = (unsigned)site; x.drop_scale = d_scale; x.drop_unscale = d_unscale;
+    };
     if (tile_bwd) {
         // ---- the whole data-gradient chain in one launch, then the four weight gradients ----
         DMPNN_CHECK_ARG(f.H0 && (T == 1 || f.Hs), "backward: the tile-kernel forward did not keep H0 / H^(t)");
@@ -1247,11 +1314,20 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
         const int64_t n = nV * (vec ? h / 4 : h);
         int64_t blocks = (n + 255) / 256;
         if (blocks > 4096) blocks = 4096;
-        if (vec) hipLaunchKernelGGL(k_act_bwd<4>, dim3((unsigned)blocks), dim3(256), 0, s, gHO_p, ld_gHO, HO, ldHO, gZO, ldh, nV, (int)h,
+        if (rows_drop) {   // (the finalize's mask: site depth - 1, rows are atoms)
+            const ActDrop d{d_thr, d_lo, d_hi, (unsigned)(T - 1), d_scale, d_unscale};
+            if (vec) hipLaunchKernelGGL(k_act_bwd_hash<4>, dim3((unsigned)blocks), dim3(256), 0, s, gHO_p, ld_gHO, HO, ldHO, gZO, ldh, nV, (int)h,
+                                        f.act, f.act_slope, f.act_slope_ptr, d);
+            else hipLaunchKernelGGL(k_act_bwd_hash<1>, dim3((unsigned)blocks), dim3(256), 0, s, gHO_p, ld_gHO, HO, ldHO, gZO, ldh, nV, (int)h,
+                                    f.act, f.act_slope, f.act_slope_ptr, d);
+            DMPNN_CHECK_LAUNCH("k_act_bwd_hash");
+        } else {
+            if (vec) hipLaunchKernelGGL(k_act_bwd<4>, dim3((unsigned)blocks), dim3(256), 0, s, gHO_p, ld_gHO, HO, ldHO, gZO, ldh, nV, (int)h,
+                                        f.act, f.act_slope, f.act_slope_ptr, 0.f);
+            else hipLaunchKernelGGL(k_act_bwd<1>, dim3((unsigned)blocks), dim3(256), 0, s, gHO_p, ld_gHO, HO, ldHO, gZO, ldh, nV, (int)h,
                                     f.act, f.act_slope, f.act_slope_ptr, 0.f);
-        else hipLaunchKernelGGL(k_act_bwd<1>, dim3((unsigned)blocks), dim3(256), 0, s, gHO_p, ld_gHO, HO, ldHO, gZO, ldh, nV, (int)h,
-                                f.act, f.act_slope, f.act_slope_ptr, 0.f);
-        DMPNN_CHECK_LAUNCH("k_act_bwd");
+            DMPNN_CHECK_LAUNCH("k_act_bwd");
+        }
     }
     if (b->gW_o || b->gb_o) {
         WgradArgs a;
@@ -1306,6 +1382,7 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
         g0.gin = gMv; g0.ld_gin = ldh;
         g0.Y = f.Hs + (int64_t)(T - 2) * slot; g0.ldy = ldh; g0.y_preact = 0;
         g0.gZ = gZa; g0.ldgz = ldh; g0.acc = gH0; g0.ldacc = ldh; g0.acc_init = 1;
+        set_drop(g0, T - 2);
         DMPNN_TRY(launch_edge_bwd<EB_GATHER>(g0, s, "k_edge_bwd<gather>"));
         float* gZ = gZa;
         float* other = gZb;
@@ -1336,6 +1413,7 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
                 m.Y = Yprev; m.ldy = ldh; m.y_preact = first ? 1 : 0;
                 m.gZ = first ? nullptr : gZ; m.ldgz = ldh;
                 m.acc = gH0; m.ldacc = ldh; m.acc_init = 0;
+                if (!first) set_drop(m, t - 2);   // (the first step reads the unmasked H0 pre-activation: no mask)
                 DMPNN_TRY(launch_edge_bwd<EB_MESSAGE>(m, s, "k_edge_bwd<message>"));
             } else {
                 m.gZ = gZ; m.ldgz = ldh;  // raw gHb

@@ -316,7 +316,11 @@ int split_weights_views(const SplitWJob* jobs, int n, SplitWView* out, hipStream
 bool split_weights_args(const SplitWJob* jobs, int n, SplitWView* out, mega16::SplitArgs* sp);   // ... the argument block only
 int launch_split_args(const mega16::SplitArgs& sp, hipStream_t s);
 bool linear16_ok(const dmpnn_gemm_args& a);
-int launch_linear16_view(const dmpnn_gemm_args& a, const SplitWView& W, const int* poison_flags, int poison_mask, hipStream_t s);
+// drop (or null): C = keep ? tau(z) / (1 - p) : +0 with keep = drop_hash(seed, site, output row, column) >= floor(p 2^32) — the row
+// kernel's builds with the mask in their epilogue (dmpnn_rows16_drop.hip); N <= 1024, Zpre stays unmasked
+struct RowsDrop { float p; uint64_t seed; int site; };
+int launch_linear16_view(const dmpnn_gemm_args& a, const SplitWView& W, const int* poison_flags, int poison_mask, hipStream_t s,
+                         const RowsDrop* drop = nullptr);
 int launch_mega16_forward(const dmpnn_fwd_args& a, float* out, int64_t ldout, hipStream_t s);
 // waves per tile workgroup of the whole-forward / backward tile kernels for this batch (4, or 8 when the launch has at most one tile per CU)
 int tile_waves(const dmpnn_fwd_args& a, int n_tiles);

@@ -16,6 +16,11 @@ DMPNN_DEFINE_ROWS16(2, 12)
 DMPNN_DEFINE_ROWS16(3, 12)
 DMPNN_DEFINE_ROWS16(4, 12)
 DMPNN_DEFINE_ROWS16(5, 12)
+// the builds with the dropout mask in the epilogue: a translation unit of their own (dmpnn_rows16_drop.hip)
+#define DMPNN_DECLARE_ROWS16_DROP(WN, GC) template <> int launch_rows16<WN, GC, false, true>(const Rows16K& g, int row_tiles, int col_blocks, hipStream_t s);
+DMPNN_DECLARE_ROWS16_DROP(1, 4) DMPNN_DECLARE_ROWS16_DROP(2, 4) DMPNN_DECLARE_ROWS16_DROP(3, 4) DMPNN_DECLARE_ROWS16_DROP(4, 4) DMPNN_DECLARE_ROWS16_DROP(5, 4)
+DMPNN_DECLARE_ROWS16_DROP(1, 12) DMPNN_DECLARE_ROWS16_DROP(2, 12) DMPNN_DECLARE_ROWS16_DROP(3, 12) DMPNN_DECLARE_ROWS16_DROP(4, 12) DMPNN_DECLARE_ROWS16_DROP(5, 12)
+#undef DMPNN_DECLARE_ROWS16_DROP
 }  // namespace rows16
 
 static size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
@@ -55,7 +60,9 @@ bool linear16_ok(const dmpnn_gemm_args& a) {
     return true;
 }
 
-int launch_linear16(const dmpnn_gemm_args& a, const mega16::SplitW& W, const int* poison_flags, int poison_mask, hipStream_t s) {
+// drop (or null): the dropout mask on C (RowsDrop, dmpnn_common.hpp) — the DROP builds of the same kernels, same launch geometry
+int launch_linear16(const dmpnn_gemm_args& a, const mega16::SplitW& W, const int* poison_flags, int poison_mask, hipStream_t s,
+                    const RowsDrop* drop = nullptr) {
     if (a.M == 0 || a.N == 0) return DMPNN_OK;
     DMPNN_CHECK_ARG(linear16_ok(a), "linear16: shapes / alignment not supported by the split kernel");
     rows16::Rows16K g;
@@ -78,6 +85,27 @@ int launch_linear16(const dmpnn_gemm_args& a, const mega16::SplitW& W, const int
     const int row_tiles = (int)((a.M + rows16::BM - 1) / rows16::BM);
     // about one tile per CU: the whole (<= 384-column) operand row in one group, one workgroup per CU
     const bool one_group = (int64_t)row_tiles * col_blocks <= 512;
+    if (drop) {
+        DMPNN_CHECK_ARG(drop->p > 0.f && drop->p < 1.f && a.N <= 1024, "linear16: dropout needs 0 < p < 1 and N <= 1024 (the hash key is row * 1024 + col)");
+        g.drop_lo = (unsigned)(drop->seed & 0xFFFFFFFFull); g.drop_hi = (unsigned)(drop->seed >> 32); g.drop_site = (unsigned)drop->site;
+        g.drop_thr = drop_threshold(drop->p); g.drop_scale = 1.f / (1.f - drop->p);
+        if (one_group) {
+            switch (WN) {
+                case 1: return rows16::launch_rows16<1, 12, false, true>(g, row_tiles, col_blocks, s);
+                case 2: return rows16::launch_rows16<2, 12, false, true>(g, row_tiles, col_blocks, s);
+                case 3: return rows16::launch_rows16<3, 12, false, true>(g, row_tiles, col_blocks, s);
+                case 4: return rows16::launch_rows16<4, 12, false, true>(g, row_tiles, col_blocks, s);
+                default: return rows16::launch_rows16<5, 12, false, true>(g, row_tiles, col_blocks, s);
+            }
+        }
+        switch (WN) {
+            case 1: return rows16::launch_rows16<1, 4, false, true>(g, row_tiles, col_blocks, s);
+            case 2: return rows16::launch_rows16<2, 4, false, true>(g, row_tiles, col_blocks, s);
+            case 3: return rows16::launch_rows16<3, 4, false, true>(g, row_tiles, col_blocks, s);
+            case 4: return rows16::launch_rows16<4, 4, false, true>(g, row_tiles, col_blocks, s);
+            default: return rows16::launch_rows16<5, 4, false, true>(g, row_tiles, col_blocks, s);
+        }
+    }
     if (one_group) {
         switch (WN) {
             case 1: return rows16::launch_rows16<1, 12>(g, row_tiles, col_blocks, s);
@@ -158,10 +186,11 @@ SplitWView split_weights_view_of(void* ws, int64_t N, int64_t K) {
     v.nc = (int)nc;
     return v;
 }
-int launch_linear16_view(const dmpnn_gemm_args& a, const SplitWView& W, const int* poison_flags, int poison_mask, hipStream_t s) {
+int launch_linear16_view(const dmpnn_gemm_args& a, const SplitWView& W, const int* poison_flags, int poison_mask, hipStream_t s,
+                         const RowsDrop* drop) {
     mega16::SplitW w;
     w.p = W.p; w.inv_scale = W.inv_scale; w.nc = W.nc;
-    return launch_linear16(a, w, poison_flags, poison_mask, s);
+    return launch_linear16(a, w, poison_flags, poison_mask, s, drop);
 }
 
 }  // namespace dmpnn
@@ -172,7 +201,7 @@ extern "C" {
 
 size_t dmpnn_linear16_wsplit_bytes(int64_t N, int64_t K) { return linear16_wsplit_bytes(N, K); }
 
-int dmpnn_linear16_fwd(const dmpnn_gemm_args* a, void* wsplit, size_t wsplit_bytes, int wsplit_ready, void* stream) {
+static int linear16_fwd(const dmpnn_gemm_args* a, void* wsplit, size_t wsplit_bytes, int wsplit_ready, void* stream, const RowsDrop* drop) {
     DMPNN_CHECK_ARG(a && a->W, "linear16: null args");
     DMPNN_CHECK_ARG(a->M >= 0 && a->N > 0 && a->K1 >= 0 && a->K2 >= 0 && a->K1 + a->K2 > 0, "linear16: bad sizes");
     dmpnn_gemm_args g = *a;
@@ -189,6 +218,8 @@ int dmpnn_linear16_fwd(const dmpnn_gemm_args* a, void* wsplit, size_t wsplit_byt
         DMPNN_CHECK_ARG(g.K2 == 0 || g.A2, "linear16: null A2 with K2 > 0");
         DMPNN_TRY(check_linear_lds(g, "linear16"));
         DMPNN_CHECK_ARG(linear16_ok(g), "linear16: shapes / alignment not supported by the split kernel");
+        DMPNN_CHECK_ARG(!drop || (drop->p > 0.f && drop->p < 1.f && g.N <= 1024 && drop->site >= 0 && g.C),
+                        "linear16: dropout needs 0 < p < 1, a site >= 0, an output C and N <= 1024 (the hash key is row * 1024 + col)");
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     mega16::SplitW W;
@@ -200,7 +231,17 @@ int dmpnn_linear16_fwd(const dmpnn_gemm_args* a, void* wsplit, size_t wsplit_byt
         W.inv_scale = reinterpret_cast<float*>(static_cast<unsigned char*>(wsplit) + al256(NT * nc * 2048));
         W.nc = (int)nc;
     }
-    return launch_linear16(g, W, nullptr, 0, s);
+    return launch_linear16(g, W, nullptr, 0, s, drop);
+}
+
+int dmpnn_linear16_fwd(const dmpnn_gemm_args* a, void* wsplit, size_t wsplit_bytes, int wsplit_ready, void* stream) {
+    return linear16_fwd(a, wsplit, wsplit_bytes, wsplit_ready, stream, nullptr);
+}
+
+int dmpnn_linear16_dropout_fwd(const dmpnn_gemm_args* a, void* wsplit, size_t wsplit_bytes, int wsplit_ready, float p, uint64_t seed, int32_t site,
+                               void* stream) {
+    const RowsDrop d{p, seed, site};
+    return linear16_fwd(a, wsplit, wsplit_bytes, wsplit_ready, stream, &d);
 }
 
 int dmpnn_linear16_ok(const dmpnn_gemm_args* a) {

@@ -51,6 +51,9 @@ struct Rows16K {
     unsigned char* Mout; int ts; float* Sout; int lds; unsigned qmagic;
     int half_out;  // Mout in half storage (DMPNN_F_STORE16)
     float* M32; int ldm32;  // training: the first message also as fp32 rows (or null)
+    // DROP builds only (block dropout of the per-step general route, dmpnn_fwd_args.dropout_p): C = keep ? tau(z) / (1 - p) : +0,
+    // keep = drop_hash(seed, site, global output row, global column) >= thr; Zpre stays the unmasked pre-activation
+    unsigned drop_lo, drop_hi, drop_site, drop_thr; float drop_scale;
 };
 
 // GC: k-chunks per operand group.  4 (128 columns, 24 operand registers, two workgroups per CU) streams large batches;
@@ -65,8 +68,9 @@ constexpr size_t lds_bytes() {
     return tile_bytes<WN, GC>() + 64 + (SEG ? (size_t)(BM + gemm::kAtomCache + 1) * sizeof(int) : 0);  // + scale words (+ segment metadata)
 }
 
-template <int WN, int GC, bool SEG = false>
+template <int WN, int GC, bool SEG = false, bool DROP = false>
 __global__ __launch_bounds__(kThreads, GC == 4 ? 2 : 1) void k_rows16(Rows16K g) {
+    static_assert(!(SEG && DROP), "the mask lives in the plain epilogue (the segment route has its own: dmpnn_step16_impl.hpp)");
     constexpr int BN = 64 * WN, LDC = BN + 4, QN = BN / 4;
     constexpr int ITEMS = BM * QN / kThreads;  // 3 WN
     constexpr int TSG = GC * 128 + 16;         // bytes of one row of the split operand tile (GC chunks)
@@ -325,7 +329,14 @@ __global__ __launch_bounds__(kThreads, GC == 4 ? 2 : 1) void k_rows16(Rows16K g)
             if (r < nrows && c < ncols) {
                 const long long row = row0 + r;
                 if (g.Zpre) *reinterpret_cast<float4*>(g.Zpre + row * g.ldz + col0 + c) = z;
-                const float4 y = apply_act4(z, g.act, slope);
+                float4 y = apply_act4(z, g.act, slope);
+                if constexpr (DROP) {
+                    const unsigned hr = (unsigned)row, hc = (unsigned)(col0 + c);
+                    y.x = drop_hash(g.drop_lo, g.drop_hi, g.drop_site, hr, hc) >= g.drop_thr ? y.x * g.drop_scale : 0.f;
+                    y.y = drop_hash(g.drop_lo, g.drop_hi, g.drop_site, hr, hc + 1u) >= g.drop_thr ? y.y * g.drop_scale : 0.f;
+                    y.z = drop_hash(g.drop_lo, g.drop_hi, g.drop_site, hr, hc + 2u) >= g.drop_thr ? y.z * g.drop_scale : 0.f;
+                    y.w = drop_hash(g.drop_lo, g.drop_hi, g.drop_site, hr, hc + 3u) >= g.drop_thr ? y.w * g.drop_scale : 0.f;
+                }
                 if (g.C) *reinterpret_cast<float4*>(g.C + row * g.ldc + col0 + c) = y;
                 if constexpr (SEG) *reinterpret_cast<float4*>(T + r * LDC + c) = y;  // tau(z): what the segment sums run over
             }
@@ -352,7 +363,12 @@ __global__ __launch_bounds__(kThreads, GC == 4 ? 2 : 1) void k_rows16(Rows16K g)
                         float v = zz[t] + (g.Cadd ? g.Cadd[row * g.ldcadd + col0 + c + t] : 0.f);
                         if (poison) v = nanv;
                         if (g.Zpre) g.Zpre[row * g.ldz + col0 + c + t] = v;
-                        if (g.C) g.C[row * g.ldc + col0 + c + t] = apply_act(v, g.act, slope);
+                        if constexpr (DROP) {
+                            const bool keep = drop_hash(g.drop_lo, g.drop_hi, g.drop_site, (unsigned)row, (unsigned)(col0 + c + t)) >= g.drop_thr;
+                            if (g.C) g.C[row * g.ldc + col0 + c + t] = keep ? apply_act(v, g.act, slope) * g.drop_scale : 0.f;
+                        } else {
+                            if (g.C) g.C[row * g.ldc + col0 + c + t] = apply_act(v, g.act, slope);
+                        }
                     }
                 }
             }
@@ -360,17 +376,19 @@ __global__ __launch_bounds__(kThreads, GC == 4 ? 2 : 1) void k_rows16(Rows16K g)
     }
 }
 
-template <int WN, int GC, bool SEG = false>
+template <int WN, int GC, bool SEG = false, bool DROP = false>
 int launch_rows16(const Rows16K& g, int row_tiles, int col_blocks, hipStream_t s);
 
-#define DMPNN_DEFINE_ROWS16(WN, GC) DMPNN_DEFINE_ROWS16_X(WN, GC, false)
-#define DMPNN_DEFINE_ROWS16_X(WN, GC, SEG)                                                                 \
+#define DMPNN_DEFINE_ROWS16(WN, GC) DMPNN_DEFINE_ROWS16_XD(WN, GC, false, false)
+#define DMPNN_DEFINE_ROWS16_X(WN, GC, SEG) DMPNN_DEFINE_ROWS16_XD(WN, GC, SEG, false)
+#define DMPNN_DEFINE_ROWS16_DROP(WN, GC) DMPNN_DEFINE_ROWS16_XD(WN, GC, false, true)
+#define DMPNN_DEFINE_ROWS16_XD(WN, GC, SEG, DROP)                                                          \
     template <>                                                                                            \
-    int launch_rows16<WN, GC, SEG>(const Rows16K& g, int row_tiles, int col_blocks, hipStream_t s) {       \
+    int launch_rows16<WN, GC, SEG, DROP>(const Rows16K& g, int row_tiles, int col_blocks, hipStream_t s) { \
         constexpr size_t lds = lds_bytes<WN, GC, SEG>();                                                   \
         static bool attr_set = false;                                                                      \
         if (!attr_set) {                                                                                   \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rows16<WN, GC, SEG>),      \
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rows16<WN, GC, SEG, DROP>), \
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);      \
             if (e != hipSuccess) {                                                                         \
                 set_error("hipFuncSetAttribute(k_rows16<%d>, %zu B LDS): %s", WN, lds, hipGetErrorString(e)); \
@@ -378,7 +396,7 @@ int launch_rows16(const Rows16K& g, int row_tiles, int col_blocks, hipStream_t s
             }                                                                                              \
             attr_set = true;                                                                               \
         }                                                                                                  \
-        hipLaunchKernelGGL((k_rows16<WN, GC, SEG>), dim3((unsigned)row_tiles, (unsigned)col_blocks), dim3(kThreads), lds, s, g); \
+        hipLaunchKernelGGL((k_rows16<WN, GC, SEG, DROP>), dim3((unsigned)row_tiles, (unsigned)col_blocks), dim3(kThreads), lds, s, g); \
         DMPNN_CHECK_LAUNCH("k_rows16");                                                                    \
         return DMPNN_OK;                                                                                   \
     }

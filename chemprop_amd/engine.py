@@ -333,6 +333,27 @@ def lean_dropout_refusal(d_v: int, d_e: int, d_h: int, depth: int, act: str, has
     return None
 
 
+def rows_dropout_refusal(d_v: int, d_e: int, d_h: int, depth: int, act: str, has_vd: bool = False, undirected: bool = False) -> Optional[str]:
+    """Why the row kernels of the per-step general route on the f16 pipe (``route="general"``, ``mfma="split16"``, ``keep``) cannot
+    carry block dropout for these shapes — the condition of ``dmpnn_forward`` (csrc/dmpnn_abi.hip: ``rows_dropout_check``) that
+    fails, in words — or ``None`` when they can.  (The workspace this package allocates meets the alignment conditions.)"""
+    if act not in ("none", "relu", "leakyrelu", "tanh", "elu"):
+        return f"activation {act!r} (none / relu / leakyrelu / tanh / elu: PReLU's slope trains, a custom module runs between the kernels)"
+    if has_vd:
+        return "a W_d layer (d_vd > 0)"
+    if undirected:
+        return "undirected messages"
+    if depth < 1:
+        return f"depth {depth} < 1"
+    if d_h > 1024:
+        return f"d_h {d_h} > 1024 (the hash key is row * 1024 + col)"
+    if d_h % 2:
+        return f"odd d_h {d_h} (the update contraction would fall to the fp32-MFMA kernel)"
+    if d_v % 2:
+        return f"odd d_v {d_v} (the finalize contraction would fall to the fp32-MFMA kernel)"
+    return None
+
+
 KEEP_ROWS_MIN = 4096   # (= DMPNN_KEEP_ROWS_MIN of include/dmpnn.h: the rule itself is the library's, dmpnn_train_route)
 
 
@@ -538,8 +559,11 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
     ``dropout = (p, seed)``: ACTIVE dropout inside the kernels (``dmpnn_fwd_args.dropout_p``) — a training forward (``keep``) of
     the tile kernel with a ReLU-class activation and no ``W_d``, or, on demand (``route="fused16"``, ``keep``, ``keep_bits``), the
     lean training forward of the per-step fused route under its own shapes (molecules beyond the tile; ``st.route`` stays
-    ``"fused16/lean"``, the same mask for the same seed); raises :class:`RouteUnavailable` when this batch takes another
-    route (the caller then runs its own ``nn.Dropout`` between the row kernels).
+    ``"fused16/lean"``, the same mask for the same seed), or, on demand as well (``route="general"``, ``mfma="split16"``,
+    ``keep``), the row kernels of the per-step general route on the f16 pipe (any molecule size, ``d_h <= 1024``, depth >= 1, relu /
+    leakyrelu / tanh / elu, no ``W_d``, directed: :func:`rows_dropout_refusal`; ``st.route`` stays ``"general16"``); raises
+    :class:`RouteUnavailable` when this batch takes another route (the caller then runs its own ``nn.Dropout`` between the row
+    kernels).
     ``launch=False`` prepares the argument block and the workspace without enqueuing anything (``trainer.FusedTrainer``).
     ``out``: the fp32 rows the output goes to (default: a new ``[n_atoms, d_h]`` tensor) — a multicomponent step hands every block
     its rows of one ``H_v`` matrix.
@@ -647,17 +671,25 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
             raise RouteUnavailable("atom messages inside the kernels: the tile kernel, 1 <= d_e <= 16, no W_d (training: even d_v / d_e / d_h)")
         a.flags |= _lib.F_ATOM
     if dropout is not None and float(dropout[0]) > 0.0:
-        # its two homes: the tile kernels, or — on demand (route="fused16", keep, keep_bits) — the lean step kernels beyond the tile
+        # its three homes: the tile kernels, or — on demand — the lean step kernels beyond the tile (route="fused16", keep, keep_bits)
+        # or the row kernels of the per-step general route on the f16 pipe (route="general", mfma="split16", keep)
         tile_home = bool(use_mega and want16 and keep and not d_vd and act in ("relu", "leakyrelu"))
         # (a DEMAND: the default rule may pick the lean form itself — it saw p = 0 — and must then refuse, as before)
         lean_home = bool(route == "fused16" and use_fused16 and keep and keep_bits and not d_vd and act in ("relu", "leakyrelu"))
-        if tile_home or lean_home:
+        # (a DEMAND as well: route="general" with mfma="split16" — never the default rule's own general16, which saw p = 0)
+        rows_why = rows_dropout_refusal(d_v, d_e, d_h, depth, act, bool(d_vd), bool(undirected))
+        rows_home = bool(route == "general" and mfma == "split16" and want16 and not use_fused and keep and not atom and rows_why is None
+                         and float(dropout[0]) < 1.0 and V.stride(0) % 2 == 0 and V.data_ptr() % 8 == 0)
+        if tile_home or lean_home or rows_home:
             a.dropout_p, a.dropout_seed = float(dropout[0]), int(dropout[1]) & 0xFFFFFFFFFFFFFFFF
-        if not tile_home and not (lean_home and _lean16_bits(lib, a) > 0):
+        if not tile_home and not rows_home and not (lean_home and _lean16_bits(lib, a) > 0):
             why = lean_dropout_refusal(d_v, d_e, d_h, depth, act, bool(d_vd)) if route == "fused16" else None
+            demanded = route == "general" and mfma == "split16" and keep
             raise RouteUnavailable("dropout inside the kernels: a training forward of the tile kernel, or the lean training forward of the "
-                                   "per-step fused route (route='fused16', keep, keep_bits); ReLU-class activation, no W_d"
-                                   + (f" — the lean step kernels refuse: {why}" if why else ""))
+                                   "per-step fused route (route='fused16', keep, keep_bits); ReLU-class activation, no W_d; or the row kernels "
+                                   "of the per-step general route on the f16 pipe (route='general', mfma='split16', keep)"
+                                   + (f" — the lean step kernels refuse: {why}" if why else "")
+                                   + (f" — the row kernels refuse: {rows_why or 'V rows must be 8-byte aligned with an even stride'}" if demanded else ""))
     bits = None
     lean16 = False
     st = ForwardState()

@@ -326,7 +326,7 @@ def hip_mpnn_class():
 
             st = {"dev": dev, "fused": None, "why": None, "route": None}
             try:
-                tr = FusedTrainer(self, lr=float(self.init_lr), ffn_dropout=True)
+                tr = FusedTrainer(self, lr=float(self.init_lr), ffn_dropout=True, rows_dropout=True)
                 st["fused"], st["sync"], st["opt"] = tr, tr.sync, tr.opt
             except NotImplementedError as e:   # (a model the fused step does not implement: module path on the same flat Adam)
                 st["why"] = str(e)
@@ -412,7 +412,7 @@ def hip_mpnn_class():
                     loss = out[0]
                     self.__dict__["_hip_applied"] = True
                     st["route"] = "fused:" + str(fused.last_route)
-                except NotImplementedError as e:   # (a batch the fused step refuses, e.g. block dropout beyond the tile kernels where the lean step kernels' shapes do not hold: d_h > 320, depth 1)
+                except NotImplementedError as e:   # (a batch the fused step refuses, e.g. block dropout where neither the tile kernels, the lean step kernels nor the row kernels take the shapes: odd d_v)
                     st["why"] = str(e)
             if loss is None:
                 # the module path: a loss with a graph; Lightning's closure runs backward() (below), the clip, HipAdam.step()

@@ -330,10 +330,12 @@ class MulticomponentMPNN(MPNN):
         return self._torch_loss(self.fingerprint(bmgs, V_ds, X_d), targets, weights, lt_mask, gt_mask)
 
 
-def fused_block(mp) -> tuple:
+def fused_block(mp, rows_dropout: bool = False) -> tuple:
     """``(activation, slope)`` of a block the one-call step takes: a bond block (this package's mirror, or the subclass of the
     reference's own class, ``integration.HipBondMessagePassing``) with a built-in activation (not PReLU), directed, dropout 0
-    or ``nn.Dropout`` with a ReLU-class activation; ``NotImplementedError`` for anything else (it trains through the module path).
+    or ``nn.Dropout`` with a ReLU-class activation — with ``rows_dropout=True`` (the mask in the row kernels of the per-step general
+    route, ``engine.rows_dropout_refusal``) with any built-in activation; ``NotImplementedError`` for anything else (it trains
+    through the module path).
     A block built with ``d_vd > 0`` is taken — its layer ``W_d`` runs as a stage of its own behind the block (``dmpnn_vd_forward`` /
     ``dmpnn_vd_backward``) — unless it also has dropout (the reference applies the block's dropout a second time behind ``W_d``: no
     mask site exists for that) or ``d_h + d_vd`` is beyond ``_lib.VD_MAX_WIDTH``."""
@@ -356,10 +358,12 @@ def fused_block(mp) -> tuple:
         if mp.W_d.in_features > _lib.VD_MAX_WIDTH:
             raise NotImplementedError(f"FusedTrainer: d_h + d_vd = {mp.W_d.in_features} is beyond the {_lib.VD_MAX_WIDTH} columns the "
                                       "atom-descriptor stage takes")
-    if mp.dropout.p > 0 and not (type(mp.dropout) is nn.Dropout and act in ("relu", "leakyrelu")):
-        # (active dropout lives inside the tile kernels and the lean step kernels, for ReLU-class activations: dmpnn_fwd_args.dropout_p; a dropout module
-        #  that is not exactly nn.Dropout has its own semantics and stays on the module path)
-        raise NotImplementedError("FusedTrainer: dropout inside the block needs nn.Dropout and a ReLU / LeakyReLU activation")
+    if mp.dropout.p > 0 and not (type(mp.dropout) is nn.Dropout and (rows_dropout or act in ("relu", "leakyrelu"))):
+        # (active dropout lives inside the tile kernels and the lean step kernels, for ReLU-class activations, and — rows_dropout — in the
+        #  row kernels of the per-step general route for every built-in one: dmpnn_fwd_args.dropout_p; a dropout module that is not
+        #  exactly nn.Dropout has its own semantics and stays on the module path)
+        raise NotImplementedError("FusedTrainer: dropout inside the block needs nn.Dropout and a ReLU / LeakyReLU activation"
+                                  + ("" if rows_dropout else " (rows_dropout=True also takes tanh / elu, on the row kernels)"))
     return act, slope
 
 
@@ -729,10 +733,15 @@ class FusedTrainer:
     ``step`` reads its ``p`` at every step and, while the model and that module are in training mode and ``p > 0``, draws one more
     seed from torch's CPU generator — after the block's — for the head's hash mask (``dmpnn_head_args.ffn_dropout_p``; kept as
     ``last_head_dropout_seed``); otherwise the head gets ``p = 0``.  The default refuses such a predictor.
+
+    ``rows_dropout=True`` gives block dropout a third home behind the tile kernels and the lean step kernels: the row kernels of the
+    per-step general route on the f16 pipe (``route == "general16"``; ``d_h <= 1024``, depth >= 1, relu / leakyrelu / tanh / elu — what
+    ``engine.rows_dropout_refusal`` takes), the same hash mask and the same one seed per step.  The default refuses what the first two
+    homes do not take.
     """
 
     def __init__(self, model: MPNN, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, group=None,
-                 tile_plan: bool = True, ffn_dropout: bool = False):
+                 tile_plan: bool = True, ffn_dropout: bool = False, rows_dropout: bool = False):
         mp, agg, pred = model.message_passing, model.agg, model.predictor
         # a multicomponent model: ONE block shared by every component (the components' graphs merged into one batch per step), or
         # one block per component (each block's forward into its rows of one H_v, the head once, each block's backward)
@@ -740,7 +749,8 @@ class FusedTrainer:
         self.blocks = list(mp.blocks) if multi else [mp]
         self.shared = multi and all(b is self.blocks[0] for b in self.blocks)
         self.n_components = len(self.blocks) if multi else 1
-        acts = [fused_block(b) for b in self.blocks]
+        self.rows_dropout = bool(rows_dropout)
+        acts = [fused_block(b, rows_dropout=self.rows_dropout) for b in self.blocks]
         if multi and any(b.dropout.p > 0 for b in self.blocks):
             raise NotImplementedError("FusedTrainer: dropout inside the blocks of a multicomponent model")
         if multi and any(b.W_d is not None for b in self.blocks):
@@ -1057,7 +1067,8 @@ class FusedTrainer:
                                           W("W_i", "bias"), W("W_h", "bias"), depth=mp.depth, act=act, slope=slope, keep=True,
                                           launch=False, dropout=drop, out=out, **kw)
         # block dropout lives in the tile kernels or — molecules beyond the tile, at any edge count — in the lean step kernels, which
-        # the route rule never picks for p > 0: the step asks for them (route="fused16") on the full plan
+        # the route rule never picks for p > 0: the step asks for them (route="fused16") on the full plan; with rows_dropout the row
+        # kernels of the per-step general route (route="general" on the f16 pipe) take what those two refuse
         st, tile_why = None, "molecules beyond the tile"
         if drop is None or level == 2 or plan.tiles_only:
             try:
@@ -1068,7 +1079,8 @@ class FusedTrainer:
                     raise NotImplementedError(f"FusedTrainer: this batch does not take the tile kernels ({e}); dropout on the other routes "
                                               "runs through the module path (MPNN.loss + autograd)") from None
         if st is None:
-            why = engine.lean_dropout_refusal(int(bmg.V.shape[1]), int(bmg.E.shape[1]), int(mp.W_h.weight.shape[0]), int(mp.depth), act)
+            d_v, d_e, d_h = int(bmg.V.shape[1]), int(bmg.E.shape[1]), int(mp.W_h.weight.shape[0])
+            why = engine.lean_dropout_refusal(d_v, d_e, d_h, int(mp.depth), act)
             if why is None:
                 try:
                     out, st = fwd(route="fused16")
@@ -1078,10 +1090,18 @@ class FusedTrainer:
                     if "route 'fused16' requested but not available" not in str(e):
                         raise
                     why = str(e)
-            if why is not None:
+            rows_why = None
+            if st is None and self.rows_dropout:
+                rows_why = engine.rows_dropout_refusal(d_v, d_e, d_h, int(mp.depth), act)
+                if rows_why is None:
+                    try:
+                        out, st = fwd(route="general", mfma="split16")
+                    except engine.RouteUnavailable as e:
+                        rows_why = str(e)
+            if st is None:
                 raise NotImplementedError(f"FusedTrainer: this batch does not take the tile kernels ({tile_why}) and the lean step kernels "
-                                          f"refuse it ({why}); dropout on the other routes runs through the module path (MPNN.loss + "
-                                          "autograd)") from None
+                                          f"refuse it ({why})" + (f", and so do the row kernels ({rows_why})" if self.rows_dropout else "")
+                                          + "; dropout on the other routes runs through the module path (MPNN.loss + autograd)") from None
         d_out = int(out.shape[1])
         if gout is None:
             gout = torch.empty(nV, d_out, dtype=torch.float32, device=self.dev)

@@ -288,6 +288,11 @@ int dmpnn_linear_fwd(const dmpnn_gemm_args* a, void* stream);
 size_t dmpnn_linear16_wsplit_bytes(int64_t N, int64_t K);
 int dmpnn_linear16_ok(const dmpnn_gemm_args* a);
 int dmpnn_linear16_fwd(const dmpnn_gemm_args* a, void* wsplit, size_t wsplit_bytes, int wsplit_ready, void* stream);
+/* dmpnn_linear16_fwd with the dropout mask of dmpnn_fwd_args.dropout_p on C: C[r][c] = keep ? act(z) / (1 - p) : +0 with
+ * keep = hash(seed, site, r, c) >= floor(p 2^32) (dmpnn_dropout_keep); Zpre stays the unmasked pre-activation.  0 < p < 1,
+ * site >= 0, N <= 1024 and an output C, else DMPNN_EINVAL (before the weight split writes into wsplit). */
+int dmpnn_linear16_dropout_fwd(const dmpnn_gemm_args* a, void* wsplit, size_t wsplit_bytes, int wsplit_ready, float p, uint64_t seed,
+                               int32_t site, void* stream);
 
 /* K3 + K2 (or + K4) fused — ONE per-depth update of the fused route, the dominant kernel of the path:
  *     H'      = tau(H0 + M . W_h^T + b_h)                                   base.py:135-141
@@ -378,6 +383,13 @@ typedef struct dmpnn_fwd_args {
      * There the kept bit stays the sign of tau(z) BEFORE dropout (one bit cannot also say "dropped") and the backward step kernels
      * regenerate the mask from the hash; the finalize output is post-dropout and carries it in its sign.  The route rules
      * (dmpnn_forward_route / dmpnn_train_route) never choose this form for dropout_p > 0: the caller asks for it.
+     * The third home: the training forward of the per-step GENERAL route on the f16 pipe (DMPNN_F_SPLIT16 | DMPNN_F_KEEP without
+     * DMPNN_F_FUSED) — any molecule size, d_h <= 1024 (the hash key is row * 1024 + col), depth >= 1 (depth 1: the finalize site
+     * only), activation none / relu / leakyrelu / tanh / elu, directed, no W_d, and an update and a finalize contraction that
+     * dmpnn_linear16_ok takes (they run on the row kernel k_rows16, whose epilogue applies the mask; the hash row is the output row:
+     * the edge tensors of this route are in the caller's edge order).  The kept H^(t) and the output are post-dropout;
+     * dmpnn_backward regenerates the mask from the hash for EVERY activation (for tanh / elu / none a zero does not say "dropped")
+     * and uses m / (1 - p) * tau'(y (1 - p)).  The route rules never choose a route for dropout_p > 0 here either: the caller asks.
      * Any other route / activation with dropout_p != 0: DMPNN_EINVAL (the caller runs its own dropout between the row kernels). */
     float dropout_p; uint64_t dropout_seed;
     /* DMPNN_F_TILE_PLAN with a ReLU-class activation (none / relu / leakyrelu) and dropout_p == 0: what the backward tile kernel
