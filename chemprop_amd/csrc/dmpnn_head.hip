@@ -1751,6 +1751,10 @@ int dmpnn_train_step(const dmpnn_step_args* a, void* stream) {
         DMPNN_CHECK_ARG(a->head.gHv == vd->gout && a->head.ldg == vd->ldgout, "train_step: head.gHv must be the atom-descriptor stage's gout");
         DMPNN_CHECK_ARG(a->head.d_h == f.d_h + vd->d_vd && vd->d_h == f.d_h, "train_step: head, block and atom-descriptor widths differ");
         DMPNN_CHECK_ARG(a->head.n_atoms == vd->n_atoms && vd->n_atoms == f.n_atoms, "train_step: head, block and atom-descriptor atom counts differ");
+        // (one nn.Dropout module in the reference: the mask behind W_d is drawn with the block's p and seed)
+        DMPNN_CHECK_ARG(!(vd->dropout_p > 0.f) || (f.dropout_p == vd->dropout_p && f.dropout_seed == vd->dropout_seed),
+                        "train_step: the atom-descriptor stage's dropout (p %g) must be the block's (p %g) under the same seed", (double)vd->dropout_p,
+                        (double)f.dropout_p);
         DMPNN_TRY(vd_check_args(vd, false));
         DMPNN_TRY(vd_check_args(vd, true));
     } else {

@@ -17,6 +17,12 @@
 //                folded into column k of gout before its rows are scaled and split.
 //   weight gradient   gW_d = gout^T . [Hv || V_d || 1]: the library's weight-gradient product (dmpnn_linear_wgrad: on the f16 pipe
 //                from 1 024 rows on when D is even — operand split, product, reduce —, its fp32 kernel below that and for odd D).
+//   dropout      dmpnn_vd_args.dropout_p in (0, 1): the block's nn.Dropout once more behind this layer (base.py:185-188), the hash mask of
+//                the other homes at site DMPNN_DROP_SITE_VD, keyed on (atom, column of out).  Second instantiations k_vd_gemm<., true>:
+//                the forward masks in its epilogue (kept: the p = 0 value times 1.f / (1.f - p); dropped: +0); the data gradient masks
+//                gout as it reads it — each element is read by exactly one lane of one workgroup — and writes the masked rows back IN
+//                PLACE, so the weight gradient launched behind it on the same stream reads the masked gradient too.  No new launch, no
+//                workspace; the p = 0 instantiations are the code they were.
 // Launches: forward 2 (split, product); backward 1 (data gradient; + the split when the image is not the forward's) + the weight
 // gradient's (3 on the f16 pipe).  Shapes: any d_vd >= 1 with D <= DMPNN_VD_MAX_WIDTH (the operand tile and one image chunk share the
 // LDS of a CU); any n_atoms.
@@ -45,6 +51,9 @@ struct VdK {
     const float* nscale;                    // multiplies output column n (the image rows' 1 / s_n), or null
     const float* bias;                      // or null
     float* C; long long ldc;
+    // DROP instantiations only (dmpnn_vd_args.dropout_p): keep(m, c) = drop_hash(seed, DMPNN_DROP_SITE_VD, m, c) >= drop_thr.
+    //   TR = false: the mask lies on C's columns;  TR = true: on A1's (gout), and the masked rows are written back through A1w
+    unsigned drop_thr, seed_lo, seed_hi; float drop_scale; float* A1w;
 };
 
 struct VdSplit { const float* W; int D, Dp; _Float16* Wh; _Float16* Wl; float* inv; };
@@ -83,7 +92,9 @@ inline size_t vd_lds_bytes(int Kp, int Np, bool tr, int rows) {
     return a + w + rows * sizeof(float);
 }
 
-template <bool TR>
+// DROP is a second instantiation, not a run-time branch: the p = 0 kernels stay the code they were (the operand rows already hold
+// 4 x kMaxKJ live registers per lane beside the prefetched image chunk; the hash's temporaries are not added to that build).
+template <bool TR, bool DROP>
 __global__ __launch_bounds__(256) void k_vd_gemm(VdK a) {
     constexpr int kBM = kRowTile * RT;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -162,6 +173,14 @@ __global__ __launch_bounds__(256) void k_vd_gemm(VdK a) {
                 float x = 0.f;
                 if (live && c < a.K1) x = a.A1[m * a.lda1 + c];
                 else if (live && c < K) x = a.A2[m * a.lda2 + (c - a.K1)];
+                if constexpr (DROP && TR) {
+                    // the masked gradient g' = keep ? gout / (1 - p) : +0 feeds this product AND the weight gradient behind it: this
+                    // lane is the only reader of the element in the launch, so it goes back in place
+                    if (live && c < K) {
+                        x = drop_hash(a.seed_lo, a.seed_hi, (unsigned)DMPNN_DROP_SITE_VD, (unsigned)m, (unsigned)c) >= a.drop_thr ? x * a.drop_scale : 0.f;
+                        a.A1w[m * a.lda1 + c] = x;
+                    }
+                }
                 v[q][j] = x;
             }
         }
@@ -250,7 +269,13 @@ __global__ __launch_bounds__(256) void k_vd_gemm(VdK a) {
             for (int j = 0; j < 4; ++j) {
                 const int r = rt * 16 + 4 * lg + j;
                 const long long m = m0 + r;
-                if (m < a.M) a.C[m * a.ldc + n] = acc[rt][t][j] * rinv[r] * ns + bv;
+                if (m < a.M) {
+                    const float y = acc[rt][t][j] * rinv[r] * ns + bv;
+                    if constexpr (DROP && !TR)
+                        a.C[m * a.ldc + n] = drop_hash(a.seed_lo, a.seed_hi, (unsigned)DMPNN_DROP_SITE_VD, (unsigned)m, (unsigned)n) >= a.drop_thr ? y * a.drop_scale : 0.f;
+                    else
+                        a.C[m * a.ldc + n] = y;
+                }
             }
     }
 }
@@ -278,6 +303,7 @@ static int vd_check(const dmpnn_vd_args* a, bool bwd) {
     DMPNN_CHECK_ARG(a->d_h + a->d_vd <= DMPNN_VD_MAX_WIDTH, "vd: d_h + d_vd = %lld is beyond the %d columns this layer takes",
                     (long long)(a->d_h + a->d_vd), DMPNN_VD_MAX_WIDTH);
     DMPNN_CHECK_ARG(a->n_atoms < (int64_t(1) << 31) - 64, "vd: too many atoms");
+    DMPNN_CHECK_ARG(a->dropout_p >= 0.f && a->dropout_p < 1.f, "vd: dropout_p (%g) must be in [0, 1)", (double)a->dropout_p);
     const bool rows = a->n_atoms > 0;   // (a batch without atoms has no row tensors to point at)
     DMPNN_CHECK_ARG(a->W_d && (!rows || (a->Hv && a->V_d)), "vd: null Hv / V_d / W_d");
     DMPNN_CHECK_ARG(a->ldhv >= a->d_h && a->ldvd >= a->d_vd, "vd: a leading dimension below its width (ldhv %lld, ldvd %lld)",
@@ -307,7 +333,15 @@ static int vd_split(const dmpnn_vd_args& a, const VdLayout& L, hipStream_t s) {
     return DMPNN_OK;
 }
 
-template <bool TR>
+// the mask of dmpnn_vd_args.dropout_p into the kernel's arguments; false: no mask (p == 0, or so small that floor(p 2^32) == 0)
+static bool vd_drop(const dmpnn_vd_args& a, VdK& k) {
+    if (!(a.dropout_p > 0.f) || drop_threshold(a.dropout_p) == 0u) return false;
+    k.drop_thr = drop_threshold(a.dropout_p); k.drop_scale = 1.f / (1.f - a.dropout_p);
+    k.seed_lo = (unsigned)(a.dropout_seed & 0xFFFFFFFFull); k.seed_hi = (unsigned)(a.dropout_seed >> 32);
+    return true;
+}
+
+template <bool TR, bool DROP>
 static int vd_launch(const VdK& k, hipStream_t s) {
     constexpr int BM = kRowTile * RT;
     const int K = k.K1 + k.K2, Kp = (K + 31) & ~31, Np = (k.N + 15) & ~15;
@@ -316,14 +350,14 @@ static int vd_launch(const VdK& k, hipStream_t s) {
     static bool attr[64] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64 || !attr[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vd_gemm<TR>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vd_gemm<TR, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) {
             set_error("hipFuncSetAttribute(k_vd_gemm): %s", hipGetErrorString(e));
             return DMPNN_EHIP;
         }
         if (dev >= 0 && dev < 64) attr[dev] = true;
     }
-    hipLaunchKernelGGL((k_vd_gemm<TR>), dim3((unsigned)((k.M + BM - 1) / BM)), dim3(256), lds, s, k);
+    hipLaunchKernelGGL((k_vd_gemm<TR, DROP>), dim3((unsigned)((k.M + BM - 1) / BM)), dim3(256), lds, s, k);
     DMPNN_CHECK_LAUNCH(TR ? "k_vd_gemm<dgrad>" : "k_vd_gemm<fwd>");
     return DMPNN_OK;
 }
@@ -345,7 +379,7 @@ int vd_forward_impl(const dmpnn_vd_args* a, void* stream) {
     k.Wh = reinterpret_cast<const _Float16*>(ws + L.wh); k.Wl = reinterpret_cast<const _Float16*>(ws + L.wl); k.Dp = L.Dp;
     k.nscale = reinterpret_cast<const float*>(ws + L.inv); k.bias = a->b_d;
     k.C = a->out; k.ldc = a->ldout;
-    return vd::vd_launch<false>(k, s);
+    return vd::vd_drop(*a, k) ? vd::vd_launch<false, true>(k, s) : vd::vd_launch<false, false>(k, s);
 }
 
 // split_ready: the workspace still holds this step's image of W_d (dmpnn_train_step: the forward ran in the same call)
@@ -373,7 +407,12 @@ int vd_backward_impl(const dmpnn_vd_args* a, void* stream, bool split_ready) {
     k.kscale = reinterpret_cast<const float*>(ws + L.inv);
     k.Wh = reinterpret_cast<const _Float16*>(ws + L.wh); k.Wl = reinterpret_cast<const _Float16*>(ws + L.wl); k.Dp = L.Dp;
     k.C = a->gHv; k.ldc = a->ldghv;
-    DMPNN_TRY(vd::vd_launch<true>(k, s));
+    if (vd::vd_drop(*a, k)) {   // (gout leaves the launch as the masked gradient: what the weight gradient below reads)
+        k.A1w = const_cast<float*>(a->gout);
+        DMPNN_TRY((vd::vd_launch<true, true>(k, s)));
+    } else {
+        DMPNN_TRY((vd::vd_launch<true, false>(k, s)));
+    }
     if (a->gW_d || a->gb_d) {
         dmpnn_gemm_args g;
         memset(&g, 0, sizeof(g));

@@ -280,7 +280,8 @@ def hip_mpnn_class():
       ``cli/train.py:1912-1919``), saves ``optimizer.state_dict()`` (``torch.optim.Adam``'s format) in its checkpoints.
     * ``training_step``: where :class:`chemprop_amd.model.FusedTrainer` applies (a bond block with a built-in activation, sum / mean /
       norm aggregation, batch norm, regression MLP, MSE / MAE; atom descriptors ``V_d`` of a block built with ``d_vd`` through
-      its ``V_d_transform`` and its layer ``W_d`` as a stage of the same call; molecule descriptors ``X_d`` through the model's
+      its ``V_d_transform`` and its layer ``W_d`` as a stage of the same call — with ``--dropout p`` the block's mask once more
+      behind ``W_d``, inside that stage's kernels (``vd_dropout=True``); molecule descriptors ``X_d`` through the model's
       ``X_d_transform``; the predictor's dropout — ``--dropout p`` — as the head kernels' hash mask) the whole step — K0, forward, head, backward,
       clip, Adam — is enqueued by that one call with this step's learning rate and ``Trainer(gradient_clip_val)``
       (``cli/train.py:1937``); the hooks Lightning runs afterwards inside ``optimizer.step(closure)`` — ``backward``,
@@ -326,7 +327,7 @@ def hip_mpnn_class():
 
             st = {"dev": dev, "fused": None, "why": None, "route": None}
             try:
-                tr = FusedTrainer(self, lr=float(self.init_lr), ffn_dropout=True, rows_dropout=True)
+                tr = FusedTrainer(self, lr=float(self.init_lr), ffn_dropout=True, rows_dropout=True, vd_dropout=True)
                 st["fused"], st["sync"], st["opt"] = tr, tr.sync, tr.opt
             except NotImplementedError as e:   # (a model the fused step does not implement: module path on the same flat Adam)
                 st["why"] = str(e)

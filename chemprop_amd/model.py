@@ -330,15 +330,17 @@ class MulticomponentMPNN(MPNN):
         return self._torch_loss(self.fingerprint(bmgs, V_ds, X_d), targets, weights, lt_mask, gt_mask)
 
 
-def fused_block(mp, rows_dropout: bool = False) -> tuple:
+def fused_block(mp, rows_dropout: bool = False, vd_dropout: bool = False) -> tuple:
     """``(activation, slope)`` of a block the one-call step takes: a bond block (this package's mirror, or the subclass of the
     reference's own class, ``integration.HipBondMessagePassing``) with a built-in activation (not PReLU), directed, dropout 0
     or ``nn.Dropout`` with a ReLU-class activation — with ``rows_dropout=True`` (the mask in the row kernels of the per-step general
     route, ``engine.rows_dropout_refusal``) with any built-in activation; ``NotImplementedError`` for anything else (it trains
     through the module path).
     A block built with ``d_vd > 0`` is taken — its layer ``W_d`` runs as a stage of its own behind the block (``dmpnn_vd_forward`` /
-    ``dmpnn_vd_backward``) — unless it also has dropout (the reference applies the block's dropout a second time behind ``W_d``: no
-    mask site exists for that) or ``d_h + d_vd`` is beyond ``_lib.VD_MAX_WIDTH``."""
+    ``dmpnn_vd_backward``) — unless ``d_h + d_vd`` is beyond ``_lib.VD_MAX_WIDTH`` or it also has dropout: the reference applies the
+    block's dropout a second time behind ``W_d``, and only ``vd_dropout=True`` asks for that fourth mask (site ``_lib.DROP_SITE_VD``
+    inside the stage's kernels, ``dmpnn_vd_args.dropout_p``).  The block is then taken under exactly the conditions it would meet
+    without ``W_d`` (``nn.Dropout``; a ReLU-class activation, or ``rows_dropout=True`` and a built-in smooth one)."""
     # (W_h is [d_h, d_h] in a bond block: the atom variant's takes d_e + d_h columns, the mol-atom-bond ones have a second read-out)
     bond = (all(isinstance(getattr(mp, n, None), nn.Linear) for n in ("W_i", "W_h", "W_o"))
             and mp.W_h.in_features == mp.W_h.out_features and mp.W_o.in_features > mp.W_h.out_features)
@@ -349,9 +351,10 @@ def fused_block(mp, rows_dropout: bool = False) -> tuple:
         raise NotImplementedError("FusedTrainer: built-in activation (not PReLU), directed — other blocks train "
                                   "through the module path (MPNN.loss + autograd)")
     if mp.W_d is not None:
-        if mp.dropout.p > 0:
+        if mp.dropout.p > 0 and not vd_dropout:
             raise NotImplementedError("FusedTrainer: atom descriptors (W_d) together with dropout inside the block — the dropout behind "
-                                      "W_d has no mask site; this model trains through the module path")
+                                      "W_d has no mask site; this model trains through the module path (vd_dropout=True masks inside "
+                                      "the atom-descriptor stage)")
         if not (isinstance(mp.W_d, nn.Linear) and mp.W_d.in_features == mp.W_d.out_features and mp.W_d.bias is not None
                 and mp.W_d.in_features > mp.W_o.out_features):
             raise NotImplementedError("FusedTrainer: W_d must be a square nn.Linear with a bias over cat(H_v, V_d)")
@@ -707,9 +710,9 @@ def head_loss(model, Hv: Tensor, batch: Tensor, n_mols: int, targets: Tensor, we
 
 class _BlockPart:
     """One block's share of a step (``FusedTrainer._block_args``): plan, kept forward state, the backward's argument block, what they
-    point into, the block's rows of ``H_v`` / ``gH_v``, the route — and what K0 reads, named as ``dmpnn_step_args`` names it."""
+    point into, the block's rows of ``H_v`` / ``gH_v``, the route, the step's dropout ``(p, seed)`` or ``None`` — and what K0 reads, named as ``dmpnn_step_args`` names it."""
 
-    __slots__ = ("plan", "st", "bwd", "keep_b", "out", "gout", "route", "bmg", "edge_index", "rev_edge_index", "batch", "plan_bytes")
+    __slots__ = ("plan", "st", "bwd", "keep_b", "out", "gout", "route", "bmg", "edge_index", "rev_edge_index", "batch", "plan_bytes", "drop")
 
     def set_on(self, c, plan_ready: int) -> None:
         """Fill the fields ``_lib.StepArgs`` and ``_lib.StepComponent`` share."""
@@ -738,10 +741,15 @@ class FusedTrainer:
     per-step general route on the f16 pipe (``route == "general16"``; ``d_h <= 1024``, depth >= 1, relu / leakyrelu / tanh / elu — what
     ``engine.rows_dropout_refusal`` takes), the same hash mask and the same one seed per step.  The default refuses what the first two
     homes do not take.
+
+    ``vd_dropout=True`` also takes a block with atom descriptors AND dropout: the reference applies the block's ``nn.Dropout`` once
+    more behind ``W_d``, and that fourth mask lives in the atom-descriptor stage's own kernels (site ``_lib.DROP_SITE_VD``;
+    ``dmpnn_vd_args.dropout_p`` / ``dropout_seed`` are the block's ``(p, seed)`` of the step: still one draw, ``last_dropout_seed``).
+    The backward stage overwrites ``gH_v'`` with the masked gradient.  The default refuses such a block.
     """
 
     def __init__(self, model: MPNN, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, group=None,
-                 tile_plan: bool = True, ffn_dropout: bool = False, rows_dropout: bool = False):
+                 tile_plan: bool = True, ffn_dropout: bool = False, rows_dropout: bool = False, vd_dropout: bool = False):
         mp, agg, pred = model.message_passing, model.agg, model.predictor
         # a multicomponent model: ONE block shared by every component (the components' graphs merged into one batch per step), or
         # one block per component (each block's forward into its rows of one H_v, the head once, each block's backward)
@@ -750,7 +758,8 @@ class FusedTrainer:
         self.shared = multi and all(b is self.blocks[0] for b in self.blocks)
         self.n_components = len(self.blocks) if multi else 1
         self.rows_dropout = bool(rows_dropout)
-        acts = [fused_block(b, rows_dropout=self.rows_dropout) for b in self.blocks]
+        self.vd_dropout = bool(vd_dropout)
+        acts = [fused_block(b, rows_dropout=self.rows_dropout, vd_dropout=self.vd_dropout) for b in self.blocks]
         if multi and any(b.dropout.p > 0 for b in self.blocks):
             raise NotImplementedError("FusedTrainer: dropout inside the blocks of a multicomponent model")
         if multi and any(b.W_d is not None for b in self.blocks):
@@ -888,7 +897,7 @@ class FusedTrainer:
         self.last_route = parts[0].route if len(parts) == 1 else tuple(p.route for p in parts)
         self._last_plan_tiles = all(p.plan.tiles_only for p in parts)
         out, gout = (parts[0].out, parts[0].gout) if H_all is None else (H_all, g_all)
-        return (parts, out, gout, None, None) if Vd is None else (parts, *self._vd_args(self.mp, Vd, out, gout))
+        return (parts, out, gout, None, None) if Vd is None else (parts, *self._vd_args(self.mp, Vd, out, gout, parts[0].drop))
 
     def _head_args(self, comps, n_mols: int, T: Tensor, weights, lt_mask, gt_mask, Xd, gout: Tensor) -> tuple:
         """The head's argument block (:meth:`HeadSpec.call_args`) over every component's rows, its gradients into the flat buffer's
@@ -994,9 +1003,10 @@ class FusedTrainer:
             V = V.to(torch.float32).contiguous()
         return V
 
-    def _vd_args(self, mp, Vd: Tensor, Hv: Tensor, gHv: Tensor) -> tuple:
+    def _vd_args(self, mp, Vd: Tensor, Hv: Tensor, gHv: Tensor, drop: Optional[tuple] = None) -> tuple:
         """``dmpnn_vd_args`` of the layer ``W_d`` behind the block's output ``Hv`` (its gradient goes to ``gHv``): allocates ``H_v'``,
-        ``gH_v'`` and the workspace, takes the gradient views of ``W_d`` from the flat buffer (``None`` for a frozen parameter)."""
+        ``gH_v'`` and the workspace, takes the gradient views of ``W_d`` from the flat buffer (``None`` for a frozen parameter).
+        ``drop``: the block's ``(p, seed)`` of this step (``None``: no dropout) — the same module masks ``H_v'``."""
         lib = _lib.load()
         nV, d_h = int(Hv.shape[0]), int(Hv.shape[1])
         D = int(mp.W_d.out_features)
@@ -1014,6 +1024,10 @@ class FusedTrainer:
         a.gout, a.ldgout = gout2.data_ptr(), gout2.stride(0)
         a.gHv, a.ldghv = gHv.data_ptr(), gHv.stride(0)
         a.gW_d, a.gb_d = self._gv(Wd), self._gv(bd)
+        if drop is not None:
+            if not self.vd_dropout:   # (fused_block refused it at construction: p was raised on the module since)
+                raise NotImplementedError("FusedTrainer: atom descriptors (W_d) together with dropout inside the block needs vd_dropout=True")
+            a.dropout_p, a.dropout_seed = drop
         nb = int(lib.dmpnn_vd_ws_bytes(C.byref(a)))
         ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=self.dev)
         a.ws, a.ws_bytes = ws.data_ptr(), nb
@@ -1118,6 +1132,7 @@ class FusedTrainer:
                 raise RuntimeError(f"FusedTrainer: the gradient view of {k} was not accepted (dtype / layout)")
         part = _BlockPart()
         part.plan, part.st, part.bwd, part.keep_b, part.out, part.gout, part.route, part.bmg = plan, st, b, keep_b, out, gout, st.route, bmg
+        part.drop = drop
         part.edge_index, part.rev_edge_index = plan.edge_index.data_ptr(), plan.rev_edge_index.data_ptr()
         part.batch = batch.data_ptr()   # (int64, contiguous: _check_inputs)
         part.plan_bytes = plan.buf.numel() * 4

@@ -722,18 +722,29 @@ typedef struct dmpnn_step_component {     /* a further block of a multicomponent
  * zero-padded inside the split: odd widths and unaligned row strides included); d_h + d_vd <= DMPNN_VD_MAX_WIDTH, else DMPNN_EINVAL.
  * No gradient flows to V_d.  forward reads Hv V_d W_d b_d, writes out; backward reads gout Hv V_d W_d, writes gHv and (when not
  * NULL) gW_d [d_h+d_vd, d_h+d_vd] dense and gb_d.  n_atoms == 0: the requested gradients are zeroed.  Every argument check runs
- * before any device work. */
+ * before any device work.
+ * dropout_p in (0, 1) (v15 growth; 0 — what a zero-filled block of an older caller carries — is no mask): the block's nn.Dropout once
+ * more behind this layer (message_passing/base.py:185-188).  Element (atom r, column c) of out is kept iff
+ * drop_hash(dropout_seed, DMPNN_DROP_SITE_VD, r, c) >= floor(p 2^32) (dmpnn_dropout_keep; c < d_h + d_vd <= 544 < 1024, the hash's
+ * column range): forward writes out = keep ? (the p = 0 value) * (1.f / (1.f - p)) : +0.  Nothing of the mask is stored: backward
+ * regenerates it and OVERWRITES gout IN PLACE with the masked gradient g' = keep ? gout * (1.f / (1.f - p)) : +0 (whether or not gW_d /
+ * gb_d are asked for); gHv, gW_d and gb_d are all formed from g'.  A second dmpnn_vd_backward on the same gout would therefore mask
+ * twice: the caller refills gout first.  A dropout_p so small that floor(p 2^32) == 0 (0 < p < 2^-32) keeps every element and its
+ * float scale is 1: such a call is the p = 0 call (no mask, no scale, gout not written), as in the other homes.  dropout_p outside
+ * [0, 1): DMPNN_EINVAL. */
 #define DMPNN_VD_MAX_WIDTH 544
+#define DMPNN_DROP_SITE_VD 0x8000          /* dmpnn_vd_args.dropout_p: the mask site behind W_d (the block's sites are 0 .. depth-1, the predictor's start at DMPNN_DROP_SITE_FFN) */
 typedef struct dmpnn_vd_args {
     int64_t n_atoms, d_h, d_vd;            /* rows; width of H_v; width of V_d (>= 1)                    */
     const float* Hv;  int64_t ldhv;        /* [n_atoms, d_h]   the block's output                        */
     const float* V_d; int64_t ldvd;        /* [n_atoms, d_vd]  already through V_d_transform             */
     const float* W_d; const float* b_d;    /* [d_h+d_vd, d_h+d_vd] nn.Linear layout; [d_h+d_vd]          */
     float* out; int64_t ldout;             /* [n_atoms, d_h+d_vd]  = cat(Hv, V_d) . W_d^T + b_d (no act) */
-    const float* gout; int64_t ldgout;     /* backward: dL/dout                                          */
+    const float* gout; int64_t ldgout;     /* backward: dL/dout (dropout_p > 0: WRITTEN, see above)      */
     float* gHv; int64_t ldghv;             /* backward: dL/dHv [n_atoms, d_h] = gout . W_d[:, :d_h]      */
     float* gW_d; float* gb_d;              /* backward: out, or NULL (not wanted)                        */
     void* ws; size_t ws_bytes;             /* >= dmpnn_vd_ws_bytes()                                     */
+    float dropout_p; uint64_t dropout_seed; /* v15 growth: the mask on out / gout (0: none)               */
 } dmpnn_vd_args;
 size_t dmpnn_vd_ws_bytes(const dmpnn_vd_args* a);
 int dmpnn_vd_forward(const dmpnn_vd_args* a, void* stream);
@@ -756,6 +767,8 @@ typedef struct dmpnn_step_args {
                                                vd->out -> dmpnn_vd_backward into bwd.gout -> block backward -> update.  Requires
                                                bwd.f.W_d == NULL, bwd.f.out == vd->Hv, bwd.gout == vd->gHv, head.gHv == vd->gout,
                                                head.d_h == bwd.f.d_h + vd->d_vd, equal atom counts, n_extra == 0, head.n_components <= 1.
+                                               vd->dropout_p > 0 requires bwd.f.dropout_p == vd->dropout_p and the same seed (one
+                                               nn.Dropout module in the reference), else DMPNN_EINVAL.
                                                Staged: the layer's forward belongs to DMPNN_STEP_FORWARD, its backward to
                                                DMPNN_STEP_BACKWARD (its gradients lie in the block's slice of the flat buffer) */
 } dmpnn_step_args;
