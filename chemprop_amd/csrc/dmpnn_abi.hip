@@ -279,7 +279,9 @@ int dmpnn_update_fwd(const void* plan, int64_t n_atoms, int64_t n_edges, int64_t
 // per-step routes with DMPNN_F_SPLIT16: W_i | W_h | W_o (| W_d) pre-split one after the other
 static size_t steps16_wsplit_bytes(const dmpnn_fwd_args& a) {
     const int64_t h = a.d_h;
-    size_t n = linear16_wsplit_bytes(h, a.d_v + a.d_e) + linear16_wsplit_bytes(h, h) + linear16_wsplit_bytes(h, a.d_v + h);
+    // (atom messages, DMPNN_F_ATOM: W_i is [d_h, d_v] and W_h [d_h, d_h + d_e])
+    const int64_t de_i = (a.flags & DMPNN_F_ATOM) ? 0 : a.d_e, de_h = (a.flags & DMPNN_F_ATOM) ? a.d_e : 0;
+    size_t n = linear16_wsplit_bytes(h, a.d_v + de_i) + linear16_wsplit_bytes(h, h + de_h) + linear16_wsplit_bytes(h, a.d_v + h);
     n += linear16_wsplit_bytes(h + a.d_vd, h + a.d_vd) * ((a.W_d && a.d_vd > 0) ? 1 : 0);
     n += linear16_wsplit_bytes(h, h) + linear16_wsplit_bytes(h, a.d_v);  // W_o[:, d_v:] | W_o[:, :d_v] on their own (the finalize on the step kernel)
     return n;
@@ -452,6 +454,10 @@ static dmpnn_gemm_args general_update_gemm(const dmpnn_fwd_args& a, const float*
     g.M = a.n_edges; g.N = a.d_h; g.K1 = a.d_h; g.K2 = 0;
     g.A1 = Mt; g.lda1 = a.ldh;
     g.W = a.W_h; g.ldw = a.d_h; g.bias = a.b_h;
+    if (a.flags & DMPNN_F_ATOM) {   // W_h [M^(t) || ME]: the bond-feature half of the atom message, the [n_edges][16] rows in `msplit`
+        g.K2 = a.d_e; g.A2 = static_cast<const float*>(a.msplit); g.lda2 = 16;
+        g.ldw = a.d_h + a.d_e;
+    }
     g.Cadd = a.H0; g.ldcadd = a.ldh;
     g.C = Ht; g.ldc = a.ldh;
     g.act = a.act; g.act_slope = a.act_slope; g.act_slope_ptr = a.act_slope_ptr;
@@ -473,7 +479,7 @@ static dmpnn_gemm_args general_finalize_gemm(const dmpnn_fwd_args& a) {
 // DMPNN_F_FUSED): the mask lives in the epilogue of the row kernel k_rows16, so both masked contractions must really run there
 static int rows_dropout_check(const dmpnn_fwd_args& a) {
     const char* who = "forward: dropout inside the row kernels (DMPNN_F_SPLIT16 | DMPNN_F_KEEP on the per-step general route)";
-    DMPNN_CHECK_ARG(!(a.flags & (DMPNN_F_MEGA | DMPNN_F_ATOM | DMPNN_F_TILE_PLAN)), "%s does not go with DMPNN_F_MEGA / DMPNN_F_ATOM / DMPNN_F_TILE_PLAN", who);
+    DMPNN_CHECK_ARG(!(a.flags & (DMPNN_F_MEGA | DMPNN_F_TILE_PLAN)), "%s does not go with DMPNN_F_MEGA / DMPNN_F_TILE_PLAN", who);
     DMPNN_CHECK_ARG(!(a.flags & DMPNN_F_UNDIRECTED), "%s: directed messages only (no DMPNN_F_UNDIRECTED)", who);
     DMPNN_CHECK_ARG(!a.W_d, "%s: no W_d (the reference's second dropout behind W_d has no mask site)", who);
     DMPNN_CHECK_ARG(a.act != DMPNN_ACT_PRELU, "%s: activation none / relu / leakyrelu / tanh / elu (not PReLU)", who);
@@ -481,7 +487,7 @@ static int rows_dropout_check(const dmpnn_fwd_args& a) {
     if (a.depth > 1 && a.n_edges > 0) {
         DMPNN_CHECK_ARG(a.Ms && a.Hs, "%s: missing Ms / Hs workspace", who);
         DMPNN_CHECK_ARG(linear16_ok(general_update_gemm(a, a.Ms, a.Hs)),
-                        "%s: the update contraction would fall to the fp32-MFMA kernel (even d_h and ldh, 8-byte aligned Ms)", who);
+                        "%s: the update contraction would fall to the fp32-MFMA kernel (even d_h and ldh, 8-byte aligned Ms; atom messages: even d_e)", who);
     }
     if (a.n_atoms > 0)
         DMPNN_CHECK_ARG(linear16_ok(general_finalize_gemm(a)),
@@ -519,14 +525,21 @@ int dmpnn_forward(const dmpnn_fwd_args* a, void* stream) {
     }
 
     if (a->flags & DMPNN_F_ATOM) {
-        DMPNN_CHECK_ARG((a->flags & DMPNN_F_FUSED) && (a->flags & DMPNN_F_MEGA) && (a->flags & DMPNN_F_SPLIT16) &&
-                        !has_vd && de >= 1 && de <= 16 && a->dropout_p == 0.f,
-                        "forward: DMPNN_F_ATOM (atom messages) runs on the whole-forward tile kernel only (DMPNN_F_FUSED | DMPNN_F_MEGA | "
-                        "DMPNN_F_SPLIT16, 1 <= d_e <= 16, no W_d, no dropout inside the kernels) — chain the row kernels otherwise");
+        const bool tile = fused && (a->flags & DMPNN_F_MEGA) && (a->flags & DMPNN_F_SPLIT16) && a->dropout_p == 0.f;
+        // ... or the per-step general route (fp32 or DMPNN_F_SPLIT16, inference or DMPNN_F_KEEP): any molecule size, any d_h the route takes
+        const bool rows = !fused && !(a->flags & (DMPNN_F_MEGA | DMPNN_F_UNDIRECTED | DMPNN_F_TILE_PLAN));
+        DMPNN_CHECK_ARG((tile || rows) && !has_vd && de >= 1 && de <= 16,
+                        "forward: DMPNN_F_ATOM (atom messages) runs on the whole-forward tile kernel (DMPNN_F_FUSED | DMPNN_F_MEGA | "
+                        "DMPNN_F_SPLIT16, no dropout inside the kernels) or on the per-step general route (no DMPNN_F_FUSED / DMPNN_F_MEGA / "
+                        "DMPNN_F_TILE_PLAN, directed) — 1 <= d_e <= 16, no W_d; chain the row kernels otherwise");
         // a TRAINING forward (round 4): the bond-feature half of the messages is kept for W_h's gradient — depth - 1 slots of [n_edges][16] in `msplit`
-        DMPNN_CHECK_ARG(!(a->flags & DMPNN_F_KEEP) || (de % 2 == 0 && dv % 2 == 0 && h % 2 == 0 &&
+        DMPNN_CHECK_ARG(!tile || !(a->flags & DMPNN_F_KEEP) || (de % 2 == 0 && dv % 2 == 0 && h % 2 == 0 &&
                         (a->depth < 2 || nE == 0 || (a->msplit && aligned16(a->msplit) && a->msplit_bytes >= (size_t)(a->depth - 1) * (size_t)nE * 16 * sizeof(float)))),
                         "forward: DMPNN_F_ATOM | DMPNN_F_KEEP needs even d_v / d_e / d_h and `msplit` >= (depth - 1) * n_edges * 64 bytes, 16-byte aligned");
+        // the general route: ONE slot (the messages of the bond features are the same in every step), kept or scratch
+        DMPNN_CHECK_ARG(tile || nE == 0 || (a->msplit && aligned16(a->msplit) && a->msplit_bytes >= (size_t)nE * 16 * sizeof(float)),
+                        "forward: DMPNN_F_ATOM on the per-step general route needs `msplit` >= n_edges * 64 bytes, 16-byte aligned "
+                        "(the atom messages of E as [n_edges][16] rows: kept with DMPNN_F_KEEP, scratch otherwise)");
     }
     if (a->dropout_p != 0.f) {
         DMPNN_CHECK_ARG(a->dropout_p > 0.f && a->dropout_p < 1.f, "forward: dropout_p must lie in [0, 1)");
@@ -691,14 +704,14 @@ int dmpnn_forward(const dmpnn_fwd_args* a, void* stream) {
     // ---- general route: any index arrays, undirected, edge tensors in the caller's edge order ----
     // With DMPNN_F_SPLIT16 the contractions run on the f16 pipe with the exact operand split (dmpnn_rows16.hip) where
     // the shapes / alignments allow it; the weights are pre-split into `wsplit` first (or found there: WSPLIT_READY).
-    const bool use16 = (a->flags & DMPNN_F_SPLIT16) != 0;
+    const bool use16 = (a->flags & DMPNN_F_SPLIT16) != 0, atom = (a->flags & DMPNN_F_ATOM) != 0;
     SplitWView w16[4];
     if (use16) {
         DMPNN_CHECK_ARG(a->wsplit && a->wsplit_bytes >= steps16_wsplit_bytes(*a), "forward(split16): wsplit workspace missing or too small");
         unsigned char* wp = static_cast<unsigned char*>(a->wsplit);
         const bool ready = (a->flags & DMPNN_F_WSPLIT_READY) != 0;
         const float* Ws[4] = {a->W_i, a->W_h, a->W_o, has_vd ? a->W_d : nullptr};
-        const int64_t Ns[4] = {h, h, h, h + a->d_vd}, Ks[4] = {dv + de, h, dv + h, h + a->d_vd};
+        const int64_t Ns[4] = {h, h, h, h + a->d_vd}, Ks[4] = {dv + (atom ? 0 : de), h + (atom ? de : 0), dv + h, h + a->d_vd};
         SplitWJob jobs[4];
         SplitWView views[4];
         int idx[4], nj = 0;
@@ -730,8 +743,18 @@ int dmpnn_forward(const dmpnn_fwd_args* a, void* stream) {
         g.A1 = a->V; g.lda1 = a->ldv; g.gather1 = pv.src; g.gather1_rows = nV;
         g.A2 = a->E; g.lda2 = a->lde;
         g.W = a->W_i; g.ldw = dv + de; g.bias = a->b_i;
+        if (atom) { g.K2 = 0; g.A2 = nullptr; g.lda2 = 0; g.ldw = dv; }   // (base.py:278-280: H0 = W_i V[src])
         g.C = a->H0; g.ldc = a->ldh; g.act = DMPNN_ACT_NONE;
         DMPNN_TRY(lin(g, 0));
+    }
+    if (atom && nE > 0) {
+        // ME = atom-message(E): the bond-feature half of every step's message, once per call — [n_edges][16] rows, zero-padded
+        float* ME = static_cast<float*>(a->msplit);
+        if (de < 16 && hipMemsetAsync(ME, 0, (size_t)nE * 16 * sizeof(float), s) != hipSuccess) {
+            set_error("forward: memset failed");
+            return DMPNN_EHIP;
+        }
+        DMPNN_TRY(launch_message(pv, nV, nE, de, a->E, a->lde, ME, 16, DMPNN_ACT_NONE, 0.f, nullptr, DMPNN_F_ATOM, s));
     }
     const float* Hprev = a->H0;   // H^(0) = tau(H0) is formed on load (base.py:200)
     int act_on_load = a->act;

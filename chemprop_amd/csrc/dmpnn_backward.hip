@@ -11,6 +11,9 @@
 //                                                kernel with read row rev(e') and write row e')
 //   gH0 accumulates every gZ^(t) plus gH^(0) * tau'(tau(H0)).
 //
+// Atom messages (DMPNN_F_ATOM: M[e] = S[src(e)], no reverse row): gHb[e'] = gS[dst(e')] — k_edge_bwd<ATOM>, the MESSAGE kernel
+// without its subtraction; W_h is [d_h, d_h + d_e] and its product reads [M^(t) || ME].
+//
 // Graph must be symmetric (every featurizer-produced graph is); on an asymmetric plan the message
 // backward writes NaN (loud) — gradients through arbitrary index arrays are not provided.
 #include <stdlib.h>
@@ -27,7 +30,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // ------------------------------------------------------------------------------------------------
 // edge-space backward kernels
 // ------------------------------------------------------------------------------------------------
-enum : int { EB_GATHER = 0, EB_MESSAGE = 1, EB_AVG = 2 };
+enum : int { EB_GATHER = 0, EB_MESSAGE = 1, EB_AVG = 2, EB_ATOM = 3 };   // (EB_ATOM: the MESSAGE kernel without the reverse row — atom messages)
 
 struct EdgeBwdArgs {
     PlanView pv;
@@ -113,7 +116,7 @@ __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(
 __device__ __forceinline__ float4 sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 
 // MESSAGE mode, atom with in-degree exactly D: D rows of gM, D rows of Y, D rows of acc in flight.
-template <int VEC, int ACT, int D, bool DROP = false>
+template <int VEC, int ACT, int D, bool DROP = false, bool ATOMM = false>
 __device__ __forceinline__ void msg_bwd_body(const EdgeBwdArgs& a, int beg, int lane, int n_cols, float slope,
                                              const float* Yp, int64_t ldy, const float* Ap, int64_t lda) {
     int eid[D], erev[D];
@@ -137,14 +140,14 @@ __device__ __forceinline__ void msg_bwd_body(const EdgeBwdArgs& a, int beg, int 
         for (int i = 1; i < D; ++i) S = add4(S, r[i]);
 #pragma unroll
         for (int i = 0; i < D; ++i) {
-            const float4 g = sub4(S, r[i]);
+            const float4 g = ATOMM ? S : sub4(S, r[i]);
             finish<VEC, ACT, DROP>(a, eid[i], c, ok, slope, g.x, g.y, g.z, g.w, y[i].x, y[i].y, y[i].z, y[i].w,
                                    ac[i].x, ac[i].y, ac[i].z, ac[i].w);
         }
     }
 }
 
-template <int VEC, int ACT, bool DROP = false>
+template <int VEC, int ACT, bool DROP = false, bool ATOMM = false>
 __device__ __forceinline__ void msg_bwd_any(const EdgeBwdArgs& a, int beg, int d, int lane, int n_cols, float slope,
                                             const float* Yp, int64_t ldy, const float* Ap, int64_t lda) {
     for (int cg = lane; cg < n_cols; cg += 64) {
@@ -153,7 +156,7 @@ __device__ __forceinline__ void msg_bwd_any(const EdgeBwdArgs& a, int beg, int d
         for (int i = 0; i < d; ++i) S = add4(S, ld<VEC>(a.gin + (int64_t)a.pv.rev[a.pv.perm[beg + i]] * a.ld_gin + c));
         for (int i = 0; i < d; ++i) {
             const int e = a.pv.perm[beg + i];
-            const float4 g = sub4(S, ld<VEC>(a.gin + (int64_t)a.pv.rev[e] * a.ld_gin + c));
+            const float4 g = ATOMM ? S : sub4(S, ld<VEC>(a.gin + (int64_t)a.pv.rev[e] * a.ld_gin + c));
             const float4 y = ld<VEC>(Yp + (int64_t)e * ldy + c);
             const float4 ac = ld<VEC>(Ap + (int64_t)e * lda + c);
             finish<VEC, ACT, DROP>(a, e, c, true, slope, g.x, g.y, g.z, g.w, y.x, y.y, y.z, y.w, ac.x, ac.y, ac.z, ac.w);
@@ -174,7 +177,8 @@ __global__ __launch_bounds__(256) void k_edge_bwd(EdgeBwdArgs a) {
     const float* Ap = (a.acc && !a.acc_init) ? a.acc : a.gin;
     const int64_t lda = (a.acc && !a.acc_init) ? a.ldacc : 0;
 
-    if (MODE == EB_MESSAGE) {
+    if (MODE == EB_MESSAGE || MODE == EB_ATOM) {
+        constexpr bool AT = MODE == EB_ATOM;
         const bool asym = a.pv.hdr[DMPNN_HDR_FLAGS] & a.poison_mask;
         if (asym) {  // gradients through a non-molecular index structure are not provided: poison loudly
             const float nanv = __int_as_float(0x7fc00000);
@@ -189,16 +193,16 @@ __global__ __launch_bounds__(256) void k_edge_bwd(EdgeBwdArgs a) {
             const int beg = a.pv.row_ptr[v];
             const int d = a.pv.row_ptr[v + 1] - beg;
             if (ACT == -1) {
-                msg_bwd_any<VEC, ACT, DROP>(a, beg, d, lane, n_cols, slope, Yp, ldy, Ap, lda);
+                msg_bwd_any<VEC, ACT, DROP, AT>(a, beg, d, lane, n_cols, slope, Yp, ldy, Ap, lda);
                 continue;
             }
             switch (d) {
                 case 0: break;
-                case 1: msg_bwd_body<VEC, ACT, 1, DROP>(a, beg, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
-                case 2: msg_bwd_body<VEC, ACT, 2, DROP>(a, beg, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
-                case 3: msg_bwd_body<VEC, ACT, 3, DROP>(a, beg, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
-                case 4: msg_bwd_body<VEC, ACT, 4, DROP>(a, beg, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
-                default: msg_bwd_any<VEC, ACT, DROP>(a, beg, d, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
+                case 1: msg_bwd_body<VEC, ACT, 1, DROP, AT>(a, beg, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
+                case 2: msg_bwd_body<VEC, ACT, 2, DROP, AT>(a, beg, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
+                case 3: msg_bwd_body<VEC, ACT, 3, DROP, AT>(a, beg, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
+                case 4: msg_bwd_body<VEC, ACT, 4, DROP, AT>(a, beg, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
+                default: msg_bwd_any<VEC, ACT, DROP, AT>(a, beg, d, lane, n_cols, slope, Yp, ldy, Ap, lda); break;
             }
         }
     } else {
@@ -224,7 +228,7 @@ int launch_edge_bwd(EdgeBwdArgs a, hipStream_t s, const char* name) {
     if (a.nE == 0 || a.h == 0) return DMPNN_OK;
     if (!a.Y) a.act = DMPNN_ACT_NONE;
     if (!a.poison_mask) a.poison_mask = PLAN_ASYMMETRIC;
-    const int64_t items = (MODE == EB_MESSAGE) ? a.nV : a.nE;
+    const int64_t items = (MODE == EB_MESSAGE || MODE == EB_ATOM) ? a.nV : a.nE;
     int64_t blocks = (items + 3) / 4;
     if (blocks > 256 * 32) blocks = 256 * 32;
     if (blocks < 1) blocks = 1;
@@ -687,12 +691,13 @@ BwdLayout bwd_layout(const dmpnn_fwd_args& f) {
     L.WhT = o; o += align_up((size_t)h * h, 4);
     L.WoT = o; o += align_up((size_t)h * h, 4);
     L.WdT = o; o += align_up((size_t)h * (h + dvd), 4);
-    L.p_h = plan_wgrad(nE, (int)h, (int)h + (f.b_h ? 1 : 0));
+    const int de_h = (f.flags & DMPNN_F_ATOM) ? (int)f.d_e : 0;   // (atom messages: W_h's product reads [M^(t) || ME])
+    L.p_h = plan_wgrad(nE, (int)h, (int)h + de_h + (f.b_h ? 1 : 0));
     L.p_i = plan_wgrad(nE, (int)h, (int)(f.d_v + f.d_e) + (f.b_i ? 1 : 0));
     L.p_o = plan_wgrad(nV, (int)h, (int)(f.d_v + h) + 1);
     L.p_d = plan_wgrad(nV, (int)(h + dvd), (int)(h + dvd) + 1);
     const int steps = f.depth > 1 ? f.depth - 1 : 1;
-    L.p_hm = plan_wgrad(nE * steps, (int)h, (int)h + (f.b_h ? 1 : 0));
+    L.p_hm = plan_wgrad(nE * steps, (int)h, (int)h + de_h + (f.b_h ? 1 : 0));
     {
         const size_t per_step = (size_t)L.p_h.max_splits() * steps * L.p_h.slab_stride, merged = (size_t)L.p_hm.max_splits() * L.p_hm.slab_stride;
         L.slab_h = o; o += align_up(per_step > merged ? per_step : merged, 4);
@@ -827,6 +832,18 @@ int dmpnn_message_bwd(const void* plan, int64_t n_atoms, int64_t n_edges, int64_
     return launch_edge_bwd<EB_MESSAGE>(a, static_cast<hipStream_t>(stream), "k_edge_bwd<message>");
 }
 
+int dmpnn_atom_message_bwd(const void* plan, int64_t n_atoms, int64_t n_edges, int64_t d_h, const float* gM, int64_t ld_gm,
+                           float* gH, int64_t ld_gh, void* stream) {
+    DMPNN_CHECK_ARG(plan && d_h >= 0 && ld_gm >= d_h && ld_gh >= d_h, "atom_message_bwd: bad arguments");
+    DMPNN_CHECK_ARG(n_edges == 0 || (gM && gH), "atom_message_bwd: null tensor");
+    EdgeBwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pv = plan_view(plan, n_atoms, n_edges);
+    a.nV = (int)n_atoms; a.nE = (int)n_edges; a.h = (int)d_h;
+    a.gin = gM; a.ld_gin = ld_gm; a.gZ = gH; a.ldgz = ld_gh;
+    return launch_edge_bwd<EB_ATOM>(a, static_cast<hipStream_t>(stream), "k_edge_bwd<atom message>");
+}
+
 int dmpnn_aggregate_bwd(const void* plan, int64_t n_atoms, int64_t n_edges, int64_t d_h, const float* gMv,
                         int64_t ld_gmv, float* gH, int64_t ld_gh, void* stream) {
     DMPNN_CHECK_ARG(plan && d_h >= 0 && ld_gmv >= d_h && ld_gh >= d_h, "aggregate_bwd: bad arguments");
@@ -898,7 +915,8 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
     const bool has_vd = f.W_d != nullptr;
     const int64_t dvd = has_vd ? f.d_vd : 0;
     const int T = f.depth;
-    // atom messages (DMPNN_F_ATOM, base.py:254-289): gW_i is [h, d_v], gW_h [h, h + d_e]; only the tile kernels carry them
+    // atom messages (DMPNN_F_ATOM, base.py:254-289): gW_i is [h, d_v], gW_h [h, h + d_e]; the tile kernels carry them, and the
+    // per-step general route (its forward kept ME = atom-message(E) as ONE slot of [n_edges][16] rows in `msplit`)
     const bool atom = (f.flags & DMPNN_F_ATOM) != 0;
     const int64_t de_i = atom ? 0 : de, de_h = atom ? de : 0;
     DMPNN_CHECK_ARG(f.plan && h > 0 && dv > 0 && T >= 1, "backward: bad forward description");
@@ -1070,15 +1088,18 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
     DMPNN_CHECK_ARG(!mega16_keeps_rows(f) || (tile_bwd && L.sr) || !(b->gW_h || b->gb_h),
                     "backward: the forward kept its messages as split rows (`msplit`): the weight gradient of W_h then needs the tile kernels — "
                     "16-byte aligned gout / out with leading dimensions that are multiples of 4, d_v + d_e and d_v + d_h <= 512");
-    DMPNN_CHECK_ARG(!atom || (tile_bwd && L.w16 && !has_vd && (T < 2 || nE == 0 || f.msplit)),
+    const bool atom_rows = atom && !fused && !(f.flags & (DMPNN_F_MEGA | DMPNN_F_UNDIRECTED | DMPNN_F_TILE_PLAN)) && !has_vd && de >= 1 && de <= 16 &&
+                           (nE == 0 || (f.msplit && aligned16(f.msplit) && f.msplit_bytes >= (size_t)nE * 16 * sizeof(float)));
+    DMPNN_CHECK_ARG(!atom || atom_rows || (tile_bwd && L.w16 && !has_vd && (T < 2 || nE == 0 || f.msplit)),
                     "backward: DMPNN_F_ATOM needs the tile-kernel forward (FUSED | MEGA | SPLIT16 | KEEP with `msplit`), even d_v / d_e / d_h and "
-                    "16-byte aligned gout / out (leading dimensions multiples of 4)");
+                    "16-byte aligned gout / out (leading dimensions multiples of 4) — or the forward of the per-step general route (directed, no "
+                    "W_d, 1 <= d_e <= 16, `msplit` >= n_edges * 64 bytes)");
     // in-kernel dropout (dmpnn_fwd_args.dropout_p): its 1 / (1 - p) lives in the backward TILE kernel and in the lean branch above (the
     // backward step kernels regenerate the mask) — every other branch below would return gradients without it, silently
     // ... or, for the per-step general route on the f16 pipe (the mask in the row kernels' epilogue), in k_act_bwd_hash / the DROP
     // builds of k_edge_bwd below, which regenerate the mask from the hash
     const bool rows_drop = f.dropout_p > 0.f && f.dropout_p < 1.f && !fused && (f.flags & DMPNN_F_SPLIT16) && (f.flags & DMPNN_F_KEEP) &&
-                           !(f.flags & (DMPNN_F_MEGA | DMPNN_F_UNDIRECTED | DMPNN_F_ATOM)) && !has_vd && h <= 1024;
+                           !(f.flags & (DMPNN_F_MEGA | DMPNN_F_UNDIRECTED)) && !has_vd && h <= 1024;
     DMPNN_CHECK_ARG(!(f.dropout_p > 0.f) || tile_bwd || rows_drop,
                     "backward: the forward ran with dropout inside the kernels; only the backward tile kernel carries its scale — it needs a "
                     "gradient of W_i or W_h to be wanted and 16-byte aligned gout / out (leading dimensions multiples of 4) — or the per-step "
@@ -1341,7 +1362,7 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
     const bool need_edges = b->gW_i || b->gb_i || b->gW_h || b->gb_h;
     if (!need_edges) return DMPNN_OK;
     if (nE == 0) {
-        zero2d(b->gW_i, h, dv + de); zero2d(b->gb_i, 1, h); zero2d(b->gW_h, h, h); zero2d(b->gb_h, 1, h);
+        zero2d(b->gW_i, h, dv + de_i); zero2d(b->gb_i, 1, h); zero2d(b->gW_h, h, h + de_h); zero2d(b->gb_h, 1, h);
         return DMPNN_OK;
     }
     // gMv = gZO . W_o[:, d_v:]
@@ -1375,8 +1396,9 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
             g.M = nE; g.N = h; g.K1 = h; g.A1 = gZa; g.lda1 = ldh; g.W = WhT; g.ldw = h; g.C = gZb; g.ldc = ldh;
             gm16 = L.use16 && linear16_ok(g);
         }
-        if (gm16) DMPNN_TRY(split_weights_view(f.W_h, h, h, h, 1, ws + L.WhT16, &wh16, s));
-        else DMPNN_TRY(launch_transpose(f.W_h, h, WhT, h, (int)h, (int)h, s));
+        // (atom messages: W_h is [h, h + d_e] — gM = gZ . W_h[:, :h], the transposed view of its first h columns)
+        if (gm16) DMPNN_TRY(split_weights_view(f.W_h, h + de_h, h, h, 1, ws + L.WhT16, &wh16, s));
+        else DMPNN_TRY(launch_transpose(f.W_h, h + de_h, WhT, h, (int)h, (int)h, s));
         // gZ^(T-1) = gMv[dst] * tau'(H^(T-1));  gH0 = gZ^(T-1)
         EdgeBwdArgs g0 = e;
         g0.gin = gMv; g0.ld_gin = ldh;
@@ -1391,8 +1413,9 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
             if (b->gW_h || b->gb_h) {
                 WgradArgs a;
                 memset(&a, 0, sizeof(a));
-                a.M = nE; a.N = (int)h; a.K1 = (int)h; a.K2 = 0; a.ones = f.b_h ? 1 : 0;
+                a.M = nE; a.N = (int)h; a.K1 = (int)h; a.K2 = (int)de_h; a.ones = f.b_h ? 1 : 0;
                 a.gZ = gZ; a.ldz = ldh; a.A1 = Mt; a.lda1 = ldh;
+                if (atom) { a.A2 = static_cast<const float*>(f.msplit); a.lda2 = 16; }   // ME: the same rows in every step
                 int ns = 0;
                 DMPNN_TRY(launch_wgrad(a, L.p_h, slab_h + (int64_t)n_slabs_h * L.p_h.slab_stride, s, ws + L.w16g, &ns));
                 n_slabs_h += ns;
@@ -1414,7 +1437,8 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
                 m.gZ = first ? nullptr : gZ; m.ldgz = ldh;
                 m.acc = gH0; m.ldacc = ldh; m.acc_init = 0;
                 if (!first) set_drop(m, t - 2);   // (the first step reads the unmasked H0 pre-activation: no mask)
-                DMPNN_TRY(launch_edge_bwd<EB_MESSAGE>(m, s, "k_edge_bwd<message>"));
+                if (atom) DMPNN_TRY(launch_edge_bwd<EB_ATOM>(m, s, "k_edge_bwd<atom message>"));
+                else DMPNN_TRY(launch_edge_bwd<EB_MESSAGE>(m, s, "k_edge_bwd<message>"));
             } else {
                 m.gZ = gZ; m.ldgz = ldh;  // raw gHb
                 DMPNN_TRY(launch_edge_bwd<EB_MESSAGE>(m, s, "k_edge_bwd<message>"));
@@ -1428,7 +1452,7 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
             }
         }
         if (b->gW_h || b->gb_h)
-            DMPNN_TRY(launch_wgrad_reduce(slab_h, L.p_h, n_slabs_h, (int)h, (int)h, f.b_h ? 1 : 0, b->gW_h, h, b->gb_h, s, pflags, pmask));
+            DMPNN_TRY(launch_wgrad_reduce(slab_h, L.p_h, n_slabs_h, (int)h, (int)(h + de_h), f.b_h ? 1 : 0, b->gW_h, h + de_h, b->gb_h, s, pflags, pmask));
     } else {
         // depth 1: gH0 = gMv[dst] * tau'(tau(H0))
         EdgeBwdArgs g0 = e;
@@ -1436,17 +1460,17 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
         g0.Y = f.H0; g0.ldy = ldh; g0.y_preact = 1;
         g0.acc = gH0; g0.ldacc = ldh; g0.acc_init = 1;
         DMPNN_TRY(launch_edge_bwd<EB_GATHER>(g0, s, "k_edge_bwd<gather>"));
-        zero2d(b->gW_h, h, h); zero2d(b->gb_h, 1, h);
+        zero2d(b->gW_h, h, h + de_h); zero2d(b->gb_h, 1, h);
     }
     if (b->gW_i || b->gb_i) {
         WgradArgs a;
         memset(&a, 0, sizeof(a));
-        a.M = nE; a.N = (int)h; a.K1 = (int)dv; a.K2 = (int)de; a.ones = f.b_i ? 1 : 0;
+        a.M = nE; a.N = (int)h; a.K1 = (int)dv; a.K2 = (int)de_i; a.ones = f.b_i ? 1 : 0;
         a.gZ = gH0; a.ldz = ldh; a.A1 = f.V; a.lda1 = f.ldv; a.gather1 = pv.src; a.A2 = f.E; a.lda2 = f.lde;
         a.gather2 = e_gather;
         int ns = 0;
         DMPNN_TRY(launch_wgrad(a, L.p_i, slab_x, s, ws + L.w16g, &ns));
-        DMPNN_TRY(launch_wgrad_reduce(slab_x, L.p_i, ns, (int)h, (int)(dv + de), f.b_i ? 1 : 0, b->gW_i, dv + de, b->gb_i, s, pflags, pmask));
+        DMPNN_TRY(launch_wgrad_reduce(slab_x, L.p_i, ns, (int)h, (int)(dv + de_i), f.b_i ? 1 : 0, b->gW_i, dv + de_i, b->gb_i, s, pflags, pmask));
     }
     return DMPNN_OK;
 }

@@ -17,6 +17,9 @@
 // Graphs that violate the symmetry invariants (plan flag PLAN_ASYMMETRIC, decided on device, no
 // host sync) take the literal edge form  M[e] = S[src(e)] - H[rev(e)]  in the same launch.
 //
+// Atom messages (mixins.py:21-30, AtomMessagePassing): M[e] = S[src(e)] without the reverse row — the third mode of the kernel, same
+// wave-per-atom form, same in-degree bodies, same summation order: M[rev(e'_i)] = S (edge form on an asymmetric plan: M[e] = S[src(e)]).
+//
 // tau-on-load: the first depth step consumes tau(H0) (base.py:200); applying tau while loading
 // saves materialising H^(0).  Undirected (base.py:202-203) averages each row with its reverse
 // while loading.
@@ -118,7 +121,7 @@ __device__ __forceinline__ void atom_body(const SegArgs& a, int v, int beg, int 
 #pragma unroll
     for (int i = 0; i < D; ++i) eid[i] = a.pv.perm[beg + i];
 #pragma unroll
-    for (int i = 0; i < D; ++i) erev[i] = (MODE == 0 || UNDIR != 0) ? a.pv.rev[eid[i]] : 0;
+    for (int i = 0; i < D; ++i) erev[i] = (MODE != 1 || UNDIR != 0) ? a.pv.rev[eid[i]] : 0;
     for (int cg0 = 0; cg0 < n_cols; cg0 += 128) {
         const int cgA = cg0 + lane, cgB = cg0 + 64 + lane;
         const bool okA = cgA < n_cols, okB = cgB < n_cols;
@@ -142,8 +145,8 @@ __device__ __forceinline__ void atom_body(const SegArgs& a, int v, int beg, int 
 #pragma unroll
             for (int i = 0; i < D; ++i) {
                 float* o = a.out + (int64_t)erev[i] * a.ld_out;
-                if (okA) V::store(o + cA, V::sub(SA, rA[i]));
-                if (okB) V::store(o + cB, V::sub(SB, rB[i]));
+                if (okA) V::store(o + cA, MODE == 2 ? SA : V::sub(SA, rA[i]));
+                if (okB) V::store(o + cB, MODE == 2 ? SB : V::sub(SB, rB[i]));
             }
         }
     }
@@ -168,13 +171,15 @@ __device__ __forceinline__ void atom_body_any(const SegArgs& a, int v, int beg, 
             for (int i = 0; i < d; ++i) {
                 const int e = a.pv.perm[beg + i];
                 const int er = a.pv.rev[e];
-                V::store(a.out + (int64_t)er * a.ld_out + c, V::sub(S, load_row<VEC, UNDIR, ACT>(a, e, er, c, slope)));
+                if (MODE == 2) V::store(a.out + (int64_t)er * a.ld_out + c, S);
+                else V::store(a.out + (int64_t)er * a.ld_out + c, V::sub(S, load_row<VEC, UNDIR, ACT>(a, e, er, c, slope)));
             }
         }
     }
 }
 
-// MODE 0: message (atom form when the graph is symmetric, edge form otherwise); MODE 1: aggregate.
+// MODE 0: message (atom form when the graph is symmetric, edge form otherwise); MODE 1: aggregate; MODE 2: atom message (as MODE 0
+// without the reverse row).
 template <int VEC, int MODE, int UNDIR, int ACT>
 __global__ __launch_bounds__(kWavesPerBlock * 64) void k_segment(SegArgs a) {
     using V = Vec<VEC>;
@@ -183,7 +188,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void k_segment(SegArgs a) {
     const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     const int n_waves = gridDim.x * kWavesPerBlock;
     const float slope = a.slope_ptr ? *a.slope_ptr : a.slope;
-    const bool asym = (MODE == 0) && (a.pv.hdr[DMPNN_HDR_FLAGS] & PLAN_ASYMMETRIC);
+    const bool asym = (MODE != 1) && (a.pv.hdr[DMPNN_HDR_FLAGS] & PLAN_ASYMMETRIC);
     const int n_cols = a.h / VEC;  // column groups of VEC floats
 
     if (!asym) {
@@ -223,7 +228,8 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void k_segment(SegArgs a) {
                     const T r = load_row<VEC, UNDIR, ACT>(a, ei, a.pv.rev[ei], c, slope);
                     S = (i == 0) ? r : V::add(S, r);
                 }
-                V::store(a.out + (int64_t)e * a.ld_out + c, V::sub(S, load_row<VEC, UNDIR, ACT>(a, er, a.pv.rev[er], c, slope)));
+                if (MODE == 2) V::store(a.out + (int64_t)e * a.ld_out + c, S);
+                else V::store(a.out + (int64_t)e * a.ld_out + c, V::sub(S, load_row<VEC, UNDIR, ACT>(a, er, a.pv.rev[er], c, slope)));
             }
         }
     }
@@ -231,7 +237,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void k_segment(SegArgs a) {
 
 template <int MODE>
 int launch_segment(const SegArgs& a, hipStream_t s, const char* name) {
-    const int64_t items = (MODE == 0) ? (a.nV > a.nE ? a.nV : a.nE) : a.nV;
+    const int64_t items = (MODE != 1) ? (a.nV > a.nE ? a.nV : a.nE) : a.nV;
     if (items == 0 || a.h == 0) return DMPNN_OK;
     int64_t blocks = (items + kWavesPerBlock - 1) / kWavesPerBlock;
     const int64_t cap = 256 * 32;  // grid-stride beyond 32 blocks per CU
@@ -258,7 +264,10 @@ int launch_message(const PlanView& pv, int64_t nV, int64_t nE, int64_t h, const 
                    const float* slope_ptr, unsigned flags, hipStream_t s) {
     SegArgs a{pv, (int)nV, (int)nE, (int)h, Hin, ld_in, M, ld_m, act, slope, slope_ptr,
               (flags & DMPNN_F_UNDIRECTED) ? 1 : 0};
+    DMPNN_CHECK_ARG((flags & (DMPNN_F_ATOM | DMPNN_F_UNDIRECTED)) != (DMPNN_F_ATOM | DMPNN_F_UNDIRECTED),
+                    "message: DMPNN_F_ATOM | DMPNN_F_UNDIRECTED is not provided (atom messages are directed)");
     if (nE == 0) return DMPNN_OK;
+    if (flags & DMPNN_F_ATOM) return launch_segment<2>(a, s, "k_segment<atom message>");
     return launch_segment<0>(a, s, "k_segment<message>");
 }
 

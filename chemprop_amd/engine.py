@@ -333,10 +333,12 @@ def lean_dropout_refusal(d_v: int, d_e: int, d_h: int, depth: int, act: str, has
     return None
 
 
-def rows_dropout_refusal(d_v: int, d_e: int, d_h: int, depth: int, act: str, has_vd: bool = False, undirected: bool = False) -> Optional[str]:
+def rows_dropout_refusal(d_v: int, d_e: int, d_h: int, depth: int, act: str, has_vd: bool = False, undirected: bool = False,
+                         atom: bool = False) -> Optional[str]:
     """Why the row kernels of the per-step general route on the f16 pipe (``route="general"``, ``mfma="split16"``, ``keep``) cannot
     carry block dropout for these shapes — the condition of ``dmpnn_forward`` (csrc/dmpnn_abi.hip: ``rows_dropout_check``) that
-    fails, in words — or ``None`` when they can.  (The workspace this package allocates meets the alignment conditions.)"""
+    fails, in words — or ``None`` when they can.  (The workspace this package allocates meets the alignment conditions.)
+    ``atom``: an atom block (``DMPNN_F_ATOM``) — its update contraction reads ``[M || ME]``, so ``d_e`` must be even as well."""
     if act not in ("none", "relu", "leakyrelu", "tanh", "elu"):
         return f"activation {act!r} (none / relu / leakyrelu / tanh / elu: PReLU's slope trains, a custom module runs between the kernels)"
     if has_vd:
@@ -351,6 +353,8 @@ def rows_dropout_refusal(d_v: int, d_e: int, d_h: int, depth: int, act: str, has
         return f"odd d_h {d_h} (the update contraction would fall to the fp32-MFMA kernel)"
     if d_v % 2:
         return f"odd d_v {d_v} (the finalize contraction would fall to the fp32-MFMA kernel)"
+    if atom and d_e % 2:
+        return f"odd d_e {d_e} (the update contraction of an atom block would fall to the fp32-MFMA kernel)"
     return None
 
 
@@ -555,7 +559,9 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
     ``form``: ``DMPNN_F_H0_RESIDUAL`` / ``DMPNN_F_ROW_FINALIZE`` bits for the per-step fused route on the f16 pipe (its other
     form of the residual / of the finalize, include/dmpnn.h; what training and wide hidden layers use anyway).
     ``atom=True``: ``AtomMessagePassing`` semantics (``DMPNN_F_ATOM``: ``W_i [d_h, d_v]``, ``W_h [d_h, d_h + d_e]``) — the tile
-    kernel, inference or (round 4) training; raises :class:`RouteUnavailable` when this batch takes another route.
+    kernel, inference or (round 4) training — or, ON DEMAND (``route="general"`` / ``fused=False``, either ``mfma``), the per-step
+    general route: any molecule size, any ``d_h``, ``1 <= d_e <= 16``, directed, no ``W_d``, with ``dropout`` under
+    :func:`rows_dropout_refusal`'s conditions; raises :class:`RouteUnavailable` when this batch takes another route.
     ``dropout = (p, seed)``: ACTIVE dropout inside the kernels (``dmpnn_fwd_args.dropout_p``) — a training forward (``keep``) of
     the tile kernel with a ReLU-class activation and no ``W_d``, or, on demand (``route="fused16"``, ``keep``, ``keep_bits``), the
     lean training forward of the per-step fused route under its own shapes (molecules beyond the tile; ``st.route`` stays
@@ -619,6 +625,7 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
     # constants, tests/test_host.py enumerates it); `route` / `fused` / `mfma` are demands of tests and A/B measurements ----
     if fused is False:
         route = "general"
+    asked_general = route == "general"   # (a demand of the caller's, not the environment's)
     if _lib.opt("DMPNN_GENERAL", "0") == "1":
         route = "general"
     a.H0 = a.Ms = a.Mv = plan.buf.data_ptr()  # any 16-byte aligned pointer: the real workspace is allocated below
@@ -667,18 +674,21 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
             want16 = False
 
     if atom:
-        if not (use_mega and want16 and not d_vd and 1 <= d_e <= 16 and (not keep or (d_e % 2 == 0 and d_v % 2 == 0 and d_h % 2 == 0))):
-            raise RouteUnavailable("atom messages inside the kernels: the tile kernel, 1 <= d_e <= 16, no W_d (training: even d_v / d_e / d_h)")
+        tile_home = use_mega and want16 and (not keep or (d_e % 2 == 0 and d_v % 2 == 0 and d_h % 2 == 0))
+        rows_home = asked_general and not use_fused and not undirected   # (the per-step general route: on demand only)
+        if not ((tile_home or rows_home) and not d_vd and 1 <= d_e <= 16):
+            raise RouteUnavailable("atom messages inside the kernels: the tile kernel, 1 <= d_e <= 16, no W_d (training: even d_v / d_e / d_h) "
+                                   "— or, on demand (route='general'), the per-step general route: directed, 1 <= d_e <= 16, no W_d")
         a.flags |= _lib.F_ATOM
     if dropout is not None and float(dropout[0]) > 0.0:
         # its three homes: the tile kernels, or — on demand — the lean step kernels beyond the tile (route="fused16", keep, keep_bits)
         # or the row kernels of the per-step general route on the f16 pipe (route="general", mfma="split16", keep)
-        tile_home = bool(use_mega and want16 and keep and not d_vd and act in ("relu", "leakyrelu"))
+        tile_home = bool(use_mega and want16 and keep and not d_vd and not atom and act in ("relu", "leakyrelu"))
         # (a DEMAND: the default rule may pick the lean form itself — it saw p = 0 — and must then refuse, as before)
         lean_home = bool(route == "fused16" and use_fused16 and keep and keep_bits and not d_vd and act in ("relu", "leakyrelu"))
         # (a DEMAND as well: route="general" with mfma="split16" — never the default rule's own general16, which saw p = 0)
-        rows_why = rows_dropout_refusal(d_v, d_e, d_h, depth, act, bool(d_vd), bool(undirected))
-        rows_home = bool(route == "general" and mfma == "split16" and want16 and not use_fused and keep and not atom and rows_why is None
+        rows_why = rows_dropout_refusal(d_v, d_e, d_h, depth, act, bool(d_vd), bool(undirected), bool(atom))
+        rows_home = bool(route == "general" and mfma == "split16" and want16 and not use_fused and keep and rows_why is None
                          and float(dropout[0]) < 1.0 and V.stride(0) % 2 == 0 and V.data_ptr() % 8 == 0)
         if tile_home or lean_home or rows_home:
             a.dropout_p, a.dropout_seed = float(dropout[0]), int(dropout[1]) & 0xFFFFFFFFFFFFFFFF
@@ -759,7 +769,10 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
     else:
         edge_ws = torch.empty(((1 if need_h0 else 0) + n_hslots + n_mslots, nE, ldh), dtype=torch.float32, device=dev)
         atom_ws = torch.empty((2, nV, ldh), dtype=torch.float32, device=dev)
-        if atom and keep:
+        if atom and not use_fused:
+            # the per-step general route: ME = atom-message(E) as ONE slot of [n_edges][16] rows — kept for W_h's gradient, or scratch
+            split_ms = torch.empty((1, nE, 16), dtype=torch.float32, device=dev)
+        elif atom and keep:
             # the bond-feature half of the atom messages, kept for W_h's gradient: depth - 1 slots of [n_edges][16] (include/dmpnn.h, DMPNN_F_ATOM)
             split_ms = torch.empty((max(n_steps, 1), nE, 16), dtype=torch.float32, device=dev)
         elif use_mega and want16 and keep and n_steps and train_route(nV, nE, d_v, d_e, d_h, depth, act, 1, max_level=2).keep_rows:
@@ -792,7 +805,7 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
             a.keep_bits, a.keep_bits_bytes = bits.data_ptr(), bits.numel()
             a.Hs = a.Ms = None
             st.Ms = split_ms      # (the kept M^(t) as split rows, CSR-row order)
-        elif split_ms is not None and keep:
+        elif split_ms is not None and (keep or (atom and not use_fused)):
             a.msplit, a.msplit_bytes = split_ms.data_ptr(), split_ms.numel() * 4
         elif split_ms is not None:
             st.Ms = split_ms

@@ -278,7 +278,8 @@ def hip_mpnn_class():
       Noam-like ``LambdaLR`` re-created on it with the reference's own ``lr_lambda`` (``schedulers.py``).  Lightning steps the
       scheduler, counts ``trainer.global_step`` through ``LightningOptimizer.step`` (what ``ModelCheckpoint`` keys on,
       ``cli/train.py:1912-1919``), saves ``optimizer.state_dict()`` (``torch.optim.Adam``'s format) in its checkpoints.
-    * ``training_step``: where :class:`chemprop_amd.model.FusedTrainer` applies (a bond block with a built-in activation, sum / mean /
+    * ``training_step``: where :class:`chemprop_amd.model.FusedTrainer` applies (a bond block — or, ``atom_messages=True``, an atom
+      block without ``W_d`` — with a built-in activation, sum / mean /
       norm aggregation, batch norm, regression MLP, MSE / MAE; atom descriptors ``V_d`` of a block built with ``d_vd`` through
       its ``V_d_transform`` and its layer ``W_d`` as a stage of the same call — with ``--dropout p`` the block's mask once more
       behind ``W_d``, inside that stage's kernels (``vd_dropout=True``); molecule descriptors ``X_d`` through the model's
@@ -327,7 +328,7 @@ def hip_mpnn_class():
 
             st = {"dev": dev, "fused": None, "why": None, "route": None}
             try:
-                tr = FusedTrainer(self, lr=float(self.init_lr), ffn_dropout=True, rows_dropout=True, vd_dropout=True)
+                tr = FusedTrainer(self, lr=float(self.init_lr), ffn_dropout=True, rows_dropout=True, vd_dropout=True, atom_messages=True)
                 st["fused"], st["sync"], st["opt"] = tr, tr.sync, tr.opt
             except NotImplementedError as e:   # (a model the fused step does not implement: module path on the same flat Adam)
                 st["why"] = str(e)

@@ -330,7 +330,15 @@ class MulticomponentMPNN(MPNN):
         return self._torch_loss(self.fingerprint(bmgs, V_ds, X_d), targets, weights, lt_mask, gt_mask)
 
 
-def fused_block(mp, rows_dropout: bool = False, vd_dropout: bool = False) -> tuple:
+def is_atom_block(mp) -> bool:
+    """An ``AtomMessagePassing`` block by its parameter shapes (base.py:278-289): ``W_i [d_h, d_v]``, ``W_h [d_h, d_h + d_e]``."""
+    if not all(isinstance(getattr(mp, n, None), nn.Linear) for n in ("W_i", "W_h", "W_o")):
+        return False
+    d_h = mp.W_h.out_features
+    return mp.W_h.in_features > d_h and mp.W_o.in_features > d_h and mp.W_i.in_features == mp.W_o.in_features - d_h
+
+
+def fused_block(mp, rows_dropout: bool = False, vd_dropout: bool = False, atom_messages: bool = False) -> tuple:
     """``(activation, slope)`` of a block the one-call step takes: a bond block (this package's mirror, or the subclass of the
     reference's own class, ``integration.HipBondMessagePassing``) with a built-in activation (not PReLU), directed, dropout 0
     or ``nn.Dropout`` with a ReLU-class activation — with ``rows_dropout=True`` (the mask in the row kernels of the per-step general
@@ -340,16 +348,32 @@ def fused_block(mp, rows_dropout: bool = False, vd_dropout: bool = False) -> tup
     ``dmpnn_vd_backward``) — unless ``d_h + d_vd`` is beyond ``_lib.VD_MAX_WIDTH`` or it also has dropout: the reference applies the
     block's dropout a second time behind ``W_d``, and only ``vd_dropout=True`` asks for that fourth mask (site ``_lib.DROP_SITE_VD``
     inside the stage's kernels, ``dmpnn_vd_args.dropout_p``).  The block is then taken under exactly the conditions it would meet
-    without ``W_d`` (``nn.Dropout``; a ReLU-class activation, or ``rows_dropout=True`` and a built-in smooth one)."""
+    without ``W_d`` (``nn.Dropout``; a ReLU-class activation, or ``rows_dropout=True`` and a built-in smooth one).
+    ``atom_messages=True`` also takes an atom block (``W_i [d_h, d_v]``, ``W_h [d_h, d_h + d_e]``: :func:`is_atom_block`) that is
+    directed, has a built-in activation other than PReLU, no ``W_d``, ``1 <= d_e <= 16`` and dropout 0 — or ``nn.Dropout`` with
+    ``rows_dropout=True`` (its only home is the row kernels: the atom tile kernels carry no mask).  The default refuses it."""
     # (W_h is [d_h, d_h] in a bond block: the atom variant's takes d_e + d_h columns, the mol-atom-bond ones have a second read-out)
     bond = (all(isinstance(getattr(mp, n, None), nn.Linear) for n in ("W_i", "W_h", "W_o"))
             and mp.W_h.in_features == mp.W_h.out_features and mp.W_o.in_features > mp.W_h.out_features)
-    if not bond:
-        raise NotImplementedError("FusedTrainer: a BondMessagePassing block (W_i / W_h [d_h, d_h] / W_o)")
+    atom = not bond and bool(atom_messages) and is_atom_block(mp)
+    if not bond and not atom:
+        raise NotImplementedError("FusedTrainer: a BondMessagePassing block (W_i / W_h [d_h, d_h] / W_o)"
+                                  + (" — atom_messages=True also takes an AtomMessagePassing block" if is_atom_block(mp) else ""))
     act, slope, slope_t = classify_activation(mp.tau)
     if act in ("custom", "prelu") or mp.undirected:
         raise NotImplementedError("FusedTrainer: built-in activation (not PReLU), directed — other blocks train "
                                   "through the module path (MPNN.loss + autograd)")
+    if atom:
+        d_e = mp.W_h.in_features - mp.W_h.out_features
+        if mp.W_d is not None:
+            raise NotImplementedError("FusedTrainer: an atom block with atom descriptors (W_d) trains through the module path")
+        if not 1 <= d_e <= 16:
+            raise NotImplementedError(f"FusedTrainer: an atom block with d_e = {d_e} (the kernels keep the bond-feature half of the "
+                                      "messages as rows of 16 columns: 1 <= d_e <= 16)")
+        if mp.dropout.p > 0 and not (type(mp.dropout) is nn.Dropout and rows_dropout):
+            raise NotImplementedError("FusedTrainer: dropout inside an atom block needs nn.Dropout and rows_dropout=True (the mask lives "
+                                      "in the row kernels; the atom tile kernels carry none)")
+        return act, slope
     if mp.W_d is not None:
         if mp.dropout.p > 0 and not vd_dropout:
             raise NotImplementedError("FusedTrainer: atom descriptors (W_d) together with dropout inside the block — the dropout behind "
@@ -746,10 +770,16 @@ class FusedTrainer:
     more behind ``W_d``, and that fourth mask lives in the atom-descriptor stage's own kernels (site ``_lib.DROP_SITE_VD``;
     ``dmpnn_vd_args.dropout_p`` / ``dropout_seed`` are the block's ``(p, seed)`` of the step: still one draw, ``last_dropout_seed``).
     The backward stage overwrites ``gH_v'`` with the masked gradient.  The default refuses such a block.
+
+    ``atom_messages=True`` also takes an ``AtomMessagePassing`` block (:func:`fused_block`).  Its two homes: with ``p = 0`` a batch
+    bound for the tile kernels (no molecule beyond the tile, at most 30 directed edges per molecule, even ``d_v / d_e / d_h``) runs
+    on them with ``DMPNN_F_ATOM``; everything else — molecules beyond the tile, wide or odd shapes, ``p > 0`` at any size — on the
+    per-step general route on the f16 pipe (``route == "general16"``).  The default refuses such a block.
     """
 
     def __init__(self, model: MPNN, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, group=None,
-                 tile_plan: bool = True, ffn_dropout: bool = False, rows_dropout: bool = False, vd_dropout: bool = False):
+                 tile_plan: bool = True, ffn_dropout: bool = False, rows_dropout: bool = False, vd_dropout: bool = False,
+                 atom_messages: bool = False):
         mp, agg, pred = model.message_passing, model.agg, model.predictor
         # a multicomponent model: ONE block shared by every component (the components' graphs merged into one batch per step), or
         # one block per component (each block's forward into its rows of one H_v, the head once, each block's backward)
@@ -759,7 +789,10 @@ class FusedTrainer:
         self.n_components = len(self.blocks) if multi else 1
         self.rows_dropout = bool(rows_dropout)
         self.vd_dropout = bool(vd_dropout)
-        acts = [fused_block(b, rows_dropout=self.rows_dropout, vd_dropout=self.vd_dropout) for b in self.blocks]
+        self.atom_messages = bool(atom_messages)
+        if multi and any(is_atom_block(b) for b in self.blocks):
+            raise NotImplementedError("FusedTrainer: atom blocks in a multicomponent model")
+        acts = [fused_block(b, rows_dropout=self.rows_dropout, vd_dropout=self.vd_dropout, atom_messages=self.atom_messages) for b in self.blocks]
         if multi and any(b.dropout.p > 0 for b in self.blocks):
             raise NotImplementedError("FusedTrainer: dropout inside the blocks of a multicomponent model")
         if multi and any(b.W_d is not None for b in self.blocks):
@@ -1042,6 +1075,9 @@ class FusedTrainer:
         act, slope = act_slope
         batch = bmg.batch
         nV, nE = int(bmg.V.shape[0]), int(bmg.E.shape[0])
+        atom = self.atom_messages and is_atom_block(mp)
+        if atom:
+            return self._atom_block_args(mp, bmg, n_mols, act_slope, validate, out, gout)
         # ---- K0: a launched plan while the first batches are validated (host read of the verdict), else inside the C call ----
         # The kind of plan: once the first batches are validated (on full plans: their verdict on the graph invariants is read on
         # the host), a batch bound for the tile kernels gets the TILE plan — K0 is then the 11 us tile table instead of the 28 us
@@ -1116,6 +1152,77 @@ class FusedTrainer:
                 raise NotImplementedError(f"FusedTrainer: this batch does not take the tile kernels ({tile_why}) and the lean step kernels "
                                           f"refuse it ({why})" + (f", and so do the row kernels ({rows_why})" if self.rows_dropout else "")
                                           + "; dropout on the other routes runs through the module path (MPNN.loss + autograd)") from None
+        return self._finish_block_args(mp, bmg, plan, st, out, gout, drop)
+
+    def _atom_block_args(self, mp, bmg, n_mols: int, act_slope: tuple, validate: bool, out: Optional[Tensor], gout: Optional[Tensor]) -> "_BlockPart":
+        """:meth:`_block_args` for an atom block (``DMPNN_F_ATOM``).  Two homes: the tile kernels (``p = 0``, no molecule beyond the
+        tile — on the atom variant such a molecule is NaN, so the host must know: ``bmg.oversize`` or ``nn.batch_oversize`` —, at most
+        30 directed edges per molecule, even ``d_v / d_e / d_h``; on the tile plan once the first batches are validated), else the
+        per-step general route on the f16 pipe, with ``p > 0`` at any molecule size.  What neither takes is refused before a seed is
+        drawn or anything is enqueued."""
+        from .nn import _route, _training_plan_kind, batch_oversize
+
+        act, slope = act_slope
+        batch = bmg.batch
+        d_v, d_e, d_h = int(bmg.V.shape[1]), int(bmg.E.shape[1]), int(mp.W_h.weight.shape[0])
+        if int(mp.W_i.weight.shape[1]) != d_v or int(mp.W_h.weight.shape[1]) != d_h + d_e or not 1 <= d_e <= 16:
+            raise NotImplementedError(f"FusedTrainer: the batch's features (d_v {d_v}, d_e {d_e}) are not the atom block's "
+                                      f"(W_i {tuple(mp.W_i.weight.shape)}, W_h {tuple(mp.W_h.weight.shape)}; 1 <= d_e <= 16)")
+        p = float(mp.dropout.p) if self.model.training else 0.0
+        if p > 0:
+            rows_why = None if self.rows_dropout else "rows_dropout=False"
+            rows_why = rows_why or engine.rows_dropout_refusal(d_v, d_e, d_h, int(mp.depth), act, atom=True)
+            if rows_why is None and (type(mp.dropout) is not nn.Dropout or p >= 1.0):
+                rows_why = "nn.Dropout with p < 1"
+            if rows_why is None and (bmg.V.dtype != torch.float32 or bmg.V.stride(0) % 2 or bmg.V.data_ptr() % 8):
+                rows_why = "V rows must be fp32, 8-byte aligned with an even stride"
+            if rows_why is not None:
+                raise NotImplementedError(f"FusedTrainer: dropout inside an atom block lives in the row kernels, which refuse it ({rows_why}); "
+                                          "this model trains through the module path (MPNN.loss + autograd)")
+        no_mega = getattr(mp, "_dmpnn_no_mega", False) or (n_mols > 0 and int(bmg.E.shape[0]) > 30 * n_mols)
+        tile_shapes = p == 0 and not no_mega and d_e >= 2 and d_v % 2 == 0 and d_e % 2 == 0 and d_h % 2 == 0 and int(bmg.E.shape[0]) > 0
+        oversize = getattr(bmg, "oversize", None)
+        if oversize is None and tile_shapes:
+            oversize = batch_oversize(bmg, n_mols)
+        level = 2 if (tile_shapes and oversize is False) else 1
+        kind = _training_plan_kind(mp, bmg, atom=True) if (self.tile_plan and not validate and level == 2) else False
+        if not kind and level == 2 and not validate:
+            # (no tile plan for these shapes / this batch size: the full plan serves the tile kernels only within the single-workgroup plan)
+            level = 2 if engine.small_plan_fits(int(bmg.V.shape[0]), int(bmg.E.shape[0])) else 1
+        plan = engine.GraphPlan.from_bmg(bmg, light=kind, launch=validate)
+        plan.oversize = oversize
+        if validate:
+            level = min(level, _route(mp, plan, n_mols, batch))
+        if not self.multi:
+            note_batch(batch, n_mols)
+        W = lambda lin, n: getattr(getattr(mp, lin), n)
+        drop = None
+        if p > 0:
+            drop = (p, int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
+            self.last_dropout_seed = drop[1]
+        fwd = lambda **kw: engine.forward(plan, bmg.V, bmg.E, W("W_i", "weight"), W("W_h", "weight"), W("W_o", "weight"), W("W_o", "bias"),
+                                          W("W_i", "bias"), W("W_h", "bias"), depth=mp.depth, act=act, slope=slope, keep=True,
+                                          launch=False, dropout=drop, out=out, atom=True, **kw)
+        st = None
+        if level == 2:
+            try:
+                out, st = fwd(max_level=2)
+            except engine.RouteUnavailable:
+                if plan.tiles_only:
+                    raise RuntimeError("FusedTrainer: a tile plan without the atom tile kernels") from None
+        if st is None:
+            try:
+                out, st = fwd(route="general", mfma="split16")
+            except engine.RouteUnavailable as e:
+                raise NotImplementedError(f"FusedTrainer: neither the tile kernels nor the per-step general route take this atom block ({e}); "
+                                          "it trains through the module path (MPNN.loss + autograd)") from None
+        return self._finish_block_args(mp, bmg, plan, st, out, gout, drop)
+
+    def _finish_block_args(self, mp, bmg, plan, st, out: Tensor, gout: Optional[Tensor], drop) -> "_BlockPart":
+        """The backward's argument block for a prepared forward ``st`` (gradients into the flat buffer's views) and the block's part."""
+        W = lambda lin, n: getattr(getattr(mp, lin), n)
+        batch = bmg.batch
+        nV = int(bmg.V.shape[0])
         d_out = int(out.shape[1])
         if gout is None:
             gout = torch.empty(nV, d_out, dtype=torch.float32, device=self.dev)

@@ -112,8 +112,16 @@ enum dmpnn_flags {
                                      (sum_{e': dst e' = src e} E[e']), is kept as depth - 1 identical slots of [n_edges][16] fp32 rows
                                      in `msplit` (>= (depth - 1) * n_edges * 64 bytes; row order = the kept M^(t) rows') so that
                                      dmpnn_backward's W_h product reads [M^(t) || ME] as one operand; H0 is kept as W_i V[src] (+ b_i)
-                                     alone.  A molecule beyond the tile comes back NaN (forward and gradients).  Any other
-                                     combination: DMPNN_EINVAL (chain the row kernels)                                               */
+                                     alone.  A molecule beyond the tile comes back NaN (forward and gradients).
+                                     WITHOUT DMPNN_F_FUSED (the per-step general route; fp32 or DMPNN_F_SPLIT16, inference or
+                                     DMPNN_F_KEEP, any molecule size, any d_h, depth >= 1; directed, no W_d, 1 <= d_e <= 16): ME is
+                                     formed once per call by the atom mode of the message kernel into ONE slot of [n_edges][16]
+                                     zero-padded fp32 rows in `msplit` (>= n_edges * 64 bytes, 16-byte aligned, caller's edge order:
+                                     kept with DMPNN_F_KEEP, scratch otherwise), every step's message is the atom mode of the same
+                                     kernel, and the update is ONE contraction W_h [M^(t) || ME]; dropout_p as for the bond block
+                                     on that route (DMPNN_F_SPLIT16 | DMPNN_F_KEEP, additionally even d_e); dmpnn_backward reads
+                                     the same block (gW_h [d_h, d_h + d_e], all zero at depth 1).  Any other combination — the
+                                     per-step fused routes, the lean route, W_d, undirected, d_e > 16: DMPNN_EINVAL                  */
     DMPNN_F_TILE_PLAN = 1u << 11, /* with DMPNN_F_FUSED | DMPNN_F_MEGA | DMPNN_F_SPLIT16 | DMPNN_F_KEEP: `plan` is a TILE plan
                                      (dmpnn_prepare_tiles: K0 is the 11 us tile table instead of the 28 us CSR plan at 512 molecules)
                                      — the kept tensors H0 / Hs / Ms are in the CALLER's edge order and dmpnn_backward runs on
@@ -239,7 +247,9 @@ int dmpnn_plan_layout(int64_t n_atoms, int64_t n_edges, int64_t offsets_out[DMPN
 
 /* K2  mixins.py:11-18 (+ base.py:200 tau-on-load, + base.py:202-203 undirected):
  *     Hin' = tau_in(Hin) [averaged with its reverse if undirected];
- *     M[e] = sum_{e': dst(e') = src(e)} Hin'[e'] - Hin'[rev(e)]                                  */
+ *     M[e] = sum_{e': dst(e') = src(e)} Hin'[e'] - Hin'[rev(e)]
+ * flags: DMPNN_F_UNDIRECTED, or DMPNN_F_ATOM — the atom message (mixins.py:21-30), the same sum without the reverse row:
+ *     M[e] = sum_{e': dst(e') = src(e)} Hin'[e']      (same kernel, same summation order; both flags together: DMPNN_EINVAL)     */
 int dmpnn_message_fwd(const void* plan, int64_t n_atoms, int64_t n_edges, int64_t d_h,
                       const float* Hin, int64_t ld_in, float* M, int64_t ld_m,
                       int act_on_load, float act_slope, const float* act_slope_ptr,
@@ -522,12 +532,15 @@ int dmpnn_backward(const dmpnn_bwd_args* a, void* stream);
 
 /* Row-level backward (used when the activation / dropout modules run in torch between kernels).
  *   message_bwd    gH[e'] = sum_{e: src(e)=dst(e')} gM[e] - gM[rev(e')]   (transpose of K2, directed)
+ *   atom_message_bwd   gH[e'] = sum_{e: src(e)=dst(e')} gM[e]             (transpose of K2 with DMPNN_F_ATOM; NaN on an asymmetric plan)
  *   aggregate_bwd  gH[e]  = gMv[dst(e)]                                   (transpose of K4)
  *   linear_wgrad   gW = gZ^T . [A1[gather] || A2],  gb = colsum(gZ)       (g describes the FORWARD
  *                  operands A1/A2/gather/M/N/K1/K2; W, C, act fields are ignored)
  * The data gradient of a contraction is dmpnn_linear_fwd on the transposed weight.               */
 int dmpnn_message_bwd(const void* plan, int64_t n_atoms, int64_t n_edges, int64_t d_h,
                       const float* gM, int64_t ld_gm, float* gH, int64_t ld_gh, void* stream);
+int dmpnn_atom_message_bwd(const void* plan, int64_t n_atoms, int64_t n_edges, int64_t d_h,
+                           const float* gM, int64_t ld_gm, float* gH, int64_t ld_gh, void* stream);
 int dmpnn_aggregate_bwd(const void* plan, int64_t n_atoms, int64_t n_edges, int64_t d_h,
                         const float* gMv, int64_t ld_gmv, float* gH, int64_t ld_gh, void* stream);
 size_t dmpnn_linear_wgrad_ws_bytes(int64_t M, int64_t N, int64_t K, int has_bias);
