@@ -50,6 +50,7 @@ F_LOADER_TILES = 64
 F_STORE16 = 128
 F_ATOM = 1024
 F_TILE_PLAN = 2048
+F_UNDIRECTED_MASK = 4096   # (opt-in: dropout_p > 0 with F_UNDIRECTED on the per-step general route, F_SPLIT16 | F_KEEP)
 F_H0_RESIDUAL = 256
 F_ROW_FINALIZE = 512
 ROUTES = ("general", "general16", "fused", "fused16", "mega", "mega16")  # enum dmpnn_route

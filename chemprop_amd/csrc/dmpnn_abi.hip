@@ -480,7 +480,8 @@ static dmpnn_gemm_args general_finalize_gemm(const dmpnn_fwd_args& a) {
 static int rows_dropout_check(const dmpnn_fwd_args& a) {
     const char* who = "forward: dropout inside the row kernels (DMPNN_F_SPLIT16 | DMPNN_F_KEEP on the per-step general route)";
     DMPNN_CHECK_ARG(!(a.flags & (DMPNN_F_MEGA | DMPNN_F_TILE_PLAN)), "%s does not go with DMPNN_F_MEGA / DMPNN_F_TILE_PLAN", who);
-    DMPNN_CHECK_ARG(!(a.flags & DMPNN_F_UNDIRECTED), "%s: directed messages only (no DMPNN_F_UNDIRECTED)", who);
+    // (undirected: only on request — the backward then regenerates the mask behind the reverse-edge average, DMPNN_F_UNDIRECTED_MASK)
+    DMPNN_CHECK_ARG(!(a.flags & DMPNN_F_UNDIRECTED) || (a.flags & DMPNN_F_UNDIRECTED_MASK), "%s: directed messages only (no DMPNN_F_UNDIRECTED)", who);
     DMPNN_CHECK_ARG(!a.W_d, "%s: no W_d (the reference's second dropout behind W_d has no mask site)", who);
     DMPNN_CHECK_ARG(a.act != DMPNN_ACT_PRELU, "%s: activation none / relu / leakyrelu / tanh / elu (not PReLU)", who);
     DMPNN_CHECK_ARG(a.d_h <= 1024, "%s: d_h <= 1024 (the hash key is row * 1024 + col; got %lld)", who, (long long)a.d_h);
@@ -518,6 +519,10 @@ int dmpnn_forward(const dmpnn_fwd_args* a, void* stream) {
     const bool fused = a->flags & DMPNN_F_FUSED;
     DMPNN_CHECK_ARG(!(a->flags & DMPNN_F_STORE16) || (fused && (a->flags & DMPNN_F_SPLIT16) && !(a->flags & (DMPNN_F_KEEP | DMPNN_F_ATOM))),
                     "forward: DMPNN_F_STORE16 only goes with the fused routes on the f16 pipe (DMPNN_F_FUSED | DMPNN_F_SPLIT16 [| DMPNN_F_MEGA]), inference, bond messages");
+    DMPNN_CHECK_ARG(!(a->flags & DMPNN_F_UNDIRECTED_MASK) ||
+                    ((a->flags & DMPNN_F_UNDIRECTED) && !(a->flags & (DMPNN_F_FUSED | DMPNN_F_MEGA | DMPNN_F_TILE_PLAN | DMPNN_F_ATOM))),
+                    "forward: DMPNN_F_UNDIRECTED_MASK only goes with DMPNN_F_UNDIRECTED on the per-step general route, bond messages "
+                    "(no DMPNN_F_FUSED / DMPNN_F_MEGA / DMPNN_F_TILE_PLAN / DMPNN_F_ATOM)");
     const bool lean16 = fused && (a->flags & DMPNN_F_SPLIT16) && (a->flags & DMPNN_F_KEEP) && !(a->flags & DMPNN_F_MEGA) && a->keep_bits;
     if (a->depth > 1 && nE > 0 && !(a->flags & DMPNN_F_MEGA) && !lean16) {
         DMPNN_CHECK_ARG(a->Ms && a->n_mslots >= 1, "forward: missing Ms workspace");

@@ -238,7 +238,7 @@ int launch_edge_bwd(EdgeBwdArgs a, hipStream_t s, const char* name) {
     if (a.acc) vec = vec && (a.ldacc % 4 == 0) && aligned16(a.acc);
     const dim3 grid((unsigned)blocks), block(256);
     if (a.drop_scale != 0.f) {   // (the mask is regenerated for every activation: the generic builds)
-        if (MODE == EB_AVG || !a.Y || a.y_preact) { set_error("backward: the dropout mask goes with a kept post-dropout H^(t), directed"); return DMPNN_EINVAL; }
+        if (!a.Y || a.y_preact) { set_error("backward: the dropout mask goes with a kept post-dropout H^(t)"); return DMPNN_EINVAL; }
         if (vec) hipLaunchKernelGGL((k_edge_bwd<4, MODE, -1, true>), grid, block, 0, s, a);
         else hipLaunchKernelGGL((k_edge_bwd<1, MODE, -1, true>), grid, block, 0, s, a);
         DMPNN_CHECK_LAUNCH(name);
@@ -922,6 +922,10 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
     DMPNN_CHECK_ARG(f.plan && h > 0 && dv > 0 && T >= 1, "backward: bad forward description");
     DMPNN_CHECK_ARG(f.act >= DMPNN_ACT_RELU && f.act <= DMPNN_ACT_ELU && f.act != DMPNN_ACT_PRELU,
                     "backward: activation %d has no fused backward (use the row kernels)", f.act);
+    DMPNN_CHECK_ARG(!(f.flags & DMPNN_F_UNDIRECTED_MASK) ||
+                    ((f.flags & DMPNN_F_UNDIRECTED) && !(f.flags & (DMPNN_F_FUSED | DMPNN_F_MEGA | DMPNN_F_TILE_PLAN | DMPNN_F_ATOM))),
+                    "backward: DMPNN_F_UNDIRECTED_MASK only goes with DMPNN_F_UNDIRECTED on the per-step general route, bond messages "
+                    "(no DMPNN_F_FUSED / DMPNN_F_MEGA / DMPNN_F_TILE_PLAN / DMPNN_F_ATOM)");
     DMPNN_CHECK_ARG(nV == 0 || b->gout, "backward: null gout");
     const BwdLayout L = bwd_layout(f);
     DMPNN_CHECK_ARG(L.lean || T == 1 || nE == 0 || (f.n_hslots >= T - 1 && f.n_mslots >= T - 1),
@@ -1099,11 +1103,11 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
     // ... or, for the per-step general route on the f16 pipe (the mask in the row kernels' epilogue), in k_act_bwd_hash / the DROP
     // builds of k_edge_bwd below, which regenerate the mask from the hash
     const bool rows_drop = f.dropout_p > 0.f && f.dropout_p < 1.f && !fused && (f.flags & DMPNN_F_SPLIT16) && (f.flags & DMPNN_F_KEEP) &&
-                           !(f.flags & (DMPNN_F_MEGA | DMPNN_F_UNDIRECTED)) && !has_vd && h <= 1024;
+                           !(f.flags & DMPNN_F_MEGA) && (!(f.flags & DMPNN_F_UNDIRECTED) || (f.flags & DMPNN_F_UNDIRECTED_MASK)) && !has_vd && h <= 1024;
     DMPNN_CHECK_ARG(!(f.dropout_p > 0.f) || tile_bwd || rows_drop,
                     "backward: the forward ran with dropout inside the kernels; only the backward tile kernel carries its scale — it needs a "
                     "gradient of W_i or W_h to be wanted and 16-byte aligned gout / out (leading dimensions multiples of 4) — or the per-step "
-                    "general route on the f16 pipe (DMPNN_F_SPLIT16 | DMPNN_F_KEEP, directed, no W_d, d_h <= 1024)");
+                    "general route on the f16 pipe (DMPNN_F_SPLIT16 | DMPNN_F_KEEP, directed — or DMPNN_F_UNDIRECTED | DMPNN_F_UNDIRECTED_MASK —, no W_d, d_h <= 1024)");
     const unsigned d_thr = rows_drop ? drop_threshold(f.dropout_p) : 0u, d_lo = (unsigned)(f.dropout_seed & 0xFFFFFFFFull), d_hi = (unsigned)(f.dropout_seed >> 32);
     const float d_scale = rows_drop ? 1.f / (1.f - f.dropout_p) : 0.f, d_unscale = 1.f - f.dropout_p;
     auto set_drop = [&](EdgeBwdArgs& x, int site) {   // Y of this launch is the post-dropout H of mask site `site`
@@ -1447,6 +1451,7 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
                 v.Y = Yprev; v.ldy = ldh; v.y_preact = first ? 1 : 0;
                 v.gZ = first ? nullptr : other; v.ldgz = ldh;
                 v.acc = gH0; v.ldacc = ldh; v.acc_init = 0;
+                if (!first) set_drop(v, t - 2);   // (the mask of H^(t-1) sits behind the average: keyed on row e, as in the forward)
                 DMPNN_TRY(launch_edge_bwd<EB_AVG>(v, s, "k_edge_bwd<avg>"));
                 float* tmp = gZ; gZ = other; other = tmp;
             }

@@ -244,11 +244,16 @@ int launch_segment(const SegArgs& a, hipStream_t s, const char* name) {
     if (blocks > cap) blocks = cap;
     const bool vec = (a.h % 4 == 0) && (a.ld_in % 4 == 0) && (a.ld_out % 4 == 0) && aligned16(a.Hin) && aligned16(a.out);
     const dim3 grid((unsigned)blocks), block(kWavesPerBlock * 64);
-    // hot instantiations: 16-byte lanes, directed, tau in {identity, ReLU}; everything else -> generic build
+    // hot instantiations: 16-byte lanes, tau in {identity, ReLU}, directed — or the undirected message (MODE 0: the aggregate and the
+    // atom message are never undirected); everything else -> generic build
     if (vec && !a.undirected && a.act == DMPNN_ACT_NONE)
         hipLaunchKernelGGL((k_segment<4, MODE, 0, DMPNN_ACT_NONE>), grid, block, 0, s, a);
     else if (vec && !a.undirected && a.act == DMPNN_ACT_RELU)
         hipLaunchKernelGGL((k_segment<4, MODE, 0, DMPNN_ACT_RELU>), grid, block, 0, s, a);
+    else if (MODE == 0 && vec && a.undirected && a.act == DMPNN_ACT_NONE)
+        hipLaunchKernelGGL((k_segment<4, 0, 1, DMPNN_ACT_NONE>), grid, block, 0, s, a);
+    else if (MODE == 0 && vec && a.undirected && a.act == DMPNN_ACT_RELU)
+        hipLaunchKernelGGL((k_segment<4, 0, 1, DMPNN_ACT_RELU>), grid, block, 0, s, a);
     else if (vec)
         hipLaunchKernelGGL((k_segment<4, MODE, -1, -1>), grid, block, 0, s, a);
     else

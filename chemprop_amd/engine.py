@@ -334,16 +334,18 @@ def lean_dropout_refusal(d_v: int, d_e: int, d_h: int, depth: int, act: str, has
 
 
 def rows_dropout_refusal(d_v: int, d_e: int, d_h: int, depth: int, act: str, has_vd: bool = False, undirected: bool = False,
-                         atom: bool = False) -> Optional[str]:
+                         atom: bool = False, *, undirected_dropout: bool = False) -> Optional[str]:
     """Why the row kernels of the per-step general route on the f16 pipe (``route="general"``, ``mfma="split16"``, ``keep``) cannot
     carry block dropout for these shapes — the condition of ``dmpnn_forward`` (csrc/dmpnn_abi.hip: ``rows_dropout_check``) that
     fails, in words — or ``None`` when they can.  (The workspace this package allocates meets the alignment conditions.)
-    ``atom``: an atom block (``DMPNN_F_ATOM``) — its update contraction reads ``[M || ME]``, so ``d_e`` must be even as well."""
+    ``atom``: an atom block (``DMPNN_F_ATOM``) — its update contraction reads ``[M || ME]``, so ``d_e`` must be even as well.
+    ``undirected_dropout=True``: the caller asks for the mask behind the reverse-edge average (``DMPNN_F_UNDIRECTED_MASK``) — then
+    ``undirected`` is no reason (a bond block only)."""
     if act not in ("none", "relu", "leakyrelu", "tanh", "elu"):
         return f"activation {act!r} (none / relu / leakyrelu / tanh / elu: PReLU's slope trains, a custom module runs between the kernels)"
     if has_vd:
         return "a W_d layer (d_vd > 0)"
-    if undirected:
+    if undirected and not (undirected_dropout and not atom):
         return "undirected messages"
     if depth < 1:
         return f"depth {depth} < 1"
@@ -542,7 +544,7 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
             keep: bool = False, fused: Optional[bool] = None, route: Optional[str] = None,
             max_level: int = 2, mfma: Optional[str] = None, wcache: Optional[dict] = None,
             launch: bool = True, form: int = 0, dropout: Optional[tuple] = None, atom: bool = False,
-            keep_bits: bool = True, out: Optional[Tensor] = None) -> tuple[Tensor, ForwardState]:
+            keep_bits: bool = True, out: Optional[Tensor] = None, undirected_dropout: bool = False) -> tuple[Tensor, ForwardState]:
     """One ``dmpnn_forward`` call.  Routes (``route`` = ``"mega" | "fused" | "general"``, default: the best
     the shapes allow):
 
@@ -567,7 +569,9 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
     lean training forward of the per-step fused route under its own shapes (molecules beyond the tile; ``st.route`` stays
     ``"fused16/lean"``, the same mask for the same seed), or, on demand as well (``route="general"``, ``mfma="split16"``,
     ``keep``), the row kernels of the per-step general route on the f16 pipe (any molecule size, ``d_h <= 1024``, depth >= 1, relu /
-    leakyrelu / tanh / elu, no ``W_d``, directed: :func:`rows_dropout_refusal`; ``st.route`` stays ``"general16"``); raises
+    leakyrelu / tanh / elu, no ``W_d``, directed — or ``undirected`` with ``undirected_dropout=True``, which sets
+    ``DMPNN_F_UNDIRECTED_MASK`` (``backward`` reads it from the forward's flags) —: :func:`rows_dropout_refusal`; ``st.route`` stays
+    ``"general16"``); raises
     :class:`RouteUnavailable` when this batch takes another route (the caller then runs its own ``nn.Dropout`` between the row
     kernels).
     ``launch=False`` prepares the argument block and the workspace without enqueuing anything (``trainer.FusedTrainer``).
@@ -687,9 +691,12 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
         # (a DEMAND: the default rule may pick the lean form itself — it saw p = 0 — and must then refuse, as before)
         lean_home = bool(route == "fused16" and use_fused16 and keep and keep_bits and not d_vd and act in ("relu", "leakyrelu"))
         # (a DEMAND as well: route="general" with mfma="split16" — never the default rule's own general16, which saw p = 0)
-        rows_why = rows_dropout_refusal(d_v, d_e, d_h, depth, act, bool(d_vd), bool(undirected), bool(atom))
+        rows_why = rows_dropout_refusal(d_v, d_e, d_h, depth, act, bool(d_vd), bool(undirected), bool(atom),
+                                        undirected_dropout=bool(undirected_dropout))
         rows_home = bool(route == "general" and mfma == "split16" and want16 and not use_fused and keep and rows_why is None
                          and float(dropout[0]) < 1.0 and V.stride(0) % 2 == 0 and V.data_ptr() % 8 == 0)
+        if rows_home and undirected:
+            a.flags |= _lib.F_UNDIRECTED_MASK
         if tile_home or lean_home or rows_home:
             a.dropout_p, a.dropout_seed = float(dropout[0]), int(dropout[1]) & 0xFFFFFFFFFFFFFFFF
         if not tile_home and not rows_home and not (lean_home and _lean16_bits(lib, a) > 0):

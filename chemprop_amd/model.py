@@ -338,7 +338,7 @@ def is_atom_block(mp) -> bool:
     return mp.W_h.in_features > d_h and mp.W_o.in_features > d_h and mp.W_i.in_features == mp.W_o.in_features - d_h
 
 
-def fused_block(mp, rows_dropout: bool = False, vd_dropout: bool = False, atom_messages: bool = False) -> tuple:
+def fused_block(mp, rows_dropout: bool = False, vd_dropout: bool = False, atom_messages: bool = False, undirected: bool = False) -> tuple:
     """``(activation, slope)`` of a block the one-call step takes: a bond block (this package's mirror, or the subclass of the
     reference's own class, ``integration.HipBondMessagePassing``) with a built-in activation (not PReLU), directed, dropout 0
     or ``nn.Dropout`` with a ReLU-class activation — with ``rows_dropout=True`` (the mask in the row kernels of the per-step general
@@ -351,7 +351,11 @@ def fused_block(mp, rows_dropout: bool = False, vd_dropout: bool = False, atom_m
     without ``W_d`` (``nn.Dropout``; a ReLU-class activation, or ``rows_dropout=True`` and a built-in smooth one).
     ``atom_messages=True`` also takes an atom block (``W_i [d_h, d_v]``, ``W_h [d_h, d_h + d_e]``: :func:`is_atom_block`) that is
     directed, has a built-in activation other than PReLU, no ``W_d``, ``1 <= d_e <= 16`` and dropout 0 — or ``nn.Dropout`` with
-    ``rows_dropout=True`` (its only home is the row kernels: the atom tile kernels carry no mask).  The default refuses it."""
+    ``rows_dropout=True`` (its only home is the row kernels: the atom tile kernels carry no mask).  The default refuses it.
+    ``undirected=True`` also takes a bond block with ``mp.undirected`` (base.py:202-203), under exactly the conditions a directed one
+    meets — except that with ``p > 0`` its only dropout home is the row kernels (``DMPNN_F_UNDIRECTED_MASK``): ``nn.Dropout`` and
+    ``rows_dropout=True`` (and ``vd_dropout=True`` beside ``W_d``, as for a directed block).  An undirected ATOM block stays refused.
+    The default refuses an undirected block."""
     # (W_h is [d_h, d_h] in a bond block: the atom variant's takes d_e + d_h columns, the mol-atom-bond ones have a second read-out)
     bond = (all(isinstance(getattr(mp, n, None), nn.Linear) for n in ("W_i", "W_h", "W_o"))
             and mp.W_h.in_features == mp.W_h.out_features and mp.W_o.in_features > mp.W_h.out_features)
@@ -360,9 +364,10 @@ def fused_block(mp, rows_dropout: bool = False, vd_dropout: bool = False, atom_m
         raise NotImplementedError("FusedTrainer: a BondMessagePassing block (W_i / W_h [d_h, d_h] / W_o)"
                                   + (" — atom_messages=True also takes an AtomMessagePassing block" if is_atom_block(mp) else ""))
     act, slope, slope_t = classify_activation(mp.tau)
-    if act in ("custom", "prelu") or mp.undirected:
+    if act in ("custom", "prelu") or (mp.undirected and not (undirected and bond)):
         raise NotImplementedError("FusedTrainer: built-in activation (not PReLU), directed — other blocks train "
-                                  "through the module path (MPNN.loss + autograd)")
+                                  "through the module path (MPNN.loss + autograd)"
+                                  + (" (undirected=True also takes an undirected bond block)" if mp.undirected and bond and not undirected else ""))
     if atom:
         d_e = mp.W_h.in_features - mp.W_h.out_features
         if mp.W_d is not None:
@@ -385,6 +390,9 @@ def fused_block(mp, rows_dropout: bool = False, vd_dropout: bool = False, atom_m
         if mp.W_d.in_features > _lib.VD_MAX_WIDTH:
             raise NotImplementedError(f"FusedTrainer: d_h + d_vd = {mp.W_d.in_features} is beyond the {_lib.VD_MAX_WIDTH} columns the "
                                       "atom-descriptor stage takes")
+    if mp.undirected and mp.dropout.p > 0 and not (type(mp.dropout) is nn.Dropout and rows_dropout):
+        raise NotImplementedError("FusedTrainer: dropout inside an undirected block needs nn.Dropout and rows_dropout=True (the mask lives "
+                                  "in the row kernels; the tile kernels and the lean step kernels are directed)")
     if mp.dropout.p > 0 and not (type(mp.dropout) is nn.Dropout and (rows_dropout or act in ("relu", "leakyrelu"))):
         # (active dropout lives inside the tile kernels and the lean step kernels, for ReLU-class activations, and — rows_dropout — in the
         #  row kernels of the per-step general route for every built-in one: dmpnn_fwd_args.dropout_p; a dropout module that is not
@@ -775,11 +783,16 @@ class FusedTrainer:
     bound for the tile kernels (no molecule beyond the tile, at most 30 directed edges per molecule, even ``d_v / d_e / d_h``) runs
     on them with ``DMPNN_F_ATOM``; everything else — molecules beyond the tile, wide or odd shapes, ``p > 0`` at any size — on the
     per-step general route on the f16 pipe (``route == "general16"``).  The default refuses such a block.
+
+    ``undirected=True`` also takes a bond block with ``undirected`` messages (:func:`fused_block`): with ``p = 0`` on the route the
+    engine's rule gives an undirected forward (``general`` / ``general16``, a full plan), with ``p > 0`` — ``rows_dropout=True`` as
+    well — on the row kernels of the per-step general route on the f16 pipe with ``DMPNN_F_UNDIRECTED_MASK``; what those refuse is
+    refused before a seed is drawn.  Not in a multicomponent model.  The default refuses such a block.
     """
 
     def __init__(self, model: MPNN, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, group=None,
                  tile_plan: bool = True, ffn_dropout: bool = False, rows_dropout: bool = False, vd_dropout: bool = False,
-                 atom_messages: bool = False):
+                 atom_messages: bool = False, undirected: bool = False):
         mp, agg, pred = model.message_passing, model.agg, model.predictor
         # a multicomponent model: ONE block shared by every component (the components' graphs merged into one batch per step), or
         # one block per component (each block's forward into its rows of one H_v, the head once, each block's backward)
@@ -790,9 +803,13 @@ class FusedTrainer:
         self.rows_dropout = bool(rows_dropout)
         self.vd_dropout = bool(vd_dropout)
         self.atom_messages = bool(atom_messages)
+        self.undirected = bool(undirected)
+        if multi and any(getattr(b, "undirected", False) for b in self.blocks):
+            raise NotImplementedError("FusedTrainer: undirected blocks in a multicomponent model")
         if multi and any(is_atom_block(b) for b in self.blocks):
             raise NotImplementedError("FusedTrainer: atom blocks in a multicomponent model")
-        acts = [fused_block(b, rows_dropout=self.rows_dropout, vd_dropout=self.vd_dropout, atom_messages=self.atom_messages) for b in self.blocks]
+        acts = [fused_block(b, rows_dropout=self.rows_dropout, vd_dropout=self.vd_dropout, atom_messages=self.atom_messages,
+                            undirected=self.undirected) for b in self.blocks]
         if multi and any(b.dropout.p > 0 for b in self.blocks):
             raise NotImplementedError("FusedTrainer: dropout inside the blocks of a multicomponent model")
         if multi and any(b.W_d is not None for b in self.blocks):
@@ -1085,7 +1102,8 @@ class FusedTrainer:
         # arrays (DMPNN_F_TILE_PLAN; every tile checks itself, a molecule beyond the tile takes the kernels' generic path).
         no_mega = getattr(mp, "_dmpnn_no_mega", False) or (n_mols > 0 and nE > 30 * n_mols)
         oversize = getattr(bmg, "oversize", None)
-        if oversize is None and mp.dropout.p > 0 and not no_mega:
+        und = bool(mp.undirected)   # (taken at construction with undirected=True only: the general route, a full plan)
+        if oversize is None and mp.dropout.p > 0 and not no_mega and not und:
             # (the tile kernels' generic path for a molecule beyond the tile has no dropout and answers NaN — which this step would feed
             #  to Adam; such a batch goes to the lean step kernels instead.  A foreign batch is counted on the device: nn.batch_oversize)
             from .nn import batch_oversize
@@ -1108,6 +1126,18 @@ class FusedTrainer:
 
         # ---- argument blocks of the block's forward / backward (workspace allocated, nothing enqueued) ----
         W = lambda lin, n: getattr(getattr(mp, lin), n)
+        if und and mp.dropout.p > 0 and self.model.training:
+            # the only dropout home of an undirected block is the row kernels: what they refuse is refused before a seed is drawn
+            d_v, d_e, d_h = int(bmg.V.shape[1]), int(bmg.E.shape[1]), int(mp.W_h.weight.shape[0])
+            rows_why = None if self.rows_dropout else "rows_dropout=False"
+            rows_why = rows_why or engine.rows_dropout_refusal(d_v, d_e, d_h, int(mp.depth), act, undirected=True, undirected_dropout=True)
+            if rows_why is None and (type(mp.dropout) is not nn.Dropout or float(mp.dropout.p) >= 1.0):
+                rows_why = "nn.Dropout with p < 1"
+            if rows_why is None and (bmg.V.dtype != torch.float32 or bmg.V.stride(0) % 2 or bmg.V.data_ptr() % 8):
+                rows_why = "V rows must be fp32, 8-byte aligned with an even stride"
+            if rows_why is not None:
+                raise NotImplementedError(f"FusedTrainer: dropout inside an undirected block lives in the row kernels, which refuse it ({rows_why}); "
+                                          "this model trains through the module path (MPNN.loss + autograd)")
         drop = None
         if mp.dropout.p > 0 and self.model.training:
             # one seed per step from torch's CPU generator (torch.manual_seed fixes the run), like the module path's fused dropout
@@ -1115,7 +1145,14 @@ class FusedTrainer:
             self.last_dropout_seed = drop[1]
         fwd = lambda **kw: engine.forward(plan, bmg.V, bmg.E, W("W_i", "weight"), W("W_h", "weight"), W("W_o", "weight"), W("W_o", "bias"),
                                           W("W_i", "bias"), W("W_h", "bias"), depth=mp.depth, act=act, slope=slope, keep=True,
-                                          launch=False, dropout=drop, out=out, **kw)
+                                          launch=False, dropout=drop, out=out, undirected=und, **kw)
+        if und and drop is not None:
+            try:
+                out, st = fwd(route="general", mfma="split16", undirected_dropout=True)
+            except engine.RouteUnavailable as e:
+                raise NotImplementedError(f"FusedTrainer: the row kernels refuse this undirected block with dropout ({e}); it trains through "
+                                          "the module path (MPNN.loss + autograd)") from None
+            return self._finish_block_args(mp, bmg, plan, st, out, gout, drop)
         # block dropout lives in the tile kernels or — molecules beyond the tile, at any edge count — in the lean step kernels, which
         # the route rule never picks for p > 0: the step asks for them (route="fused16") on the full plan; with rows_dropout the row
         # kernels of the per-step general route (route="general" on the f16 pipe) take what those two refuse

@@ -55,7 +55,8 @@ extern "C" {
  * fp32-class; it was DMPNN_EINVAL there).  Grown at its end, same version: dmpnn_head_args.X_d / ld_xd (molecule descriptors behind
  * the batch norm; the two fields are zero in a caller built before them, which is the NULL they default to); dmpnn_head_args.n_components
  * and dmpnn_step_args.n_extra / extra (multicomponent models: zero in an older caller, which is one block); dmpnn_head_args.ffn_dropout_p /
- * ffn_dropout_seed (the predictor's dropout as a hash mask: zero in an older caller, which is no dropout). */
+ * ffn_dropout_seed (the predictor's dropout as a hash mask: zero in an older caller, which is no dropout); DMPNN_F_UNDIRECTED_MASK
+ * (a flag bit no older caller sets: dropout_p > 0 with DMPNN_F_UNDIRECTED on the per-step general route, DMPNN_EINVAL without it). */
 #define DMPNN_ABI_VERSION 15
 
 enum dmpnn_status {
@@ -78,6 +79,14 @@ enum dmpnn_activation {
 
 enum dmpnn_flags {
     DMPNN_F_UNDIRECTED = 1u << 0, /* base.py:202-203: H <- (H + H[rev]) / 2 before every message() */
+    DMPNN_F_UNDIRECTED_MASK = 1u << 12, /* with DMPNN_F_UNDIRECTED | DMPNN_F_SPLIT16 | DMPNN_F_KEEP, without DMPNN_F_FUSED (a training
+                                     forward of the per-step general route on the f16 pipe): dropout_p in (0, 1) is taken for
+                                     undirected messages too — the row kernels' mask does not care about direction, and
+                                     dmpnn_backward, which reads the flag from the forward's block, regenerates it behind the
+                                     reverse-edge average (keyed on the row of H^(t), as in the forward).  Opt-in: without it
+                                     dropout_p > 0 with DMPNN_F_UNDIRECTED stays DMPNN_EINVAL.  With dropout_p == 0 it is accepted
+                                     and ignored.  Without DMPNN_F_UNDIRECTED, or with DMPNN_F_FUSED / DMPNN_F_MEGA /
+                                     DMPNN_F_TILE_PLAN / DMPNN_F_ATOM: DMPNN_EINVAL before any device work                       */
     DMPNN_F_FUSED = 1u << 1,      /* dmpnn_forward / dmpnn_backward: edge tensors live in CSR-row
                                      order and the segment sums are formed in the contraction
                                      epilogues (molecular graphs: symmetric, in-degree <= 24;
@@ -395,7 +404,8 @@ typedef struct dmpnn_fwd_args {
      * (dmpnn_forward_route / dmpnn_train_route) never choose this form for dropout_p > 0: the caller asks for it.
      * The third home: the training forward of the per-step GENERAL route on the f16 pipe (DMPNN_F_SPLIT16 | DMPNN_F_KEEP without
      * DMPNN_F_FUSED) — any molecule size, d_h <= 1024 (the hash key is row * 1024 + col), depth >= 1 (depth 1: the finalize site
-     * only), activation none / relu / leakyrelu / tanh / elu, directed, no W_d, and an update and a finalize contraction that
+     * only), activation none / relu / leakyrelu / tanh / elu, directed (or, the fourth admitted case, DMPNN_F_UNDIRECTED with
+     * DMPNN_F_UNDIRECTED_MASK: the same mask sites, behind the reverse-edge average in dmpnn_backward), no W_d, and an update and a finalize contraction that
      * dmpnn_linear16_ok takes (they run on the row kernel k_rows16, whose epilogue applies the mask; the hash row is the output row:
      * the edge tensors of this route are in the caller's edge order).  The kept H^(t) and the output are post-dropout;
      * dmpnn_backward regenerates the mask from the hash for EVERY activation (for tanh / elu / none a zero does not say "dropped")
