@@ -81,11 +81,15 @@ __global__ __launch_bounds__(256) void k_clip_scale(float* __restrict__ g, int64
     }
 }
 
-// torch.nn.utils.clip_grad_value_ (algorithm "value"): clamp every (averaged) gradient element to [-c, c]
+// torch.nn.utils.clip_grad_value_ (algorithm "value"): clamp every (averaged) gradient element to [-c, c].  Compare-and-select, not
+// fminf(fmaxf(v, -c), c): fmaxf(NaN, -c) is -c, which turned a NaN gradient into -c; torch.clamp keeps the NaN, and a diverged step
+// must stay visible here as it does in the norm branch.
+__device__ __forceinline__ float clamp_keep_nan(float v, float c) { return v > c ? c : (v < -c ? -c : v); }
+
 __global__ __launch_bounds__(256) void k_clip_value(float* __restrict__ g, int64_t n4, float c) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         float4 v = reinterpret_cast<float4*>(g)[i];
-        v.x = fminf(fmaxf(v.x, -c), c); v.y = fminf(fmaxf(v.y, -c), c); v.z = fminf(fmaxf(v.z, -c), c); v.w = fminf(fmaxf(v.w, -c), c);
+        v.x = clamp_keep_nan(v.x, c); v.y = clamp_keep_nan(v.y, c); v.z = clamp_keep_nan(v.z, c); v.w = clamp_keep_nan(v.w, c);
         reinterpret_cast<float4*>(g)[i] = v;
     }
 }
