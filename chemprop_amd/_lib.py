@@ -21,7 +21,7 @@ INCLUDE = os.path.join(_ROOT, "include")
 # DMPNN_LIB: an alternative build of the same sources (kernel experiments: scripts/build_variant.py), same ABI
 LIB_PATH = os.environ.get("DMPNN_LIB") or os.path.join(_HERE, "libdmpnn_gfx950.so")
 SOURCES = ["dmpnn_abi.hip", "dmpnn_prepare.hip", "dmpnn_segment.hip", "dmpnn_gemm.hip", "dmpnn_gemm_p1.hip",
-           "dmpnn_gemm_p2.hip", "dmpnn_gemm_p3.hip", "dmpnn_gemm_p4.hip", "dmpnn_gemm_s1.hip", "dmpnn_rows16_drop.hip", "dmpnn_mega.hip", "dmpnn_mega16.hip", "dmpnn_mega16_lp.hip", "dmpnn_mega16_bwd.hip", "dmpnn_rows16.hip", "dmpnn_step16.hip", "dmpnn_bstep16.hip", "dmpnn_backward.hip", "dmpnn_molagg.hip", "dmpnn_collate.hip", "dmpnn_tiles_large.hip", "dmpnn_optim.hip", "dmpnn_wgrad16.hip", "dmpnn_head.hip", "dmpnn_vd.hip"]
+           "dmpnn_gemm_p2.hip", "dmpnn_gemm_p3.hip", "dmpnn_gemm_p4.hip", "dmpnn_gemm_s1.hip", "dmpnn_rows16_drop.hip", "dmpnn_mega.hip", "dmpnn_mega16.hip", "dmpnn_mega16_lp.hip", "dmpnn_mega16_bwd.hip", "dmpnn_rows16.hip", "dmpnn_step16.hip", "dmpnn_bstep16.hip", "dmpnn_backward.hip", "dmpnn_molagg.hip", "dmpnn_collate.hip", "dmpnn_tiles_large.hip", "dmpnn_optim.hip", "dmpnn_wgrad16.hip", "dmpnn_head.hip", "dmpnn_vd.hip", "dmpnn_attn.hip"]
 HEADERS = ["dmpnn_common.hpp", "dmpnn_spill_impl.hpp", "dmpnn_gemm_impl.hpp", "dmpnn_mega_impl.hpp", "dmpnn_mega16_impl.hpp", "dmpnn_mega16_bwd_impl.hpp", "dmpnn_rows16_impl.hpp", "dmpnn_seg16.hpp", "dmpnn_step16_impl.hpp"]
 ABI_VERSION = 15
 PLAN_NOFFSETS = 15
@@ -37,6 +37,7 @@ EXPORTS = [
     "dmpnn_full_plan_keeps_tiles", "dmpnn_head_ws_bytes", "dmpnn_head", "dmpnn_train_step", "dmpnn_forward_tiles", "dmpnn_forward_route", "dmpnn_dropout_keep",
     "dmpnn_clip_grad", "dmpnn_clip_grad_ws_bytes", "dmpnn_train_route", "dmpnn_forward_h0_bytes", "dmpnn_tile_waves", "dmpnn_debug_lds_poison",
     "dmpnn_vd_ws_bytes", "dmpnn_vd_forward", "dmpnn_vd_backward", "dmpnn_linear16_dropout_fwd",
+    "dmpnn_molagg_attn_ws_bytes", "dmpnn_molagg_attn_fwd", "dmpnn_molagg_attn_bwd",
 ]
 
 ACT = {"none": 0, "relu": 1, "leakyrelu": 2, "prelu": 3, "tanh": 4, "elu": 5}
@@ -139,7 +140,26 @@ class HeadArgs(C.Structure):
         ("X_d", C.c_void_p), ("ld_xd", C.c_int64),
         ("n_components", C.c_int32),
         ("ffn_dropout_p", C.c_float), ("ffn_dropout_seed", C.c_uint64),
+        ("att_W", C.c_void_p), ("att_b", C.c_void_p), ("g_att_W", C.c_void_p), ("g_att_b", C.c_void_p),
     ]
+
+
+class MolAggAttnArgs(C.Structure):
+    _fields_ = [
+        ("n_atoms", C.c_int64), ("n_mols", C.c_int64), ("d_h", C.c_int64),
+        ("H", C.c_void_p), ("ldh", C.c_int64),
+        ("batch", C.c_void_p), ("bounds", C.c_void_p),
+        ("W", C.c_void_p), ("b", C.c_void_p),
+        ("out", C.c_void_p), ("ldo", C.c_int64),
+        ("keep_s", C.c_void_p), ("keep_Z", C.c_void_p),
+        ("gout", C.c_void_p), ("ldgo", C.c_int64),
+        ("gH", C.c_void_p), ("ldgh", C.c_int64),
+        ("gW", C.c_void_p), ("gb", C.c_void_p),
+        ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+    ]
+
+
+MOLAGG_ATTENTIVE = 3   # (DMPNN_MOLAGG_ATTENTIVE: dmpnn_head_args.agg_mode)
 
 
 class TrainRouteInfo(C.Structure):
@@ -304,7 +324,8 @@ def load() -> C.CDLL:
                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     size_t_fns = ("dmpnn_plan_bytes", "dmpnn_backward_ws_bytes", "dmpnn_linear_wgrad_ws_bytes", "dmpnn_forward_wsplit_bytes", "dmpnn_forward_spill_bytes",
                   "dmpnn_forward_keep_bits_bytes",
-                  "dmpnn_molagg_ws_bytes", "dmpnn_linear16_wsplit_bytes", "dmpnn_head_ws_bytes", "dmpnn_clip_grad_ws_bytes", "dmpnn_forward_h0_bytes", "dmpnn_vd_ws_bytes")
+                  "dmpnn_molagg_ws_bytes", "dmpnn_linear16_wsplit_bytes", "dmpnn_head_ws_bytes", "dmpnn_clip_grad_ws_bytes", "dmpnn_forward_h0_bytes", "dmpnn_vd_ws_bytes",
+                  "dmpnn_molagg_attn_ws_bytes")
     lib.dmpnn_linear16_wsplit_bytes.argtypes = [C.c_int64, C.c_int64]
     lib.dmpnn_linear16_ok.argtypes = [C.POINTER(GemmArgs)]
     lib.dmpnn_linear16_fwd.argtypes = [C.POINTER(GemmArgs), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
@@ -351,6 +372,9 @@ def load() -> C.CDLL:
     lib.dmpnn_vd_ws_bytes.argtypes = [C.POINTER(VdArgs)]
     lib.dmpnn_vd_forward.argtypes = [C.POINTER(VdArgs), C.c_void_p]
     lib.dmpnn_vd_backward.argtypes = [C.POINTER(VdArgs), C.c_void_p]
+    lib.dmpnn_molagg_attn_ws_bytes.argtypes = [C.POINTER(MolAggAttnArgs)]
+    lib.dmpnn_molagg_attn_fwd.argtypes = [C.POINTER(MolAggAttnArgs), C.c_void_p]
+    lib.dmpnn_molagg_attn_bwd.argtypes = [C.POINTER(MolAggAttnArgs), C.c_void_p]
     lib.dmpnn_split_row_floats.argtypes = [C.c_int64]
     lib.dmpnn_split_row_floats.restype = C.c_int64
     lib.dmpnn_debug_timestamps.argtypes = [C.c_void_p]

@@ -4,7 +4,8 @@
 ``MeanAggregation`` / ``SumAggregation`` / ``NormAggregation`` (``agg.py:66-113``) are ONE segment
 reduction over the sorted ``batch`` vector (``dmpnn_molagg_*``: no ``[V, h]`` int64 index, rows added in
 increasing atom order = the reference's sequential scatter order, so results are bit-identical);
-``AttentiveAggregation`` (``agg.py:116-133``) is the same reduction twice around its small linear layer.
+``AttentiveAggregation`` (``agg.py:116-133``) is one autograd node on its own two kernels (``dmpnn_molagg_attn_*``;
+``DMPNN_ATTN=chain``: the reduction twice around its small linear layer, as before them).
 Same constructor arguments, ``hparams`` and (for the attentive variant) ``state_dict`` keys as the
 reference.  No CPU fallback: tensors must live on a HIP device.
 
@@ -110,13 +111,75 @@ class _Expand(torch.autograd.Function):
         return mol_reduce(g.contiguous(), ctx.b), None
 
 
+def _attn_args(H: Tensor, b: MolBounds, W: Tensor, bias: Tensor) -> "_lib.MolAggAttnArgs":
+    a = _lib.MolAggAttnArgs()
+    a.n_atoms, a.n_mols, a.d_h = b.n_atoms, b.n_mols, int(H.shape[1])
+    a.H, a.ldh = H.data_ptr(), (H.stride(0) if b.n_atoms else H.shape[1])
+    a.batch, a.bounds = b.batch.data_ptr(), b.ws.data_ptr()
+    a.W, a.b = W.data_ptr(), bias.data_ptr()
+    return a
+
+
+class _Attentive(torch.autograd.Function):
+    """``AttentiveAggregation.forward`` as ONE autograd node on ``dmpnn_molagg_attn_fwd`` / ``_bwd``: one launch forward (behind the
+    bounds table), two backward; kept between them: ``s [n_atoms]``, ``Z [n_mols]`` and ``H`` itself — no ``[V, d_h]`` temporary."""
+
+    @staticmethod
+    def forward(ctx, H, W, bias, b):
+        H = engine._f32c(H, "H")
+        if H.dim() != 2 or H.shape[0] != b.n_atoms or H.shape[1] < 1:
+            raise ValueError(f"H must be [n_atoms={b.n_atoms}, d >= 1]; got {tuple(H.shape)}")
+        Wc, bc = engine._f32c(W, "W").reshape(-1).contiguous(), engine._f32c(bias, "b").reshape(-1).contiguous()
+        if Wc.numel() != H.shape[1] or bc.numel() != 1:
+            raise ValueError(f"AttentiveAggregation: W must be [1, {H.shape[1]}] with one bias; got {tuple(W.shape)}, {tuple(bias.shape)}")
+        dev = H.device
+        out = torch.empty(b.n_mols, H.shape[1], dtype=torch.float32, device=dev)
+        a = _attn_args(H, b, Wc, bc)
+        a.out, a.ldo = out.data_ptr(), H.shape[1]
+        keep = ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        s = Z = None
+        if keep:
+            s = torch.empty(max(b.n_atoms, 1), dtype=torch.float32, device=dev)   # (never a NULL pointer: keep_s and keep_Z go together)
+            Z = torch.empty(max(b.n_mols, 1), dtype=torch.float32, device=dev)
+            a.keep_s, a.keep_Z = s.data_ptr(), Z.data_ptr()
+        lib = _lib.load()
+        with engine._OnDevice(dev):
+            _lib.check(lib.dmpnn_molagg_attn_fwd(C.byref(a), engine._stream_ptr(dev)), "dmpnn_molagg_attn_fwd")
+        ctx.b, ctx.shapes = b, (W.shape, bias.shape)
+        ctx.save_for_backward(H, Wc, bc, s, Z)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        H, Wc, bc, s, Z = ctx.saved_tensors
+        b, dev, d = ctx.b, H.device, int(H.shape[1])
+        g = engine._f32c(g, "grad").contiguous()
+        gH = torch.empty(b.n_atoms, d, dtype=torch.float32, device=dev)
+        gW = torch.empty(d, dtype=torch.float32, device=dev)
+        gb = torch.empty(1, dtype=torch.float32, device=dev)
+        a = _attn_args(H, b, Wc, bc)
+        a.keep_s, a.keep_Z = s.data_ptr(), Z.data_ptr()
+        a.gout, a.ldgo = g.data_ptr(), d
+        a.gH, a.ldgh = gH.data_ptr(), d
+        a.gW, a.gb = gW.data_ptr(), gb.data_ptr()
+        lib = _lib.load()
+        nb = int(lib.dmpnn_molagg_attn_ws_bytes(C.byref(a)))
+        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
+        a.ws, a.ws_bytes = ws.data_ptr(), nb
+        with engine._OnDevice(dev):
+            _lib.check(lib.dmpnn_molagg_attn_bwd(C.byref(a), engine._stream_ptr(dev)), "dmpnn_molagg_attn_bwd")
+        return gH, gW.reshape(ctx.shapes[0]), gb.reshape(ctx.shapes[1]), None
+
+
 def aggregation_forward(mod, H: Tensor, batch: Tensor, mode: str) -> Tensor:
     """``forward`` of any module with the reference's attributes (``norm`` for the norm variant, ``W`` for the
     attentive one); shared by the mirrors below and by the subclasses of the real chemprop classes
     (``chemprop_amd.integration``)."""
     engine._require_device(H, "H")
     b = MolBounds(batch, n_molecules(batch))
-    if mode == "attentive":
+    if mode == "attentive" and _lib.opt("DMPNN_ATTN", "fused") != "chain":
+        return _Attentive.apply(H, mod.W.weight, mod.W.bias, b)
+    if mode == "attentive":   # DMPNN_ATTN=chain: the reference's chain of ops around two generic reductions (the A/B switch)
         from .backward import linear_fn
 
         logits = linear_fn(H, mod.W.weight, mod.W.bias).exp()

@@ -269,6 +269,10 @@ int molagg_fwd_rows(const float* H, int64_t ldh, int64_t n_atoms, int64_t d_h, i
                     float norm, float* out, int64_t ldo, int64_t rows, void* stream);
 int molagg_bwd_rows(const float* gout, int64_t ldg, const int64_t* batch, int64_t n_atoms, int64_t d_h, int64_t n_mols,
                     const void* ws, int mode, float norm, float* gH, int64_t ldgh, int64_t rows, void* stream);
+// AttentiveAggregation (dmpnn_attn.hip).  id_bounds / id_batch (the head): the forward launch also writes the bounds table and the batch
+// vector of n_mols one-atom molecules.
+int attn_fwd_impl(const dmpnn_molagg_attn_args* a, int* id_bounds, int64_t* id_batch, void* stream);
+int attn_bwd_impl(const dmpnn_molagg_attn_args* a, void* stream);
 // the same tables for batches beyond the single-workgroup plan (dmpnn_tiles_large.hip)
 bool tiles_large_fits(int64_t nV, int64_t nE);
 int launch_prepare_tiles_large(const int64_t* edge_index, const int64_t* batch, int64_t nV, int64_t nE, int* plan, hipStream_t s);

@@ -1282,6 +1282,9 @@ struct HeadLayout {
     // the four-launch form (rows_shape): the hidden layer's split weight in both orientations, their row scales, the row kernel's partials
     size_t W0f, W0b, isf, isb, part;
     int part_stride, n_part;
+    // agg_mode == DMPNN_MOLAGG_ATTENTIVE (behind everything else: the other offsets do not move): the aggregate A [B, d] and its gradient,
+    // the batch vector of B one-atom molecules, the bounds table of the real batch, the kept s [n_atoms] | Z [B], the attention's own scratch
+    size_t att_A, att_gA, att_idb, att_bounds, att_s, att_Z, att_ws, att_ws_bytes;
 };
 // the shapes the four-launch form takes (training or not is the caller's business): one hidden layer, a handful of outputs
 // (with molecule descriptors the first layer's reduction may be up to kRowsMaxK wide: d_h + d_xd; its data gradient stays d_h wide)
@@ -1337,6 +1340,20 @@ HeadLayout head_layout(const dmpnn_head_args& h) {
         L.part_stride = (int)(t * N + t + 2);
         L.part = o; o += al256((size_t)L.n_part * L.part_stride * 4);
     }
+    if (h.agg_mode == DMPNN_MOLAGG_ATTENTIVE) {
+        const int64_t nV = h.n_atoms > 0 ? h.n_atoms : 0;
+        L.att_A = o; o += al256((size_t)B * d * 4);
+        L.att_gA = o; o += al256((size_t)B * d * 4);
+        L.att_idb = o; o += al256((size_t)B * 8);
+        L.att_bounds = o; o += al256(dmpnn_molagg_ws_bytes(B));
+        L.att_s = o; o += al256((size_t)nV * 4);
+        L.att_Z = o; o += al256((size_t)B * 4);
+        dmpnn_molagg_attn_args q;
+        memset(&q, 0, sizeof(q));
+        q.n_mols = B; q.d_h = d; q.bounds = &q;   // (a table is given: the partial rows alone)
+        L.att_ws_bytes = dmpnn_molagg_attn_ws_bytes(&q);
+        L.att_ws = o; o += al256(L.att_ws_bytes);
+    }
     L.total = o;
     return L;
 }
@@ -1356,7 +1373,8 @@ size_t dmpnn_head_ws_bytes(const dmpnn_head_args* h) {
 }  // extern "C"
 
 namespace {
-int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* stream, bool bounds_done, ExtraWgrad* defer, bool agg_rode = false);
+int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* stream, bool bounds_done, ExtraWgrad* defer, bool agg_rode = false,
+             bool check_only = false);
 }  // namespace
 
 extern "C" {
@@ -1395,9 +1413,51 @@ int launch_bn_agg_bwd(const BnAggBwdArgs& q, bool bn, hipStream_t s) {
 // layer's input) stay untouched in the workspace until then
 // agg_rode (a whole training step only): the forward tile kernel wrote the aggregate of the molecules it carried into the workspace's H
 // and marked them in the bounds table's done[] (AggRide)
-int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* stream, bool bounds_done, ExtraWgrad* defer, bool agg_rode) {
+// agg_mode == DMPNN_MOLAGG_ATTENTIVE: the attention forward into the aggregate A, the head as it is on A — B one-atom molecules under SUM,
+// a one-row sum is the row itself, so every form of the head below is taken unchanged — and the attention backward from A's gradient
+// into the caller's gHv / g_att_W / g_att_b.  bounds_done: K0 wrote the REAL batch's table at att_bounds.
+int head_attentive(const dmpnn_head_args& h, const float* Hv, int64_t ldhv, void* stream, bool bounds_done, ExtraWgrad* defer) {
+    const int64_t B = h.n_mols, d = h.d_h, nV = h.n_atoms;
+    DMPNN_CHECK_ARG(h.att_W && h.att_b, "head: DMPNN_MOLAGG_ATTENTIVE needs att_W and att_b");
+    DMPNN_CHECK_ARG(h.n_components <= 1, "head: DMPNN_MOLAGG_ATTENTIVE takes one component (n_components %d)", (int)h.n_components);
+    DMPNN_CHECK_ARG(B >= 0 && nV >= 0 && d > 0 && ldhv >= d, "head: bad sizes");
+    DMPNN_CHECK_ARG(nV == 0 || (Hv && h.batch), "head: null H_v / batch / preds");
+    const bool want_grad = h.gHv != nullptr;
+    DMPNN_CHECK_ARG(!want_grad || h.ldg >= d, "head: gradients need targets, loss_out and ldg >= d_h");
+    const HeadLayout L = head_layout(h);
+    unsigned char* ws = static_cast<unsigned char*>(h.ws);
+    dmpnn_head_args hi = h;   // the head on A: its layout is the front of this one
+    hi.agg_mode = DMPNN_MOLAGG_SUM; hi.n_atoms = B;
+    hi.batch = ws ? reinterpret_cast<const int64_t*>(ws + L.att_idb) : reinterpret_cast<const int64_t*>(&hi);   // (no workspace: a non-NULL stand-in for the checks)
+    hi.gHv = want_grad ? (ws ? reinterpret_cast<float*>(ws + L.att_gA) : reinterpret_cast<float*>(&hi)) : nullptr; hi.ldg = d;
+    hi.att_W = hi.att_b = nullptr; hi.g_att_W = hi.g_att_b = nullptr;
+    const float* A = ws ? reinterpret_cast<const float*>(ws + L.att_A) : reinterpret_cast<const float*>(&hi);
+    DMPNN_TRY(head_run(&hi, A, d, stream, true, defer, false, true));   // every other argument check, before any device work
+    if (!h.ws || h.ws_bytes < L.total) {
+        set_error("head: workspace missing or too small (%zu < %zu bytes)", h.ws_bytes, L.total);
+        return DMPNN_ENOSPC;
+    }
+    if (B == 0) return DMPNN_OK;
+    if (!bounds_done) DMPNN_TRY(dmpnn_molagg_bounds(h.batch, nV, B, ws + L.att_bounds, dmpnn_molagg_ws_bytes(B), stream));
+    dmpnn_molagg_attn_args q;
+    memset(&q, 0, sizeof(q));
+    q.n_atoms = nV; q.n_mols = B; q.d_h = d; q.H = Hv; q.ldh = ldhv; q.batch = h.batch; q.bounds = ws + L.att_bounds;
+    q.W = h.att_W; q.b = h.att_b;
+    q.out = reinterpret_cast<float*>(ws + L.att_A); q.ldo = d;
+    if (want_grad) { q.keep_s = reinterpret_cast<float*>(ws + L.att_s); q.keep_Z = reinterpret_cast<float*>(ws + L.att_Z); }
+    q.gout = reinterpret_cast<const float*>(ws + L.att_gA); q.ldgo = d; q.gH = h.gHv; q.ldgh = h.ldg;
+    q.gW = h.g_att_W; q.gb = h.g_att_b;
+    q.ws = ws + L.att_ws; q.ws_bytes = L.att_ws_bytes;
+    DMPNN_TRY(attn_fwd_impl(&q, reinterpret_cast<int*>(ws + L.bounds), reinterpret_cast<int64_t*>(ws + L.att_idb), stream));
+    DMPNN_TRY(head_run(&hi, A, d, stream, true, defer));
+    if (want_grad) DMPNN_TRY(attn_bwd_impl(&q, stream));
+    return DMPNN_OK;
+}
+
+int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* stream, bool bounds_done, ExtraWgrad* defer, bool agg_rode, bool check_only) {
     DMPNN_CHECK_ARG(hp != nullptr, "head: null args");
     const dmpnn_head_args& h = *hp;
+    if (h.agg_mode == DMPNN_MOLAGG_ATTENTIVE) return head_attentive(h, Hv, ldhv, stream, bounds_done, defer);
     hipStream_t s = static_cast<hipStream_t>(stream);
     DMPNN_CHECK_ARG(h.n_components >= 0 && h.n_components <= DMPNN_MAX_COMPONENTS, "head: n_components (%d) outside 0..%d", (int)h.n_components,
                     DMPNN_MAX_COMPONENTS);
@@ -1429,12 +1489,13 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     const bool want_grad = h.gHv != nullptr;
     DMPNN_CHECK_ARG(!want_grad || (h.targets && h.loss_out && h.ldg >= dc), "head: gradients need targets, loss_out and ldg >= d_h");
     const HeadLayout L = head_layout(h);
+    if (check_only && !h.ws) return DMPNN_OK;   // (the attentive mode's check pass: it judges the workspace's size itself)
     if (!h.ws || h.ws_bytes < L.total) {
         set_error("head: workspace missing or too small (%zu < %zu bytes)", h.ws_bytes, L.total);
         return DMPNN_ENOSPC;
     }
     DMPNN_CHECK_ARG(aligned16(h.ws), "head: workspace must be 16-byte aligned");
-    if (B == 0) return DMPNN_OK;
+    if (B == 0 || check_only) return DMPNN_OK;
     unsigned char* ws = static_cast<unsigned char*>(h.ws);
     // H = agg(H_v) [B, ldH] and bn(H) [B, ldY]; with descriptors bn(H) — or H itself without batch norm — is written straight into the
     // first d_h columns of the fingerprint Zx [B, Kp], whose other columns are X_d and zeros (XdFill)
@@ -1784,10 +1845,12 @@ int dmpnn_train_step(const dmpnn_step_args* a, void* stream) {
         if (!a->plan_ready && (f.flags & DMPNN_F_TILE_PLAN) && h.ws && h.n_mols > 0 && h.batch == a->batch && h.n_atoms == f.n_atoms && ncomp == 1) {
             const HeadLayout HL = head_layout(h);
             unsigned char* hws = static_cast<unsigned char*>(h.ws);
-            if (h.ws_bytes >= HL.total) mb = reinterpret_cast<int*>(hws + HL.bounds);
+            // (the attentive mode: its stage reads the table at att_bounds; the head's own table is of one-atom molecules)
+            if (h.ws_bytes >= HL.total) mb = reinterpret_cast<int*>(hws + (h.agg_mode == DMPNN_MOLAGG_ATTENTIVE ? HL.att_bounds : HL.bounds));
             const char *he = getenv("DMPNN_HEAD"), *ae = getenv("DMPNN_HEAD_AGG");   // (DMPNN_HEAD_AGG=fused | split switches the ride off)
             // (with descriptors and no batch norm the aggregate is written into the fingerprint's rows, not into H: no ride there)
-            if (mb && h.n_mols <= kRowsMaxB && h.d_h % 4 == 0 && h.d_h == f.d_h && !f.W_d && !vd && !(he && !strcmp(he, "chain")) &&
+            // (no ride in the attentive mode: the aggregate needs every atom's logit first)
+            if (mb && h.agg_mode != DMPNN_MOLAGG_ATTENTIVE && h.n_mols <= kRowsMaxB && h.d_h % 4 == 0 && h.d_h == f.d_h && !f.W_d && !vd && !(he && !strcmp(he, "chain")) &&
                 (!h.X_d || h.bn_weight) && !(ae && strcmp(ae, "tile")))
                 ride = AggRide{reinterpret_cast<float*>(hws + HL.Hm), (int)h.d_h, a->batch, mb, (int)h.n_mols, h.agg_mode, h.agg_norm, false};
         }

@@ -329,7 +329,7 @@ def hip_mpnn_class():
             st = {"dev": dev, "fused": None, "why": None, "route": None}
             try:
                 tr = FusedTrainer(self, lr=float(self.init_lr), ffn_dropout=True, rows_dropout=True, vd_dropout=True, atom_messages=True,
-                                  undirected=True)
+                                  undirected=True, attentive=True)
                 st["fused"], st["sync"], st["opt"] = tr, tr.sync, tr.opt
             except NotImplementedError as e:   # (a model the fused step does not implement: module path on the same flat Adam)
                 st["why"] = str(e)

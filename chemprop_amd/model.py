@@ -466,12 +466,29 @@ class HeadSpec:
 
     ``ffn_dropout=True``: the predictor's dropout may be active — ONE ``nn.Dropout`` shared by its blocks (``MLP.build``), kept as
     ``drop``; ``fill(..., ffn_dropout=(p, seed))`` hands it to the kernels as their hash mask (``dmpnn_head_args.ffn_dropout_p``).
-    Without it a predictor with dropout is refused (the module path keeps torch's ``nn.Dropout``)."""
+    Without it a predictor with dropout is refused (the module path keeps torch's ``nn.Dropout``).
 
-    def __init__(self, model, ffn_dropout: bool = False):
+    ``attentive=True`` also takes ``AttentiveAggregation`` (this package's mirror, the reference's class or a subclass of it,
+    ``nn/agg.py:116-133``) when its ``W`` is an ``nn.Linear(d_h, 1)`` with a bias over the head's input width and the model has one
+    component: ``dmpnn_head_args.agg_mode = DMPNN_MOLAGG_ATTENTIVE`` with ``att_W`` / ``att_b``; ``att`` is that layer (``None``
+    otherwise).  The default refuses it like any aggregation that is not sum / mean / norm."""
+
+    def __init__(self, model, ffn_dropout: bool = False, attentive: bool = False):
         agg, pred = model.agg, model.predictor
         mode = aggregation_mode(agg)
-        if mode is None:
+        self.att = None
+        if mode is None and attentive and (getattr(agg, "mode", None) == "attentive" or "AttentiveAggregation" in _mro_names(agg)):
+            mp_ = model.message_passing
+            if isinstance(getattr(mp_, "blocks", None), nn.ModuleList) and hasattr(mp_, "n_components"):
+                raise NotImplementedError("attentive aggregation in a multicomponent model (dmpnn_head takes it with one component)")
+            W, width = getattr(agg, "W", None), int(getattr(mp_, "output_dim", 0))
+            if not isinstance(W, nn.Linear) or W.out_features != 1 or W.in_features != width:
+                raise NotImplementedError(f"attentive aggregation: W must be an nn.Linear({width}, 1) over the block's output "
+                                          f"(got {W!r})")
+            if W.bias is None:
+                raise NotImplementedError("attentive aggregation: W must be an nn.Linear with a bias (the kernels read att_b)")
+            self.att = W
+        elif mode is None:
             raise NotImplementedError(f"sum / mean / norm aggregation (got {type(agg).__name__})")
         blocks = list(pred.ffn)
         if len(blocks) > _lib.MAX_FFN_LAYERS:
@@ -515,7 +532,7 @@ class HeadSpec:
             raise NotImplementedError("a multiclass predictor (n_classes >= 2) with CrossEntropyLoss, or neither")
         if kind == "ce" and int(blocks[-1][-1].out_features) % self.n_classes:
             raise NotImplementedError("the output width must be n_tasks * n_classes")
-        self.agg_mode, self.agg_norm = MODES[mode], float(getattr(agg, "norm", 1.0))
+        self.agg_mode, self.agg_norm = (_lib.MOLAGG_ATTENTIVE if self.att is not None else MODES[mode]), float(getattr(agg, "norm", 1.0))
         self.f_act, self.f_slope, self.kind = f_act, f_slope, kind
         self.layers = [b[-1] for b in blocks]
         # a multicomponent model (models/multi.py): the fingerprint is the components' aggregates side by side, ONE width per block
@@ -551,7 +568,9 @@ class HeadSpec:
 
     def params(self) -> list:
         """The head's parameters in the order ``fill`` asks ``gptr`` about them."""
-        ps = [] if self.bn is None else [self.bn.weight, self.bn.bias]
+        ps = [] if self.att is None else [self.att.weight, self.att.bias]   # (model.parameters() order: agg, bn, predictor)
+        if self.bn is not None:
+            ps += [self.bn.weight, self.bn.bias]
         for lin in self.layers:
             ps.append(lin.weight)
             if lin.bias is not None:
@@ -591,6 +610,9 @@ class HeadSpec:
             h.n_components = self.n_components
         h.batch = batch.data_ptr()
         h.agg_mode, h.agg_norm = self.agg_mode, self.agg_norm
+        if self.att is not None:
+            h.att_W, h.att_b = self.att.weight.data_ptr(), self.att.bias.data_ptr()
+            h.g_att_W, h.g_att_b = gptr(self.att.weight), gptr(self.att.bias)
         bn = self.bn
         if bn is not None:
             h.bn_weight, h.bn_bias = bn.weight.data_ptr(), bn.bias.data_ptr()
@@ -788,11 +810,16 @@ class FusedTrainer:
     engine's rule gives an undirected forward (``general`` / ``general16``, a full plan), with ``p > 0`` — ``rows_dropout=True`` as
     well — on the row kernels of the per-step general route on the f16 pipe with ``DMPNN_F_UNDIRECTED_MASK``; what those refuse is
     refused before a seed is drawn.  Not in a multicomponent model.  The default refuses such a block.
+
+    ``attentive=True`` also takes a model with ``AttentiveAggregation`` (:class:`HeadSpec`): the attention is a stage of two kernels
+    around the head inside the same call, its ``W`` trains with the head's slice of the flat buffer.  Not in a multicomponent model.
+    The gradient of ``W.bias`` is analytically zero (the softmax is shift invariant): what the kernels — and the reference — return is
+    rounding noise, which Adam turns into steps of about ``lr``.  The default refuses such a model.
     """
 
     def __init__(self, model: MPNN, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, group=None,
                  tile_plan: bool = True, ffn_dropout: bool = False, rows_dropout: bool = False, vd_dropout: bool = False,
-                 atom_messages: bool = False, undirected: bool = False):
+                 atom_messages: bool = False, undirected: bool = False, attentive: bool = False):
         mp, agg, pred = model.message_passing, model.agg, model.predictor
         # a multicomponent model: ONE block shared by every component (the components' graphs merged into one batch per step), or
         # one block per component (each block's forward into its rows of one H_v, the head once, each block's backward)
@@ -815,7 +842,7 @@ class FusedTrainer:
         if multi and any(b.W_d is not None for b in self.blocks):
             raise NotImplementedError("FusedTrainer: atom descriptors (V_ds) in a multicomponent model")
         try:
-            self.head = HeadSpec(model, ffn_dropout=ffn_dropout)
+            self.head = HeadSpec(model, ffn_dropout=ffn_dropout, attentive=attentive)
         except NotImplementedError as e:
             raise NotImplementedError(f"FusedTrainer: {e}") from None
         self.model, self.mp, self.multi, self.acts = model, self.blocks[0], multi, acts

@@ -55,7 +55,8 @@ extern "C" {
  * fp32-class; it was DMPNN_EINVAL there).  Grown at its end, same version: dmpnn_head_args.X_d / ld_xd (molecule descriptors behind
  * the batch norm; the two fields are zero in a caller built before them, which is the NULL they default to); dmpnn_head_args.n_components
  * and dmpnn_step_args.n_extra / extra (multicomponent models: zero in an older caller, which is one block); dmpnn_head_args.ffn_dropout_p /
- * ffn_dropout_seed (the predictor's dropout as a hash mask: zero in an older caller, which is no dropout); DMPNN_F_UNDIRECTED_MASK
+ * ffn_dropout_seed (the predictor's dropout as a hash mask: zero in an older caller, which is no dropout); DMPNN_MOLAGG_ATTENTIVE with
+ * dmpnn_molagg_attn_fwd / _bwd / _ws_bytes and dmpnn_head_args.att_W / att_b / g_att_W / g_att_b (zero in an older caller); DMPNN_F_UNDIRECTED_MASK
  * (a flag bit no older caller sets: dropout_p > 0 with DMPNN_F_UNDIRECTED on the per-step general route, DMPNN_EINVAL without it). */
 #define DMPNN_ABI_VERSION 15
 
@@ -571,13 +572,46 @@ int dmpnn_linear_wgrad(const dmpnn_gemm_args* g, const float* gZ, int64_t ldgz, 
  *   dmpnn_molagg_fwd     out[m] = sum_{v in m} H[v]   (MEAN: / count, NORM: / norm; true divisions)
  *   dmpnn_molagg_bwd     gH[v]  = gOut[batch[v]]      (MEAN: / count, NORM: / norm)
  * ------------------------------------------------------------------------------------------- */
-enum dmpnn_molagg_mode { DMPNN_MOLAGG_SUM = 0, DMPNN_MOLAGG_MEAN = 1, DMPNN_MOLAGG_NORM = 2 };
+enum dmpnn_molagg_mode { DMPNN_MOLAGG_SUM = 0, DMPNN_MOLAGG_MEAN = 1, DMPNN_MOLAGG_NORM = 2,
+                         DMPNN_MOLAGG_ATTENTIVE = 3 /* dmpnn_head_args.agg_mode only (att_W / att_b); dmpnn_molagg_fwd / _bwd answer
+                                                       DMPNN_EINVAL for it: the attentive aggregation has its own entry points below */ };
 size_t dmpnn_molagg_ws_bytes(int64_t n_mols);
 int dmpnn_molagg_bounds(const int64_t* batch, int64_t n_atoms, int64_t n_mols, void* ws, size_t ws_bytes, void* stream);
 int dmpnn_molagg_fwd(const float* H, int64_t ldh, int64_t n_atoms, int64_t d_h, int64_t n_mols, const void* ws, int mode,
                      float norm, float* out, int64_t ldo, void* stream);
 int dmpnn_molagg_bwd(const float* gout, int64_t ldg, const int64_t* batch, int64_t n_atoms, int64_t d_h, int64_t n_mols,
                      const void* ws, int mode, float norm, float* gH, int64_t ldgh, void* stream);
+
+/* AttentiveAggregation (chemprop/nn/agg.py:116-133), W = nn.Linear(d_h, 1):
+ *   s_v = exp(W h_v + b)   Z_m = sum_{v in m} s_v   out[m] = (sum_{v in m} s_v h_v) / Z_m     (atoms in increasing order; plain exp, no max
+ *                                                                                              subtraction, a true division)
+ *   a_v = gout[m] h_v   alpha_v = s_v / Z_m   c_m = sum alpha_v a_v   dl_v = alpha_v (a_v - c_m)
+ *   gH[v] = alpha_v gout[m] + dl_v W     gW = sum_v dl_v h_v     gb = sum_v dl_v   (analytically zero: what comes back is rounding)
+ * dmpnn_molagg_attn_fwd: ONE launch, every row of H read once; keep_s [n_atoms] / keep_Z [n_mols] (both or neither; NULL: inference)
+ * are all the backward pass needs beside H.  dmpnn_molagg_attn_bwd: one launch for gH and per-wave partial rows of gW | gb, one small
+ * launch that adds the rows in a fixed order (gW == gb == NULL: not run) — no floating-point atomics, the same bits on every call.
+ * Any d_h >= 1, any row stride >= d_h (columns beyond d_h are never written); rows move as 16-byte quads when d_h, every stride and
+ * every base pointer allow it, as single floats otherwise.  `bounds`: the table dmpnn_molagg_bounds wrote; NULL: the forward pass
+ * builds it from `batch` at the head of `ws` (one more launch) and the backward pass on the same `ws` finds it there.  Its flag (an
+ * invalid batch vector) poisons out, gH, gW and gb with NaN; a molecule without atoms gives a zero row.  n_atoms == 0 or n_mols == 0
+ * in the backward pass: the requested gradients are zeroed.  Every argument check runs before any device work (DMPNN_EINVAL;
+ * DMPNN_ENOSPC for ws: the forward pass needs it only for the table, the backward pass also for gW / gb). */
+typedef struct dmpnn_molagg_attn_args {
+    int64_t n_atoms, n_mols, d_h;
+    const float* H; int64_t ldh;            /* [n_atoms, ldh]                                                      */
+    const int64_t* batch;                   /* [n_atoms], read only when bounds == NULL                             */
+    const void* bounds;                     /* dmpnn_molagg_bounds' table for (batch, n_mols), or NULL              */
+    const float* W; const float* b;         /* [d_h], [1]: the nn.Linear(d_h, 1)                                    */
+    float* out; int64_t ldo;                /* forward: out [n_mols, ldo]                                           */
+    float* keep_s; float* keep_Z;           /* forward: out, [n_atoms] / [n_mols] or NULL; backward: in             */
+    const float* gout; int64_t ldgo;        /* backward: in [n_mols, ldgo]                                          */
+    float* gH; int64_t ldgh;                /* backward: out [n_atoms, ldgh]                                        */
+    float* gW; float* gb;                   /* backward: out [d_h], [1]; NULL: not wanted                           */
+    void* ws; size_t ws_bytes;              /* >= dmpnn_molagg_attn_ws_bytes(), 16-byte aligned                     */
+} dmpnn_molagg_attn_args;
+size_t dmpnn_molagg_attn_ws_bytes(const dmpnn_molagg_attn_args* a);
+int dmpnn_molagg_attn_fwd(const dmpnn_molagg_attn_args* a, void* stream);
+int dmpnn_molagg_attn_bwd(const dmpnn_molagg_attn_args* a, void* stream);
 
 /* f2 (atom messages, mixins.py:21-30): out[i] = X[idx[i]], i < n_out (an index outside [0, n_src) gives a NaN
  * row).  M[e] = S[src(e)] with S = dmpnn_aggregate_fwd of the edge rows; its transpose is
@@ -717,6 +751,13 @@ typedef struct dmpnn_head_args {
                                                floor(p 2^32) (the hash of dmpnn_fwd_args.dropout_p; dmpnn_dropout_keep).  Applied whenever
                                                p > 0: the caller decides when training is on.  No mask is stored: the backward pass
                                                regenerates it */
+    const float* att_W; const float* att_b; float* g_att_W; float* g_att_b;  /* v15 growth: agg_mode == DMPNN_MOLAGG_ATTENTIVE —
+                                               AttentiveAggregation's W [d_h] and b [1] (both required, else DMPNN_EINVAL) and their
+                                               gradients (out, NULL: not wanted; final when dmpnn_head returns, like the predictor's).
+                                               The aggregate is formed by dmpnn_molagg_attn_fwd into the workspace, the head runs on it
+                                               as on a batch of one-atom molecules, dmpnn_molagg_attn_bwd carries its input gradient back
+                                               to gHv.  n_components > 1 with it: DMPNN_EINVAL.  Zero in an older caller; ignored in the
+                                               other modes.  dmpnn_head_ws_bytes() grows in this mode only */
 } dmpnn_head_args;
 size_t dmpnn_head_ws_bytes(const dmpnn_head_args* h);
 int dmpnn_head(const dmpnn_head_args* h, const float* Hv, int64_t ldhv, void* stream);
