@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256, 2) void k_bstep16(BStepK g) {
             const rsrc_t rG = gemm::make_rsrc(g.gMv, gemm::clamp_bytes((long long)g.n_atoms * g.ldg * 4));
             for (int i = wave; i < n_inst; i += NW) {
                 const unsigned o = (unsigned)(i * 1024 + lane * 16);
-                const unsigned r = __umulhi(o >> 4, g.qmagic);     // o / row_b  (row_b = 16 qn)
+                const unsigned r = qn == 1 ? o >> 4 : __umulhi(o >> 4, g.qmagic);   // o / row_b  (row_b = 16 qn; qmagic_of(4) is 0)
                 const unsigned cb = o - r * row_b;
                 const unsigned off = r < (unsigned)nrows ? (unsigned)meta[r] * (unsigned)g.ldg * 4u + cb : kOOB;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rG, (__attribute__((address_space(3))) void*)(lds + i * 1024), 16, off, 0, 0, 0);

@@ -52,7 +52,9 @@ bool fused16_lean_shapes(const dmpnn_fwd_args& a, bool on_demand) {
         if (!(a.act == DMPNN_ACT_RELU || a.act == DMPNN_ACT_LEAKYRELU)) return false;
     }
     if (a.W_d || a.depth < 2 || a.depth > kWProdMaxJobs || a.n_edges <= 0 || a.n_atoms <= 0) return false;
-    if (a.d_h <= 0 || a.d_h % 4 != 0 || a.ldh % 4 != 0 || a.d_v % 2 || a.d_e % 2 || a.ldv % 2 || a.lde % 2) return false;
+    // (ldh == d_h: the backward step kernels read T as contiguous rows of d_h floats — k_bstep16's message mode fetches a tile's rows
+    //  as ONE run of nrows * d_h * 4 bytes — while the launch before wrote them at stride ldh: a padded stride cannot be honoured)
+    if (a.d_h <= 0 || a.d_h % 4 != 0 || a.ldh != a.d_h || a.d_v % 2 || a.d_e % 2 || a.ldv % 2 || a.lde % 2) return false;
     return x_path_shapes(a);
 }
 size_t fused16_lean_bits_bytes(const dmpnn_fwd_args& a) {

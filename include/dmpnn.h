@@ -419,7 +419,8 @@ typedef struct dmpnn_fwd_args {
      * fragments — instead of the fp32 rows (57.6 KB per tile and tensor through an LDS transpose); H0 / Hs must still be there:
      * a molecule beyond the tile keeps its fp32 rows in them (the kernels' generic path).  NULL: fp32 rows as before. */
     /* DMPNN_F_FUSED | DMPNN_F_SPLIT16 | DMPNN_F_KEEP with `keep_bits` (ABI 10; ReLU-class activation, no W_d, no dropout, d_h <= 320,
-     * depth >= 2, a full plan): the LEAN training forward of the per-step fused route.  `msplit` then holds depth - 1 slots of split
+     * depth 2 .. 8, ldh == d_h — the backward step kernels read their rows as one contiguous run; a padded ldh makes
+     * dmpnn_forward_keep_bits_bytes() 0 —, a full plan): the LEAN training forward of the per-step fused route.  `msplit` then holds depth - 1 slots of split
      * message rows (M^(t) of every step, CSR-row order: nothing is copied to fp32), `H0` holds the split K1 operand [V[src] || E]
      * — rows of ceil((d_v + d_e) / 32) * 128 + 16 bytes, so the buffer must span n_edges * max(4 ldh, that) bytes — (no H0
      * tensor: the residual is recomputed per step), `keep_bits` one bit per element of H0 and of
