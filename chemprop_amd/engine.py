@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 from torch import Tensor
@@ -20,7 +20,8 @@ from ._lib import (ACT, F_FUSED, F_H0_RESIDUAL, F_KEEP, F_LOADER_TILES, F_MEGA, 
 
 # The measured crossovers of the route rule live in the library (dmpnn_forward_route, csrc/dmpnn_abi.hip): from 20 000 directed
 # edges on the per-step routes run their contractions on the f16 pipe; from 2 048 on an inference forward that is not the tile
-# kernel's takes the per-step fused route on the f16 pipe.  (Mirrors for the host-side plan choice of nn.py.)
+# kernel's takes the per-step fused route on the f16 pipe.  Mirrors, with no export behind them: the rows of tests/test_prepared_calls.py
+# at 20 000 / 19 984 and 2 048 / 2 032 directed edges hold them to the library (a demanded general route and the rule must cross together).
 STEPS16_MIN_EDGES = 20000
 FUSED16_MIN_EDGES = 2048
 
@@ -93,6 +94,14 @@ def _f32c(t: Tensor, name: str) -> Tensor:
         # concatenation has strides (0, 0)): the C ABI wants a leading dimension >= the row length
         return torch.empty(t.shape, dtype=t.dtype, device=t.device).copy_(t)
     return t.contiguous()
+
+
+def _dense32(t: Optional[Tensor], name: str) -> Optional[Tensor]:
+    """A weight (or ``None``): fp32 and dense — ``_f32c(t, name).contiguous()`` without asking for the strides first."""
+    if t is None:
+        return None
+    _require_device(t, name)
+    return (t if t.dtype == torch.float32 else t.float()).contiguous()
 
 
 def _ptr(t: Optional[Tensor]) -> Optional[int]:
@@ -276,26 +285,25 @@ class GraphPlan:
         return self._view(4).long()
 
 
+def _ask(rule, a, flags: int) -> int:
+    """``rule(a)`` — a shape rule of the library — with ``flags`` as the block's flag word for the duration of the question."""
+    saved, a.flags = a.flags, flags
+    try:
+        return int(rule(C.byref(a)))
+    finally:
+        a.flags = saved
+
+
 def fuse16_shapes(a) -> bool:
     """``dmpnn_forward_can_fuse16`` on the SHAPES of ``a`` (for a training forward its workspace requirements — kept slots,
     ``msplit`` — are met by the allocation that follows the route decision, so they are left out of the question here)."""
-    flags = a.flags
-    a.flags = flags & ~_lib.F_KEEP
-    try:
-        return bool(_lib.load().dmpnn_forward_can_fuse16(C.byref(a)))
-    finally:
-        a.flags = flags
+    return bool(_ask(_lib.load().dmpnn_forward_can_fuse16, a, a.flags & ~_lib.F_KEEP))
 
 
 def _lean16_bits(lib, a) -> int:
     """``dmpnn_forward_keep_bits_bytes`` for the per-step fused route's LEAN training forward on the shapes / options of ``a`` (0: not
     taken — another activation class, W_d, d_h > 320, depth 1)"""
-    flags = a.flags
-    a.flags = (flags | F_FUSED | F_SPLIT16 | F_KEEP) & ~F_MEGA
-    try:
-        return int(lib.dmpnn_forward_keep_bits_bytes(C.byref(a)))
-    finally:
-        a.flags = flags
+    return _ask(lib.dmpnn_forward_keep_bits_bytes, a, (a.flags | F_FUSED | F_SPLIT16 | F_KEEP) & ~F_MEGA)
 
 
 def lean_sign_bits(st: "ForwardState") -> Tensor:
@@ -537,6 +545,365 @@ class ForwardState:
                  "fused", "route")
 
 
+class _Route(NamedTuple):
+    """What the route stage decides, read by every later stage: ``demand`` is the caller's ``route`` after ``fused=False`` and
+    ``DMPNN_GENERAL=1`` (``asked_general``: the caller itself said ``general``), ``mf`` the matrix arithmetic in force."""
+    demand: Optional[str]
+    use_mega: bool
+    use_fused: bool
+    use_fused16: bool
+    want16: bool
+    asked_general: bool
+    mf: str
+
+
+class _Workspace(NamedTuple):
+    """The buffers of one layout and the slot counts the argument block gets (``edge_ws = [H0 | Hs | Ms]`` slots of ``[n_edges, ldh]``;
+    ``None``: nothing leaves the CU but ``out``).  ``bits``: the sign bits of the lean training layout; ``h0_bytes``: ``dmpnn_fwd_args.h0_bytes``; ``spill``: the inference tile kernel's scratch."""
+    edge_ws: Optional[Tensor]
+    atom_ws: Optional[Tensor]
+    split_ms: Optional[Tensor] = None
+    bits: Optional[Tensor] = None
+    n_hslots: int = 0
+    n_mslots: int = 0
+    h0_bytes: int = 0
+    spill: Optional[Tensor] = None
+
+
+def _forward_args(plan: GraphPlan, V, E, W_i, W_h, W_o, b_o, b_i, b_h, W_d, b_d, V_d, depth: int, act: str, slope: float, slope_t,
+                  undirected: bool, form: int, atom: bool, out: Optional[Tensor]) -> tuple:
+    """Stage 1: ``dmpnn_fwd_args`` with the inputs, the weights and ``out`` (no workspace yet).  Returns ``(a, out, tensors, dims)``;
+    ``tensors`` are the eleven the block points into, as ``ForwardState.refs`` lists them, ``dims`` is ``ForwardState.dims``."""
+    V = _f32c(V, "V")
+    E = _f32c(E, "E")
+    dev = V.device
+    nV, nE = plan.n_atoms, plan.n_edges
+    if V.shape[0] != nV or E.shape[0] != nE:
+        raise RuntimeError(f"forward: plan is for V={nV}, E={nE} but got V={V.shape[0]}, E={E.shape[0]}")
+    d_v, d_e, d_h = int(V.shape[1]), int(E.shape[1]), int(W_h.shape[0])
+    if atom and (int(W_i.shape[1]) != d_v or int(W_h.shape[1]) != d_h + d_e):
+        raise RuntimeError("forward(atom): W_i must be [d_h, d_v] and W_h [d_h, d_h + d_e] (base.py:278-289)")
+    d_vd = int(V_d.shape[1]) if (W_d is not None and V_d is not None) else 0
+
+    a = FwdArgs()
+    a.plan, a.n_atoms, a.n_edges = plan.buf.data_ptr(), nV, nE
+    a.edge_index, a.rev_edge_index = plan.edge_index.data_ptr(), plan.rev_edge_index.data_ptr()
+    a.d_v, a.d_e, a.d_h, a.d_vd = d_v, d_e, d_h, d_vd
+    a.depth, a.flags = int(depth), (F_UNDIRECTED if undirected else 0) | (int(form) & (F_H0_RESIDUAL | F_ROW_FINALIZE))
+    if getattr(plan, "loader_tiles", 0) or getattr(plan, "any_size", False):
+        a.flags |= F_LOADER_TILES              # a tile plan of any batch size
+        a.n_tiles_launch = plan.loader_tiles   # (0: the launch bound — the tile count is on the device only)
+    a.act, a.act_slope, a.act_slope_ptr = act_code(act), float(slope), _ptr(slope_t)
+    a.V, a.ldv = V.data_ptr(), V.stride(0)
+    a.E, a.lde = E.data_ptr(), E.stride(0)
+    if d_vd:
+        V_d = _f32c(V_d, "V_d")
+        a.V_d, a.ldvd = V_d.data_ptr(), V_d.stride(0)
+    W_i, W_h, W_o, b_o = _dense32(W_i, "W_i"), _dense32(W_h, "W_h"), _dense32(W_o, "W_o"), _dense32(b_o, "b_o")
+    b_i, b_h = _dense32(b_i, "b_i"), _dense32(b_h, "b_h")
+    a.W_i, a.b_i, a.W_h, a.b_h, a.W_o, a.b_o = W_i.data_ptr(), _ptr(b_i), W_h.data_ptr(), _ptr(b_h), W_o.data_ptr(), b_o.data_ptr()
+    if d_vd:
+        W_d, b_d = _dense32(W_d, "W_d"), _dense32(b_d, "b_d")
+        a.W_d, a.b_d = _ptr(W_d), _ptr(b_d)
+    a.ldh = (d_h + 3) // 4 * 4
+    if out is None:
+        out = torch.empty(nV, d_h + d_vd, dtype=torch.float32, device=dev)
+    elif (out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (nV, d_h + d_vd) or out.stride(1) != 1
+          or out.stride(0) % 4 or out.data_ptr() % 16):
+        # (out=: the rows of a bigger buffer — a multicomponent step writes every block's H_v into ONE [sum n_atoms, d_h] matrix)
+        raise ValueError(f"forward: out must be fp32 [{nV}, {d_h + d_vd}] on {dev}, unit column stride, 16-byte aligned rows")
+    a.out, a.ldout = out.data_ptr(), out.stride(0)
+    a.H0 = a.Ms = a.Mv = plan.buf.data_ptr()  # any 16-byte aligned pointer for the library's shape rules: the workspace comes later
+    dims = dict(d_v=d_v, d_e=d_e, d_h=d_h, d_vd=d_vd, has_bi=b_i is not None, has_bh=b_h is not None, atom=bool(atom))
+    return a, out, (V, E, V_d, W_i, W_h, W_o, b_o, b_i, b_h, W_d, b_d), dims
+
+
+def _forward_route(lib, a, plan: GraphPlan, keep: bool, fused: Optional[bool], route: Optional[str], max_level: int, mfma: Optional[str],
+                   undirected: bool) -> _Route:
+    """Stage 2: the route.  The DEFAULT policy is ONE shape rule in the library (``dmpnn_forward_route``: the measured crossovers are
+    its constants, tests/test_host.py enumerates it); ``route`` / ``fused`` / ``mfma`` are demands of tests and A/B measurements."""
+    if fused is False:
+        route = "general"
+    asked_general = route == "general"   # (a demand of the caller's, not the environment's)
+    if _lib.opt("DMPNN_GENERAL", "0") == "1":
+        route = "general"
+    mf = mfma or _lib.opt("DMPNN_MFMA", "split16")
+    light, tiles_only = bool(getattr(plan, "light", False)), bool(getattr(plan, "tiles_only", False))
+    if route is None and fused is None and mfma is None:
+        cap = min(int(max_level), 1) if _lib.opt("DMPNN_MEGA", "1") == "0" else int(max_level)
+        rc = int(lib.dmpnn_forward_route(C.byref(a), 1 if keep else 0, cap, 2 if tiles_only else (1 if light else 0), 1 if mf == "f32" else 0))
+        if rc < 0:
+            raise RuntimeError("forward: " + ("a tile plan (light='tiles') only serves the whole-forward tile kernel on the f16 pipe" if tiles_only else
+                                              "a light GraphPlan only serves inference forwards of the fused routes (build the plan with "
+                                              "light=False for the general route or for training)"))
+        name = _lib.ROUTES[rc]
+        use_mega, use_fused16 = name.startswith("mega"), name == "fused16"
+        return _Route(route, use_mega, use_mega or use_fused16 or name == "fused", use_fused16, name.endswith("16"), asked_general, mf)
+    level = 0 if (route == "general" or undirected) else int(lib.dmpnn_forward_can_fuse(C.byref(a)))
+    if route == "fused" or _lib.opt("DMPNN_MEGA", "1") == "0":
+        level = min(level, 1)
+    if route is None:  # (`fused=` / `mfma=` alone demand an arithmetic, not a route: the caller's cap still holds)
+        level = min(level, int(max_level))
+    if (fused is True or route in ("fused", "mega")) and level < (2 if route == "mega" else 1):
+        raise RuntimeError(f"forward: route {route or 'fused'!r} requested but the shapes do not allow it "
+                           "(fused: d_h % 4 == 0, d_h <= 320, even d_v / d_e, directed; mega: additionally a batch within the "
+                           "single-workgroup plan, or a plan with molecule tiles)")
+    # the per-step FUSED route on the f16 pipe on demand — also for a TRAINING forward (keep): k_step16 then writes H^(t) and an fp32
+    # copy of every message for the backward pass; those stores eat what it saves, so the default rule does not take it (profiles/README.md)
+    use_fused16 = (route == "fused16" and not undirected and not tiles_only and mf == "split16" and not (keep and light) and fuse16_shapes(a))
+    if route == "fused16" and not use_fused16:
+        raise RuntimeError("forward: route 'fused16' requested but not available (directed, d_h % 4 == 0, d_h <= 640, "
+                           "even d_v / d_e, a full or light plan — training: a full plan)")
+    if use_fused16:
+        level = 1
+    use_fused, use_mega = level >= 1, level >= 2
+    if light and (not use_fused or (keep and not (tiles_only and use_mega and not a.d_vd))):
+        raise RuntimeError("forward: a light GraphPlan only serves inference forwards of the fused routes "
+                           "(build the plan with light=False for the general route or for training; the tile plan also "
+                           "serves a training forward of the tile kernel without W_d)")
+    if tiles_only and (not use_mega or mf == "f32"):
+        raise RuntimeError("forward: a tile plan (light='tiles') only serves the whole-forward tile kernel on the f16 pipe")
+    # the per-step routes' contractions on the f16 pipe: mfma="split16" forces them, "f32" forbids them, else the rule's crossover
+    want16 = mf != "f32" and (use_mega or use_fused16 or (not use_fused and (mfma == "split16" or (mfma is None and mf == "split16" and (
+        a.d_h > 320 or a.n_edges >= STEPS16_MIN_EDGES)))))
+    return _Route(route, use_mega, use_fused, use_fused16, want16, asked_general, mf)
+
+
+def _forward_homes(lib, a, r: _Route, V: Tensor, act: str, mfma: Optional[str], keep: bool, keep_bits: bool, atom: bool,
+                   dropout: Optional[tuple], undirected: bool, undirected_dropout: bool) -> None:
+    """Stage 3: where atom messages and active dropout live on this route — sets ``DMPNN_F_ATOM``, ``DMPNN_F_UNDIRECTED_MASK`` and
+    ``dropout_p`` / ``dropout_seed``, or raises :class:`RouteUnavailable`."""
+    d_v, d_e, d_h, d_vd = a.d_v, a.d_e, a.d_h, a.d_vd
+    if atom:
+        tile_home = r.use_mega and r.want16 and (not keep or (d_e % 2 == 0 and d_v % 2 == 0 and d_h % 2 == 0))
+        rows_home = r.asked_general and not r.use_fused and not undirected   # (the per-step general route: on demand only)
+        if not ((tile_home or rows_home) and not d_vd and 1 <= d_e <= 16):
+            raise RouteUnavailable("atom messages inside the kernels: the tile kernel, 1 <= d_e <= 16, no W_d (training: even d_v / d_e / d_h) "
+                                   "— or, on demand (route='general'), the per-step general route: directed, 1 <= d_e <= 16, no W_d")
+        a.flags |= _lib.F_ATOM
+    if dropout is None or not float(dropout[0]) > 0.0:
+        return
+    # its three homes: the tile kernels, or — on demand — the lean step kernels beyond the tile (route="fused16", keep, keep_bits)
+    # or the row kernels of the per-step general route on the f16 pipe (route="general", mfma="split16", keep)
+    relu_class = act in ("relu", "leakyrelu")
+    tile_home = bool(r.use_mega and r.want16 and keep and not d_vd and not atom and relu_class)
+    # (a DEMAND: the default rule may pick the lean form itself — it saw p = 0 — and must then refuse, as before)
+    lean_home = bool(r.demand == "fused16" and r.use_fused16 and keep and keep_bits and not d_vd and relu_class)
+    # (a DEMAND as well: route="general" with mfma="split16" — never the default rule's own general16, which saw p = 0)
+    rows_why = rows_dropout_refusal(d_v, d_e, d_h, a.depth, act, bool(d_vd), bool(undirected), bool(atom),
+                                    undirected_dropout=bool(undirected_dropout))
+    rows_home = bool(r.demand == "general" and mfma == "split16" and r.want16 and not r.use_fused and keep and rows_why is None
+                     and float(dropout[0]) < 1.0 and V.stride(0) % 2 == 0 and V.data_ptr() % 8 == 0)
+    if rows_home and undirected:
+        a.flags |= _lib.F_UNDIRECTED_MASK
+    if tile_home or lean_home or rows_home:
+        a.dropout_p, a.dropout_seed = float(dropout[0]), int(dropout[1]) & 0xFFFFFFFFFFFFFFFF
+    if not tile_home and not rows_home and not (lean_home and _lean16_bits(lib, a) > 0):
+        why = lean_dropout_refusal(d_v, d_e, d_h, a.depth, act, bool(d_vd)) if r.demand == "fused16" else None
+        demanded = r.demand == "general" and mfma == "split16" and keep
+        raise RouteUnavailable("dropout inside the kernels: a training forward of the tile kernel, or the lean training forward of the "
+                               "per-step fused route (route='fused16', keep, keep_bits); ReLU-class activation, no W_d; or the row kernels "
+                               "of the per-step general route on the f16 pipe (route='general', mfma='split16', keep)"
+                               + (f" — the lean step kernels refuse: {why}" if why else "")
+                               + (f" — the row kernels refuse: {rows_why or 'V rows must be 8-byte aligned with an even stride'}" if demanded else ""))
+
+
+def _nominal_slots(r: _Route, keep: bool, n_steps: int) -> tuple:
+    """``(n_hslots, n_mslots)`` of the route before its layout is known — what ``ForwardState`` reports and the plain layout allocates."""
+    if r.use_mega:
+        return (n_steps, n_steps) if keep else (0, 0)            # inference: H / M never leave the CU
+    if r.use_fused:
+        return (n_steps, n_steps) if keep else (0, min(n_steps, 2))   # H^(t) only matters to the backward pass
+    return (max(n_steps, 1), max(n_steps, 1)) if keep else (1, 1)
+
+
+def _ws_lean(lib, a, n_steps: int, dev) -> _Workspace:
+    """LEAN training forward of the per-step fused route (ReLU-class activation, no W_d, d_h <= 320): nothing is kept that the backward
+    step kernels (csrc/dmpnn_bstep16.hip) do not read — the split message rows of every step (depth - 1 slots), the split K1 operand (in
+    the H0 buffer: no H0 tensor, the residual is recomputed per step as in inference), one sign bit per element of H0 / H^(t)."""
+    nV, nE, ldh = a.n_atoms, a.n_edges, a.ldh
+    # (the H0 buffer holds the split K1 operand, rows of ceil((d_v + d_e) / 32) * 128 + 16 bytes: include/dmpnn.h, keep_bits)
+    xrow = ((a.d_v + a.d_e + 31) // 32 * 128 + 16) // 4
+    return _Workspace(edge_ws=torch.empty((1, nE, max(ldh, xrow)), dtype=torch.float32, device=dev),
+                      split_ms=torch.empty((max(n_steps, 1), nE, int(lib.dmpnn_split_row_floats(a.d_h))), dtype=torch.float32, device=dev),
+                      atom_ws=torch.empty((2, nV, ldh), dtype=torch.float32, device=dev),
+                      bits=torch.empty(_lean16_bits(lib, a), dtype=torch.uint8, device=dev))
+
+
+def _ws_fused16_kept(lib, a, n_steps: int, dev) -> _Workspace:
+    """Training on the per-step fused route: H0 | H^(t) | M^(t) fp32 (what dmpnn_backward reads, CSR-row order) + the two split ping-pong
+    slots in ``msplit``."""
+    nV, nE, ldh = a.n_atoms, a.n_edges, a.ldh
+    return _Workspace(edge_ws=torch.empty((1 + 2 * n_steps, nE, ldh), dtype=torch.float32, device=dev),
+                      split_ms=torch.empty((2, nE, int(lib.dmpnn_split_row_floats(a.d_h))), dtype=torch.float32, device=dev),
+                      atom_ws=torch.empty((2, nV, ldh), dtype=torch.float32, device=dev), n_hslots=n_steps, n_mslots=n_steps)
+
+
+def _ws_fused16_inference(lib, a, dev) -> _Workspace:
+    """Inference on the per-step fused route: H0 fp32 | two slots of split message rows (row = chunks of [hi | lo] halfs + a 16-byte
+    tail with the row's scale).  With a buffer of ``dmpnn_forward_h0_bytes()`` the route keeps H0 as ROW QUADS — the step kernel's
+    accumulator-fragment layout — instead of recomputing ``W_i x`` in every step (d_h <= 320) or gathering fp32 rows word by word
+    (d_h > 320): include/dmpnn.h, ``dmpnn_fwd_args.h0_bytes``.  ``DMPNN_H0=x`` keeps the forms of ABI <= 11 (A/B measurements)."""
+    nV, nE, ldh = a.n_atoms, a.n_edges, a.ldh
+    h0_rows, h0_bytes = nE, 0
+    if _lib.opt("DMPNN_H0", "quads") != "x":
+        # (form bits stay: DMPNN_F_H0_RESIDUAL asks for fp32 rows)
+        need = _ask(lib.dmpnn_forward_h0_bytes, a, (a.flags | F_FUSED | F_SPLIT16) & ~(F_MEGA | F_KEEP))
+        if need:
+            h0_rows = max(nE, (need // 4 + ldh - 1) // ldh)
+            h0_bytes = h0_rows * ldh * 4
+    return _Workspace(edge_ws=torch.empty((1, h0_rows, ldh), dtype=torch.float32, device=dev),
+                      split_ms=torch.empty((2, nE, int(lib.dmpnn_split_row_floats(a.d_h))), dtype=torch.float32, device=dev),
+                      atom_ws=torch.empty((2, nV, ldh), dtype=torch.float32, device=dev), n_hslots=0, n_mslots=2, h0_bytes=h0_bytes)
+
+
+def _ws_plain(lib, a, r: _Route, slots: tuple, keep: bool, atom: bool, act: str, n_steps: int, spill, dev) -> _Workspace:
+    """Every other layout: ``[H0] | Hs | Ms`` in the route's nominal slot counts, and beside them what a kept or an atom forward adds."""
+    nV, nE, ldh = a.n_atoms, a.n_edges, a.ldh
+    n_hslots, n_mslots = slots
+    _, use_mega, use_fused, _, want16, _, _ = r
+    split_ms = None
+    if atom and not use_fused:
+        # the per-step general route: ME = atom-message(E) as ONE slot of [n_edges][16] rows — kept for W_h's gradient, or scratch
+        split_ms = torch.empty((1, nE, 16), dtype=torch.float32, device=dev)
+    elif atom and keep:
+        # the bond-feature half of the atom messages, kept for W_h's gradient: depth - 1 slots of [n_edges][16] (include/dmpnn.h, DMPNN_F_ATOM)
+        split_ms = torch.empty((max(n_steps, 1), nE, 16), dtype=torch.float32, device=dev)
+    elif use_mega and want16 and keep and n_steps and train_route(nV, nE, a.d_v, a.d_e, a.d_h, a.depth, act, 1, max_level=2).keep_rows:
+        # the tile kernel keeps M^(t) as SPLIT ROWS (depth - 1 slots of n_edges rows of dmpnn_split_row_floats(d_h) floats) — what the
+        # weight-gradient products read as they are (csrc/dmpnn_wgrad16.hip: k_wgrad16r); the fp32 Ms slots then only serve a molecule
+        # beyond the tile.  From KEEP_ROWS_MIN message rows on (the crossover: profiles/README.md)
+        split_ms = torch.empty((n_steps, nE, int(lib.dmpnn_split_row_floats(a.d_h))), dtype=torch.float32, device=dev)
+    n_slots = (0 if use_mega and not keep else 1) + n_hslots + n_mslots   # (H0: not for the inference tile kernel)
+    return _Workspace(torch.empty((n_slots, nE, ldh), dtype=torch.float32, device=dev),
+                      torch.empty((2, nV, ldh), dtype=torch.float32, device=dev), split_ms, None, n_hslots, n_mslots, 0, spill)
+
+
+def _forward_workspace(lib, a, r: _Route, plan: GraphPlan, slots: tuple, keep: bool, keep_bits: bool, atom: bool, act: str, dev) -> _Workspace:
+    """Stage 4: the workspace layout of this route and keeping (``slots``: the route's nominal counts)."""
+    n_steps = max(a.depth - 1, 0)
+    spill = None
+    if r.use_mega and not keep:
+        if getattr(plan, "oversize", None) is not False and a.n_atoms:
+            # scratch of the tile kernel's generic path, should a molecule exceed its tile (never touched otherwise)
+            spill = torch.empty((3 * a.n_edges + a.n_atoms) * a.ldh, dtype=torch.float32, device=dev)
+        if not a.d_vd:  # inference tile kernel: nothing leaves the CU but `out`
+            return _Workspace(None, None, spill=spill)
+    if r.use_fused16 and keep and keep_bits and _lean16_bits(lib, a) > 0:
+        return _ws_lean(lib, a, n_steps, dev)
+    if r.use_fused16:
+        return _ws_fused16_kept(lib, a, n_steps, dev) if keep else _ws_fused16_inference(lib, a, dev)
+    return _ws_plain(lib, a, r, slots, keep, atom, act, n_steps, spill, dev)
+
+
+def _bind_workspace(a, st: ForwardState, ws: _Workspace, r: _Route, plan: GraphPlan, keep: bool, atom: bool) -> None:
+    """Write a layout into the argument block and the state."""
+    edge_ws, atom_ws, split_ms, bits, n_hslots, n_mslots, h0_bytes, spill = ws
+    if spill is not None:
+        a.spill_ws, a.spill_bytes = spill.data_ptr(), spill.numel() * 4
+    if edge_ws is None:
+        st.H0 = st.Hs = st.Ms = st.Mv = st.Hv = None
+        a.H0 = a.Hs = a.Ms = None
+        a.n_hslots, a.n_mslots = 0, 1
+        a.Mv = a.Hv = plan.buf.data_ptr()  # (never written: the tile kernel stores kept tensors with DMPNN_F_KEEP only)
+        return
+    if a.ldh != a.d_h:  # pad columns are read by vector loads of later kernels: keep them finite
+        edge_ws.zero_()
+        atom_ws.zero_()
+    need_h0 = not (r.use_mega and not keep)
+    i0 = 1 if need_h0 else 0
+    st.H0, st.Hs, st.Ms = (edge_ws[0] if need_h0 else None), edge_ws[i0:i0 + n_hslots], edge_ws[i0 + n_hslots:]
+    st.Mv, st.Hv = atom_ws[0], atom_ws[1]
+    a.H0 = st.H0.data_ptr() if need_h0 else None
+    a.Hs, a.n_hslots = (st.Hs.data_ptr() if n_hslots else None), n_hslots
+    a.Ms, a.n_mslots = (st.Ms.data_ptr() if n_mslots else None), max(n_mslots, 1)
+    a.Mv, a.Hv, a.h0_bytes = st.Mv.data_ptr(), st.Hv.data_ptr(), h0_bytes
+    if bits is not None:   # (the lean training layout)
+        a.msplit, a.msplit_bytes = split_ms.data_ptr(), split_ms.numel() * 4
+        a.keep_bits, a.keep_bits_bytes = bits.data_ptr(), bits.numel()
+        a.Hs = a.Ms = None
+        st.Ms = split_ms      # (the kept M^(t) as split rows, CSR-row order)
+    elif split_ms is not None and (keep or (atom and not r.use_fused)):
+        a.msplit, a.msplit_bytes = split_ms.data_ptr(), split_ms.numel() * 4
+    elif split_ms is not None:
+        st.Ms = split_ms
+        a.Ms, a.n_mslots = split_ms.data_ptr(), 2
+
+
+def _forward_flags(lib, a, r: _Route, plan: GraphPlan, lean: bool, keep: bool, keep_bits: bool, atom: bool, wcache: Optional[dict], dev) -> tuple:
+    """Stage 5: the flag word, the scratch of the weights' pre-split and — training on a tile plan — the sign bits.  Returns
+    ``(route name, wsplit, bits)``."""
+    _, use_mega, use_fused, use_fused16, want16, _, _ = r
+    name = ("mega" if use_mega else ("fused" if use_fused else "general")) + ("16" if want16 else "")
+    if use_fused:
+        a.flags |= F_FUSED
+    wsplit = bits = None
+    if want16:
+        if use_mega:
+            a.flags |= F_MEGA
+        a.flags |= F_SPLIT16
+        if keep:
+            a.flags |= F_KEEP  # (the size below then includes the backward tile kernel's two transposed matrices)
+        nb = int(lib.dmpnn_forward_wsplit_bytes(C.byref(a)))
+        # scratch of the weights' pre-split — redone by EVERY forward (nothing about the weights is cached: a write through `param.data`
+        # bumps no autograd version); `wcache`, when given, only keeps the BUFFER of a module between its inference calls
+        # (a TRAINING forward gets a buffer of its own: the backward pass reads the transposed matrices in it later)
+        wsplit = wcache.get("buf") if (wcache is not None and not keep) else None
+        if wsplit is None or wsplit.numel() != nb or wsplit.device != dev:
+            wsplit = torch.empty(nb, dtype=torch.uint8, device=dev)
+            if wcache is not None and not keep:
+                wcache["buf"] = wsplit
+        a.wsplit, a.wsplit_bytes = wsplit.data_ptr(), nb
+        if lean:
+            name = "fused16/lean"
+        if use_fused16 and not keep and storage_f16():
+            # OPT-IN half storage of the message tensor between the steps (DMPNN_F_STORE16): not fp32-class, see include/dmpnn.h
+            a.flags |= F_STORE16
+            name = "fused16/f16-storage"
+        elif use_mega and not keep and not atom and storage_f16():
+            # ... and on the whole-forward tile kernel: every product on the hi halves alone — operands, messages and weights as one
+            # f16 per element under the same power-of-two scales, one MFMA pass instead of three (k_mpnn_tile16<..., LP>)
+            a.flags |= F_STORE16
+            name = "mega16/f16-operands"
+    elif use_mega:
+        a.flags |= F_MEGA
+    if keep:
+        a.flags |= F_KEEP
+        if getattr(plan, "tiles_only", False):
+            # training on a tile plan: K0 is the tile table alone; the kept tensors are in the caller's edge order and
+            # dmpnn_backward runs the tile kernel on the caller's index arrays (it cannot see the plan's kind: this flag says so)
+            if not (use_mega and want16 and not a.d_vd):
+                raise RuntimeError("forward: a tile plan serves a training forward only on the tile kernel (f16 pipe), without W_d")
+            a.flags |= F_TILE_PLAN
+            # ... and for a ReLU-class activation without dropout the backward tile kernel needs only the SIGN of H0 / H^(t): one bit
+            # per element straight from the matrix-pipe fragments (2 KB per tile and tensor instead of 57.6 KB of fp32 rows through an
+            # LDS transpose); the fp32 slots stay allocated — a molecule beyond the tile keeps its rows there — but are not touched
+            nbits = int(lib.dmpnn_forward_keep_bits_bytes(C.byref(a))) if keep_bits else 0
+            if nbits:
+                bits = torch.empty(nbits, dtype=torch.uint8, device=dev)
+                a.keep_bits, a.keep_bits_bytes = bits.data_ptr(), nbits
+    return name, wsplit, bits
+
+
+def _forward_launch(lib, a, r: _Route, plan: GraphPlan, keep: bool, dev) -> None:
+    """Stage 6: enqueue — ``dmpnn_forward``, or with a deferred K0 the tile table, the weight pre-split and the tile kernel as ONE
+    foreign call (``dmpnn_forward_tiles``)."""
+    pend = getattr(plan, "pending", None)
+    with _OnDevice(dev):
+        if pend is not None and r.use_mega and r.want16 and getattr(plan, "tiles_only", False):
+            plan.pending = None
+            ht = getattr(plan, "host_tiles", None) if not keep else None
+            rows, atoms, n_tiles = (None, None, 0) if ht is None else (ht[0].data_ptr(), ht[1].data_ptr(), ht[2])
+            if ht is not None:  # (the exact grid: the table's tile count)
+                a.n_tiles_launch = n_tiles
+            _lib.check(lib.dmpnn_forward_tiles(C.byref(a), pend.data_ptr(), rows, atoms, n_tiles, plan.buf.numel() * 4, _stream_ptr(dev)),
+                       "dmpnn_forward_tiles")
+        else:
+            if pend is not None:
+                plan.ensure_launched()
+            _lib.check(lib.dmpnn_forward(C.byref(a), _stream_ptr(dev)), "dmpnn_forward")
+
+
 def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o: Tensor, b_o: Tensor,
             b_i: Optional[Tensor] = None, b_h: Optional[Tensor] = None, W_d: Optional[Tensor] = None,
             b_d: Optional[Tensor] = None, V_d: Optional[Tensor] = None, depth: int = 3, act: str = "relu",
@@ -583,307 +950,22 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
     Graph properties are decided on the device by the plan: a graph a route cannot represent makes that
     route return NaN (see ``GraphPlan.fusable`` / ``GraphPlan.mega_ok``)."""
     lib = _lib.load()
-    V = _f32c(V, "V")
-    E = _f32c(E, "E")
-    dev = V.device
-    nV, nE = plan.n_atoms, plan.n_edges
-    if V.shape[0] != nV or E.shape[0] != nE:
-        raise RuntimeError(f"forward: plan is for V={nV}, E={nE} but got V={V.shape[0]}, E={E.shape[0]}")
-    d_v, d_e, d_h = int(V.shape[1]), int(E.shape[1]), int(W_h.shape[0])
-    if atom and (int(W_i.shape[1]) != d_v or int(W_h.shape[1]) != d_h + d_e):
-        raise RuntimeError("forward(atom): W_i must be [d_h, d_v] and W_h [d_h, d_h + d_e] (base.py:278-289)")
-    d_vd = int(V_d.shape[1]) if (W_d is not None and V_d is not None) else 0
-    ldh = (d_h + 3) // 4 * 4
-    n_steps = max(depth - 1, 0)
-
-    a = FwdArgs()
-    a.plan, a.n_atoms, a.n_edges = plan.buf.data_ptr(), nV, nE
-    a.edge_index, a.rev_edge_index = plan.edge_index.data_ptr(), plan.rev_edge_index.data_ptr()
-    a.d_v, a.d_e, a.d_h, a.d_vd = d_v, d_e, d_h, d_vd
-    a.depth, a.flags = int(depth), (F_UNDIRECTED if undirected else 0) | (int(form) & (F_H0_RESIDUAL | F_ROW_FINALIZE))
-    if getattr(plan, "loader_tiles", 0) or getattr(plan, "any_size", False):
-        a.flags |= F_LOADER_TILES              # a tile plan of any batch size
-        a.n_tiles_launch = plan.loader_tiles   # (0: the launch bound — the tile count is on the device only)
-    a.act, a.act_slope, a.act_slope_ptr = act_code(act), float(slope), _ptr(slope_t)
-    a.V, a.ldv = V.data_ptr(), V.stride(0)
-    a.E, a.lde = E.data_ptr(), E.stride(0)
-    if d_vd:
-        V_d = _f32c(V_d, "V_d")
-        a.V_d, a.ldvd = V_d.data_ptr(), V_d.stride(0)
-    Wc = lambda t, n: None if t is None else _f32c(t, n).contiguous()
-    W_i, W_h, W_o, b_o, b_i, b_h = Wc(W_i, "W_i"), Wc(W_h, "W_h"), Wc(W_o, "W_o"), Wc(b_o, "b_o"), Wc(b_i, "b_i"), Wc(b_h, "b_h")
-    a.W_i, a.b_i, a.W_h, a.b_h, a.W_o, a.b_o = _ptr(W_i), _ptr(b_i), _ptr(W_h), _ptr(b_h), _ptr(W_o), _ptr(b_o)
-    if d_vd:
-        W_d, b_d = Wc(W_d, "W_d"), Wc(b_d, "b_d")
-        a.W_d, a.b_d = _ptr(W_d), _ptr(b_d)
-    a.ldh = ldh
-    if out is None:
-        out = torch.empty(nV, d_h + d_vd, dtype=torch.float32, device=dev)
-    elif (out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (nV, d_h + d_vd) or out.stride(1) != 1
-          or out.stride(0) % 4 or out.data_ptr() % 16):
-        # (out=: the rows of a bigger buffer — a multicomponent step writes every block's H_v into ONE [sum n_atoms, d_h] matrix)
-        raise ValueError(f"forward: out must be fp32 [{nV}, {d_h + d_vd}] on {dev}, unit column stride, 16-byte aligned rows")
-    a.out, a.ldout = out.data_ptr(), out.stride(0)
-
-    # ---- route.  The DEFAULT policy is ONE shape rule in the library (dmpnn_forward_route: the measured crossovers are its
-    # constants, tests/test_host.py enumerates it); `route` / `fused` / `mfma` are demands of tests and A/B measurements ----
-    if fused is False:
-        route = "general"
-    asked_general = route == "general"   # (a demand of the caller's, not the environment's)
-    if _lib.opt("DMPNN_GENERAL", "0") == "1":
-        route = "general"
-    a.H0 = a.Ms = a.Mv = plan.buf.data_ptr()  # any 16-byte aligned pointer: the real workspace is allocated below
-    mf = mfma or _lib.opt("DMPNN_MFMA", "split16")
-    light, tiles_only = bool(getattr(plan, "light", False)), bool(getattr(plan, "tiles_only", False))
-    if route is None and fused is None and mfma is None:
-        cap = min(int(max_level), 1) if _lib.opt("DMPNN_MEGA", "1") == "0" else int(max_level)
-        rc = int(lib.dmpnn_forward_route(C.byref(a), 1 if keep else 0, cap, 2 if tiles_only else (1 if light else 0), 1 if mf == "f32" else 0))
-        if rc < 0:
-            raise RuntimeError("forward: " + ("a tile plan (light='tiles') only serves the whole-forward tile kernel on the f16 pipe" if tiles_only else
-                                              "a light GraphPlan only serves inference forwards of the fused routes (build the plan with "
-                                              "light=False for the general route or for training)"))
-        name = _lib.ROUTES[rc]
-        use_mega, use_fused16 = name.startswith("mega"), name == "fused16"
-        use_fused = use_mega or use_fused16 or name == "fused"
-        want16 = name.endswith("16")
-    else:
-        level = 0 if (route == "general" or undirected) else int(lib.dmpnn_forward_can_fuse(C.byref(a)))
-        if route == "fused" or _lib.opt("DMPNN_MEGA", "1") == "0":
-            level = min(level, 1)
-        if route is None:  # (`fused=` / `mfma=` alone demand an arithmetic, not a route: the caller's cap still holds)
-            level = min(level, int(max_level))
-        if (fused is True or route in ("fused", "mega")) and level < (2 if route == "mega" else 1):
-            raise RuntimeError(f"forward: route {route or 'fused'!r} requested but the shapes do not allow it "
-                               "(fused: d_h % 4 == 0, d_h <= 320, even d_v / d_e, directed; mega: additionally a batch within the "
-                               "single-workgroup plan, or a plan with molecule tiles)")
-        # the per-step FUSED route on the f16 pipe on demand — also for a TRAINING forward (keep): k_step16 then writes H^(t) and an
-        # fp32 copy of every message for the backward pass.  Built and measured in round 3 (40-atom x 4 096: step 6 989 us against
-        # 6 949 us with the general forward): those stores eat what the fused forward saves, so the default rule does not take it
-        use_fused16 = (route == "fused16" and not undirected and not tiles_only and mf == "split16" and not (keep and light) and fuse16_shapes(a))
-        if route == "fused16" and not use_fused16:
-            raise RuntimeError("forward: route 'fused16' requested but not available (directed, d_h % 4 == 0, d_h <= 640, "
-                               "even d_v / d_e, a full or light plan — training: a full plan)")
-        if use_fused16:
-            level = 1
-        use_fused, use_mega = level >= 1, level >= 2
-        if light and (not use_fused or (keep and not (tiles_only and use_mega and not d_vd))):
-            raise RuntimeError("forward: a light GraphPlan only serves inference forwards of the fused routes "
-                               "(build the plan with light=False for the general route or for training; the tile plan also "
-                               "serves a training forward of the tile kernel without W_d)")
-        if tiles_only and (not use_mega or mf == "f32"):
-            raise RuntimeError("forward: a tile plan (light='tiles') only serves the whole-forward tile kernel on the f16 pipe")
-        # the per-step routes' contractions on the f16 pipe: mfma="split16" forces them, "f32" forbids them, else the rule's crossover
-        want16 = use_mega or use_fused16 or (not use_fused and (mfma == "split16" or (mfma is None and mf == "split16" and (d_h > 320 or nE >= STEPS16_MIN_EDGES))))
-        if mf == "f32":
-            want16 = False
-
-    if atom:
-        tile_home = use_mega and want16 and (not keep or (d_e % 2 == 0 and d_v % 2 == 0 and d_h % 2 == 0))
-        rows_home = asked_general and not use_fused and not undirected   # (the per-step general route: on demand only)
-        if not ((tile_home or rows_home) and not d_vd and 1 <= d_e <= 16):
-            raise RouteUnavailable("atom messages inside the kernels: the tile kernel, 1 <= d_e <= 16, no W_d (training: even d_v / d_e / d_h) "
-                                   "— or, on demand (route='general'), the per-step general route: directed, 1 <= d_e <= 16, no W_d")
-        a.flags |= _lib.F_ATOM
-    if dropout is not None and float(dropout[0]) > 0.0:
-        # its three homes: the tile kernels, or — on demand — the lean step kernels beyond the tile (route="fused16", keep, keep_bits)
-        # or the row kernels of the per-step general route on the f16 pipe (route="general", mfma="split16", keep)
-        tile_home = bool(use_mega and want16 and keep and not d_vd and not atom and act in ("relu", "leakyrelu"))
-        # (a DEMAND: the default rule may pick the lean form itself — it saw p = 0 — and must then refuse, as before)
-        lean_home = bool(route == "fused16" and use_fused16 and keep and keep_bits and not d_vd and act in ("relu", "leakyrelu"))
-        # (a DEMAND as well: route="general" with mfma="split16" — never the default rule's own general16, which saw p = 0)
-        rows_why = rows_dropout_refusal(d_v, d_e, d_h, depth, act, bool(d_vd), bool(undirected), bool(atom),
-                                        undirected_dropout=bool(undirected_dropout))
-        rows_home = bool(route == "general" and mfma == "split16" and want16 and not use_fused and keep and rows_why is None
-                         and float(dropout[0]) < 1.0 and V.stride(0) % 2 == 0 and V.data_ptr() % 8 == 0)
-        if rows_home and undirected:
-            a.flags |= _lib.F_UNDIRECTED_MASK
-        if tile_home or lean_home or rows_home:
-            a.dropout_p, a.dropout_seed = float(dropout[0]), int(dropout[1]) & 0xFFFFFFFFFFFFFFFF
-        if not tile_home and not rows_home and not (lean_home and _lean16_bits(lib, a) > 0):
-            why = lean_dropout_refusal(d_v, d_e, d_h, depth, act, bool(d_vd)) if route == "fused16" else None
-            demanded = route == "general" and mfma == "split16" and keep
-            raise RouteUnavailable("dropout inside the kernels: a training forward of the tile kernel, or the lean training forward of the "
-                                   "per-step fused route (route='fused16', keep, keep_bits); ReLU-class activation, no W_d; or the row kernels "
-                                   "of the per-step general route on the f16 pipe (route='general', mfma='split16', keep)"
-                                   + (f" — the lean step kernels refuse: {why}" if why else "")
-                                   + (f" — the row kernels refuse: {rows_why or 'V rows must be 8-byte aligned with an even stride'}" if demanded else ""))
-    bits = None
-    lean16 = False
+    a, out, tensors, st_dims = _forward_args(plan, V, E, W_i, W_h, W_o, b_o, b_i, b_h, W_d, b_d, V_d, depth, act, slope, slope_t, undirected, form, atom, out)
+    dev = tensors[0].device
+    r = _forward_route(lib, a, plan, keep, fused, route, max_level, mfma, undirected)
+    if atom or dropout is not None:
+        _forward_homes(lib, a, r, tensors[0], act, mfma, keep, keep_bits, atom, dropout, undirected, undirected_dropout)
     st = ForwardState()
-    st.fused = use_fused
-    st.route = "mega" if use_mega else ("fused16" if use_fused16 else ("fused" if use_fused else "general"))
-    if use_mega:
-        n_hslots = n_steps if keep else 0           # inference: H / M never leave the CU
-        n_mslots = n_steps if keep else 0
-    elif use_fused:
-        n_hslots = n_steps if keep else 0           # H^(t) only matters to the backward pass
-        n_mslots = n_steps if keep else min(n_steps, 2)
-    else:
-        n_hslots = max(n_steps, 1) if keep else 1
-        n_mslots = max(n_steps, 1) if keep else 1
-    st.plan, st.ldh, st.n_hslots, st.n_mslots = plan, ldh, n_hslots, n_mslots
-    need_h0 = not (use_mega and not keep)
-    spill_ws = None
-    if use_mega and not keep and getattr(plan, "oversize", None) is not False and nV:
-        # scratch of the tile kernel's generic path, should a molecule exceed its tile (never touched otherwise)
-        spill_ws = torch.empty((3 * nE + nV) * ldh, dtype=torch.float32, device=dev)
-        a.spill_ws, a.spill_bytes = spill_ws.data_ptr(), spill_ws.numel() * 4
-    split_ms = None
-    if use_mega and not keep and not d_vd:  # inference tile kernel: nothing leaves the CU but `out`
-        edge_ws = atom_ws = None
-    elif use_fused16 and keep and keep_bits and _lean16_bits(lib, a) > 0:
-        # LEAN training forward (round 4; ReLU-class activation, no W_d, d_h <= 320): nothing is kept that the backward step kernels
-        # (csrc/dmpnn_bstep16.hip) do not read — the split message rows of every step (depth - 1 slots), the split K1 operand (in
-        # the H0 buffer: no H0 tensor, the residual is recomputed per step as in inference), one sign bit per element of H0 / H^(t)
-        srf = int(lib.dmpnn_split_row_floats(d_h))
-        lean16 = True
-        n_hslots = n_mslots = 0
-        # (the H0 buffer holds the split K1 operand, rows of ceil((d_v + d_e) / 32) * 128 + 16 bytes: include/dmpnn.h, keep_bits)
-        xrow = ((d_v + d_e + 31) // 32 * 128 + 16) // 4
-        edge_ws = torch.empty((1, nE, max(ldh, xrow)), dtype=torch.float32, device=dev)
-        split_ms = torch.empty((max(n_steps, 1), nE, srf), dtype=torch.float32, device=dev)
-        atom_ws = torch.empty((2, nV, ldh), dtype=torch.float32, device=dev)
-        bits = torch.empty(_lean16_bits(lib, a), dtype=torch.uint8, device=dev)
-    elif use_fused16 and keep:
-        # training: H0 | H^(t) | M^(t) fp32 (what dmpnn_backward reads, CSR-row order) + the two split ping-pong slots in `msplit`
-        srf = int(lib.dmpnn_split_row_floats(d_h))
-        n_hslots = n_mslots = n_steps
-        edge_ws = torch.empty((1 + 2 * n_steps, nE, ldh), dtype=torch.float32, device=dev)
-        split_ms = torch.empty((2, nE, srf), dtype=torch.float32, device=dev)
-        atom_ws = torch.empty((2, nV, ldh), dtype=torch.float32, device=dev)
-    elif use_fused16:
-        # H0 fp32 | two slots of split message rows (row = chunks of [hi | lo] halfs + a 16-byte tail with the row's scale)
-        srf = int(lib.dmpnn_split_row_floats(d_h))
-        # round 5: with a buffer of dmpnn_forward_h0_bytes() the route keeps H0 as ROW QUADS — the step kernel's accumulator-fragment
-        # layout, written by K1 from its registers, read back by every depth step with coalesced 16-byte loads — instead of recomputing
-        # W_i x in every step (d_h <= 320) or gathering fp32 rows word by word (d_h > 320): include/dmpnn.h, dmpnn_fwd_args.h0_bytes.
-        # DMPNN_H0=x keeps the forms of ABI <= 11 (A/B measurements)
-        h0_rows = nE
-        if _lib.opt("DMPNN_H0", "quads") != "x":
-            flags = a.flags
-            a.flags = (flags | F_FUSED | F_SPLIT16) & ~(F_MEGA | F_KEEP)   # (form bits stay: DMPNN_F_H0_RESIDUAL asks for fp32 rows)
-            try:
-                need = int(lib.dmpnn_forward_h0_bytes(C.byref(a)))
-            finally:
-                a.flags = flags
-            if need:
-                h0_rows = max(nE, (need // 4 + ldh - 1) // ldh)
-                a.h0_bytes = h0_rows * ldh * 4
-        edge_ws = torch.empty((1, h0_rows, ldh), dtype=torch.float32, device=dev)
-        split_ms = torch.empty((2, nE, srf), dtype=torch.float32, device=dev)
-        atom_ws = torch.empty((2, nV, ldh), dtype=torch.float32, device=dev)
-        n_hslots, n_mslots = 0, 2
-    else:
-        edge_ws = torch.empty(((1 if need_h0 else 0) + n_hslots + n_mslots, nE, ldh), dtype=torch.float32, device=dev)
-        atom_ws = torch.empty((2, nV, ldh), dtype=torch.float32, device=dev)
-        if atom and not use_fused:
-            # the per-step general route: ME = atom-message(E) as ONE slot of [n_edges][16] rows — kept for W_h's gradient, or scratch
-            split_ms = torch.empty((1, nE, 16), dtype=torch.float32, device=dev)
-        elif atom and keep:
-            # the bond-feature half of the atom messages, kept for W_h's gradient: depth - 1 slots of [n_edges][16] (include/dmpnn.h, DMPNN_F_ATOM)
-            split_ms = torch.empty((max(n_steps, 1), nE, 16), dtype=torch.float32, device=dev)
-        elif use_mega and want16 and keep and n_steps and train_route(nV, nE, d_v, d_e, d_h, depth, act, 1, max_level=2).keep_rows:
-            # round 4: the tile kernel keeps M^(t) as SPLIT ROWS (depth - 1 slots of n_edges rows of dmpnn_split_row_floats(d_h) floats) —
-            # what the weight-gradient products read as they are (csrc/dmpnn_wgrad16.hip: k_wgrad16r); the fp32 Ms slots above then only
-            # serve a molecule beyond the tile.  From KEEP_ROWS_MIN message rows on — 4 096 since round 6 (k_wgrad16r rebuilt for one
-            # workgroup per CU: 49 -> 31.7 us per launch at 512 QM9-shaped molecules); whole-model step, split rows | blocks, same box
-            # (profiles/r06_rows_crossover.txt): 128 molecules 145 | 149 us, 256 156 | 162, 512 177 | 195, 768 253 | 300, 1 024 281 | 364;
-            # 64 molecules (2 184 message rows) 140 | 137: the rule's lower end
-            split_ms = torch.empty((n_steps, nE, int(lib.dmpnn_split_row_floats(d_h))), dtype=torch.float32, device=dev)
-    st.out = out
-    if edge_ws is None:
-        st.H0 = st.Hs = st.Ms = st.Mv = st.Hv = None
-        a.H0 = a.Hs = a.Ms = None
-        a.n_hslots, a.n_mslots = 0, 1
-        a.Mv = a.Hv = plan.buf.data_ptr()  # (never written: the tile kernel stores kept tensors with DMPNN_F_KEEP only)
-    else:
-        if ldh != d_h:  # pad columns are read by vector loads of later kernels: keep them finite
-            edge_ws.zero_()
-            atom_ws.zero_()
-        i0 = 1 if need_h0 else 0
-        st.H0, st.Hs, st.Ms = (edge_ws[0] if need_h0 else None), edge_ws[i0:i0 + n_hslots], edge_ws[i0 + n_hslots:]
-        st.Mv, st.Hv = atom_ws[0], atom_ws[1]
-        a.H0 = st.H0.data_ptr() if need_h0 else None
-        a.Hs, a.n_hslots = (st.Hs.data_ptr() if n_hslots else None), n_hslots
-        a.Ms, a.n_mslots = (st.Ms.data_ptr() if n_mslots else None), max(n_mslots, 1)
-        a.Mv, a.Hv = st.Mv.data_ptr(), st.Hv.data_ptr()
-        if lean16:
-            a.msplit, a.msplit_bytes = split_ms.data_ptr(), split_ms.numel() * 4
-            a.keep_bits, a.keep_bits_bytes = bits.data_ptr(), bits.numel()
-            a.Hs = a.Ms = None
-            st.Ms = split_ms      # (the kept M^(t) as split rows, CSR-row order)
-        elif split_ms is not None and (keep or (atom and not use_fused)):
-            a.msplit, a.msplit_bytes = split_ms.data_ptr(), split_ms.numel() * 4
-        elif split_ms is not None:
-            st.Ms = split_ms
-            a.Ms, a.n_mslots = split_ms.data_ptr(), 2
-    if use_fused:
-        a.flags |= F_FUSED
-    wsplit = None
-    if want16:
-        if use_mega:
-            a.flags |= F_MEGA
-        a.flags |= F_SPLIT16
-        if keep:
-            a.flags |= F_KEEP  # (the size below then includes the backward tile kernel's two transposed matrices)
-        nb = int(lib.dmpnn_forward_wsplit_bytes(C.byref(a)))
-        # scratch of the weights' pre-split — redone by EVERY forward (round 4: it rides in K0's launch on the steady path, so keeping
-        # it between forwards on the strength of the tensors' autograd versions — which a write through `param.data` does not bump —
-        # bought nothing and could go stale silently); `wcache`, when given, only keeps the BUFFER of a module between its calls
-        # (a TRAINING forward gets a buffer of its own: the backward pass reads the transposed matrices in it later)
-        wsplit = wcache.get("buf") if (wcache is not None and not keep) else None
-        if wsplit is None or wsplit.numel() != nb or wsplit.device != dev:
-            wsplit = torch.empty(nb, dtype=torch.uint8, device=dev)
-            if wcache is not None and not keep:
-                wcache["buf"] = wsplit
-        a.wsplit, a.wsplit_bytes = wsplit.data_ptr(), nb
-        st.route = "mega16" if use_mega else (("fused16/lean" if lean16 else "fused16") if use_fused16 else "general16")
-        if use_fused16 and storage_f16() and not keep:
-            # OPT-IN half storage of the message tensor between the steps (DMPNN_F_STORE16): not fp32-class, see include/dmpnn.h
-            a.flags |= F_STORE16
-            st.route = "fused16/f16-storage"
-        elif use_mega and storage_f16() and not keep and not atom:
-            # ... and on the whole-forward tile kernel (round 6): every product on the hi halves alone — operands, messages and weights as
-            # one f16 per element under the same power-of-two scales, one MFMA pass instead of three (k_mpnn_tile16<..., LP>)
-            a.flags |= F_STORE16
-            st.route = "mega16/f16-operands"
-    elif use_mega:
-        a.flags |= F_MEGA
-    if keep:
-        a.flags |= F_KEEP
-        if tiles_only:
-            # training on a tile plan: K0 is the tile table alone; the kept tensors are in the caller's edge order and
-            # dmpnn_backward runs the tile kernel on the caller's index arrays (it cannot see the plan's kind: this flag says so)
-            if not (use_mega and want16 and not d_vd):
-                raise RuntimeError("forward: a tile plan serves a training forward only on the tile kernel (f16 pipe), without W_d")
-            a.flags |= F_TILE_PLAN
-            # ... and for a ReLU-class activation without dropout the backward tile kernel needs only the SIGN of H0 / H^(t): one bit
-            # per element straight from the matrix-pipe fragments (2 KB per tile and tensor instead of 57.6 KB of fp32 rows through an
-            # LDS transpose); the fp32 slots stay allocated — a molecule beyond the tile keeps its rows there — but are not touched
-            nbits = int(lib.dmpnn_forward_keep_bits_bytes(C.byref(a))) if keep_bits else 0
-            if nbits:
-                bits = torch.empty(nbits, dtype=torch.uint8, device=dev)
-                a.keep_bits, a.keep_bits_bytes = bits.data_ptr(), nbits
+    st.fused, st.plan, st.ldh, st.out = r.use_fused, plan, a.ldh, out
+    st.n_hslots, st.n_mslots = slots = _nominal_slots(r, keep, max(depth - 1, 0))
+    ws = _forward_workspace(lib, a, r, plan, slots, keep, keep_bits, atom, act, dev)
+    _bind_workspace(a, st, ws, r, plan, keep, atom)
+    st.route, wsplit, bits = _forward_flags(lib, a, r, plan, ws.bits is not None, keep, keep_bits, atom, wcache, dev)
     if launch:  # (launch=False: the argument block and the workspace only — dmpnn_train_step enqueues the forward itself)
-        pend = getattr(plan, "pending", None)
-        with _OnDevice(dev):
-            if pend is not None and use_mega and want16 and tiles_only:
-                # K0 was deferred to this call: tile table + weight pre-split (ONE launch) + tile kernel as one foreign call
-                plan.pending = None
-                ht = getattr(plan, "host_tiles", None) if not keep else None
-                if ht is not None:  # (the exact grid: the table's tile count)
-                    a.n_tiles_launch = ht[2]
-                    _lib.check(lib.dmpnn_forward_tiles(C.byref(a), pend.data_ptr(), ht[0].data_ptr(), ht[1].data_ptr(), ht[2],
-                                                       plan.buf.numel() * 4, _stream_ptr(dev)), "dmpnn_forward_tiles")
-                else:
-                    _lib.check(lib.dmpnn_forward_tiles(C.byref(a), pend.data_ptr(), None, None, 0, plan.buf.numel() * 4, _stream_ptr(dev)), "dmpnn_forward_tiles")
-            else:
-                if pend is not None:
-                    plan.ensure_launched()
-                _lib.check(lib.dmpnn_forward(C.byref(a), _stream_ptr(dev)), "dmpnn_forward")
+        _forward_launch(lib, a, r, plan, keep, dev)
     st.args = a
-    st.refs = (V, E, V_d, W_i, W_h, W_o, b_o, b_i, b_h, W_d, b_d, slope_t, edge_ws, atom_ws, spill_ws, split_ms, bits, wsplit)  # (wsplit last: nn._make_replay)
-    st.dims = dict(d_v=d_v, d_e=d_e, d_h=d_h, d_vd=d_vd, has_bi=b_i is not None, has_bh=b_h is not None, atom=bool(atom))
+    st.refs = (*tensors, slope_t, ws.edge_ws, ws.atom_ws, ws.spill, ws.split_ms, bits if ws.bits is None else ws.bits, wsplit)  # (wsplit last: nn._make_replay)
+    st.dims = st_dims
     return out, st
 
 

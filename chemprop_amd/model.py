@@ -1110,181 +1110,163 @@ class FusedTrainer:
         a.ws, a.ws_bytes = ws.data_ptr(), nb
         return out2, gout2, a, [Vd, Hv, gHv, ws, Wd, bd]
 
-    def _block_args(self, mp, bmg, n_mols: int, act_slope: tuple, validate: bool, out: Optional[Tensor], gout: Optional[Tensor]) -> "_BlockPart":
-        """K0's plan and the argument blocks of one block's forward / backward on ``bmg`` (workspace allocated, nothing enqueued but —
-        while the first batches are validated — the plan).  ``out`` / ``gout``: the block's rows of a multicomponent step's H_v / gHv
-        (``None``: allocated here)."""
-        from .nn import _route, _training_plan_kind
+    def _rows_gate(self, mp, bmg, act: str, what: str, **kind) -> None:
+        """A block whose only dropout home is the row kernels (``what``; ``kind``: its ``rows_dropout_refusal`` switches): what they
+        refuse is refused here, before a seed is drawn."""
+        d_v, d_e, d_h = int(bmg.V.shape[1]), int(bmg.E.shape[1]), int(mp.W_h.weight.shape[0])
+        why = None if self.rows_dropout else "rows_dropout=False"
+        why = why or engine.rows_dropout_refusal(d_v, d_e, d_h, int(mp.depth), act, **kind)
+        if why is None and (type(mp.dropout) is not nn.Dropout or float(mp.dropout.p) >= 1.0):
+            why = "nn.Dropout with p < 1"
+        if why is None and (bmg.V.dtype != torch.float32 or bmg.V.stride(0) % 2 or bmg.V.data_ptr() % 8):
+            why = "V rows must be fp32, 8-byte aligned with an even stride"
+        if why is not None:
+            raise NotImplementedError(f"FusedTrainer: dropout inside {what} lives in the row kernels, which refuse it ({why}); "
+                                      "this model trains through the module path (MPNN.loss + autograd)")
 
-        act, slope = act_slope
-        batch = bmg.batch
-        nV, nE = int(bmg.V.shape[0]), int(bmg.E.shape[0])
-        atom = self.atom_messages and is_atom_block(mp)
-        if atom:
-            return self._atom_block_args(mp, bmg, n_mols, act_slope, validate, out, gout)
-        # ---- K0: a launched plan while the first batches are validated (host read of the verdict), else inside the C call ----
-        # The kind of plan: once the first batches are validated (on full plans: their verdict on the graph invariants is read on
-        # the host), a batch bound for the tile kernels gets the TILE plan — K0 is then the 11 us tile table instead of the 28 us
-        # CSR plan, the kept tensors stay in the caller's edge order and the backward tile kernel reads the batch's own index
-        # arrays (DMPNN_F_TILE_PLAN; every tile checks itself, a molecule beyond the tile takes the kernels' generic path).
+    def _block_plan(self, mp, bmg, n_mols: int, validate: bool, atom: bool, p: float) -> tuple:
+        """``(plan, level)``: K0's plan of one block — launched while the first batches are validated (host read of the verdict), else
+        built inside the C call — and the cap on its route (2: the tile kernels).  Once the first batches are validated, a batch bound
+        for the tile kernels gets the TILE plan: K0 is then the 11 us tile table instead of the 28 us CSR plan, the kept tensors stay
+        in the caller's edge order and the backward tile kernel reads the batch's own index arrays (``DMPNN_F_TILE_PLAN``; every tile
+        checks itself, a molecule beyond the tile takes the kernels' generic path)."""
+        from .nn import _route, _training_plan_kind, batch_oversize
+
+        nV, nE, d_v, d_e = int(bmg.V.shape[0]), int(bmg.E.shape[0]), int(bmg.V.shape[1]), int(bmg.E.shape[1])
         no_mega = getattr(mp, "_dmpnn_no_mega", False) or (n_mols > 0 and nE > 30 * n_mols)
         oversize = getattr(bmg, "oversize", None)
-        und = bool(mp.undirected)   # (taken at construction with undirected=True only: the general route, a full plan)
-        if oversize is None and mp.dropout.p > 0 and not no_mega and not und:
-            # (the tile kernels' generic path for a molecule beyond the tile has no dropout and answers NaN — which this step would feed
-            #  to Adam; such a batch goes to the lean step kernels instead.  A foreign batch is counted on the device: nn.batch_oversize)
-            from .nn import batch_oversize
-
-            oversize = batch_oversize(bmg, n_mols)
-        level = 1 if (no_mega or oversize is True) else 2
+        if atom:
+            # the atom tile kernels carry no mask, take even shapes only, and answer NaN for a molecule beyond the tile: the host must KNOW
+            tile_shapes = p == 0 and d_e >= 2 and d_v % 2 == 0 and d_e % 2 == 0 and int(mp.W_h.weight.shape[0]) % 2 == 0 and nE > 0
+            count = tile_shapes
+        else:
+            # (with dropout the tile kernels' generic path for a molecule beyond the tile answers NaN as well — which this step would
+            #  feed to Adam; such a batch goes to the lean step kernels instead)
+            tile_shapes, count = True, mp.dropout.p > 0 and not mp.undirected
+        if oversize is None and count and not no_mega:
+            oversize = batch_oversize(bmg, n_mols)   # (a foreign batch is counted on the device)
+        level = 2 if (tile_shapes and not no_mega and (oversize is False if atom else oversize is not True)) else 1
         # (ONE rule for "this training forward runs on the tile plan", the module path's: shapes of the tile kernel — d_h <= 320, even
         #  d_v / d_e —, the environment switches, a plan the library can build; anything else keeps the full plan and the per-step routes)
-        kind = _training_plan_kind(mp, bmg, vd_outside=True) if (self.tile_plan and not validate and level == 2) else False
+        kind = _training_plan_kind(mp, bmg, atom=atom, vd_outside=True) if (self.tile_plan and not validate and level == 2) else False
+        if atom and not kind and level == 2 and not validate:
+            # (no tile plan for these shapes / this batch size: the full plan serves the atom tile kernels only within the single-workgroup plan)
+            level = 2 if engine.small_plan_fits(nV, nE) else 1
         plan = engine.GraphPlan.from_bmg(bmg, light=kind, launch=validate)
         plan.oversize = oversize
         if validate:
-            level = _route(mp, plan, n_mols, batch)
-            if plan.oversize is True:
-                level = min(level, 1)
+            level = min(level, _route(mp, plan, n_mols, bmg.batch))
         if plan.tiles_only and level < 2:  # (cannot happen: the tile plan was only asked for at level 2)
             raise RuntimeError("FusedTrainer: a tile plan without the tile kernels")
         if not self.multi:
-            note_batch(batch, n_mols)
+            note_batch(bmg.batch, n_mols)
+        return plan, level
 
-        # ---- argument blocks of the block's forward / backward (workspace allocated, nothing enqueued) ----
-        W = lambda lin, n: getattr(getattr(mp, lin), n)
-        if und and mp.dropout.p > 0 and self.model.training:
-            # the only dropout home of an undirected block is the row kernels: what they refuse is refused before a seed is drawn
-            d_v, d_e, d_h = int(bmg.V.shape[1]), int(bmg.E.shape[1]), int(mp.W_h.weight.shape[0])
-            rows_why = None if self.rows_dropout else "rows_dropout=False"
-            rows_why = rows_why or engine.rows_dropout_refusal(d_v, d_e, d_h, int(mp.depth), act, undirected=True, undirected_dropout=True)
-            if rows_why is None and (type(mp.dropout) is not nn.Dropout or float(mp.dropout.p) >= 1.0):
-                rows_why = "nn.Dropout with p < 1"
-            if rows_why is None and (bmg.V.dtype != torch.float32 or bmg.V.stride(0) % 2 or bmg.V.data_ptr() % 8):
-                rows_why = "V rows must be fp32, 8-byte aligned with an even stride"
-            if rows_why is not None:
-                raise NotImplementedError(f"FusedTrainer: dropout inside an undirected block lives in the row kernels, which refuse it ({rows_why}); "
-                                          "this model trains through the module path (MPNN.loss + autograd)")
-        drop = None
-        if mp.dropout.p > 0 and self.model.training:
-            # one seed per step from torch's CPU generator (torch.manual_seed fixes the run), like the module path's fused dropout
-            drop = (float(mp.dropout.p), int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
-            self.last_dropout_seed = drop[1]
-        fwd = lambda **kw: engine.forward(plan, bmg.V, bmg.E, W("W_i", "weight"), W("W_h", "weight"), W("W_o", "weight"), W("W_o", "bias"),
-                                          W("W_i", "bias"), W("W_h", "bias"), depth=mp.depth, act=act, slope=slope, keep=True,
-                                          launch=False, dropout=drop, out=out, undirected=und, **kw)
-        if und and drop is not None:
+    def _draw_seed(self, p: float) -> Optional[tuple]:
+        """The step's ``(p, seed)``: one seed from torch's CPU generator (``torch.manual_seed`` fixes the run), like the module path's
+        fused dropout — after every refusal of the step's own, before anything is prepared.  ``None``: no dropout."""
+        if not p > 0:
+            return None
+        drop = (p, int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
+        self.last_dropout_seed = drop[1]
+        return drop
+
+    @staticmethod
+    def _prepare(mp, plan, bmg, act_slope: tuple, drop: Optional[tuple], out: Optional[Tensor]):
+        """``fwd(**demands on the route)``: ``engine.forward`` of a block's kept forward, prepared and not enqueued."""
+        from .nn import _param as W
+
+        return lambda **kw: engine.forward(
+            plan, bmg.V, bmg.E, W(mp, "W_i", "weight"), W(mp, "W_h", "weight"), W(mp, "W_o", "weight"), W(mp, "W_o", "bias"),
+            W(mp, "W_i", "bias"), W(mp, "W_h", "bias"), depth=mp.depth, act=act_slope[0], slope=act_slope[1], keep=True,
+            launch=False, dropout=drop, out=out, **kw)
+
+    def _block_args(self, mp, bmg, n_mols: int, act_slope: tuple, validate: bool, out: Optional[Tensor], gout: Optional[Tensor]) -> "_BlockPart":
+        """K0's plan and the argument blocks of one block's forward / backward on ``bmg`` (workspace allocated, nothing enqueued but —
+        while the first batches are validated — the plan).  ``out`` / ``gout``: the block's rows of a multicomponent step's H_v / gHv
+        (``None``: allocated here).  The homes of a block's forward:
+
+        * a directed bond block: the tile kernels; with ``p > 0`` and molecules beyond the tile — at any edge count — the lean step
+          kernels, which the route rule never picks for ``p > 0`` (the step asks: ``route="fused16"`` on the full plan); with
+          ``rows_dropout`` the row kernels of the per-step general route on the f16 pipe take what those two refuse;
+        * an undirected bond block with ``p > 0``: the row kernels only;
+        * an atom block (``DMPNN_F_ATOM``): the tile kernels (``p = 0``, no molecule beyond the tile, at most 30 directed edges per
+          molecule, even ``d_v / d_e / d_h``), else the per-step general route on the f16 pipe, with ``p > 0`` at any molecule size.
+        Every refusal of the step's own comes before the seed is drawn, the seed before anything is prepared."""
+        act = act_slope[0]
+        atom = self.atom_messages and is_atom_block(mp)
+        und = bool(mp.undirected)   # (taken at construction with undirected=True only: the general route, a full plan)
+        p = float(mp.dropout.p) if self.model.training else 0.0
+        d_v, d_e, d_h = int(bmg.V.shape[1]), int(bmg.E.shape[1]), int(mp.W_h.weight.shape[0])
+        if atom and (int(mp.W_i.weight.shape[1]) != d_v or int(mp.W_h.weight.shape[1]) != d_h + d_e or not 1 <= d_e <= 16):
+            raise NotImplementedError(f"FusedTrainer: the batch's features (d_v {d_v}, d_e {d_e}) are not the atom block's "
+                                      f"(W_i {tuple(mp.W_i.weight.shape)}, W_h {tuple(mp.W_h.weight.shape)}; 1 <= d_e <= 16)")
+        if atom and p > 0:   # (before the plan: its prologue may count the batch's molecules on the device)
+            self._rows_gate(mp, bmg, act, "an atom block", atom=True)
+        plan, level = self._block_plan(mp, bmg, n_mols, validate, atom, p)
+        if und and p > 0:
+            self._rows_gate(mp, bmg, act, "an undirected block", undirected=True, undirected_dropout=True)
+        drop = self._draw_seed(p)
+        fwd = self._prepare(mp, plan, bmg, act_slope, drop, out)
+        st = None
+        if atom:
+            if level == 2:
+                try:
+                    out, st = fwd(atom=True, max_level=2)
+                except engine.RouteUnavailable:
+                    if plan.tiles_only:
+                        raise RuntimeError("FusedTrainer: a tile plan without the atom tile kernels") from None
+            if st is None:   # (the general route on demand: for every p)
+                try:
+                    out, st = fwd(atom=True, route="general", mfma="split16")
+                except engine.RouteUnavailable as e:
+                    raise NotImplementedError(f"FusedTrainer: neither the tile kernels nor the per-step general route take this atom block ({e}); "
+                                              "it trains through the module path (MPNN.loss + autograd)") from None
+        elif und and drop is not None:
             try:
-                out, st = fwd(route="general", mfma="split16", undirected_dropout=True)
+                out, st = fwd(undirected=True, route="general", mfma="split16", undirected_dropout=True)
             except engine.RouteUnavailable as e:
                 raise NotImplementedError(f"FusedTrainer: the row kernels refuse this undirected block with dropout ({e}); it trains through "
                                           "the module path (MPNN.loss + autograd)") from None
-            return self._finish_block_args(mp, bmg, plan, st, out, gout, drop)
-        # block dropout lives in the tile kernels or — molecules beyond the tile, at any edge count — in the lean step kernels, which
-        # the route rule never picks for p > 0: the step asks for them (route="fused16") on the full plan; with rows_dropout the row
-        # kernels of the per-step general route (route="general" on the f16 pipe) take what those two refuse
-        st, tile_why = None, "molecules beyond the tile"
-        if drop is None or level == 2 or plan.tiles_only:
-            try:
-                out, st = fwd(max_level=level)
-            except engine.RouteUnavailable as e:
-                tile_why = str(e)
-                if drop is None or plan.tiles_only or getattr(plan, "light", False):
-                    raise NotImplementedError(f"FusedTrainer: this batch does not take the tile kernels ({e}); dropout on the other routes "
-                                              "runs through the module path (MPNN.loss + autograd)") from None
-        if st is None:
-            d_v, d_e, d_h = int(bmg.V.shape[1]), int(bmg.E.shape[1]), int(mp.W_h.weight.shape[0])
-            why = engine.lean_dropout_refusal(d_v, d_e, d_h, int(mp.depth), act)
-            if why is None:
+        else:   # a bond block: tile, then lean, then rows
+            tile_why = "molecules beyond the tile"
+            if drop is None or level == 2 or plan.tiles_only:
                 try:
-                    out, st = fwd(route="fused16")
+                    out, st = fwd(undirected=und, max_level=level)
                 except engine.RouteUnavailable as e:
-                    why = str(e)
-                except RuntimeError as e:   # (only the refusal of the demanded route is this step's to translate)
-                    if "route 'fused16' requested but not available" not in str(e):
-                        raise
-                    why = str(e)
-            rows_why = None
-            if st is None and self.rows_dropout:
-                rows_why = engine.rows_dropout_refusal(d_v, d_e, d_h, int(mp.depth), act)
-                if rows_why is None:
-                    try:
-                        out, st = fwd(route="general", mfma="split16")
-                    except engine.RouteUnavailable as e:
-                        rows_why = str(e)
+                    tile_why = str(e)
+                    if drop is None or plan.tiles_only or getattr(plan, "light", False):
+                        raise NotImplementedError(f"FusedTrainer: this batch does not take the tile kernels ({e}); dropout on the other routes "
+                                                  "runs through the module path (MPNN.loss + autograd)") from None
             if st is None:
-                raise NotImplementedError(f"FusedTrainer: this batch does not take the tile kernels ({tile_why}) and the lean step kernels "
-                                          f"refuse it ({why})" + (f", and so do the row kernels ({rows_why})" if self.rows_dropout else "")
-                                          + "; dropout on the other routes runs through the module path (MPNN.loss + autograd)") from None
-        return self._finish_block_args(mp, bmg, plan, st, out, gout, drop)
-
-    def _atom_block_args(self, mp, bmg, n_mols: int, act_slope: tuple, validate: bool, out: Optional[Tensor], gout: Optional[Tensor]) -> "_BlockPart":
-        """:meth:`_block_args` for an atom block (``DMPNN_F_ATOM``).  Two homes: the tile kernels (``p = 0``, no molecule beyond the
-        tile — on the atom variant such a molecule is NaN, so the host must know: ``bmg.oversize`` or ``nn.batch_oversize`` —, at most
-        30 directed edges per molecule, even ``d_v / d_e / d_h``; on the tile plan once the first batches are validated), else the
-        per-step general route on the f16 pipe, with ``p > 0`` at any molecule size.  What neither takes is refused before a seed is
-        drawn or anything is enqueued."""
-        from .nn import _route, _training_plan_kind, batch_oversize
-
-        act, slope = act_slope
-        batch = bmg.batch
-        d_v, d_e, d_h = int(bmg.V.shape[1]), int(bmg.E.shape[1]), int(mp.W_h.weight.shape[0])
-        if int(mp.W_i.weight.shape[1]) != d_v or int(mp.W_h.weight.shape[1]) != d_h + d_e or not 1 <= d_e <= 16:
-            raise NotImplementedError(f"FusedTrainer: the batch's features (d_v {d_v}, d_e {d_e}) are not the atom block's "
-                                      f"(W_i {tuple(mp.W_i.weight.shape)}, W_h {tuple(mp.W_h.weight.shape)}; 1 <= d_e <= 16)")
-        p = float(mp.dropout.p) if self.model.training else 0.0
-        if p > 0:
-            rows_why = None if self.rows_dropout else "rows_dropout=False"
-            rows_why = rows_why or engine.rows_dropout_refusal(d_v, d_e, d_h, int(mp.depth), act, atom=True)
-            if rows_why is None and (type(mp.dropout) is not nn.Dropout or p >= 1.0):
-                rows_why = "nn.Dropout with p < 1"
-            if rows_why is None and (bmg.V.dtype != torch.float32 or bmg.V.stride(0) % 2 or bmg.V.data_ptr() % 8):
-                rows_why = "V rows must be fp32, 8-byte aligned with an even stride"
-            if rows_why is not None:
-                raise NotImplementedError(f"FusedTrainer: dropout inside an atom block lives in the row kernels, which refuse it ({rows_why}); "
-                                          "this model trains through the module path (MPNN.loss + autograd)")
-        no_mega = getattr(mp, "_dmpnn_no_mega", False) or (n_mols > 0 and int(bmg.E.shape[0]) > 30 * n_mols)
-        tile_shapes = p == 0 and not no_mega and d_e >= 2 and d_v % 2 == 0 and d_e % 2 == 0 and d_h % 2 == 0 and int(bmg.E.shape[0]) > 0
-        oversize = getattr(bmg, "oversize", None)
-        if oversize is None and tile_shapes:
-            oversize = batch_oversize(bmg, n_mols)
-        level = 2 if (tile_shapes and oversize is False) else 1
-        kind = _training_plan_kind(mp, bmg, atom=True) if (self.tile_plan and not validate and level == 2) else False
-        if not kind and level == 2 and not validate:
-            # (no tile plan for these shapes / this batch size: the full plan serves the tile kernels only within the single-workgroup plan)
-            level = 2 if engine.small_plan_fits(int(bmg.V.shape[0]), int(bmg.E.shape[0])) else 1
-        plan = engine.GraphPlan.from_bmg(bmg, light=kind, launch=validate)
-        plan.oversize = oversize
-        if validate:
-            level = min(level, _route(mp, plan, n_mols, batch))
-        if not self.multi:
-            note_batch(batch, n_mols)
-        W = lambda lin, n: getattr(getattr(mp, lin), n)
-        drop = None
-        if p > 0:
-            drop = (p, int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
-            self.last_dropout_seed = drop[1]
-        fwd = lambda **kw: engine.forward(plan, bmg.V, bmg.E, W("W_i", "weight"), W("W_h", "weight"), W("W_o", "weight"), W("W_o", "bias"),
-                                          W("W_i", "bias"), W("W_h", "bias"), depth=mp.depth, act=act, slope=slope, keep=True,
-                                          launch=False, dropout=drop, out=out, atom=True, **kw)
-        st = None
-        if level == 2:
-            try:
-                out, st = fwd(max_level=2)
-            except engine.RouteUnavailable:
-                if plan.tiles_only:
-                    raise RuntimeError("FusedTrainer: a tile plan without the atom tile kernels") from None
-        if st is None:
-            try:
-                out, st = fwd(route="general", mfma="split16")
-            except engine.RouteUnavailable as e:
-                raise NotImplementedError(f"FusedTrainer: neither the tile kernels nor the per-step general route take this atom block ({e}); "
-                                          "it trains through the module path (MPNN.loss + autograd)") from None
+                why = engine.lean_dropout_refusal(d_v, d_e, d_h, int(mp.depth), act)
+                if why is None:
+                    try:
+                        out, st = fwd(undirected=und, route="fused16")
+                    except engine.RouteUnavailable as e:
+                        why = str(e)
+                    except RuntimeError as e:   # (only the refusal of the demanded route is this step's to translate)
+                        if "route 'fused16' requested but not available" not in str(e):
+                            raise
+                        why = str(e)
+                rows_why = None
+                if st is None and self.rows_dropout:
+                    rows_why = engine.rows_dropout_refusal(d_v, d_e, d_h, int(mp.depth), act)
+                    if rows_why is None:
+                        try:
+                            out, st = fwd(undirected=und, route="general", mfma="split16")
+                        except engine.RouteUnavailable as e:
+                            rows_why = str(e)
+                if st is None:
+                    raise NotImplementedError(f"FusedTrainer: this batch does not take the tile kernels ({tile_why}) and the lean step kernels "
+                                              f"refuse it ({why})" + (f", and so do the row kernels ({rows_why})" if self.rows_dropout else "")
+                                              + "; dropout on the other routes runs through the module path (MPNN.loss + autograd)") from None
         return self._finish_block_args(mp, bmg, plan, st, out, gout, drop)
 
     def _finish_block_args(self, mp, bmg, plan, st, out: Tensor, gout: Optional[Tensor], drop) -> "_BlockPart":
         """The backward's argument block for a prepared forward ``st`` (gradients into the flat buffer's views) and the block's part."""
-        W = lambda lin, n: getattr(getattr(mp, lin), n)
+        from .nn import _param
+
         batch = bmg.batch
         nV = int(bmg.V.shape[0])
         d_out = int(out.shape[1])
@@ -1293,7 +1275,7 @@ class FusedTrainer:
         need, views = {}, {}
         for k, (lin, n) in dict(W_i=("W_i", "weight"), b_i=("W_i", "bias"), W_h=("W_h", "weight"), b_h=("W_h", "bias"),
                                 W_o=("W_o", "weight"), b_o=("W_o", "bias")).items():
-            p = W(lin, n)
+            p = _param(mp, lin, n)
             need[k] = p is not None and p.requires_grad
             if need[k]:
                 views[k] = self._views[id(p)]
