@@ -399,7 +399,7 @@ int dmpnn_train_route(const dmpnn_fwd_args* a, int64_t n_mols, int32_t have, int
     // (keep_rows is a size rule of the tile kernels' training forward — meaningful when that is the route — and answered whatever
     //  `route` says, so that a caller that already holds the route, engine.forward, can ask for it alone)
     const bool rows = keep_rows == 1 || (keep_rows < 0 && nE * n_steps >= DMPNN_KEEP_ROWS_MIN);
-    out->keep_rows = (!atom && n_steps > 0 && h > 0 && h <= 320 && rows) ? 1 : 0;
+    out->keep_rows = (!atom && n_steps > 0 && mega16_rows_width_ok(h) && rows) ? 1 : 0;   // (not for d_h in (128, 256]: see there)
     if (out->route == DMPNN_ROUTE_MEGA16) {
         out->keep_bits = (out->plan_kind == 2 && (relu_class || a->act == DMPNN_ACT_NONE) && !(a->dropout_p > 0.f)) ? 1 : 0;
     } else if (out->route == DMPNN_ROUTE_FUSED16) {

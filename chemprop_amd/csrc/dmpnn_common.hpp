@@ -258,6 +258,7 @@ int launch_prepare_tiles_batch(const int64_t* edge_index, const int64_t* batch, 
 bool mega16_split_args(const dmpnn_fwd_args& a, mega16::SplitArgs* sp);
 size_t fused16_h0q_bytes(const dmpnn_fwd_args& a);   // (dmpnn_step16.hip: H0 as row quads on the per-step fused route's inference forward)
 bool mega16_keeps_rows(const dmpnn_fwd_args& a);   // M^(t) kept as split rows in `msplit` (the product operands of k_wgrad16r)
+bool mega16_rows_width_ok(int64_t d_h);            // ... which the tile kernel can only write where its tile row IS the kept row (see there)
 // dmpnn_prepare_tiles for a training step that also aggregates per molecule: *wrote_bounds says whether `mol_bounds` was filled
 // (the single-workgroup planner from the batch vector does it on the side; every other planner leaves it to dmpnn_molagg_bounds)
 int prepare_tiles_and_bounds(const int64_t* edge_index, const int64_t* rev, const int64_t* batch, int64_t nV, int64_t nE, void* plan,

@@ -103,9 +103,18 @@ bool mega16_split_args(const dmpnn_fwd_args& a, mega16::SplitArgs* spp) {
 // A training forward of the tile kernel (bond messages) keeps M^(t) as SPLIT ROWS in `msplit` — depth - 1 slots of n_edges rows of
 // split_row_floats(d_h) floats — when the caller provides that buffer: the weight-gradient product (k_wgrad16r) reads them as they are,
 // and so does dmpnn_backward decide (the same test on the same argument block)
+// k_mpnn_tile16 copies the kept rows out of its LDS tile as WHOLE rows of the build's width — 64 WN columns, 256 WN + 16 bytes
+// (flush_rows) — while `msplit`, the backward tile kernel and k_wgrad16r count rows of split_row_floats(d_h) floats: 64-column blocks.
+// The two agree for d_h <= 128 and d_h in (256, 320]; for d_h in (128, 256] the WN = 5 build would write rows of 1 296 bytes into a
+// buffer of 784- or 1 040-byte rows (past its end, and nothing where the products read).  There the messages stay fp32 rows in `Ms`
+// (the block products): found by reading for tests/test_tile_boundaries.py, which pins the rule.
+bool mega16_rows_width_ok(int64_t d_h) {
+    const int64_t bn = d_h <= 64 ? 64 : (d_h <= 128 ? 128 : 320);
+    return d_h > 0 && d_h <= 320 && split_row_floats(d_h) * 4 == bn * 4 + 16;
+}
 bool mega16_keeps_rows(const dmpnn_fwd_args& a) {
     const unsigned need = DMPNN_F_FUSED | DMPNN_F_MEGA | DMPNN_F_SPLIT16 | DMPNN_F_KEEP;
-    if ((a.flags & need) != need || (a.flags & DMPNN_F_ATOM) || a.depth < 2 || a.n_edges <= 0 || a.d_h > 320) return false;
+    if ((a.flags & need) != need || (a.flags & DMPNN_F_ATOM) || a.depth < 2 || a.n_edges <= 0 || !mega16_rows_width_ok(a.d_h)) return false;
     const size_t bytes = (size_t)(a.depth - 1) * (size_t)a.n_edges * (size_t)(split_row_floats(a.d_h) * 4);
     return a.msplit && aligned16(a.msplit) && a.msplit_bytes >= bytes;
 }

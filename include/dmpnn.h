@@ -511,7 +511,8 @@ typedef struct dmpnn_train_route_info {
     int32_t plan_kind;      /* 0 | 2                                                                                          */
     int32_t route;          /* enum dmpnn_route of the training forward on that plan (dmpnn_forward_route with keep)           */
     int32_t keep_rows;      /* 1: the tile kernel keeps M^(t) as split rows in `msplit` (every weight gradient on k_wgrad16r);
-                               a size rule, answered whatever `route` is                                                      */
+                               a size rule, answered whatever `route` is — and only where the kernel's tile row is the kept row:
+                               d_h <= 128 or 256 < d_h <= 320 (in between the messages stay fp32 rows in `Ms`)               */
     int32_t keep_bits;      /* 1: H0 / H^(t) leave as sign bits (`keep_bits`): the tile plan or the lean route, ReLU-class, no dropout */
     int32_t lean;           /* 1: the per-step fused route's LEAN training forward (split rows of every step + sign bits)      */
 } dmpnn_train_route_info;

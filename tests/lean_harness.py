@@ -6,7 +6,8 @@ message rows and one sign bit per element), ``engine.backward`` -> one ``k_bstep
 (csrc/dmpnn_bstep16.hip) and the split-row products ``k_wgrad16r`` (csrc/dmpnn_wgrad16.hip).
 
 * ``Case`` / ``graph`` / ``inputs``: a case is a graph by name, the widths, depth, activation, bias, dropout and the form of the
-  gradient input; its float32 CPU operands are drawn from a seed derived from its id.
+  gradient input; its float32 CPU operands are drawn from a seed derived from its id.  (``TILE_PIECES``, ``name@mol`` and
+  ``name@rows`` are the graphs of the tile kernels' sweep, ``tests/tile_harness.py``, which shares ``Case`` and the reference.)
 * ``reference``: the block in ``dtype`` from the ops of ``oracle/dmpnn_torch.py`` (``initialize`` / ``message`` / ``update`` /
   ``segment_sum_dst`` / ``finalize``), the pre-activation of every site recorded; with ``masks`` every ReLU-class activation is
   replaced by the fixed 0 / 1 decisions handed in (a kinked activation makes a gradient only as reproducible as its decisions), with
@@ -31,7 +32,9 @@ LEAKY_SLOPE = 0.1            # (``oracle.dmpnn_torch.activation_fn("leakyrelu")`
 # ``dmpnn_forward`` refuses ``DMPNN_ACT_NONE`` on every route ("activation 0 is not built in"): the branch of the lean kernels without
 # kept bits cannot be reached through the ABI.  The activation that needs no decisions is LeakyReLU with slope 1: the backward step
 # kernels multiply by 1 on either side of the kink, so everything holds unconditionally.
-ENGINE_ACT = dict(relu=("relu", 0.0), leakyrelu=("leakyrelu", LEAKY_SLOPE), identity=("leakyrelu", 1.0))
+ENGINE_ACT = dict(relu=("relu", 0.0), leakyrelu=("leakyrelu", LEAKY_SLOPE), identity=("leakyrelu", 1.0),
+                  tanh=("tanh", 0.0), elu=("elu", 0.0))   # (the smooth ones: the tile kernels' sweep, tests/tile_harness.py — no decisions)
+RELU_CLASS = ("relu", "leakyrelu")   # the activations whose gradient is as reproducible as their decisions
 BAND = 64 * 2.0 ** -24       # a kept bit may differ from the float64 sign only where |z| < BAND max|z| of its tensor
 MAX_FLIPS = 2                # ... and in at most that many entries of a case
 DROP_SEED = 0x1234_5678_9ABC_DEF
@@ -90,7 +93,76 @@ def graph(name):
         return synth.random_batch(12, "qm9", seed=3)
     if name == "chains-split":
         return rh.chain_graph(SPLIT_CHAINS, 6)
+    # ---- the tile kernels' sweep (tests/tile_harness.py): the batch vector makes the molecules, the edges of ONE molecule lie side by
+    # side — shuffled among themselves — as a tile plan needs them (a tile's rows are a range of the caller's edges)
+    if name.endswith("@mol"):
+        return molecule_order(graph(name[:-4]))
+    if name.endswith("@rows"):
+        return row_order(graph(name[:-5]))
+    if name in TILE_PIECES:
+        return molecule_order(rh._graph(TILE_PIECES[name](), zlib.crc32(name.encode()) % 1000, True))
     raise KeyError(name)
+
+
+def _chain(n):
+    return (n, [(i, i + 1) for i in range(n - 1)])
+
+
+def _ions(n):
+    """ONE molecule: a chain of three atoms and ``n - 3`` atoms without a bond (counter-ions of a salt)."""
+    return (n, [(0, 1), (1, 2)])
+
+
+def pieces_of(bmg):
+    """``[(n_atoms, [(u, v), ..])]`` per molecule of a batch (each bond once, molecule-local atom ids)."""
+    src, dst = bmg.edge_index
+    first = torch.cumsum(torch.bincount(bmg.batch, minlength=len(bmg)), 0) - torch.bincount(bmg.batch, minlength=len(bmg))
+    out = [(int((bmg.batch == m).sum()), []) for m in range(len(bmg))]
+    for u, v in zip(src.tolist(), dst.tolist()):
+        if u < v:
+            m = int(bmg.batch[u])
+            out[m][1].append((u - int(first[m]), v - int(first[m])))
+    return out
+
+
+def _mixed_oversize():
+    small = pieces_of(graph("qm9x12"))
+    return small[:6] + [_chain(26)] + small[6:]
+
+
+ATOM = (1, [])
+TILE_PIECES = {
+    "chain25": lambda: [_chain(25)],                                    # ONE tile of exactly 48 rows
+    "chain26": lambda: [_chain(26)],                                    # 50 rows: beyond the tile by rows — the generic path
+    "star24": lambda: [(25, [(0, i) for i in range(1, 25)])],            # 48 rows, in-degree 24
+    "ions32": lambda: [_ions(32)],                                      # exactly 32 atoms (4 rows)
+    "ions33": lambda: [_ions(33)],                                      # beyond the tile by ATOMS (a connected molecule hits the rows first)
+    "atoms40": lambda: [ATOM] * 35 + [BOND] + [ATOM] * 5,               # tiles closed by the 32-atom limit: 32 atoms without a row | 10 atoms, 2 rows
+    "pack-exact": lambda: [_chain(10), _chain(10), _chain(7), BOND],    # 18 + 18 + 12 = 48 rows, then a tile of two rows
+    "mixed-oversize": _mixed_oversize,                                  # regular tiles on both sides of a molecule of 50 rows
+    "bonds2600": lambda: [BOND] * 2600,                                 # 5 200 atoms and rows: a launch of 4-wave WN = 5 tiles (256 CUs) — every message zero
+    "chains3x1700": lambda: [CHAIN3] * 1700,                            # ... and one whose messages are not: 5 100 atoms, 6 800 rows
+}
+
+
+def _reordered(bmg, p):
+    """The same batch with its edges in another order: position ``k`` holds edge ``p[k]``."""
+    from chemprop_amd.data import BatchMolGraph
+
+    src, dst = bmg.edge_index
+    inv = torch.empty_like(p)
+    inv[p] = torch.arange(p.numel())
+    return BatchMolGraph.from_tensors(bmg.V, bmg.E, torch.stack((src[p], dst[p])), inv[bmg.rev_edge_index[p]], bmg.batch, len(bmg))
+
+
+def molecule_order(bmg):
+    """The edges of one molecule side by side (a stable sort: the shuffled order inside a molecule stays)."""
+    return _reordered(bmg, torch.sort(bmg.batch[bmg.edge_index[0]], stable=True).indices)
+
+
+def row_order(bmg):
+    """The edges by destination atom, stable: the caller's order IS the plan's CSR-row order (and a molecule's edges lie side by side)."""
+    return _reordered(bmg, torch.sort(bmg.edge_index[1], stable=True).indices)
 
 
 def tile_table(bmg):
@@ -207,7 +279,7 @@ def reference(case: Case, dtype=torch.float64, masks=None, keeps=None, grads=Tru
     def tau(z):
         i = len(pre)
         pre.append(z.detach())
-        if masks is None or case.act == "identity":
+        if masks is None or case.act not in RELU_CLASS:
             return act(z)
         m = masks[i].to(dtype)
         return z * (m + (1 - m) * slope)
@@ -260,7 +332,7 @@ def yardsticks(case: Case):
     float32 oracle's own decisions.  No dropout (the dropout case replays its masks in the test)."""
     out64, pre64, g64 = reference(case)
     out32, pre32, _ = reference(case, torch.float32, grads=False)
-    relu_class = case.act != "identity"
+    relu_class = case.act in RELU_CLASS
     _, _, g32 = reference(case, torch.float32, masks=true_masks(pre64) if relu_class else None)
     e32 = rh.yardstick(dict(out=out64, **g64), dict(out=out32, **g32))
     fails32 = sign_check(case.id, true_masks(pre32), pre64)[0] if relu_class else []
