@@ -1,5 +1,5 @@
 """Shared helpers of the atom-message tests (``tests/test_atom_edge_kernels.py``, ``tests/test_atom_general_route.py``,
-``tests/test_atom_step.py``): no fixtures, no pytest settings — a plain module.
+``tests/test_atom_step.py``, ``tests/test_atom_tile_boundaries.py``): no fixtures, no pytest settings — a plain module.
 
 * ``atom_message_ref`` / ``atom_message_seq32`` / ``atom_message_bwd_ref``: the atom message ``M[e] = sum_{e': dst e' = src e} X[e']``
   (mixins.py:21-30) in float64 / float32, as the float32 sum in increasing edge id the kernel forms (bit for bit), and its transpose
@@ -8,7 +8,7 @@
   through ctypes on ``rows_harness.Mat`` buffers (NaN padding, guard regions).
 * ``mixed_batch``: a single-atom molecule, QM9-shaped ones and one 40-atom molecule in one batch, at any ``d_v`` / ``d_e``.
 * ``block_weights`` / ``block_ref``: an atom block's parameters and its restatement (base.py:196-212 with the atom mixin) in any
-  dtype — with the biases, with fixed ReLU decisions and with dropout keep masks — equal to ``oracle.dmpnn_torch.atom_forward``
+  dtype — with the biases, any activation of ``lean_harness.ENGINE_ACT``, fixed ReLU-class decisions and dropout keep masks — equal to ``oracle.dmpnn_torch.atom_forward``
   where that applies (checked by the CPU tests).
 * ``compare``: ``rows_harness.compare`` (``err <= min(MARGIN max(e32, 2**-23), cap)``) returning the worst ratio as well.
 """
@@ -117,9 +117,13 @@ def scale32(p):
     return float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
 
 
+RELU_SLOPE = dict(relu=0.0, leakyrelu=0.1)   # the ReLU class: the factor of a negative entry (leakyrelu: ``lean_harness.LEAKY_SLOPE``)
+
+
 def block_ref(bmg, w, depth, act, dtype=torch.float64, decisions=None, keeps=None, p=0.0, leaves=False):
-    """base.py:196-212 with the atom mixin (mixins.py:21-30) in ``dtype`` on the CPU.  ``decisions`` (``act == "relu"``): one bool
-    tensor per activation site (H0, the updates, the finalize) that replaces the ReLU by a fixed 0 / 1 factor.  ``keeps``: the dropout
+    """base.py:196-212 with the atom mixin (mixins.py:21-30) in ``dtype`` on the CPU.  ``act``: the names of ``lean_harness.ENGINE_ACT``
+    — relu | leakyrelu (slope 0.1) | identity (LeakyReLU with slope 1) | tanh | elu.  ``decisions`` (the ReLU class): one bool
+    tensor per activation site (H0, the updates, the finalize) that replaces the activation by a fixed factor, 1 or the slope.  ``keeps``: the dropout
     keep masks of the update sites and the finalize (``oracle.dropout_hash.keep_mask``), applied with the kernels' float scale.
     Returns ``(out, leaves, pre, made)``: the parameters as leaves with autograd, every pre-activation, every decision made.
     ``leaves``: ``w`` already holds the leaves in ``dtype`` (a training loop's own parameters)."""
@@ -134,10 +138,17 @@ def block_ref(bmg, w, depth, act, dtype=torch.float64, decisions=None, keeps=Non
         pre.append(z.detach())
         if act == "tanh":
             return torch.tanh(z)
-        assert act == "relu"
+        if act == "elu":
+            return torch.nn.functional.elu(z)
+        if act == "identity":          # (the engine's LeakyReLU with slope 1: either decision gives the factor 1)
+            return z
+        assert act in RELU_SLOPE, act
         m = (z.detach() > 0) if decisions is None else decisions[len(made)]
         made.append(m)
-        return z * m.to(dtype)
+        if act == "relu":
+            return z * m.to(dtype)
+        f = m.to(dtype)
+        return z * (f + (1 - f) * RELU_SLOPE[act])
 
     site = [0]
 

@@ -17,7 +17,7 @@ the inference forward (``keep=False``: the ``KEEP = false`` builds and, beyond t
 Dropout: the hash of an edge site takes the CALLER's edge id on either plan (``dropout_frags``: under a CSR plan row ``r`` of a tile
 is edge ``perm[rs + r]``, under a tile plan edge ``rs + r``), the finalize the atom id: ``lean_harness.keep_masks`` as it stands.
 
-Left out: atom messages (``tests/test_atom_mp.py``); the f16-operand inference form (not fp32-class); corrupted plans and batches
+Left out: atom messages (their own sweep: ``tests/test_atom_tile_boundaries.py``); the f16-operand inference form (not fp32-class); corrupted plans and batches
 (``tests/test_host_plan_gpu.py``); in-degree 25; the aggregate ride of ``dmpnn_train_step``; no case poisons or faults a launch.
 
 Instantiation -> case (forward ``launch_mega16<WN, SA, KEEP[, 8]>``; every case runs KEEP = true and KEEP = false):

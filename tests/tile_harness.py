@@ -84,14 +84,27 @@ def plan_of(name, kind, dev):
     return _PLANS[(name, kind)]
 
 
-def run_tile(dev, case, kind, keep=True, bits=True, backward=2):
+def grad_mats(dev, case, atom=False):
+    """One NaN-prefilled buffer per gradient of the case; ``atom``: ``W_i [d_h, d_v]``, ``W_h [d_h, d_h + d_e]`` (base.py:278-289)."""
+    if not atom:
+        return lh._grad_mats(dev, case)
+    h = case.d_h
+    shapes = dict(W_i=(h, case.d_v), b_i=(1, h), W_h=(h, h + case.d_e), b_h=(1, h), W_o=(h, case.d_v + h), b_o=(1, h))
+    if not case.bias:
+        del shapes["b_i"], shapes["b_h"]
+    return {k: rh.Mat(dev, *s, off=4) for k, s in shapes.items()}
+
+
+def run_tile(dev, case, kind, keep=True, bits=True, backward=2, atom=False, inputs=None):
     """One forward on ``route="mega"`` (``keep``: a training forward, ``bits``: ``keep_bits``) and ``backward`` backward passes with every
     gradient requested -> a dict: ``st``, ``out`` (read back: the guard regions checked), ``sites`` (``depth + 1`` bool tensors — the
     decisions at H0, every H^(t) and the finalize, edge sites in the CALLER's edge order; ``None`` where the run kept sign bits or
-    nothing) and ``grads``: one ``{name: tensor}`` per pass.  ``case.pad``: padding columns of ``out`` and ``G`` and of ``V`` and ``E``."""
+    nothing) and ``grads``: one ``{name: tensor}`` per pass.  ``case.pad``: padding columns of ``out`` and ``G`` and of ``V`` and ``E``.
+    ``atom``: atom messages (``DMPNN_F_ATOM``); ``inputs``: the operands instead of ``lean_harness.inputs(case)`` — the same keys, the
+    weights in the block's own shapes."""
     from chemprop_amd import _lib, engine
 
-    bmg, inp = lh.graph(case.graph), lh.inputs(case)
+    bmg, inp = lh.graph(case.graph), (lh.inputs(case) if inputs is None else inputs)
     plan, _ = plan_of(case.graph, kind, dev)
     nV, nE = int(bmg.V.shape[0]), int(bmg.edge_index.shape[1])
     mv = lambda k: None if inp[k] is None else inp[k].to(dev)
@@ -102,9 +115,12 @@ def run_tile(dev, case, kind, keep=True, bits=True, backward=2):
     kw = dict(depth=case.depth, act=act, slope=slope, keep=keep, keep_bits=bits, route="mega", out=out_m.view())
     if case.p:
         kw["dropout"] = (case.p, lh.DROP_SEED)
+    if atom:
+        kw["atom"] = True
     _, st = engine.forward(plan, V_m.view(), E_m.view(), mv("W_i"), mv("W_h"), mv("W_o"), mv("b_o"), mv("b_i"), mv("b_h"), **kw)
     assert st.route == "mega16", st.route
     assert bool(st.args.flags & _lib.F_TILE_PLAN) == (kind == "tiles" and keep), (kind, keep, hex(st.args.flags))
+    assert bool(st.args.flags & _lib.F_ATOM) == bool(atom) and bool(st.plan.tiles_only) == (kind == "tiles"), (kind, hex(st.args.flags))
     torch.cuda.synchronize()
     res = dict(st=st, out=out_m.read("out"), sites=None, grads=[])
     if not keep:
@@ -115,7 +131,7 @@ def run_tile(dev, case, kind, keep=True, bits=True, backward=2):
         res["sites"] = [H0 > 0] + [Hs[t] > 0 for t in range(case.depth - 1)] + [res["out"] > 0]
     G_m = rh.Mat(dev, nV, case.d_h, case.d_h + case.pad, off=4, data=inp["G"])
     for _ in range(backward):
-        mats = lh._grad_mats(dev, case)
+        mats = grad_mats(dev, case, atom)
         bufs = {k: (m.view()[0] if k.startswith("b_") else m.view()) for k, m in mats.items()}
         got = engine.backward(st, G_m.view(), {k: True for k in lh.GRADS}, out=bufs)
         torch.cuda.synchronize()
