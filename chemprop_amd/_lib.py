@@ -21,7 +21,7 @@ INCLUDE = os.path.join(_ROOT, "include")
 # DMPNN_LIB: an alternative build of the same sources (kernel experiments: scripts/build_variant.py), same ABI
 LIB_PATH = os.environ.get("DMPNN_LIB") or os.path.join(_HERE, "libdmpnn_gfx950.so")
 SOURCES = ["dmpnn_abi.hip", "dmpnn_prepare.hip", "dmpnn_segment.hip", "dmpnn_gemm.hip", "dmpnn_gemm_p1.hip",
-           "dmpnn_gemm_p2.hip", "dmpnn_gemm_p3.hip", "dmpnn_gemm_p4.hip", "dmpnn_gemm_s1.hip", "dmpnn_rows16_drop.hip", "dmpnn_mega.hip", "dmpnn_mega16.hip", "dmpnn_mega16_lp.hip", "dmpnn_mega16_bwd.hip", "dmpnn_rows16.hip", "dmpnn_step16.hip", "dmpnn_bstep16.hip", "dmpnn_backward.hip", "dmpnn_molagg.hip", "dmpnn_collate.hip", "dmpnn_tiles_large.hip", "dmpnn_optim.hip", "dmpnn_wgrad16.hip", "dmpnn_head.hip", "dmpnn_vd.hip", "dmpnn_attn.hip"]
+           "dmpnn_gemm_p2.hip", "dmpnn_gemm_p3.hip", "dmpnn_gemm_p4.hip", "dmpnn_gemm_s1.hip", "dmpnn_rows16_drop.hip", "dmpnn_mega.hip", "dmpnn_mega16.hip", "dmpnn_mega16_lp.hip", "dmpnn_mega16_bwd.hip", "dmpnn_rows16.hip", "dmpnn_step16.hip", "dmpnn_bstep16.hip", "dmpnn_backward.hip", "dmpnn_molagg.hip", "dmpnn_collate.hip", "dmpnn_tiles_large.hip", "dmpnn_optim.hip", "dmpnn_wgrad16.hip", "dmpnn_head.hip", "dmpnn_vd.hip", "dmpnn_attn.hip", "dmpnn_inputgrad.hip"]
 HEADERS = ["dmpnn_common.hpp", "dmpnn_spill_impl.hpp", "dmpnn_gemm_impl.hpp", "dmpnn_mega_impl.hpp", "dmpnn_mega16_impl.hpp", "dmpnn_mega16_bwd_impl.hpp", "dmpnn_rows16_impl.hpp", "dmpnn_seg16.hpp", "dmpnn_step16_impl.hpp"]
 ABI_VERSION = 15
 PLAN_NOFFSETS = 15
@@ -38,6 +38,7 @@ EXPORTS = [
     "dmpnn_clip_grad", "dmpnn_clip_grad_ws_bytes", "dmpnn_train_route", "dmpnn_forward_h0_bytes", "dmpnn_tile_waves", "dmpnn_debug_lds_poison",
     "dmpnn_vd_ws_bytes", "dmpnn_vd_forward", "dmpnn_vd_backward", "dmpnn_linear16_dropout_fwd",
     "dmpnn_molagg_attn_ws_bytes", "dmpnn_molagg_attn_fwd", "dmpnn_molagg_attn_bwd",
+    "dmpnn_backward_inputs", "dmpnn_backward_inputs_ws_bytes", "dmpnn_src_sum",
 ]
 
 ACT = {"none": 0, "relu": 1, "leakyrelu": 2, "prelu": 3, "tanh": 4, "elu": 5}
@@ -108,6 +109,16 @@ class BwdArgs(C.Structure):
         ("gW_o", C.c_void_p), ("gb_o", C.c_void_p), ("gW_d", C.c_void_p), ("gb_d", C.c_void_p),
         ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
         ("g_edge", C.c_void_p), ("ld_gedge", C.c_int64),
+    ]
+
+
+class BwdInputsArgs(C.Structure):
+    """``dmpnn_bwd_inputs_args``: a backward pass that also returns the gradients of V, E and V_d (``dmpnn_backward_inputs``)."""
+    _fields_ = [
+        ("b", BwdArgs),
+        ("gV", C.c_void_p), ("ldgv", C.c_int64),
+        ("gE", C.c_void_p), ("ldge", C.c_int64),
+        ("gV_d", C.c_void_p), ("ldgvd", C.c_int64),
     ]
 
 
@@ -315,6 +326,9 @@ def load() -> C.CDLL:
     lib.dmpnn_forward.argtypes = [C.POINTER(FwdArgs), C.c_void_p]
     lib.dmpnn_backward_ws_bytes.argtypes = [C.POINTER(FwdArgs)]
     lib.dmpnn_backward.argtypes = [C.POINTER(BwdArgs), C.c_void_p]
+    lib.dmpnn_backward_inputs_ws_bytes.argtypes = [C.POINTER(FwdArgs)]
+    lib.dmpnn_backward_inputs.argtypes = [C.POINTER(BwdInputsArgs), C.c_void_p]
+    lib.dmpnn_src_sum.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     lib.dmpnn_message_bwd.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
                                       C.c_void_p, C.c_int64, C.c_void_p]
     lib.dmpnn_aggregate_bwd.argtypes = lib.dmpnn_message_bwd.argtypes
@@ -325,7 +339,7 @@ def load() -> C.CDLL:
     size_t_fns = ("dmpnn_plan_bytes", "dmpnn_backward_ws_bytes", "dmpnn_linear_wgrad_ws_bytes", "dmpnn_forward_wsplit_bytes", "dmpnn_forward_spill_bytes",
                   "dmpnn_forward_keep_bits_bytes",
                   "dmpnn_molagg_ws_bytes", "dmpnn_linear16_wsplit_bytes", "dmpnn_head_ws_bytes", "dmpnn_clip_grad_ws_bytes", "dmpnn_forward_h0_bytes", "dmpnn_vd_ws_bytes",
-                  "dmpnn_molagg_attn_ws_bytes")
+                  "dmpnn_molagg_attn_ws_bytes", "dmpnn_backward_inputs_ws_bytes")
     lib.dmpnn_linear16_wsplit_bytes.argtypes = [C.c_int64, C.c_int64]
     lib.dmpnn_linear16_ok.argtypes = [C.POINTER(GemmArgs)]
     lib.dmpnn_linear16_fwd.argtypes = [C.POINTER(GemmArgs), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]

@@ -26,12 +26,17 @@ class FusedMP(torch.autograd.Function):
         # the mol-atom-bond blocks (mab.py): the kept H^(depth-1) is a second OUTPUT, for the edge read-out — in the caller's edge order —
         # and its gradient a second input of the backward tile kernel (dmpnn_bwd_args.g_edge); tile-kernel forwards only, depth >= 2
         want_edge = bool(slope_and_route[4]) if len(slope_and_route) > 4 else False
+        # a demanded route (autograd.mp_forward: "general" when V, E or V_d requires grad — the route whose backward pass also returns
+        # the input gradients, dmpnn_backward_inputs)
+        route = slope_and_route[5] if len(slope_and_route) > 5 else None
         has_vd = V_d is not None and W_d is not None
         out, st = engine.forward(plan, V, E, W_i, W_h, W_o, b_o, b_i, b_h, W_d if has_vd else None,
                                  b_d if has_vd else None, V_d if has_vd else None, depth=mp.depth, act=act,
                                  slope=slope, slope_t=slope_t, undirected=mp.undirected, keep=True, max_level=max_level, dropout=dropout,
-                                 atom=atom, keep_bits=not want_edge)
+                                 atom=atom, keep_bits=not want_edge, route=route)
         ctx.st = st
+        if route is not None:
+            mp.__dict__["_dmpnn_last"] = st   # (nn.py reads the route of a demanded forward from it, and drops it at once)
         ctx.has_vd = has_vd
         ctx.mp = mp
         ctx.edge_rows = None
@@ -77,23 +82,33 @@ class FusedMP(torch.autograd.Function):
                 gout = torch.zeros_like(st.out)
             if g_edge is not None and ctx.edge_rows == "csr":
                 g_edge = engine.gather_rows(g_edge.contiguous(), st.plan.perm32)
-        grads = engine.backward(st, gout.contiguous(), need, out=direct, g_edge=g_edge)
+        # gradients with respect to the inputs V, E, V_d (positions 2, 3, 4): the per-step general route's backward pass returns them
+        inputs = {k for i, k in ((2, "V"), (3, "E"), (4, "V_d")) if ctx.needs_input_grad[i] and (k != "V_d" or ctx.has_vd)}
+        if inputs and st.route not in ("general", "general16"):
+            raise NotImplementedError(f"chemprop_amd: gradients w.r.t. {sorted(inputs)} are provided on the per-step general route, "
+                                      f"not on {st.route!r}")
+        grads = engine.backward(st, gout.contiguous(), need, out=direct, g_edge=g_edge, inputs=inputs)
         if engine._lib.opt("DMPNN_KEEP_WORKSPACE", "0") != "1":
             ctx.st = None  # release the kept workspace
         # (a view the engine did not take — wrong dtype / layout — got a fresh tensor instead: that one goes to autograd)
         took = {k for k, v in direct.items() if grads.get(k) is v}
         if written is not None:
             written.update(direct[k].data_ptr() for k in took)
-        return (None,) * 8 + tuple(None if k in took else grads[k] for k in _PARAM_ORDER)
+        return (None, None, grads.get("V"), grads.get("E"), grads.get("V_d"), None, None, None) + tuple(
+            None if k in took else grads[k] for k in _PARAM_ORDER)
 
 
 class _Linear(torch.autograd.Function):
-    """``[A1[gather] || A2] @ W.T + b + Cadd``; grads for W, b, A1 (ungathered only), A2, Cadd."""
+    """``[A1[gather] || A2] @ W.T + b + Cadd``; grads for W, b, A1, A2, Cadd.  A gathered ``A1`` gets its gradient when the
+    plan of the gather is handed in (``gather`` is then ``plan.src32``: the transpose is ``engine.src_sum``)."""
 
     @staticmethod
-    def forward(ctx, A1, W, b, A2, gather, n_rows, Cadd):
+    def forward(ctx, A1, W, b, A2, gather, n_rows, Cadd, plan=None):
+        if plan is not None and (gather is None or gather.data_ptr() != plan.src32.data_ptr()):   # (src_sum is the transpose of THAT gather and of no other)
+            raise ValueError("linear_fn: plan= goes with gather=plan.src32 (the gather whose transpose is engine.src_sum)")
         out = engine.linear(A1, W, b, A2=A2, gather1=gather, n_rows=n_rows, Cadd=Cadd)
         ctx.save_for_backward(A1, W, A2, gather)
+        ctx.plan = plan
         ctx.has_b = b is not None
         ctx.has_cadd = Cadd is not None
         return out
@@ -109,14 +124,16 @@ class _Linear(torch.autograd.Function):
             if not need_W:
                 gW = None
         if need_A1 or need_A2:
-            if gather is not None and need_A1:
-                raise NotImplementedError("gradient w.r.t. gathered features is not provided")
+            if gather is not None and need_A1 and ctx.plan is None:
+                raise NotImplementedError("gradient w.r.t. gathered features needs the plan of the gather (linear_fn(..., plan=))")
             gA = engine.linear(gZ, W.t().contiguous(), None)  # data gradient: the same MFMA kernel on W^T
             K1 = A1.shape[1]
             gA1 = gA[:, :K1] if need_A1 else None
+            if gather is not None and need_A1:   # rows were A1[src(e)]: sum the edge rows back onto their source atoms
+                gA1 = engine.src_sum(ctx.plan, gA1)
             gA2 = gA[:, K1:] if (need_A2 and A2 is not None) else None
         gCadd = gZ if (ctx.has_cadd and ctx.needs_input_grad[6]) else None
-        return gA1, gW, gb, gA2, None, None, gCadd
+        return gA1, gW, gb, gA2, None, None, gCadd, None
 
 
 class _Message(torch.autograd.Function):
@@ -165,8 +182,8 @@ def gather_src_fn(plan, S: Tensor) -> Tensor:
 
 
 def linear_fn(A1: Tensor, W: Tensor, b: Optional[Tensor], A2: Optional[Tensor] = None,
-              gather: Optional[Tensor] = None, n_rows: Optional[int] = None, Cadd: Optional[Tensor] = None) -> Tensor:
-    return _Linear.apply(A1, W, b, A2, gather, n_rows, Cadd)
+              gather: Optional[Tensor] = None, n_rows: Optional[int] = None, Cadd: Optional[Tensor] = None, plan=None) -> Tensor:
+    return _Linear.apply(A1, W, b, A2, gather, n_rows, Cadd, plan)
 
 
 def message_fn(plan, H: Tensor) -> Tensor:

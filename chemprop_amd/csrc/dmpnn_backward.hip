@@ -907,9 +907,11 @@ size_t extra_wgrad_ws_floats(int64_t M, int N, int Kt) {
     return blocks > rows ? blocks : rows;
 }
 
-int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra, bool* extra_done) {
+int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra, bool* extra_done, const InputGrads* ig) {
     if (extra_done) *extra_done = false;
     DMPNN_CHECK_ARG(b != nullptr, "backward: null args");
+    DMPNN_CHECK_ARG(!ig || !(b->f.flags & (DMPNN_F_FUSED | DMPNN_F_MEGA | DMPNN_F_TILE_PLAN | DMPNN_F_ATOM)),
+                    "backward: input gradients are provided on the per-step general route only");
     const dmpnn_fwd_args& f = b->f;
     const int64_t nV = f.n_atoms, nE = f.n_edges, h = f.d_h, dv = f.d_v, de = f.d_e;
     const bool has_vd = f.W_d != nullptr;
@@ -1363,11 +1365,14 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
         DMPNN_TRY(launch_wgrad(a, L.p_o, slab_x, s, ws + L.w16g, &ns));
         DMPNN_TRY(launch_wgrad_reduce(slab_x, L.p_o, ns, (int)h, (int)(dv + h), 1, b->gW_o, dv + h, b->gb_o, s, pflags, pmask));
     }
-    const bool need_edges = b->gW_i || b->gb_i || b->gW_h || b->gb_h;
-    if (!need_edges) return DMPNN_OK;
+    // (input gradients, dmpnn_backward_inputs: gV and gE read gH0, so the data-gradient chain runs for them even with every parameter
+    //  frozen; gMv is dead once the chain has gathered from it and serves as the [n_atoms, ldh] scratch of the source sums)
+    auto inputs_tail = [&]() -> int { return ig ? input_grads(f, *ig, b->gout, b->ldgout, gZO, gH0, gMv, L.use16, s) : DMPNN_OK; };
+    const bool need_edges = b->gW_i || b->gb_i || b->gW_h || b->gb_h || (ig && (ig->gV || ig->gE));
+    if (!need_edges) return inputs_tail();
     if (nE == 0) {
         zero2d(b->gW_i, h, dv + de_i); zero2d(b->gb_i, 1, h); zero2d(b->gW_h, h, h + de_h); zero2d(b->gb_h, 1, h);
-        return DMPNN_OK;
+        return inputs_tail();
     }
     // gMv = gZO . W_o[:, d_v:]
     {
@@ -1477,7 +1482,7 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
         DMPNN_TRY(launch_wgrad(a, L.p_i, slab_x, s, ws + L.w16g, &ns));
         DMPNN_TRY(launch_wgrad_reduce(slab_x, L.p_i, ns, (int)h, (int)(dv + de_i), f.b_i ? 1 : 0, b->gW_i, dv + de_i, b->gb_i, s, pflags, pmask));
     }
-    return DMPNN_OK;
+    return inputs_tail();
 }
 
 }  // namespace dmpnn

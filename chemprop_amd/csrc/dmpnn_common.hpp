@@ -395,7 +395,17 @@ struct ExtraWgrad {
     float* gW; int64_t ldgw; float* gb; float* ws;
 };
 size_t extra_wgrad_ws_floats(int64_t M, int N, int Kt);
-int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra, bool* extra_done);
+// The gradients with respect to the block's INPUTS (dmpnn_inputgrad.hip; dmpnn_backward_inputs): one more optional argument of
+// backward_impl, taken by the per-step general route only.  Any output may be null; ws: >= input_grads_ws_floats() floats behind the
+// backward pass's own workspace (the transposed weight slices and their pre-splits).
+struct InputGrads { float* gV; int64_t ldgv; float* gE; int64_t ldge; float* gV_d; int64_t ldgvd; float* ws; };
+size_t input_grads_ws_floats(const dmpnn_fwd_args& f);
+// S[v] = sum_{e': dst(e') = v} G[rev(e')] (= sum_{e: src(e) = v} G[e] on a symmetric graph; NaN on a plan that is not)
+int launch_src_sum(const PlanView& pv, int64_t nV, int64_t nE, int64_t h, const float* G, int64_t ldg, float* S, int64_t lds, hipStream_t s);
+// gV_d from gout, gE from G0, gV from [GO || S] (S: [n_atoms, ldh] scratch) — the tail of the data-gradient chain
+int input_grads(const dmpnn_fwd_args& f, const InputGrads& ig, const float* gout, int64_t ldgout, const float* GO, const float* G0, float* S,
+                bool use16, hipStream_t s);
+int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra, bool* extra_done, const InputGrads* ig = nullptr);
 void wsplit16_job(WSplitJob* j, int64_t M, int C, const float* A1, int64_t lda1, const int* g1, int K1, const float* A2, int64_t lda2,
                   const int* g2, int K2, int ones, void* ws);
 int launch_wsplit16(WSplitArgs& a, hipStream_t s);

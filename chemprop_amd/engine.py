@@ -969,14 +969,23 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
     return out, st
 
 
-def backward(st: ForwardState, gout: Tensor, need: dict, out: Optional[dict] = None, launch: bool = True, g_edge: Optional[Tensor] = None):
+def backward(st: ForwardState, gout: Tensor, need: dict, out: Optional[dict] = None, launch: bool = True, g_edge: Optional[Tensor] = None,
+             inputs=None):
     """K6: parameter gradients of a kept forward.  ``need`` maps W_i/b_i/W_h/b_h/W_o/b_o/W_d/b_d -> bool.
+    ``inputs``: a set drawn from ``{"V", "E", "V_d"}`` — the call then goes through ``dmpnn_backward_inputs`` (a kept forward of the
+    per-step general route, bond messages, a built-in activation other than PReLU) and the returned dict also carries the gradients
+    with respect to those inputs under the same names (``E`` in the caller's edge order); empty / ``None``: ``dmpnn_backward``.
+    ``launch=False`` enqueues nothing and returns ``(grads, block, refs)``: ``block`` is the ``dmpnn_bwd_args`` of the call — with
+    ``inputs``, the ``dmpnn_bwd_inputs_args`` around it, its ``gV`` / ``gE`` / ``gV_d`` pointing at ``grads["V" | "E" | "V_d"]``.
     ``out``: optional ``{name: tensor}`` the kernels write the gradients INTO (contiguous fp32 of the parameter's shape, on
     the device — e.g. views of one flat gradient buffer, ``distributed.GradSync``); names missing there are allocated.
     ``g_edge``: a second gradient input, w.r.t. the kept ``H^(depth-1)`` rows (``dmpnn_bwd_args.g_edge``: the edge read-out of the
     mol-atom-bond blocks), ``[n_edges, d_h]`` in the kept tensors' row order — the backward tile kernel only."""
     from ._lib import BwdArgs
 
+    inputs = set(inputs) if inputs else set()
+    if not inputs <= {"V", "E", "V_d"}:   # (before anything is allocated or enqueued)
+        raise ValueError(f"backward: inputs must be drawn from {{'V', 'E', 'V_d'}}, got {sorted(map(str, inputs))}")
     lib = _lib.load()
     gout = _f32c(gout, "grad_output")
     dev = gout.device
@@ -998,7 +1007,8 @@ def backward(st: ForwardState, gout: Tensor, need: dict, out: Optional[dict] = N
     b.gout, b.ldgout = gout.data_ptr(), gout.stride(0)
     for k, g in grads.items():
         setattr(b, "g" + k, _ptr(g))
-    nbytes = lib.dmpnn_backward_ws_bytes(C.byref(st.args))
+    # (the workspace of dmpnn_backward_inputs is dmpnn_backward's plus the transposed weight slices behind it)
+    nbytes = (lib.dmpnn_backward_inputs_ws_bytes if inputs else lib.dmpnn_backward_ws_bytes)(C.byref(st.args))
     ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
     b.ws, b.ws_bytes = ws.data_ptr(), nbytes
     if g_edge is not None:
@@ -1006,11 +1016,52 @@ def backward(st: ForwardState, gout: Tensor, need: dict, out: Optional[dict] = N
         if g_edge.shape[0] != st.args.n_edges or g_edge.shape[1] < h or g_edge.stride(0) % 4:
             raise RuntimeError("backward: g_edge must be [n_edges, d_h] with a row stride that is a multiple of 4")
         b.g_edge, b.ld_gedge = g_edge.data_ptr(), g_edge.stride(0)
+    if inputs:   # (the block becomes dmpnn_bwd_inputs_args, `grads` also holds the input gradients it points to)
+        b = _inputs_block(st, b, grads, inputs, dev)
     if not launch:  # (trainer.FusedTrainer: the argument block only; `refs` keeps the scratch alive)
         return grads, b, (ws, gout)
+    if inputs:
+        with _OnDevice(dev):
+            _lib.check(lib.dmpnn_backward_inputs(C.byref(b), _stream_ptr(dev)), "dmpnn_backward_inputs")
+        return grads
     with _OnDevice(dev):
         _lib.check(lib.dmpnn_backward(C.byref(b), _stream_ptr(dev)), "dmpnn_backward")
     return grads
+
+
+def _inputs_block(st: ForwardState, b, grads: dict, inputs: set, dev):
+    """``dmpnn_bwd_inputs_args`` over the argument block ``backward`` built; the ``V`` / ``E`` / ``V_d`` gradients it points to are
+    allocated into ``grads``."""
+    from ._lib import BwdInputsArgs
+
+    d = st.dims
+    if "V_d" in inputs and not d["d_vd"]:
+        raise RuntimeError("backward: a gradient w.r.t. V_d needs a forward with W_d and V_d")
+    a = BwdInputsArgs()
+    a.b = b
+    nV, nE = int(st.args.n_atoms), int(st.args.n_edges)
+    for name, rows, width in (("V", nV, d["d_v"]), ("E", nE, d["d_e"]), ("V_d", nV, d["d_vd"])):
+        if name in inputs:
+            g = grads[name] = torch.empty(rows, width, dtype=torch.float32, device=dev)
+            setattr(a, "g" + name, g.data_ptr())
+            setattr(a, {"V": "ldgv", "E": "ldge", "V_d": "ldgvd"}[name], max(width, 1))
+    return a
+
+
+def src_sum(plan: GraphPlan, G: Tensor) -> Tensor:
+    """``S[v] = sum_{e: src(e) = v} G[e]`` (``dmpnn_src_sum``): the transpose of the row gather ``A[plan.src32]``, formed as the
+    incoming-edge segment sum of the rows taken through ``rev`` — a fixed order, no atomics; NaN on an asymmetric plan."""
+    G = _f32c(G, "G")
+    if G.dim() != 2 or int(G.shape[0]) != plan.n_edges:
+        raise RuntimeError(f"src_sum: G must be [n_edges = {plan.n_edges}, d] but is {tuple(G.shape)}")
+    S = torch.empty(plan.n_atoms, G.shape[1], dtype=torch.float32, device=G.device)
+    if G.shape[1] == 0:
+        return S
+    with _OnDevice(G.device):
+        _lib.check(_lib.load().dmpnn_src_sum(plan.buf.data_ptr(), plan.n_atoms, plan.n_edges, G.shape[1], G.data_ptr(),
+                                             G.stride(0) if plan.n_edges else G.shape[1], S.data_ptr(), S.stride(0) if plan.n_atoms else G.shape[1],
+                                             _stream_ptr(G.device)), "dmpnn_src_sum")
+    return S
 
 
 def message_bwd(plan: GraphPlan, gM: Tensor) -> Tensor:

@@ -21,7 +21,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib, engine
-from .autograd import mp_forward
+from .autograd import input_grad_plan, input_grad_wanted, mp_forward
 from .data import BatchMolGraph as _OwnBatch
 
 DEFAULT_ATOM_FDIM, DEFAULT_BOND_FDIM = 72, 14  # chemprop/conf.py:8 (v2 featurizers)
@@ -392,6 +392,10 @@ def bond_message_passing_forward(mp, bmg, V_d: Optional[Tensor] = None) -> Tenso
     if not light and torch.is_grad_enabled() and V_d is None:
         # a training forward bound for the tile kernels: the tile plan (DMPNN_F_TILE_PLAN)
         light = _training_plan_kind(mp, bmg) if oversize is not True else False
+    # an input that requires grad (attributions on a frozen model in eval() included): a full plan and the general route, whatever the
+    # parameters say — the two routes that return input gradients read the CSR arrays and rev
+    in_grad = input_grad_wanted(bmg.V, bmg.E, V_d)
+    light, cap = input_grad_plan(in_grad, light, 2)
     # (a tile plan: K0 is deferred into the forward's own call where the library can run it with the weight pre-split in ONE launch)
     plan = engine.GraphPlan.from_bmg(bmg, light=light, launch="defer" if light == "tiles" else True)
     own = getattr(bmg, "plan_table", None)
@@ -406,6 +410,7 @@ def bond_message_passing_forward(mp, bmg, V_d: Optional[Tensor] = None) -> Tenso
     level = _route(mp, plan, n_mols, getattr(bmg, "batch", None))
     if oversize is True:
         level = min(level, 1)
+    level = min(level, cap)
     out = mp_forward(mp, plan, bmg.V, bmg.E, V_d, max_level=level)
     last = mp.__dict__.pop("_dmpnn_last", None)  # (the forward's workspace must not outlive the call)
     mp.__dict__["_dmpnn_route"] = getattr(last, "route", None)  # diagnostics: the route the last slow-path forward took
@@ -596,9 +601,11 @@ def atom_message_passing_forward(mp, bmg, V_d: Optional[Tensor] = None) -> Tenso
     # activation, molecules that fit a tile, d_e <= 16.  Everything else: the per-step kernels chained below. ----
     act, slope, slope_t = classify_activation(mp.tau)
     grad = torch.is_grad_enabled() and any(p.requires_grad for p in mp.parameters())
+    # V, E or V_d requires grad: the rows route on a full plan (every row Function below has a data gradient), also with the block frozen
+    in_grad = input_grad_wanted(V, E, V_d)
     # (an oversize molecule is NaN on the atom variant of the tile kernels — their generic path knows bond messages only — so the
     #  host must KNOW: counted on the device for a foreign batch, batch_oversize)
-    if (not grad and not has_vd and act != "custom" and not mp.undirected and not (mp.training and mp.dropout.p > 0)
+    if (not grad and not in_grad and not has_vd and act != "custom" and not mp.undirected and not (mp.training and mp.dropout.p > 0)
             and 1 <= int(E.shape[1]) <= 16 and int(E.shape[0]) > 0 and batch_oversize(bmg, n_mols) is False):
         nV_, nE_ = int(V.shape[0]), int(E.shape[0])
         loader_tiles = getattr(bmg, "tiles", None) is not None or (
@@ -621,7 +628,7 @@ def atom_message_passing_forward(mp, bmg, V_d: Optional[Tensor] = None) -> Tenso
             plan = engine.GraphPlan.from_bmg(bmg)
     elif (grad and not has_vd and act not in ("custom", "prelu") and not mp.undirected and not (mp.training and mp.dropout.p > 0)
           and 2 <= int(E.shape[1]) <= 16 and int(E.shape[1]) % 2 == 0 and int(E.shape[0]) > 0 and batch_oversize(bmg, n_mols) is False
-          and not V.requires_grad and not E.requires_grad):
+          and not in_grad):
         # ---- round 4: TRAINING on the tile kernels (DMPNN_F_ATOM | DMPNN_F_KEEP): one forward launch that keeps what the backward tile
         # kernel and the weight-gradient products read (sign bits or H^(t), M^(t), the bond-feature half of the messages), one autograd
         # node — the bond block's (backward.FusedMP).  Molecules beyond the tile, W_d, active dropout: the chain below. ----
@@ -648,11 +655,14 @@ def atom_message_passing_forward(mp, bmg, V_d: Optional[Tensor] = None) -> Tenso
     mp.__dict__["_dmpnn_route"] = "rows/atom"
     tau, drop = mp.tau, mp.dropout
     nE = plan.n_edges
-    H0 = linear_fn(V, mp.W_i.weight, mp.W_i.bias, gather=plan.src32, n_rows=nE)
+    H0 = linear_fn(V, mp.W_i.weight, mp.W_i.bias, gather=plan.src32, n_rows=nE, plan=plan if in_grad else None)
     H = tau(H0)
     if mp.depth > 1 and nE:
-        with torch.no_grad():
-            ME = engine.gather_rows(engine.aggregate(plan, E), plan.src32)      # [E, d_e], constant over the loop
+        if torch.is_grad_enabled() and E.requires_grad:
+            ME = gather_src_fn(plan, aggregate_fn(plan, E))                     # (the same two kernels, with their transposes)
+        else:
+            with torch.no_grad():
+                ME = engine.gather_rows(engine.aggregate(plan, E), plan.src32)      # [E, d_e], constant over the loop
     rev = None
     for _ in range(1, mp.depth):
         if mp.undirected:

@@ -57,7 +57,9 @@ extern "C" {
  * and dmpnn_step_args.n_extra / extra (multicomponent models: zero in an older caller, which is one block); dmpnn_head_args.ffn_dropout_p /
  * ffn_dropout_seed (the predictor's dropout as a hash mask: zero in an older caller, which is no dropout); DMPNN_MOLAGG_ATTENTIVE with
  * dmpnn_molagg_attn_fwd / _bwd / _ws_bytes and dmpnn_head_args.att_W / att_b / g_att_W / g_att_b (zero in an older caller); DMPNN_F_UNDIRECTED_MASK
- * (a flag bit no older caller sets: dropout_p > 0 with DMPNN_F_UNDIRECTED on the per-step general route, DMPNN_EINVAL without it). */
+ * (a flag bit no older caller sets: dropout_p > 0 with DMPNN_F_UNDIRECTED on the per-step general route, DMPNN_EINVAL without it).
+ * Added, same version (new entries only; no existing struct or entry changes): dmpnn_backward_inputs / dmpnn_backward_inputs_ws_bytes /
+ * dmpnn_bwd_inputs_args (gradients with respect to V, E and V_d on the per-step general route) and dmpnn_src_sum. */
 #define DMPNN_ABI_VERSION 15
 
 enum dmpnn_status {
@@ -523,7 +525,8 @@ int dmpnn_train_route(const dmpnn_fwd_args* a, int64_t n_mols, int32_t have, int
  * K6  backward.  The reference has no backward code of its own: gradients come from torch autograd
  * through the ATen ops of base.py:196-212 / mixins.py:8-18 (training: models/model.py:148-161).
  * These entry points are what a torch.autograd.Function around the forward calls.
- * Gradients are produced for the parameters only (features and indices are data).
+ * dmpnn_backward produces the gradients of the parameters (in training, features are data); dmpnn_backward_inputs (below) also
+ * those of the inputs V, E and V_d, on the per-step general route.  Indices are data everywhere.
  * ------------------------------------------------------------------------------------------- */
 typedef struct dmpnn_bwd_args {
     dmpnn_fwd_args f;                    /* the forward call, with its KEPT workspace
@@ -542,6 +545,34 @@ typedef struct dmpnn_bwd_args {
 } dmpnn_bwd_args;
 size_t dmpnn_backward_ws_bytes(const dmpnn_fwd_args* f);
 int dmpnn_backward(const dmpnn_bwd_args* a, void* stream);
+
+/* K6 with the gradients of the block's INPUTS (attributions on a frozen model, a learned featurizer or descriptor network in front of
+ * the block).  dmpnn_backward's chain ends with GO = dL/d(W_o [V || Mv] + b_o) and G0 = dL/d(W_i [V[src] || E] + b_i); from them
+ *     gE   = G0 . W_i[:, d_v:]
+ *     gV   = GO . W_o[:, :d_v] + S . W_i[:, :d_v],   S[v] = sum_{e: src(e) = v} G0[e]     (dmpnn_src_sum: sum first, then contract)
+ *     gV_d = gout . W_d[:, d_h:]
+ * Per-step general route only: b.f is a kept forward WITHOUT DMPNN_F_FUSED / DMPNN_F_MEGA / DMPNN_F_TILE_PLAN / DMPNN_F_ATOM (bond
+ * messages, directed or DMPNN_F_UNDIRECTED, with or without W_d, every built-in activation but PReLU); anything else, gV_d without
+ * b.f.W_d, or a leading dimension below its width is DMPNN_EINVAL before any device work.  The parameter gradients of `b` are written
+ * exactly as dmpnn_backward writes them (any may be NULL — all of them: the data-gradient chain still runs for gV / gE).  Outputs
+ * are overwritten, not accumulated.  n_edges == 0: gV = GO . W_o[:, :d_v], gE is empty; n_atoms == 0: nothing is written.  S holds
+ * on a symmetric graph only: on a plan whose header says otherwise (DMPNN_HDR_FLAGS bit 0) gV is NaN, never silently wrong.
+ * b.ws / b.ws_bytes: >= dmpnn_backward_inputs_ws_bytes(&b.f) (dmpnn_backward's workspace + the pre-split / transposed weight slices);
+ * DMPNN_ENOSPC otherwise. */
+typedef struct dmpnn_bwd_inputs_args {
+    dmpnn_bwd_args b;                 /* as for dmpnn_backward; any parameter-gradient pointer may be NULL */
+    float* gV;   int64_t ldgv;        /* [n_atoms, d_v]  or NULL */
+    float* gE;   int64_t ldge;        /* [n_edges, d_e]  or NULL; rows in the caller's edge order */
+    float* gV_d; int64_t ldgvd;       /* [n_atoms, d_vd] or NULL (needs b.f.W_d) */
+} dmpnn_bwd_inputs_args;
+size_t dmpnn_backward_inputs_ws_bytes(const dmpnn_fwd_args* f);
+int dmpnn_backward_inputs(const dmpnn_bwd_inputs_args* a, void* stream);
+/* S[v, 0:d_h] = sum_{e': dst(e') = v} G[rev(e'), 0:d_h] — on a symmetric graph the sum of G over the edges that LEAVE v, the transpose
+ * of the gather A[src(e)] (mixins.py:8-9).  One pass over the plan's incoming-edge CSR in its fixed order (no atomics: the same bits
+ * on every call), 16-byte row quads where d_h, the strides and the pointers allow it; any d_h >= 1, ldg / lds >= d_h, columns beyond
+ * d_h are never written.  A full plan (dmpnn_prepare); on an asymmetric graph, a light plan or a tile plan every row is NaN. */
+int dmpnn_src_sum(const void* plan, int64_t n_atoms, int64_t n_edges, int64_t d_h, const float* G, int64_t ldg, float* S, int64_t lds,
+                  void* stream);
 
 /* Row-level backward (used when the activation / dropout modules run in torch between kernels).
  *   message_bwd    gH[e'] = sum_{e: src(e)=dst(e')} gM[e] - gM[rev(e')]   (transpose of K2, directed)
