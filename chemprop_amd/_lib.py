@@ -21,7 +21,7 @@ INCLUDE = os.path.join(_ROOT, "include")
 # DMPNN_LIB: an alternative build of the same sources (kernel experiments: scripts/build_variant.py), same ABI
 LIB_PATH = os.environ.get("DMPNN_LIB") or os.path.join(_HERE, "libdmpnn_gfx950.so")
 SOURCES = ["dmpnn_abi.hip", "dmpnn_prepare.hip", "dmpnn_segment.hip", "dmpnn_gemm.hip", "dmpnn_gemm_p1.hip",
-           "dmpnn_gemm_p2.hip", "dmpnn_gemm_p3.hip", "dmpnn_gemm_p4.hip", "dmpnn_gemm_s1.hip", "dmpnn_rows16_drop.hip", "dmpnn_mega.hip", "dmpnn_mega16.hip", "dmpnn_mega16_lp.hip", "dmpnn_mega16_bwd.hip", "dmpnn_rows16.hip", "dmpnn_step16.hip", "dmpnn_bstep16.hip", "dmpnn_backward.hip", "dmpnn_molagg.hip", "dmpnn_collate.hip", "dmpnn_tiles_large.hip", "dmpnn_optim.hip", "dmpnn_wgrad16.hip", "dmpnn_head.hip", "dmpnn_vd.hip", "dmpnn_attn.hip", "dmpnn_inputgrad.hip"]
+           "dmpnn_gemm_p2.hip", "dmpnn_gemm_p3.hip", "dmpnn_gemm_p4.hip", "dmpnn_gemm_s1.hip", "dmpnn_rows16_drop.hip", "dmpnn_mega.hip", "dmpnn_mega16.hip", "dmpnn_mega16_lp.hip", "dmpnn_mega16_bwd.hip", "dmpnn_rows16.hip", "dmpnn_step16.hip", "dmpnn_bstep16.hip", "dmpnn_backward.hip", "dmpnn_molagg.hip", "dmpnn_collate.hip", "dmpnn_tiles_large.hip", "dmpnn_optim.hip", "dmpnn_wgrad16.hip", "dmpnn_head.hip", "dmpnn_vd.hip", "dmpnn_attn.hip", "dmpnn_inputgrad.hip", "dmpnn_predict.hip"]
 HEADERS = ["dmpnn_common.hpp", "dmpnn_spill_impl.hpp", "dmpnn_gemm_impl.hpp", "dmpnn_mega_impl.hpp", "dmpnn_mega16_impl.hpp", "dmpnn_mega16_bwd_impl.hpp", "dmpnn_rows16_impl.hpp", "dmpnn_seg16.hpp", "dmpnn_step16_impl.hpp"]
 ABI_VERSION = 15
 PLAN_NOFFSETS = 15
@@ -39,6 +39,7 @@ EXPORTS = [
     "dmpnn_vd_ws_bytes", "dmpnn_vd_forward", "dmpnn_vd_backward", "dmpnn_linear16_dropout_fwd",
     "dmpnn_molagg_attn_ws_bytes", "dmpnn_molagg_attn_fwd", "dmpnn_molagg_attn_bwd",
     "dmpnn_backward_inputs", "dmpnn_backward_inputs_ws_bytes", "dmpnn_src_sum",
+    "dmpnn_predict_head_ws_bytes", "dmpnn_predict_head_wsplit_bytes", "dmpnn_predict_head",
 ]
 
 ACT = {"none": 0, "relu": 1, "leakyrelu": 2, "prelu": 3, "tanh": 4, "elu": 5}
@@ -171,6 +172,20 @@ class MolAggAttnArgs(C.Structure):
 
 
 MOLAGG_ATTENTIVE = 3   # (DMPNN_MOLAGG_ATTENTIVE: dmpnn_head_args.agg_mode)
+PREDICT_TRANSFORM = {"none": 0, "unscale": 1, "sigmoid": 2, "softmax": 3, "mve": 4, "evidential": 5, "quantile": 6}   # enum dmpnn_predict_transform
+PREDICT_MAX_OUT = 64   # (DMPNN_PREDICT_MAX_OUT: output layers up to this width ride in k_predict_tail)
+
+
+class PredictArgs(C.Structure):
+    """``dmpnn_predict_args``: the inference head (``dmpnn_predict_head``)."""
+    _fields_ = [
+        ("head", HeadArgs),
+        ("transform", C.c_int32),
+        ("out_mean", C.c_void_p), ("out_scale", C.c_void_p),
+        ("preds", C.c_void_p),
+        ("fingerprint", C.c_void_p), ("ld_fp", C.c_int64),
+        ("wsplit", C.c_void_p), ("wsplit_bytes", C.c_size_t), ("wsplit_ready", C.c_int32),
+    ]
 
 
 class TrainRouteInfo(C.Structure):
@@ -230,6 +245,31 @@ def _stale() -> bool:
     return any(os.path.getmtime(d) > t for d in deps if os.path.isfile(d))
 
 
+# sources whose kernels must not spill: compiled with the resource remarks on, a kernel with scratch fails the build
+NO_SCRATCH = ("dmpnn_predict.hip",)
+
+
+def _check_no_scratch(src: str, remarks: str, verbose: bool) -> None:
+    """``-Rpass-analysis=kernel-resource-usage`` of one source: every kernel's VGPRs / LDS / scratch (printed when ``verbose``);
+    ``RuntimeError`` for a kernel with scratch."""
+    import re
+
+    fields = ("Function Name", "VGPRs", "LDS Size [bytes/block]", "ScratchSize [bytes/lane]")
+    found = [dict()]
+    for key, val in re.findall(r"remark:\s+(%s): (\S+)" % "|".join(re.escape(f) for f in fields), remarks):
+        if key == "Function Name":
+            found.append({})
+        found[-1][key] = val
+    kernels = [k for k in found if "Function Name" in k]
+    if not kernels:
+        raise RuntimeError(f"{src}: the compiler reported no kernel resource usage")
+    for k in kernels:
+        if verbose:
+            print(f"{os.path.basename(src)}: {k['Function Name']} VGPRs {k.get('VGPRs')} LDS {k.get(fields[2])} B scratch {k.get(fields[3])} B/lane")
+        if int(k.get(fields[3], "0")) != 0:
+            raise RuntimeError(f"{src}: kernel {k['Function Name']} spills ({k[fields[3]]} bytes of scratch per lane)")
+
+
 def build(force: bool = False, verbose: bool = False, defines=(), out: Optional[str] = None) -> str:
     """Compile every HIP source for gfx950 into ``chemprop_amd/libdmpnn_gfx950.so`` (``out`` / ``defines``: a variant build)."""
     lib_path = out or LIB_PATH
@@ -245,12 +285,15 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: Optional[
     with tempfile.TemporaryDirectory(prefix="dmpnn_build_") as tmp:
         def cc(src):
             obj = os.path.join(tmp, os.path.basename(src) + ".o")
-            cmd = [hipcc, *flags, "-c", src, "-o", obj]
+            no_scratch = os.path.basename(src) in NO_SCRATCH
+            cmd = [hipcc, *flags, *(["-Rpass-analysis=kernel-resource-usage"] if no_scratch else []), "-c", src, "-o", obj]
             if verbose:
                 print(" ".join(cmd))
             r = subprocess.run(cmd, capture_output=True, text=True)
             if r.returncode != 0:
                 raise RuntimeError(f"hipcc failed on {src} ({r.returncode}):\n{r.stdout}\n{r.stderr}")
+            if no_scratch:
+                _check_no_scratch(src, r.stderr, verbose)
             return obj
 
         with cf.ThreadPoolExecutor(max_workers=8) as ex:
@@ -339,7 +382,7 @@ def load() -> C.CDLL:
     size_t_fns = ("dmpnn_plan_bytes", "dmpnn_backward_ws_bytes", "dmpnn_linear_wgrad_ws_bytes", "dmpnn_forward_wsplit_bytes", "dmpnn_forward_spill_bytes",
                   "dmpnn_forward_keep_bits_bytes",
                   "dmpnn_molagg_ws_bytes", "dmpnn_linear16_wsplit_bytes", "dmpnn_head_ws_bytes", "dmpnn_clip_grad_ws_bytes", "dmpnn_forward_h0_bytes", "dmpnn_vd_ws_bytes",
-                  "dmpnn_molagg_attn_ws_bytes", "dmpnn_backward_inputs_ws_bytes")
+                  "dmpnn_molagg_attn_ws_bytes", "dmpnn_backward_inputs_ws_bytes", "dmpnn_predict_head_ws_bytes", "dmpnn_predict_head_wsplit_bytes")
     lib.dmpnn_linear16_wsplit_bytes.argtypes = [C.c_int64, C.c_int64]
     lib.dmpnn_linear16_ok.argtypes = [C.POINTER(GemmArgs)]
     lib.dmpnn_linear16_fwd.argtypes = [C.POINTER(GemmArgs), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
@@ -389,6 +432,9 @@ def load() -> C.CDLL:
     lib.dmpnn_molagg_attn_ws_bytes.argtypes = [C.POINTER(MolAggAttnArgs)]
     lib.dmpnn_molagg_attn_fwd.argtypes = [C.POINTER(MolAggAttnArgs), C.c_void_p]
     lib.dmpnn_molagg_attn_bwd.argtypes = [C.POINTER(MolAggAttnArgs), C.c_void_p]
+    lib.dmpnn_predict_head_ws_bytes.argtypes = [C.POINTER(PredictArgs)]
+    lib.dmpnn_predict_head_wsplit_bytes.argtypes = [C.POINTER(PredictArgs)]
+    lib.dmpnn_predict_head.argtypes = [C.POINTER(PredictArgs), C.c_void_p, C.c_int64, C.c_void_p]
     lib.dmpnn_split_row_floats.argtypes = [C.c_int64]
     lib.dmpnn_split_row_floats.restype = C.c_int64
     lib.dmpnn_debug_timestamps.argtypes = [C.c_void_p]

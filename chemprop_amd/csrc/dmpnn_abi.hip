@@ -18,6 +18,7 @@ void set_error(const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
+void reset_launch_count() { g_launches = 0; }
 // DMPNN_DEBUG_LDS_POISON=1 (debugging aid, round 6): after EVERY launch of the library the whole LDS of every CU is filled with a NaN
 // pattern (fp32 NaN = two f16 NaNs), on the legacy default stream — the stream the tests run on.  LDS is not cleared between kernels: a
 // kernel that reads LDS it never wrote multiplies, on a warm box, the previous kernel's finite leftovers (by a zero weight, typically:

@@ -15,6 +15,7 @@ namespace mega16 { struct SplitArgs; }   // (argument block of the weight pre-sp
 // ---- error plumbing -------------------------------------------------------------------------
 void set_error(const char* fmt, ...);
 void count_launch(const char* name);
+void reset_launch_count();   // (dmpnn_last_launch_count counts from here: the entry points that report their launches)
 
 #define DMPNN_CHECK_ARG(cond, ...)                 \
     do {                                           \
@@ -181,6 +182,8 @@ __device__ __forceinline__ float4 apply_act4(float4 z, int act, float slope) {
     return make_float4(apply_act(z.x, act, slope), apply_act(z.y, act, slope),
                        apply_act(z.z, act, slope), apply_act(z.w, act, slope));
 }
+// F.softplus (beta 1, threshold 20): the criterion kernels' and the inference tail's
+__device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 // d tau / dz given pre-activation z (when available) or output y.
 __device__ __forceinline__ float act_grad_from_out(float y, int act, float slope) {
     switch (act) {
@@ -433,6 +436,20 @@ int launch_mega16_backward(const dmpnn_fwd_args& f, const float* gHO, int64_t ld
 int vd_check_args(const dmpnn_vd_args* a, bool bwd);   // every argument check of dmpnn_vd_forward (bwd: of dmpnn_vd_backward), no device work
 int vd_forward_impl(const dmpnn_vd_args* a, void* stream);
 int vd_backward_impl(const dmpnn_vd_args* a, void* stream, bool split_ready);
+
+// The inference head's last launch (dmpnn_predict.hip: k_predict_tail) — per molecule row the output layer raw = A W^T + b (n_out <=
+// DMPNN_PREDICT_MAX_OUT; W == NULL: `raw` was written by a contraction in front and is only read), the predictor's output transform
+// (enum dmpnn_predict_transform over t tasks, nc classes per task for the softmax; mean / scale [t] or both NULL) into `preds`
+// (NULL: not wanted) and the row's fp_w columns of Z into `fp` (NULL: not wanted).
+struct PredictTail {
+    const float* A; int64_t lda; int K;            // the output layer's input rows [B, K]
+    const float* W; const float* b; int n_out;     // [n_out, K] (nn.Linear layout), [n_out] | NULL
+    int64_t B;
+    float* raw;                                    // [B, n_out]
+    float* preds; int transform, t, nc; const float* mean; const float* scale;
+    float* fp; int64_t ld_fp; const float* Z; int64_t ldz; int fp_w;
+};
+int launch_predict_tail(const PredictTail& q, hipStream_t s);
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 

@@ -244,8 +244,7 @@ __device__ __forceinline__ float pinball(float e, float tau, float* g) {
     if (g) *g = e > 0.f ? -tau : (e < 0.f ? 1.f - tau : 0.5f - tau);
     return fmaxf(tau * e, (tau - 1.f) * e);
 }
-// F.softplus (beta 1, threshold 20) and its derivative
-__device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
+// the derivative of F.softplus (softplus_f, dmpnn_common.hpp: beta 1, threshold 20)
 __device__ __forceinline__ float softplus_d(float x) { return x > 20.f ? 1.f : 1.f / (1.f + expf(-x)); }
 // digamma for x >= 1 (alpha = softplus + 1): the recurrence up to x >= 6, then the asymptotic series (error < 1e-7 there)
 __device__ __forceinline__ float digamma_f(float x) {
@@ -647,6 +646,7 @@ struct AggBnArgs {
     long long* dbg;                        // optional cycle stamps: [0..5] column workgroup 1, [6..9] the first split workgroup
     int dh_c; int64_t nBt;                 // a multicomponent fingerprint: column c of X / Y is column c % dh_c of component c / dh_c, whose
                                            // molecule r is c / dh_c B + r of the bounds table (nBt molecules); one block: dh_c = d, nBt = B
+    const int64_t* batch;                  // k_agg_bn_fwd_own_bounds: the batch vector [nV] the workgroups take the molecules' bounds from
 };
 // Geometry of the two column kernels: a workgroup = QPW column QUADS (16-byte loads and stores: a quarter of the memory instructions
 // of a thread-per-column layout, whose 1 500 four-segment wave loads per CU cost the aggregation 11 us) x 1024 / QPW row lanes; thread
@@ -683,8 +683,12 @@ __device__ __forceinline__ void quad_col_sum2(float4 (*red)[2][4], int tq, float
 #pragma unroll 4
     for (int w = 1; w < 16; ++w) { u = f4_add(u, red[w][0][tq]); v = f4_add(v, red[w][1][tq]); }
 }
-template <int QPW, int RR, bool BN>
-__global__ __launch_bounds__(1024) void k_agg_bn_fwd(AggBnArgs q) {
+// OWN (k_agg_bn_fwd_own_bounds, the inference head): no bounds table in memory — every column workgroup takes the molecules' atom
+// ranges and the validity flag from the batch vector itself, into LDS (k_mol_bounds_one's pass: nV x 8 bytes per workgroup, beside
+// the nV x 16 bytes per quad of H_v it is about to read; cheaper than the launch it replaces); nBt <= kOwnBoundsMols.
+constexpr int64_t kOwnBoundsMols = 2048;
+template <int QPW, int RR, bool BN, bool OWN>
+__device__ __forceinline__ void agg_bn_fwd_body(const AggBnArgs& q) {
     constexpr int kQLanes = 1024 / QPW;
     if ((int)blockIdx.x >= q.n_col_blocks) {   // (uniform per workgroup)
         if ((int)blockIdx.x >= q.n_col_blocks + q.n_split_blocks) {
@@ -712,15 +716,42 @@ __global__ __launch_bounds__(1024) void k_agg_bn_fwd(AggBnArgs q) {
     const int comp = ok ? c / q.dh_c : 0;
     const int cv = c - comp * q.dh_c;
     const int64_t mo = (int64_t)comp * a.B, nBt = q.nBt;
-    const gemm::rsrc_t rBd = gemm::make_rsrc(q.bounds, (unsigned)((3 * nBt + 4) * 4));
-    const int flag = col_ldi(rBd, true, 2 * nBt);
+    __shared__ int own_tb[OWN ? 2 * kOwnBoundsMols + 1 : 1];   // first[nBt] | end[nBt] | flag
+    int flag;
     int v0[RR], nv[RR], dn[RR];
+    if constexpr (OWN) {
+        for (int i = threadIdx.x; i < 2 * (int)nBt + 1; i += 1024) own_tb[i] = 0;
+        __syncthreads();
+        int bad = 0;
+        for (int64_t v = threadIdx.x; v < q.nV; v += 1024) {   // (k_mol_bounds_one's pass and rules)
+            const int64_t b = q.batch[v];
+            const int64_t prev = v > 0 ? q.batch[v - 1] : -1;
+            const int64_t next = v + 1 < q.nV ? q.batch[v + 1] : nBt;
+            if (b < 0 || b >= nBt) { bad |= 1; continue; }
+            if (b < prev) bad |= 2;
+            if (b != prev) own_tb[b] = (int)v;
+            if (b != next) own_tb[nBt + b] = (int)(v + 1);
+        }
+        if (bad) atomicOr(&own_tb[2 * nBt], bad);
+        __syncthreads();
+        flag = own_tb[2 * nBt];
 #pragma unroll
-    for (int i = 0; i < RR; ++i) {
-        const int64_t r = ty + (int64_t)kQLanes * i;
-        v0[i] = col_ldi(rBd, r < a.B, mo + r);
-        nv[i] = col_ldi(rBd, r < a.B, nBt + mo + r);
-        dn[i] = col_ldi(rBd, q.use_done && r < a.B, 2 * nBt + 4 + mo + r);
+        for (int i = 0; i < RR; ++i) {
+            const int64_t r = ty + (int64_t)kQLanes * i;
+            v0[i] = r < a.B ? own_tb[mo + r] : 0;
+            nv[i] = r < a.B ? own_tb[nBt + mo + r] : 0;
+            dn[i] = 0;
+        }
+    } else {
+        const gemm::rsrc_t rBd = gemm::make_rsrc(q.bounds, (unsigned)((3 * nBt + 4) * 4));
+        flag = col_ldi(rBd, true, 2 * nBt);
+#pragma unroll
+        for (int i = 0; i < RR; ++i) {
+            const int64_t r = ty + (int64_t)kQLanes * i;
+            v0[i] = col_ldi(rBd, r < a.B, mo + r);
+            nv[i] = col_ldi(rBd, r < a.B, nBt + mo + r);
+            dn[i] = col_ldi(rBd, q.use_done && r < a.B, 2 * nBt + 4 + mo + r);
+        }
     }
     // (batch norm's per-column constants: requested now, used behind the statistics)
     auto ldq = [&](const float* p) {
@@ -837,6 +868,10 @@ __global__ __launch_bounds__(1024) void k_agg_bn_fwd(AggBnArgs q) {
     }
     stamp();  // 5 end
 }
+template <int QPW, int RR, bool BN>
+__global__ __launch_bounds__(1024) void k_agg_bn_fwd(AggBnArgs q) { agg_bn_fwd_body<QPW, RR, BN, false>(q); }
+template <int QPW, int RR, bool BN>
+__global__ __launch_bounds__(1024) void k_agg_bn_fwd_own_bounds(AggBnArgs q) { agg_bn_fwd_body<QPW, RR, BN, true>(q); }
 
 struct BnAggBwdArgs {
     BnBwdArgs b;                           // gY = dl/dZ [B, d], X = H; gX unused (the rows go to the atoms)
@@ -1375,6 +1410,8 @@ size_t dmpnn_head_ws_bytes(const dmpnn_head_args* h) {
 namespace {
 int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* stream, bool bounds_done, ExtraWgrad* defer, bool agg_rode = false,
              bool check_only = false);
+// the inference head (dmpnn_predict_head) on the model `h` — p.head, or the attentive mode's head on one-atom molecules
+int predict_core(const dmpnn_predict_args& p, const dmpnn_head_args& h, const float* Hv, int64_t ldhv, void* stream, bool bounds_done, bool check_only);
 }  // namespace
 
 extern "C" {
@@ -1408,6 +1445,96 @@ int launch_bn_agg_bwd(const BnAggBwdArgs& q, bool bn, hipStream_t s) {
     DMPNN_CHECK_LAUNCH("k_bn_agg_bwd");
     return DMPNN_OK;
 }
+// Does the column kernel k_agg_bn_fwd take this call's aggregation and batch norm?  (DMPNN_HEAD=chain, read per call: the chain's kernels)
+// (the column kernels move 16-byte quads: widths and strides in multiples of 4 floats, 16-byte aligned rows)
+// (a multicomponent fingerprint: a quad must not straddle two components — d_h % 4 == 0 — or the chain takes it)
+bool head_cols_fused(const dmpnn_head_args& h, const float* Hv, int64_t ldhv, bool want_grad) {
+    const char* head_env = getenv("DMPNN_HEAD");
+    const bool chain = head_env && !strcmp(head_env, "chain");
+    const int64_t B = h.n_mols, nV = h.n_atoms, dc = h.d_h;
+    return !chain && B <= kRowsMaxB && nV > 0 && dc % 4 == 0 && ldhv % 4 == 0 && aligned16(Hv) &&
+           (!want_grad || (h.ldg % 4 == 0 && aligned16(h.gHv))) && (int64_t)nV * ldhv < (1ll << 29) &&
+           (!h.bn_weight || (aligned16(h.bn_weight) && aligned16(h.bn_bias) && aligned16(h.bn_running_mean) && aligned16(h.bn_running_var) &&
+                             (!h.g_bn_weight || aligned16(h.g_bn_weight)) && (!h.g_bn_bias || aligned16(h.g_bn_bias))));
+}
+// The front of a head call's forward, behind the bounds table: H = agg(H_v) [B, ldH], Z = bn(H) and the X_d columns — the predictor's
+// input Z [B, ldz] — into the workspace.  cols_fused (head_cols_fused): ONE column kernel, in whose launch the hidden layer's weight
+// split rides when `split` is given (the four-launch form); else the chain's kernels.  Shared by head_run and the inference head.
+struct HeadFront { const float* Z; int64_t ldz; float* Hm; int64_t ldH; };
+// lean (the inference head, see head_front_own_bounds): no bounds table was written — the column kernel's workgroups take the bounds from
+// the batch vector themselves, and the aggregation stays inside it beyond kFuseAggMols molecules too: two launches less.
+bool head_front_own_bounds(const dmpnn_head_args& h, bool cols_fused) { return cols_fused && head_ncomp(h) * h.n_mols <= kOwnBoundsMols; }
+int head_front(const dmpnn_head_args& h, const HeadLayout& L, const float* Hv, int64_t ldhv, void* stream, bool agg_rode, bool cols_fused,
+               const HeadSplit* split, HeadFront* out, bool lean = false) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t ncomp = head_ncomp(h), dc = h.d_h;
+    const int64_t B = h.n_mols, d = ncomp * dc, nV = h.n_atoms, nBt = ncomp * B;
+    const bool xd = h.X_d != nullptr;
+    unsigned char* ws = static_cast<unsigned char*>(h.ws);
+    // H = agg(H_v) [B, ldH] and bn(H) [B, ldY]; with descriptors bn(H) — or H itself without batch norm — is written straight into the
+    // first d_h columns of the fingerprint Zx [B, Kp], whose other columns are X_d and zeros (XdFill)
+    float* Zx = xd ? reinterpret_cast<float*>(ws + L.Zx) : nullptr;
+    const int64_t Kp = L.Kp;
+    float* Hm = (xd && !h.bn_weight) ? Zx : reinterpret_cast<float*>(ws + L.Hm);
+    const int64_t ldH = (xd && !h.bn_weight) ? Kp : d;
+    float* Ybn = xd ? Zx : reinterpret_cast<float*>(ws + L.Z);
+    const int64_t ldY = xd ? Kp : d;
+    XdFill xf{h.X_d, h.ld_xd, Zx, Kp, B, (int)d, (int)(Kp - d), (int)(h.dims[0] - d), 4096};
+    const float* Z = Hm;
+    int64_t ldz = ldH;
+    float* mean = reinterpret_cast<float*>(ws + L.mean);
+    float* invstd = reinterpret_cast<float*>(ws + L.invstd);
+    if (cols_fused) {
+        AggBnArgs q;
+        memset(&q, 0, sizeof(q));
+        q.b = BnArgs{Hm, ldH, Ybn, ldY, h.bn_weight, h.bn_bias, h.bn_running_mean, h.bn_running_var, mean, invstd,
+                     B, (int)d, h.bn_eps, h.bn_momentum, h.bn_training, h.bn_num_batches_tracked};
+        // the aggregation inside this launch up to 512 molecules (one launch less: 159 against 166 us per step at 64 molecules, 221
+        // against 220 at 512 — the column workgroups pull H_v at ~55 GB/s each, 5.5 MB over 38 of them); beyond that
+        // dmpnn_molagg_fwd — every CU — runs in front (DMPNN_HEAD_AGG=fused | split: the A/B switch)
+        const char* agg_env = getenv("DMPNN_HEAD_AGG");
+        const bool fuse_agg = agg_rode || lean || (agg_env ? !strcmp(agg_env, "fused") : B <= kFuseAggMols);   // (rode: only what the tile kernel left is summed here)
+        q.use_done = agg_rode ? 1 : 0;
+        if (!fuse_agg) DMPNN_TRY(molagg_fwd_rows(Hv, ldhv, nV, dc, nBt, ws + L.bounds, h.agg_mode, h.agg_norm, Hm, ldH, B, stream));
+        q.Hv = fuse_agg ? Hv : nullptr; q.ldhv = ldhv; q.nV = nV; q.bounds = reinterpret_cast<const int*>(ws + L.bounds); q.agg_mode = h.agg_mode; q.agg_norm = h.agg_norm;
+        const int qpw = col_quads(B);
+        q.n_col_blocks = (int)((d + 4 * qpw - 1) / (4 * qpw));
+        q.dbg = g_debug_stamps ? g_debug_stamps + 80 : nullptr;
+        q.dh_c = (int)dc; q.nBt = nBt;
+        q.batch = h.batch;
+        int split_blocks = 0;
+        if (split) {
+            q.split = *split;
+            split_blocks = split->ncb;
+        }
+        q.n_split_blocks = split_blocks;
+        const int xd_blocks = xd ? xd_fill_blocks(xf) : 0;   // (the descriptor columns of Zx: the launch's last workgroups)
+        q.xd = xf;
+        const dim3 grid((unsigned)(q.n_col_blocks + split_blocks + xd_blocks));
+        const bool bn = h.bn_weight != nullptr;
+        if (lean) DMPNN_COL_LAUNCH(k_agg_bn_fwd_own_bounds, qpw, B, bn, grid, s, q);
+        else if (fuse_agg || bn || split_blocks || xd_blocks) DMPNN_COL_LAUNCH(k_agg_bn_fwd, qpw, B, bn, grid, s, q);
+        DMPNN_CHECK_LAUNCH("k_agg_bn_fwd");
+        if (bn) { Z = Ybn; ldz = ldY; }
+    } else {
+        DMPNN_TRY(molagg_fwd_rows(Hv, ldhv, nV, dc, nBt, ws + L.bounds, h.agg_mode, h.agg_norm, Hm, ldH, B, stream));
+        if (xd) {
+            hipLaunchKernelGGL(k_xd_fill, dim3((unsigned)xd_fill_blocks(xf)), dim3(1024), 0, s, xf);
+            DMPNN_CHECK_LAUNCH("k_xd_fill");
+        }
+    }
+    if (h.bn_weight && !cols_fused) {
+        BnArgs b{Hm, ldH, Ybn, ldY, h.bn_weight, h.bn_bias, h.bn_running_mean, h.bn_running_var, mean, invstd,
+                 B, (int)d, h.bn_eps, h.bn_momentum, h.bn_training, h.bn_num_batches_tracked};
+        if (B <= kBnRegRows * kBnLanes) hipLaunchKernelGGL(k_bn_fwd<true>, dim3((unsigned)((d + kBnCols - 1) / kBnCols)), dim3(1024), 0, s, b);
+        else hipLaunchKernelGGL(k_bn_fwd<false>, dim3((unsigned)((d + kBnCols - 1) / kBnCols)), dim3(1024), 0, s, b);
+        DMPNN_CHECK_LAUNCH("k_bn_fwd");
+        Z = Ybn; ldz = ldY;
+    }
+    *out = HeadFront{Z, ldz, Hm, ldH};
+    return DMPNN_OK;
+}
+
 // defer (a whole training step only): the weight gradient of the predictor's FIRST layer is not launched here but described in
 // *defer — it rides in the launches of the block's backward pass (ExtraWgrad); its inputs (the layer's output gradient, the
 // layer's input) stay untouched in the workspace until then
@@ -1416,7 +1543,9 @@ int launch_bn_agg_bwd(const BnAggBwdArgs& q, bool bn, hipStream_t s) {
 // agg_mode == DMPNN_MOLAGG_ATTENTIVE: the attention forward into the aggregate A, the head as it is on A — B one-atom molecules under SUM,
 // a one-row sum is the row itself, so every form of the head below is taken unchanged — and the attention backward from A's gradient
 // into the caller's gHv / g_att_W / g_att_b.  bounds_done: K0 wrote the REAL batch's table at att_bounds.
-int head_attentive(const dmpnn_head_args& h, const float* Hv, int64_t ldhv, void* stream, bool bounds_done, ExtraWgrad* defer) {
+// pred (dmpnn_predict_head): the head on A is the inference head of *pred instead of head_run
+int head_attentive(const dmpnn_head_args& h, const float* Hv, int64_t ldhv, void* stream, bool bounds_done, ExtraWgrad* defer,
+                   const dmpnn_predict_args* pred = nullptr) {
     const int64_t B = h.n_mols, d = h.d_h, nV = h.n_atoms;
     DMPNN_CHECK_ARG(h.att_W && h.att_b, "head: DMPNN_MOLAGG_ATTENTIVE needs att_W and att_b");
     DMPNN_CHECK_ARG(h.n_components <= 1, "head: DMPNN_MOLAGG_ATTENTIVE takes one component (n_components %d)", (int)h.n_components);
@@ -1432,7 +1561,8 @@ int head_attentive(const dmpnn_head_args& h, const float* Hv, int64_t ldhv, void
     hi.gHv = want_grad ? (ws ? reinterpret_cast<float*>(ws + L.att_gA) : reinterpret_cast<float*>(&hi)) : nullptr; hi.ldg = d;
     hi.att_W = hi.att_b = nullptr; hi.g_att_W = hi.g_att_b = nullptr;
     const float* A = ws ? reinterpret_cast<const float*>(ws + L.att_A) : reinterpret_cast<const float*>(&hi);
-    DMPNN_TRY(head_run(&hi, A, d, stream, true, defer, false, true));   // every other argument check, before any device work
+    auto head_on_A = [&](bool check_only) { return pred ? predict_core(*pred, hi, A, d, stream, true, check_only) : head_run(&hi, A, d, stream, true, defer, false, check_only); };
+    DMPNN_TRY(head_on_A(true));   // every other argument check, before any device work
     if (!h.ws || h.ws_bytes < L.total) {
         set_error("head: workspace missing or too small (%zu < %zu bytes)", h.ws_bytes, L.total);
         return DMPNN_ENOSPC;
@@ -1449,7 +1579,7 @@ int head_attentive(const dmpnn_head_args& h, const float* Hv, int64_t ldhv, void
     q.gW = h.g_att_W; q.gb = h.g_att_b;
     q.ws = ws + L.att_ws; q.ws_bytes = L.att_ws_bytes;
     DMPNN_TRY(attn_fwd_impl(&q, reinterpret_cast<int*>(ws + L.bounds), reinterpret_cast<int64_t*>(ws + L.att_idb), stream));
-    DMPNN_TRY(head_run(&hi, A, d, stream, true, defer));
+    DMPNN_TRY(head_on_A(false));
     if (want_grad) DMPNN_TRY(attn_bwd_impl(&q, stream));
     return DMPNN_OK;
 }
@@ -1497,15 +1627,6 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     DMPNN_CHECK_ARG(aligned16(h.ws), "head: workspace must be 16-byte aligned");
     if (B == 0 || check_only) return DMPNN_OK;
     unsigned char* ws = static_cast<unsigned char*>(h.ws);
-    // H = agg(H_v) [B, ldH] and bn(H) [B, ldY]; with descriptors bn(H) — or H itself without batch norm — is written straight into the
-    // first d_h columns of the fingerprint Zx [B, Kp], whose other columns are X_d and zeros (XdFill)
-    float* Zx = xd ? reinterpret_cast<float*>(ws + L.Zx) : nullptr;
-    const int64_t Kp = L.Kp;
-    float* Hm = (xd && !h.bn_weight) ? Zx : reinterpret_cast<float*>(ws + L.Hm);
-    const int64_t ldH = (xd && !h.bn_weight) ? Kp : d;
-    float* Ybn = xd ? Zx : reinterpret_cast<float*>(ws + L.Z);
-    const int64_t ldY = xd ? Kp : d;
-    XdFill xf{h.X_d, h.ld_xd, Zx, Kp, B, (int)d, (int)(Kp - d), (int)(h.dims[0] - d), 4096};
     const int t_out = (int)h.dims[Ln];                                  // width of the output layer
     const int nc = h.loss == DMPNN_LOSS_CE ? h.n_classes : ((h.loss == DMPNN_LOSS_MVE || h.loss == DMPNN_LOSS_QUANTILE) ? 2 : (h.loss == DMPNN_LOSS_EVIDENTIAL ? 4 : 1));   // outputs per task
     const int t = t_out / nc;                                           // tasks (= columns of `targets`)
@@ -1515,68 +1636,22 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     // round 5: the four-launch form (see k_agg_bn_fwd) — aggregation + batch norm as ONE column kernel for <= kRowsMaxB molecules
     // (forward, inference included), the whole predictor + criterion + their backward as ONE row kernel when the shape fits
     const char* head_env = getenv("DMPNN_HEAD");
-    const bool chain = head_env && !strcmp(head_env, "chain");
-    // (the column kernels move 16-byte quads: widths and strides in multiples of 4 floats, 16-byte aligned rows)
-    // (a multicomponent fingerprint: a quad must not straddle two components — dc % 4 == 0 — or the chain takes it)
-    const bool cols_fused = !chain && B <= kRowsMaxB && nV > 0 && dc % 4 == 0 && ldhv % 4 == 0 && aligned16(Hv) &&
-                            (!want_grad || (h.ldg % 4 == 0 && aligned16(h.gHv))) && (int64_t)nV * ldhv < (1ll << 29) &&
-                            (!h.bn_weight || (aligned16(h.bn_weight) && aligned16(h.bn_bias) && aligned16(h.bn_running_mean) && aligned16(h.bn_running_var) &&
-                                              (!h.g_bn_weight || aligned16(h.g_bn_weight)) && (!h.g_bn_bias || aligned16(h.g_bn_bias))));
+    const bool cols_fused = head_cols_fused(h, Hv, ldhv, want_grad);
     const bool rows = cols_fused && want_grad && h.targets && rows_shape(h) && aligned16(h.W[0]);
     // (DMPNN_HEAD=rows: tests — a training call that does NOT take the four-launch form is an error instead of a silent chain)
     DMPNN_CHECK_ARG(!(head_env && !strcmp(head_env, "rows")) || rows || !want_grad, "head: DMPNN_HEAD=rows, but this shape takes the chain");
-    const float* Z = Hm;
-    int64_t ldz = ldH;
     float* mean = reinterpret_cast<float*>(ws + L.mean);
     float* invstd = reinterpret_cast<float*>(ws + L.invstd);
     SplitW W0f{ws + L.W0f, reinterpret_cast<float*>(ws + L.isf), (int)((h.dims[0] + 31) / 32)};
     SplitW W0b{ws + L.W0b, reinterpret_cast<float*>(ws + L.isb), (int)((h.dims[1] + 31) / 32)};
-    if (cols_fused) {
-        AggBnArgs q;
-        memset(&q, 0, sizeof(q));
-        q.b = BnArgs{Hm, ldH, Ybn, ldY, h.bn_weight, h.bn_bias, h.bn_running_mean, h.bn_running_var, mean, invstd,
-                     B, (int)d, h.bn_eps, h.bn_momentum, h.bn_training, h.bn_num_batches_tracked};
-        // the aggregation inside this launch up to 512 molecules (one launch less: 159 against 166 us per step at 64 molecules, 221
-        // against 220 at 512 — the column workgroups pull H_v at ~55 GB/s each, 5.5 MB over 38 of them); beyond that
-        // dmpnn_molagg_fwd — every CU — runs in front (DMPNN_HEAD_AGG=fused | split: the A/B switch)
-        const char* agg_env = getenv("DMPNN_HEAD_AGG");
-        const bool fuse_agg = agg_rode || (agg_env ? !strcmp(agg_env, "fused") : B <= kFuseAggMols);   // (rode: only what the tile kernel left is summed here)
-        q.use_done = agg_rode ? 1 : 0;
-        if (!fuse_agg) DMPNN_TRY(molagg_fwd_rows(Hv, ldhv, nV, dc, nBt, ws + L.bounds, h.agg_mode, h.agg_norm, Hm, ldH, B, stream));
-        q.Hv = fuse_agg ? Hv : nullptr; q.ldhv = ldhv; q.nV = nV; q.bounds = reinterpret_cast<const int*>(ws + L.bounds); q.agg_mode = h.agg_mode; q.agg_norm = h.agg_norm;
-        const int qpw = col_quads(B);
-        q.n_col_blocks = (int)((d + 4 * qpw - 1) / (4 * qpw));
-        q.dbg = g_debug_stamps ? g_debug_stamps + 80 : nullptr;
-        q.dh_c = (int)dc; q.nBt = nBt;
-        int split_blocks = 0;
-        if (rows) {
-            const int N = (int)h.dims[1], K = (int)h.dims[0];
-            q.split = HeadSplit{h.W[0], N, K, ws + L.W0f, ws + L.W0b, reinterpret_cast<float*>(ws + L.isf), W0f.nc, W0b.nc, (int)d};
-            split_blocks = W0b.nc;
-        }
-        q.n_split_blocks = split_blocks;
-        const int xd_blocks = xd ? xd_fill_blocks(xf) : 0;   // (the descriptor columns of Zx: the launch's last workgroups)
-        q.xd = xf;
-        const dim3 grid((unsigned)(q.n_col_blocks + split_blocks + xd_blocks));
-        const bool bn = h.bn_weight != nullptr;
-        if (fuse_agg || bn || split_blocks || xd_blocks) DMPNN_COL_LAUNCH(k_agg_bn_fwd, qpw, B, bn, grid, s, q);
-        DMPNN_CHECK_LAUNCH("k_agg_bn_fwd");
-        if (bn) { Z = Ybn; ldz = ldY; }
-    } else {
-        DMPNN_TRY(molagg_fwd_rows(Hv, ldhv, nV, dc, nBt, ws + L.bounds, h.agg_mode, h.agg_norm, Hm, ldH, B, stream));
-        if (xd) {
-            hipLaunchKernelGGL(k_xd_fill, dim3((unsigned)xd_fill_blocks(xf)), dim3(1024), 0, s, xf);
-            DMPNN_CHECK_LAUNCH("k_xd_fill");
-        }
-    }
-    if (h.bn_weight && !cols_fused) {
-        BnArgs b{Hm, ldH, Ybn, ldY, h.bn_weight, h.bn_bias, h.bn_running_mean, h.bn_running_var, mean, invstd,
-                 B, (int)d, h.bn_eps, h.bn_momentum, h.bn_training, h.bn_num_batches_tracked};
-        if (B <= kBnRegRows * kBnLanes) hipLaunchKernelGGL(k_bn_fwd<true>, dim3((unsigned)((d + kBnCols - 1) / kBnCols)), dim3(1024), 0, s, b);
-        else hipLaunchKernelGGL(k_bn_fwd<false>, dim3((unsigned)((d + kBnCols - 1) / kBnCols)), dim3(1024), 0, s, b);
-        DMPNN_CHECK_LAUNCH("k_bn_fwd");
-        Z = Ybn; ldz = ldY;
-    }
+    HeadSplit split;
+    memset(&split, 0, sizeof(split));
+    if (rows) split = HeadSplit{h.W[0], (int)h.dims[1], (int)h.dims[0], ws + L.W0f, ws + L.W0b, reinterpret_cast<float*>(ws + L.isf), W0f.nc, W0b.nc, (int)d};
+    HeadFront fr;
+    DMPNN_TRY(head_front(h, L, Hv, ldhv, stream, agg_rode, cols_fused, rows ? &split : nullptr, &fr));
+    const float* Z = fr.Z;
+    const int64_t ldz = fr.ldz, ldH = fr.ldH;
+    float* Hm = fr.Hm;
     if (rows) {
         const int N = (int)h.dims[1], K = (int)h.dims[0];
         float* gA1 = reinterpret_cast<float*>(ws + L.gA);
@@ -1748,6 +1823,152 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     return molagg_bwd_rows(gZ, ldgz, h.batch, nV, dc, nBt, ws + L.bounds, h.agg_mode, h.agg_norm, h.gHv, h.ldg, B, stream);
 }
 
+// ---- the inference head: dmpnn_predict_head (dmpnn.h) --------------------------------------------------------------------------------
+// outputs per task of an output transform and of a criterion
+int transform_per_task(int transform, int n_classes) {
+    return transform == DMPNN_PT_SOFTMAX ? n_classes : (transform == DMPNN_PT_EVIDENTIAL ? 4 : ((transform == DMPNN_PT_MVE || transform == DMPNN_PT_QUANTILE) ? 2 : 1));
+}
+int loss_per_task(const dmpnn_head_args& h) {
+    return h.loss == DMPNN_LOSS_CE ? h.n_classes : (h.loss == DMPNN_LOSS_EVIDENTIAL ? 4 : ((h.loss == DMPNN_LOSS_MVE || h.loss == DMPNN_LOSS_QUANTILE) ? 2 : 1));
+}
+// hidden layer l < n_layers - 1 as a contraction call: tau(A W_l^T + b_l) into C
+dmpnn_gemm_args predict_layer(const dmpnn_head_args& h, int l, int64_t M, const float* A, int64_t lda, float* C) {
+    dmpnn_gemm_args g;
+    memset(&g, 0, sizeof(g));
+    g.M = M; g.N = h.dims[l + 1]; g.K1 = h.dims[l];
+    g.A1 = A; g.lda1 = lda;
+    g.W = h.W[l]; g.ldw = h.dims[l]; g.bias = h.b[l];
+    g.C = C; g.ldc = h.dims[l + 1];
+    g.act = h.act; g.act_slope = h.act_slope;   // sigma of the NEXT block fused here (ffn.py:49-58)
+    return g;
+}
+// bytes of layer l's slot in dmpnn_predict_args.wsplit: its split image where the f16 row kernel takes the layer's shape — a rule of
+// the widths alone (the rows it reads live in the workspace: 16-byte aligned, strides Kp | d | dims[l]), so the slots of a model
+// do not move with the batch — else 0
+size_t predict_slot_bytes(const dmpnn_head_args& h, const HeadLayout& L, int l) {
+    const int64_t ld0 = h.X_d ? L.Kp : head_ncomp(h) * h.d_h;
+    const dmpnn_gemm_args g = predict_layer(h, l, 1, reinterpret_cast<const float*>(uintptr_t(256)), l == 0 ? ld0 : h.dims[l], nullptr);
+    return linear16_ok(g) ? linear16_wsplit_bytes(g.N, g.K1) : 0;
+}
+bool predict_sizes_ok(const dmpnn_predict_args* p) {
+    return p && p->head.n_layers >= 1 && p->head.n_layers <= DMPNN_MAX_FFN_LAYERS && p->head.d_h > 0 && p->head.n_mols >= 0 && p->head.n_components >= 0 &&
+           p->head.n_components <= DMPNN_MAX_COMPONENTS && p->transform >= DMPNN_PT_NONE && p->transform <= DMPNN_PT_QUANTILE;
+}
+size_t predict_wsplit_total(const dmpnn_head_args& h, const HeadLayout& L) {
+    size_t n = 0;
+    for (int l = 0; l + 1 < h.n_layers; ++l)
+        if (h.dims[l] > 0 && h.dims[l + 1] > 0) n += predict_slot_bytes(h, L, l);
+    return n;
+}
+// every rule of dmpnn.h that is the inference head's own (dmpnn_head's follow in predict_core), before any device work
+int predict_check(const dmpnn_predict_args* pp) {
+    DMPNN_CHECK_ARG(pp != nullptr, "predict_head: null args");
+    const dmpnn_predict_args& p = *pp;
+    const dmpnn_head_args& h = p.head;
+    bool grads = h.gHv || h.g_bn_weight || h.g_bn_bias || h.g_att_W || h.g_att_b;
+    for (int l = 0; l < DMPNN_MAX_FFN_LAYERS; ++l) grads = grads || h.gW[l] || h.gb[l];
+    DMPNN_CHECK_ARG(!grads, "predict_head: inference only — head.gHv and every head.g* gradient pointer must be NULL");
+    DMPNN_CHECK_ARG(h.bn_training == 0, "predict_head: inference only — head.bn_training must be 0 (running statistics)");
+    DMPNN_CHECK_ARG(h.ffn_dropout_p == 0.f, "predict_head: inference only — head.ffn_dropout_p must be 0 (got %g)", (double)h.ffn_dropout_p);
+    DMPNN_CHECK_ARG((p.out_mean == nullptr) == (p.out_scale == nullptr), "predict_head: out_mean and out_scale come together (both or neither)");
+    DMPNN_CHECK_ARG(p.transform >= DMPNN_PT_NONE && p.transform <= DMPNN_PT_QUANTILE, "predict_head: unknown transform %d", (int)p.transform);
+    DMPNN_CHECK_ARG(h.n_layers >= 1 && h.n_layers <= DMPNN_MAX_FFN_LAYERS, "predict_head: 1..%d predictor layers", DMPNN_MAX_FFN_LAYERS);
+    const int64_t n_out = h.dims[h.n_layers];
+    DMPNN_CHECK_ARG(n_out > 0 && n_out < (int64_t(1) << 24), "predict_head: bad output width %lld", (long long)n_out);
+    DMPNN_CHECK_ARG(p.transform != DMPNN_PT_SOFTMAX || (h.n_classes >= 2 && n_out % h.n_classes == 0),
+                    "predict_head: the softmax transform needs head.n_classes >= 2 dividing the output width (%d, %lld)", (int)h.n_classes, (long long)n_out);
+    DMPNN_CHECK_ARG((p.transform != DMPNN_PT_MVE && p.transform != DMPNN_PT_QUANTILE) || n_out % 2 == 0,
+                    "predict_head: the MVE / quantile transforms need an output layer 2 n_tasks wide (got %lld)", (long long)n_out);
+    DMPNN_CHECK_ARG(p.transform != DMPNN_PT_EVIDENTIAL || n_out % 4 == 0, "predict_head: the evidential transform needs an output layer 4 n_tasks wide (got %lld)",
+                    (long long)n_out);
+    if (h.targets) {
+        DMPNN_CHECK_ARG(h.loss >= DMPNN_LOSS_MSE && h.loss <= DMPNN_LOSS_QUANTILE, "head: unknown criterion %d", h.loss);
+        DMPNN_CHECK_ARG(loss_per_task(h) == transform_per_task(p.transform, h.n_classes),
+                        "predict_head: the criterion (%d) and the transform (%d) disagree on the outputs per task (%d against %d)", (int)h.loss, (int)p.transform,
+                        loss_per_task(h), transform_per_task(p.transform, h.n_classes));
+        DMPNN_CHECK_ARG(h.loss_out != nullptr, "predict_head: targets without loss_out");
+    }
+    DMPNN_CHECK_ARG(!p.fingerprint || p.ld_fp >= h.dims[0], "predict_head: ld_fp (%lld) < dims[0] (%lld)", (long long)p.ld_fp, (long long)h.dims[0]);
+    DMPNN_CHECK_ARG(!p.wsplit || aligned16(p.wsplit), "predict_head: wsplit must be 16-byte aligned");
+    return DMPNN_OK;
+}
+int predict_core(const dmpnn_predict_args& p, const dmpnn_head_args& h, const float* Hv, int64_t ldhv, void* stream, bool bounds_done, bool check_only) {
+    if (h.agg_mode == DMPNN_MOLAGG_ATTENTIVE) return head_attentive(h, Hv, ldhv, stream, bounds_done, nullptr, &p);
+    DMPNN_TRY(head_run(&h, Hv, ldhv, stream, bounds_done, nullptr, false, true));   // dmpnn_head's argument checks, and its workspace's size when there is one
+    const HeadLayout L = head_layout(h);
+    if (p.wsplit && p.wsplit_bytes < predict_wsplit_total(h, L)) {
+        set_error("predict_head: wsplit too small (%zu < %zu bytes)", p.wsplit_bytes, predict_wsplit_total(h, L));
+        return DMPNN_ENOSPC;
+    }
+    if (check_only && !h.ws) return DMPNN_OK;   // (the attentive mode's check pass: it judges the workspace's size itself)
+    if (!h.ws || h.ws_bytes < L.total) {
+        set_error("predict_head: workspace missing or too small (%zu < %zu bytes)", h.ws_bytes, L.total);
+        return DMPNN_ENOSPC;
+    }
+    const int64_t B = h.n_mols, nBt = head_ncomp(h) * B;
+    if (B == 0 || check_only) return DMPNN_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    unsigned char* ws = static_cast<unsigned char*>(h.ws);
+    const int Ln = h.n_layers;
+    // (the column kernel takes the bounds from the batch vector itself where it can: no launch for the table)
+    const bool cols_fused = head_cols_fused(h, Hv, ldhv, false), lean = !bounds_done && head_front_own_bounds(h, cols_fused);
+    if (!bounds_done && !lean) DMPNN_TRY(dmpnn_molagg_bounds(h.batch, h.n_atoms, nBt, ws + L.bounds, dmpnn_molagg_ws_bytes(nBt), stream));
+    HeadFront fr;
+    DMPNN_TRY(head_front(h, L, Hv, ldhv, stream, false, cols_fused, nullptr, &fr, lean));
+    // the hidden layers: the f16 row kernel on the layer's cached split image, or the fp32 contraction
+    const float* A = fr.Z;
+    int64_t lda = fr.ldz;
+    unsigned char* slot = static_cast<unsigned char*>(p.wsplit);
+    for (int l = 0; l + 1 < Ln; ++l) {
+        float* out = reinterpret_cast<float*>(ws + L.act[l]);
+        const dmpnn_gemm_args g = predict_layer(h, l, B, A, lda, out);
+        const size_t bytes = predict_slot_bytes(h, L, l);
+        if (p.wsplit && bytes && linear16_ok(g)) {
+            SplitWView w = split_weights_view_of(slot, g.N, g.K1);
+            if (!p.wsplit_ready) DMPNN_TRY(split_weights_view(g.W, g.ldw, g.N, g.K1, 0, slot, &w, s));
+            // up to kRowsMaxB molecules the training head's row kernel takes the layer (k_head_rows<., 1>: 16 molecules x 64 columns per
+            // workgroup, 160 workgroups at 512 x 300, from the same split image) where its loads fit — a reduction width of whole quads up
+            // to kRowsMaxK, 16-byte rows: k_rows16's 48-row tiles are 11 workgroups there (31 us against the fp32 contraction's 10.5)
+            if (B <= kRowsMaxB && g.K1 % 4 == 0 && g.K1 <= kRowsMaxK && lda % 4 == 0 && aligned16(A)) {
+                RowsArgs r;
+                memset(&r, 0, sizeof(r));
+                r.Z = A; r.ldz = lda; r.W0f = SplitW{w.p, w.inv_scale, w.nc}; r.b0 = g.bias; r.A1 = out;
+                r.B = B; r.N = (int)g.N; r.K = (int)g.K1; r.act = h.act; r.slope = h.act_slope;
+                const dim3 grid((unsigned)((B + 15) / 16), (unsigned)((g.N + 63) / 64));
+                if (g.K1 <= 128) hipLaunchKernelGGL((k_head_rows<2, 1>), grid, dim3(256), 0, s, r);
+                else if (g.K1 <= kRowsMaxWidth) hipLaunchKernelGGL((k_head_rows<5, 1>), grid, dim3(256), 0, s, r);
+                else hipLaunchKernelGGL((k_head_rows<8, 1>), grid, dim3(256), 0, s, r);
+                DMPNN_CHECK_LAUNCH("k_head_rows");
+            } else {
+                DMPNN_TRY(launch_linear16_view(g, w, nullptr, 0, s));
+            }
+        } else {
+            DMPNN_TRY(launch_linear(g, s));
+        }
+        if (p.wsplit) slot += bytes;
+        A = out; lda = h.dims[l + 1];
+    }
+    // the output layer, the transform and every store: one launch (beyond DMPNN_PREDICT_MAX_OUT outputs the layer is a contraction of
+    // its own and the launch transforms its rows)
+    const int n_out = (int)h.dims[Ln], per = transform_per_task(p.transform, h.n_classes);
+    PredictTail q{A, lda, (int)h.dims[Ln - 1], h.W[Ln - 1], h.b[Ln - 1], n_out, B, h.preds, p.preds, p.transform, n_out / per, per, p.out_mean, p.out_scale,
+                  p.fingerprint, p.ld_fp, fr.Z, fr.ldz, (int)h.dims[0]};
+    if (n_out > DMPNN_PREDICT_MAX_OUT) {
+        dmpnn_gemm_args g = predict_layer(h, Ln - 1, B, A, lda, h.preds);
+        g.act = DMPNN_ACT_NONE;
+        DMPNN_TRY(launch_linear(g, s));
+        q.W = nullptr;
+    }
+    if (q.W || q.preds || q.fp) DMPNN_TRY(launch_predict_tail(q, s));
+    if (!h.targets) return DMPNN_OK;
+    const int t = n_out / per;
+    LossArgs lq{h.preds, n_out, h.targets, t, h.weights, h.task_weights, h.lt_mask, h.gt_mask, nullptr, n_out, h.loss_out, B, t, h.loss, per,
+                h.evid_v_kl, h.evid_eps, h.quantile_alpha};
+    hipLaunchKernelGGL(k_loss, dim3(1), dim3(1024), 0, s, lq);
+    DMPNN_CHECK_LAUNCH("k_loss");
+    return DMPNN_OK;
+}
+
 constexpr AggRide kNoAggRide = {nullptr, 0, nullptr, nullptr, 0, 0, 0.f, false};
 
 // (round 6: on a tile plan built in the step from the batch vector, the tile kernels' launches are bounded by the batch's molecule count — a
@@ -1889,6 +2110,14 @@ int dmpnn_train_step(const dmpnn_step_args* a, void* stream) {
         DMPNN_TRY(dmpnn_adam_step(a->p, a->g, a->m, a->v, a->n_params, a->lr, a->beta1, a->beta2, a->eps, a->weight_decay, a->bias_corr1,
                                   a->sqrt_bias_corr2, a->grad_scale, a->dev_scalars, stream));
     return DMPNN_OK;
+}
+
+size_t dmpnn_predict_head_ws_bytes(const dmpnn_predict_args* p) { return predict_sizes_ok(p) ? head_layout(p->head).total : 0; }
+size_t dmpnn_predict_head_wsplit_bytes(const dmpnn_predict_args* p) { return predict_sizes_ok(p) ? predict_wsplit_total(p->head, head_layout(p->head)) : 0; }
+int dmpnn_predict_head(const dmpnn_predict_args* p, const float* Hv, int64_t ldhv, void* stream) {
+    reset_launch_count();
+    DMPNN_TRY(predict_check(p));
+    return predict_core(*p, p->head, Hv, ldhv, stream, false, false);
 }
 
 }  // extern "C"

@@ -301,6 +301,15 @@ class MPNN(nn.Module):
         """The tail of ``loss`` on torch ops: the criterion on ``predictor.train_step`` of the fingerprint ``Z``."""
         return criterion_loss(self.criterion, self.predictor.train_step(Z), targets, weights, lt_mask, gt_mask)
 
+    def predict(self, bmg, V_d: Optional[Tensor] = None, X_d: Optional[Tensor] = None) -> Tensor:
+        """``self(bmg, V_d, X_d)`` without autograd; in eval mode everything behind the block is ONE C call
+        (:func:`chemprop_amd.predict.fused_predict`) where the inference head takes this model and these inputs."""
+        from .predict import fused_predict
+
+        with torch.no_grad():
+            r = fused_predict(self, bmg, V_d, X_d)
+            return self(bmg, V_d, X_d) if r is None else r.preds
+
 
 class MulticomponentMPNN(MPNN):
     """``chemprop.models.MulticomponentMPNN`` (``models/multi.py``): a :class:`~chemprop_amd.nn.MulticomponentMessagePassing` block,
@@ -328,6 +337,10 @@ class MulticomponentMPNN(MPNN):
                 if l is not None:
                     return l
         return self._torch_loss(self.fingerprint(bmgs, V_ds, X_d), targets, weights, lt_mask, gt_mask)
+
+    def predict(self, bmgs, V_ds=None, X_d: Optional[Tensor] = None) -> Tensor:
+        """:meth:`MPNN.predict` on the components' batches: ``self(bmgs, V_ds, X_d)`` without autograd."""
+        return super().predict(bmgs, V_ds, X_d)
 
 
 def is_atom_block(mp) -> bool:
@@ -713,18 +726,23 @@ class _HeadLoss(torch.autograd.Function):
         return (None, gH, None, None, None, None, None, None, None, *gp)
 
 
+def _head_spec_key(model) -> tuple:
+    """What a spec cached on the model (``head_loss``, ``predict.predict_spec``) is keyed on: the identities of what it was read
+    from — swapping model.predictor / criterion / bn / agg, or changing a predictor dropout p, after the first call must not leave
+    the old modules in use (round-4 ADVICE)."""
+    pred = model.predictor
+    return (id(model.agg), id(model.bn), id(pred), id(getattr(pred, "criterion", None)), id(getattr(pred, "ffn", None)),
+            id(getattr(pred, "output_transform", None)),
+            tuple(float(getattr(m, "p", 0.0)) for m in pred.modules() if isinstance(m, nn.Dropout)) if isinstance(pred, nn.Module) else ())
+
+
 def head_loss(model, Hv: Tensor, batch: Tensor, n_mols: int, targets: Tensor, weights: Optional[Tensor] = None,
               lt_mask: Optional[Tensor] = None, gt_mask: Optional[Tensor] = None, X_d: Optional[Tensor] = None) -> Optional[Tensor]:
     """``criterion(predictor.train_step(cat(bn(agg(H_v, batch)), X_d)), targets, ...)`` (``models/model.py:152-157``) as ONE autograd
     node on the head kernels (:class:`_HeadLoss`); ``X_d``: the molecule descriptors already through ``X_d_transform`` (no gradient
     flows to them).  ``None`` when the head kernels do not implement this model or these inputs — ``X_d`` that needs a gradient
     included (the caller then runs the torch modules)."""
-    # (cached on the identities of what the spec was read from — swapping model.predictor / criterion / bn / agg, or changing a
-    #  predictor dropout p, after the first step must not leave the old modules in use: round-4 ADVICE)
-    pred = model.predictor
-    key = (id(model.agg), id(model.bn), id(pred), id(getattr(pred, "criterion", None)), id(getattr(pred, "ffn", None)),
-           id(getattr(pred, "output_transform", None)),
-           tuple(float(getattr(m, "p", 0.0)) for m in pred.modules() if isinstance(m, nn.Dropout)) if isinstance(pred, nn.Module) else ())
+    key = _head_spec_key(model)
     cached = model.__dict__.get("_dmpnn_head_spec")
     if cached is not None and cached[0] == key:
         spec = cached[1]

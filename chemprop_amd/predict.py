@@ -1,0 +1,190 @@
+"""Inference behind the block as ONE C call: ``dmpnn_predict_head`` (``include/dmpnn.h``).
+
+``MPNN.forward`` in eval mode runs, after ``message_passing``, the aggregation (one C call), ``nn.BatchNorm1d`` and ``torch.cat``
+on torch, one :class:`~chemprop_amd.nn.HipMLP` call per predictor layer and two to six torch ops of the predictor's output transform;
+``validation_step`` then forms the fingerprint a second time for ``val_loss``.  :func:`fused_predict` keeps the block's forward as
+it is and hands everything behind it — aggregation, eval-mode batch norm, ``X_d``, the predictor, its output transform, and the
+criterion on the raw outputs when targets are given — to the library in one call: three launches for the usual model, four with
+targets.  :meth:`chemprop_amd.model.MPNN.predict` is the entry a caller uses; it falls back to the modules where this returns ``None``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import NamedTuple, Optional
+
+import torch
+from torch import Tensor, nn
+
+from . import _lib, engine
+from .model import HeadSpec, _batch_vector_ok, _component_batch, _head_spec_key, _mro_names
+
+# the predictor classes (this package's mirrors and the reference's, by MRO name: nn/predictors.py) and the output transform their
+# eval-mode forward applies; the specific classes first — every one of them derives from RegressionFFN
+_TRANSFORM_OF = (("MveFFN", "mve"), ("EvidentialFFN", "evidential"), ("QuantileFFN", "quantile"),
+                 ("MulticlassClassificationFFN", "softmax"), ("BinaryClassificationFFN", "sigmoid"), ("RegressionFFN", "unscale"))
+_GROUP = {"mve": 2, "evidential": 4, "quantile": 2}
+
+
+class PredictResult(NamedTuple):
+    """``preds``: what ``model(bmg, V_d, X_d)`` returns in eval mode; ``raw``: the MLP's outputs ``[n_mols, n_out]``
+    (``predictor.train_step``'s values, in the MLP's column layout); ``fingerprint``: the predictor's input ``[n_mols, d]`` or
+    ``None``; ``loss``: the device tensor ``[loss, n_finite]`` of the criterion on ``raw`` or ``None`` (no targets)."""
+    preds: Tensor
+    raw: Tensor
+    fingerprint: Optional[Tensor]
+    loss: Optional[Tensor]
+
+
+class PredictSpec(HeadSpec):
+    """What ``dmpnn_predict_head`` needs to know of the model: :class:`~chemprop_amd.model.HeadSpec` with the predictor's dropout and
+    attentive aggregation allowed, plus the output transform (``transform``: a key of ``_lib.PREDICT_TRANSFORM``, told from the
+    predictor's class) and the ``UnscaleTransform`` behind it (``unscale``: the module, or ``None`` for ``nn.Identity``).  Raises
+    ``NotImplementedError`` for what the inference head does not take.  Also holds the per-model workspace and the cached split
+    images of the hidden layers' weights."""
+
+    def __init__(self, model):
+        super().__init__(model, ffn_dropout=True, attentive=True)
+        pred = model.predictor
+        names = _mro_names(pred)
+        self.transform = next((tr for cls, tr in _TRANSFORM_OF if cls in names), None)
+        if self.transform is None:
+            raise NotImplementedError(f"a predictor of a known class (got {type(pred).__name__})")
+        ot = pred.output_transform
+        self.unscale = None
+        if not isinstance(ot, nn.Identity):   # (HeadSpec: an UnscaleTransform by name — identity while training, X * scale + mean in eval mode)
+            if self.transform in ("sigmoid", "softmax"):
+                raise NotImplementedError("a classification predictor without an UnscaleTransform")
+            mean, scale = getattr(ot, "mean", None), getattr(ot, "scale", None)
+            if not (torch.is_tensor(mean) and torch.is_tensor(scale) and mean.numel() == self.n_tasks and scale.numel() == self.n_tasks):
+                raise NotImplementedError(f"an UnscaleTransform with {self.n_tasks} means and scales (one per task)")
+            self.unscale = ot
+        self._ws: Optional[Tensor] = None
+        self._wsplit: Optional[Tensor] = None
+        self._wsplit_key = None
+        self._sizes: dict = {}
+
+    def out_shape(self, n_mols: int) -> tuple:
+        """The shape ``model(...)`` returns in eval mode."""
+        if self.transform == "softmax":
+            return (n_mols, self.n_tasks, self.n_classes)
+        if self.transform in _GROUP:
+            return (n_mols, self.n_tasks, _GROUP[self.transform])
+        return (n_mols, self.n_tasks)
+
+    def hidden_key(self) -> tuple:
+        """Identity and version of every hidden layer's weight: the split images are current while this does not change."""
+        return tuple((lin.weight.data_ptr(), lin.weight._version) for lin in self.layers[:-1])
+
+
+def predict_spec(model) -> Optional[PredictSpec]:
+    """The model's :class:`PredictSpec`, cached on the model under the identities ``head_loss`` keys its own cache on; ``None``: refused."""
+    key = _head_spec_key(model)
+    cached = model.__dict__.get("_dmpnn_predict_spec")
+    if cached is not None and cached[0] == key:
+        spec = cached[1]
+    else:
+        try:
+            spec = PredictSpec(model)
+        except NotImplementedError as e:
+            spec = str(e)
+        model.__dict__["_dmpnn_predict_spec"] = (key, spec)
+    return None if isinstance(spec, str) else spec
+
+
+def _grown(buf: Optional[Tensor], nbytes: int, dev) -> Tensor:
+    if buf is None or buf.device != dev or buf.numel() < nbytes:
+        buf = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    return buf
+
+
+def fused_predict(model, bmg, V_d=None, X_d=None, *, targets: Optional[Tensor] = None, weights: Optional[Tensor] = None,
+                  lt_mask: Optional[Tensor] = None, gt_mask: Optional[Tensor] = None, fingerprint: bool = False) -> Optional[PredictResult]:
+    """``model(bmg, V_d, X_d)`` in eval mode: ``model.message_passing`` as it is, then ONE ``dmpnn_predict_head`` call for everything
+    behind it.  ``targets`` (with ``weights`` / ``lt_mask`` / ``gt_mask``): also the criterion on the raw outputs, chemprop's
+    ``val_loss``.  ``fingerprint=True``: also the predictor's input.  A multicomponent model takes lists, as its ``forward`` does.
+
+    ``None`` — the caller takes the module path — when the model is refused (:class:`PredictSpec`), is in training mode, grad mode
+    is on, the inputs are not on the device, a batch vector is not what the kernels read, or ``X_d`` / ``targets`` / ``weights``
+    are missing or misshapen.  The workspace and the split images of the hidden weights are kept per model: calls on one model belong
+    on one stream.  An in-place change of a hidden weight through ``.data`` does not advance its version: clear
+    ``model.__dict__["_dmpnn_predict_spec"]`` after one."""
+    spec = predict_spec(model)
+    if spec is None or model.training or torch.is_grad_enabled():
+        return None
+    is_list = isinstance(bmg, (list, tuple))
+    bmgs = list(bmg) if is_list else [bmg]
+    if is_list != (spec.blocks is not None) or len(bmgs) != spec.n_components:
+        return None
+    dev = spec.layers[0].weight.device
+    if dev.type != "cuda":
+        return None
+    n_mols = len(bmgs[0])
+    for b in bmgs:
+        if len(b) != n_mols or b.V.device != dev or not _batch_vector_ok(b.batch, int(b.V.shape[0]), dev):
+            return None
+    try:
+        Xd = spec.descriptors(None if X_d is None else model.X_d_transform(X_d), n_mols, dev)
+    except ValueError:
+        return None
+    T = None
+    if targets is not None:
+        T = targets if (targets.dtype == torch.float32 and targets.is_contiguous()) else targets.float().contiguous()
+        if T.device != dev or T.dim() != 2 or tuple(T.shape) != (n_mols, spec.n_tasks):
+            return None
+        if weights is not None and (weights.numel() != n_mols or weights.device != dev):
+            return None
+    Hv = model.message_passing(bmg, V_d)
+    if is_list:
+        batch = _component_batch([b.batch for b in bmgs], n_mols)
+        Hv = torch.cat(list(Hv)) if len(Hv) > 1 else Hv[0]
+    else:
+        batch = bmg.batch
+    if Hv.device != dev or Hv.dtype != torch.float32:
+        return None
+    Hv = engine._f32c(Hv, "H_v")
+    nV, d_out = int(Hv.shape[0]), int(Hv.shape[1])
+    if spec.n_components * d_out + spec.d_xd != int(spec.layers[0].in_features):
+        return None
+
+    lib = _lib.load()
+    p = _lib.PredictArgs()
+    h = p.head
+    keep = spec.fill(h, nV, n_mols, d_out, batch, Hv if T is None else T, weights if T is not None else None, lt_mask if T is not None else None,
+                     gt_mask if T is not None else None, lambda prm: None, bn_training=False, X_d=Xd)
+    p.transform = _lib.PREDICT_TRANSFORM[spec.transform]
+    if spec.unscale is not None:
+        mean, scale = (t.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous() for t in (spec.unscale.mean, spec.unscale.scale))
+        p.out_mean, p.out_scale = mean.data_ptr(), scale.data_ptr()
+        keep += [mean, scale]
+    raw = torch.empty(n_mols, spec.n_out, dtype=torch.float32, device=dev)
+    preds = torch.empty(spec.out_shape(n_mols), dtype=torch.float32, device=dev)
+    h.preds, p.preds = raw.data_ptr(), preds.data_ptr()
+    loss = fp = None
+    if T is None:
+        h.targets = None
+    else:
+        loss = torch.empty(2, dtype=torch.float32, device=dev)
+        h.loss_out = loss.data_ptr()
+    if fingerprint:
+        fp = torch.empty(n_mols, int(h.dims[0]), dtype=torch.float32, device=dev)
+        p.fingerprint, p.ld_fp = fp.data_ptr(), fp.stride(0)
+    size_key = (nV if spec.att is not None else 0, n_mols, d_out, Xd is not None)
+    sizes = spec._sizes.get(size_key)
+    if sizes is None:
+        if len(spec._sizes) > 256:
+            spec._sizes.clear()
+        sizes = spec._sizes[size_key] = (int(lib.dmpnn_predict_head_ws_bytes(C.byref(p))), int(lib.dmpnn_predict_head_wsplit_bytes(C.byref(p))))
+    spec._ws = _grown(spec._ws, sizes[0], dev)
+    h.ws, h.ws_bytes = spec._ws.data_ptr(), spec._ws.numel()
+    wkey = (spec.hidden_key(), d_out, Xd is not None)
+    if sizes[1]:
+        if spec._wsplit is None or spec._wsplit.device != dev or spec._wsplit.numel() < sizes[1]:
+            spec._wsplit, spec._wsplit_key = _grown(None, sizes[1], dev), None
+        p.wsplit, p.wsplit_bytes = spec._wsplit.data_ptr(), spec._wsplit.numel()
+        p.wsplit_ready = 1 if spec._wsplit_key == wkey else 0
+    with engine._OnDevice(dev):
+        _lib.check(lib.dmpnn_predict_head(C.byref(p), Hv.data_ptr(), Hv.stride(0), engine._stream_ptr(dev)), "dmpnn_predict_head")
+    if sizes[1]:
+        spec._wsplit_key = wkey
+    del keep
+    return PredictResult(preds, raw, fp, loss)

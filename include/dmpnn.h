@@ -795,6 +795,57 @@ typedef struct dmpnn_head_args {
 size_t dmpnn_head_ws_bytes(const dmpnn_head_args* h);
 int dmpnn_head(const dmpnn_head_args* h, const float* Hv, int64_t ldhv, void* stream);
 
+/* The same model behind the block at INFERENCE, as one call with kernels of its own: what MPNN.forward / fingerprint do in eval mode
+ * after message_passing (models/model.py:126-146) and what validation_step adds (the criterion on the raw outputs: val_loss) —
+ * aggregation, eval-mode batch norm and the X_d columns (k_agg_bn_fwd, or the chain's kernels where the column kernel does not take
+ * the shape), every hidden layer on the f16 pipe from its split image, activation fused (up to 1 024 molecules the training head's row
+ * kernel k_head_rows<., 1>, 16 molecules x 64 columns per workgroup, where the reduction width is whole quads up to 512; k_rows16
+ * otherwise; a layer whose shape dmpnn_linear16_ok refuses — odd widths, unaligned rows — runs as dmpnn_linear_fwd), then ONE launch
+ * (k_predict_tail) for the output layer, the predictor's output
+ * transform and every store, and k_loss when targets are given.  The usual model (sum / mean / norm aggregation, batch norm, one hidden
+ * layer, <= DMPNN_PREDICT_MAX_OUT outputs, <= 1 024 molecules, widths in whole quads) with a ready split: three launches, four with
+ * targets (dmpnn_last_launch_count()).  Output layers wider than DMPNN_PREDICT_MAX_OUT run on the contraction kernels and
+ * k_predict_tail transforms their rows.
+ *
+ * Inference only — each of these is DMPNN_EINVAL before any device work: head.gHv or any head.g* pointer non-NULL; head.bn_training
+ * != 0; head.ffn_dropout_p != 0; only one of out_mean / out_scale; an unknown transform; DMPNN_PT_SOFTMAX with head.n_classes < 2 or
+ * n_classes not dividing n_out = head.dims[head.n_layers]; DMPNN_PT_MVE / _QUANTILE with n_out % 2 != 0, DMPNN_PT_EVIDENTIAL with
+ * n_out % 4 != 0; with head.targets, a head.loss whose outputs per task (cross entropy: n_classes; MVE / quantile: 2; evidential: 4;
+ * else 1) disagree with the transform's (softmax: n_classes; MVE / quantile: 2; evidential: 4; else 1), or no head.loss_out; and
+ * whatever dmpnn_head refuses.  A workspace (head.ws) or wsplit that is too small: DMPNN_ENOSPC.  The running statistics and
+ * bn_num_batches_tracked are never written.  head.targets != NULL also writes head.loss_out: the criterion on the RAW outputs
+ * (chemprop's val_loss), k_loss's arithmetic unchanged.  n_components > 1 and DMPNN_MOLAGG_ATTENTIVE are taken as dmpnn_head takes
+ * them (attentive: dmpnn_molagg_attn_fwd into the workspace, then this head on one-atom molecules).
+ *
+ * Transforms — x a raw row, t = n_tasks, s / m = out_scale[j] / out_mean[j] (1 / 0 when NULL), softplus = F.softplus (beta 1,
+ * threshold 20):  NONE p[j] = x[j];  UNSCALE p[j] = x[j] s + m;  SIGMOID p[j] = 1 / (1 + exp(-x[j]));  SOFTMAX p[j][k] =
+ * softmax_k(x[j nc + k]) (the maximum subtracted first);  MVE p[j] = (x[j] s + m, softplus(x[t+j]) s^2);  EVIDENTIAL p[j] = (x[j] s
+ * + m, softplus(x[t+j]), softplus(x[2t+j]) + 1, softplus(x[3t+j]) s^2);  QUANTILE lo = x[j] s + m, up = x[t+j] s + m: p[j] = ((lo +
+ * up) / 2, up - lo).  These are the eval-mode forward of nn/predictors.py with UnscaleTransform / transform_variance.
+ *
+ * wsplit: the f16 split images of the hidden layers' weights, one slot per layer l < n_layers - 1 in layer order, each
+ * dmpnn_linear16_wsplit_bytes(dims[l+1], dims[l]) long — 0 for a layer that runs as dmpnn_linear_fwd — kept by the caller between
+ * calls (the convention of dmpnn_linear16_fwd): wsplit_ready == 0 splits every layer first (one launch each), != 0 says the images
+ * are current and launches nothing for them; whether they are is the caller's business.  wsplit == NULL: no cache, the hidden
+ * layers run as dmpnn_linear_fwd (fp32 contraction).  dmpnn_predict_head_ws_bytes() / _wsplit_bytes(): 0 for a NULL or malformed
+ * struct. */
+enum dmpnn_predict_transform { DMPNN_PT_NONE = 0, DMPNN_PT_UNSCALE, DMPNN_PT_SIGMOID, DMPNN_PT_SOFTMAX,
+                               DMPNN_PT_MVE, DMPNN_PT_EVIDENTIAL, DMPNN_PT_QUANTILE };
+#define DMPNN_PREDICT_MAX_OUT 64
+typedef struct dmpnn_predict_args {
+    dmpnn_head_args head;          /* the model behind the block, as dmpnn_head reads it. head.preds = the RAW outputs
+                                      [n_mols, n_out] (predictor.train_step's, in the MLP's column layout), required */
+    int32_t transform;             /* enum dmpnn_predict_transform */
+    const float* out_mean; const float* out_scale;   /* [n_tasks] each, or both NULL (identity): UnscaleTransform in eval mode */
+    float* preds;                  /* out, transformed: [n_mols, n_tasks] | [n_mols, n_tasks, n_classes] | [n_mols, n_tasks, 2 or 4]; NULL: not wanted */
+    float* fingerprint; int64_t ld_fp;   /* out or NULL: the predictor's input cat(bn(agg(H_v)), X_d) [n_mols, dims[0]], ld_fp >= dims[0] */
+    void* wsplit; size_t wsplit_bytes; int32_t wsplit_ready;   /* f16 split images of the hidden layers' weights, kept by the caller
+                                      between calls (the convention of dmpnn_linear16_fwd); NULL: no cache, fp32 contraction */
+} dmpnn_predict_args;
+size_t dmpnn_predict_head_ws_bytes(const dmpnn_predict_args* p);
+size_t dmpnn_predict_head_wsplit_bytes(const dmpnn_predict_args* p);
+int    dmpnn_predict_head(const dmpnn_predict_args* p, const float* Hv, int64_t ldhv, void* stream);
+
 /* One training step of models/model.py:148-161 with torch.optim.Adam (model.py:208-231), every kernel enqueued by ONE call:
  * K0 (dmpnn_prepare_with_batch into bwd.f.plan unless plan_ready) -> dmpnn_forward(&bwd.f) (DMPNN_F_KEEP) -> dmpnn_head on
  * bwd.f.out (head.gHv must be bwd.gout) -> dmpnn_backward(&bwd) -> dmpnn_adam_step over the flat buffers (n_params == 0: no
