@@ -232,10 +232,11 @@ struct LossArgs {
     const unsigned char* lt; const unsigned char* gt;
     float* gP; int64_t ldg; float* out;   // out[0] = loss, out[1] = number of finite targets
     int64_t B; int t; int kind;
-    int nc;                               // DMPNN_LOSS_CE: classes per task — P / gP rows hold t * nc logits, T the class index of every task
+    int nc;                               // DMPNN_LOSS_CE / _DIRICHLET: classes per task — P / gP rows hold t * nc logits / raw evidences, T the class index of every task
                                           // DMPNN_LOSS_MVE / _EVIDENTIAL: 2 / 4 — P / gP rows hold nc chunks of t columns (torch.chunk(Y, n_targets, 1))
-    float v_kl, eps;                      // DMPNN_LOSS_EVIDENTIAL
+    float v_kl, eps;                      // DMPNN_LOSS_EVIDENTIAL; v_kl also DMPNN_LOSS_DIRICHLET
     float q_alpha;                        // DMPNN_LOSS_QUANTILE
+    float lg_nc;                          // DMPNN_LOSS_DIRICHLET: lgamma(nc), formed on the host (the same number for every pair)
 };
 // QuantileLoss (nn/metrics.py:589-610) on the raw outputs of QuantileFFN (predictors.py:215-232): mean -+ interval / 2 ARE the lower and
 // upper bounds the MLP put out; per bound amax(tau e, (tau - 1) e) with e = y - bound, tau = alpha / 2 | 1 - alpha / 2
@@ -252,6 +253,45 @@ __device__ __forceinline__ float digamma_f(float x) {
     while (x < 6.f) { r -= 1.f / x; x += 1.f; }
     const float i = 1.f / x, i2 = i * i;
     return r + logf(x) - 0.5f * i - i2 * (1.f / 12.f - i2 * (1.f / 120.f - i2 * (1.f / 252.f)));
+}
+// trigamma for x >= 1: the recurrence up to x >= 6, then the asymptotic series (its next term, 1 / (30 x^9), is < 4e-9 there)
+__device__ __forceinline__ float trigamma_f(float x) {
+    float r = 0.f;
+    while (x < 6.f) { r += 1.f / (x * x); x += 1.f; }
+    const float i = 1.f / x, i2 = i * i;
+    return r + i * (1.f + 0.5f * i + i2 * (1.f / 6.f - i2 * (1.f / 30.f - i2 * (1.f / 42.f))));
+}
+// DirichletLoss (nn/metrics.py) on the raw outputs x[0 .. K) of one task of BinaryDirichletFFN / MulticlassDirichletFFN (predictors.py):
+// alpha = softplus(x) + 1, S = sum alpha, p = alpha / S, y = one_hot(cls);  L = sum (y - p)^2 + sum p (1 - p) / (S + 1) + v_kl KL(Dir(alpha~) || Dir(1))
+// with alpha~ = y + (1 - y) alpha; lgK = lgamma(K).  x is read from memory in every pass (an array indexed by a runtime K would live in scratch).
+// g != NULL: g[m] = f dL/dx_m —  dL_mse/dalpha_m = -2 ([m == cls] - p_cls) / S + 2 (p_m - Q) / (S + 1) - (1 - Q) / (S + 1)^2, Q = sum p^2;
+// dL_kl/dalpha_m = (alpha_m - 1) psi'(alpha_m) - (S~ - K) psi'(S~) for m != cls (the digammas cancel), 0 for m == cls
+__device__ __forceinline__ float dirichlet_loss(const float* __restrict__ x, int K, float lgK, int cls, float v_kl, float* __restrict__ g, float f) {
+    float S = 0.f, St = 0.f, A2 = 0.f, ac = 0.f;
+    for (int k = 0; k < K; ++k) {
+        const float al = softplus_f(x[k]) + 1.f;
+        S += al; A2 += al * al;
+        St += k == cls ? 1.f : al;
+        if (k == cls) ac = al;
+    }
+    const float iS = 1.f / S, iS1 = 1.f / (S + 1.f);
+    const float dgS = digamma_f(St);
+    float mse = 0.f, var = 0.f, kl = lgammaf(St) - lgK;
+    for (int k = 0; k < K; ++k) {
+        const float al = softplus_f(x[k]) + 1.f, p = al * iS, e = (k == cls ? 1.f : 0.f) - p;
+        mse += e * e; var += p * (1.f - p);
+        if (k != cls) kl += (al - 1.f) * (digamma_f(al) - dgS) - lgammaf(al);
+    }
+    if (g) {
+        const float Q = A2 * iS * iS, pc = ac * iS, tgS = ((float)K - St) * trigamma_f(St), c0 = (1.f - Q) * iS1 * iS1;
+        for (int m = 0; m < K; ++m) {
+            const float al = softplus_f(x[m]) + 1.f;
+            const float dmse = -2.f * ((m == cls ? 1.f : 0.f) - pc) * iS + 2.f * (al * iS - Q) * iS1 - c0;
+            const float dkl = m == cls ? 0.f : (al - 1.f) * trigamma_f(al) + tgS;
+            g[m] = (dmse + v_kl * dkl) * softplus_d(x[m]) * f;
+        }
+    }
+    return mse + var * iS1 + v_kl * kl;
 }
 // MVELoss (nn/metrics.py:203-219) on the raw outputs of MveFFN (predictors.py:173-190): unreduced loss, d / d mean, d / d raw variance
 __device__ __forceinline__ float mve_loss(float mean, float raw, float y, float* g_mean, float* g_raw) {
@@ -282,6 +322,19 @@ __global__ __launch_bounds__(1024) void k_loss(LossArgs a) {
     __shared__ float tot[2];
     const int64_t n = a.B * a.t;
     float sl = 0.f, sm = 0.f;
+    // (uniform) the Dirichlet criterion — the task's nc evidence outputs, laid out like the logits of cross entropy — in a loop of its
+    // own, in front of the tests that mean "chunked outputs": its registers stay out of the other criteria's loop
+    if (a.kind == DMPNN_LOSS_DIRICHLET) {
+        for (int64_t i = threadIdx.x; i < n; i += 1024) {
+            const int64_t r = i / a.t; const int j = (int)(i - r * a.t);
+            const float y = a.T[r * a.ldt + j];
+            if (!isfinite(y)) continue;
+            const int cls = (int)y;
+            const float L = dirichlet_loss(a.P + r * a.ldp + (int64_t)j * a.nc, a.nc, a.lg_nc, cls, a.v_kl, nullptr, 0.f);
+            sl += ((cls >= 0 && cls < a.nc) ? L : __int_as_float(0x7fc00000)) * (a.w ? a.w[r] : 1.f) * (a.tw ? a.tw[j] : 1.f);
+            sm += 1.f;
+        }
+    } else
     for (int64_t i = threadIdx.x; i < n; i += 1024) {
         const int64_t r = i / a.t; const int j = (int)(i - r * a.t);
         const float y = a.T[r * a.ldt + j];
@@ -328,6 +381,19 @@ __global__ __launch_bounds__(1024) void k_loss(LossArgs a) {
     __syncthreads();
     if (!a.gP) return;
     const float inv = 1.f / tot[1];
+    if (a.kind == DMPNN_LOSS_DIRICHLET) {   // (uniform; a loop of its own, as above)
+        for (int64_t i = threadIdx.x; i < n; i += 1024) {
+            const int64_t r = i / a.t; const int j = (int)(i - r * a.t);
+            const float y = a.T[r * a.ldt + j];
+            float* gx = a.gP + r * a.ldg + (int64_t)j * a.nc;
+            if (!isfinite(y)) {
+                for (int k = 0; k < a.nc; ++k) gx[k] = 0.f;
+                continue;
+            }
+            dirichlet_loss(a.P + r * a.ldp + (int64_t)j * a.nc, a.nc, a.lg_nc, (int)y, a.v_kl, gx, (a.w ? a.w[r] : 1.f) * (a.tw ? a.tw[j] : 1.f) * inv);
+        }
+        return;
+    }
     for (int64_t i = threadIdx.x; i < n; i += 1024) {
         const int64_t r = i / a.t; const int j = (int)(i - r * a.t);
         const float y = a.T[r * a.ldt + j];
@@ -1605,12 +1671,13 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     DMPNN_CHECK_ARG(!xd || h.ld_xd >= h.dims[0] - d, "head: ld_xd (%lld) < d_xd (%lld)", (long long)h.ld_xd, (long long)(h.dims[0] - d));
     for (int l = 0; l < Ln; ++l) DMPNN_CHECK_ARG(h.W[l] && h.dims[l + 1] > 0, "head: layer %d has no weight / width", l);
     DMPNN_CHECK_ARG(h.act >= DMPNN_ACT_NONE && h.act <= DMPNN_ACT_ELU && h.act != DMPNN_ACT_PRELU, "head: activation %d is not built in", h.act);
-    DMPNN_CHECK_ARG(h.loss >= DMPNN_LOSS_MSE && h.loss <= DMPNN_LOSS_QUANTILE, "head: unknown criterion %d", h.loss);
+    DMPNN_CHECK_ARG(h.loss >= DMPNN_LOSS_MSE && h.loss <= DMPNN_LOSS_DIRICHLET, "head: unknown criterion %d", h.loss);
     DMPNN_CHECK_ARG(h.loss <= DMPNN_LOSS_MAE || (!h.lt_mask && !h.gt_mask), "head: only the MSE / MAE criteria have bounds (lt_mask / gt_mask)");
     DMPNN_CHECK_ARG((h.loss != DMPNN_LOSS_MVE && h.loss != DMPNN_LOSS_QUANTILE) || h.dims[Ln] % 2 == 0, "head: the MVE / quantile criteria need an output layer 2 n_tasks wide");
     DMPNN_CHECK_ARG(h.loss != DMPNN_LOSS_QUANTILE || (h.quantile_alpha > 0.f && h.quantile_alpha < 1.f), "head: the quantile criterion needs 0 < quantile_alpha < 1");
     DMPNN_CHECK_ARG(h.loss != DMPNN_LOSS_EVIDENTIAL || h.dims[Ln] % 4 == 0, "head: the evidential criterion needs an output layer 4 n_tasks wide");
     DMPNN_CHECK_ARG(h.loss != DMPNN_LOSS_CE || (h.n_classes >= 2 && h.dims[Ln] % h.n_classes == 0), "head: cross entropy needs n_classes >= 2 dividing the output width");
+    DMPNN_CHECK_ARG(h.loss != DMPNN_LOSS_DIRICHLET || (h.n_classes >= 2 && h.dims[Ln] % h.n_classes == 0), "head: the Dirichlet criterion needs n_classes >= 2 dividing the output width");
     DMPNN_CHECK_ARG(h.preds && (nV == 0 || (Hv && h.batch)), "head: null H_v / batch / preds");
     DMPNN_CHECK_ARG(!h.bn_weight || (h.bn_running_mean && h.bn_running_var), "head: batch norm without running statistics");
     // (torch.nn.BatchNorm1d in training mode — hence the reference — raises "Expected more than 1 value per channel": a batch of one
@@ -1628,7 +1695,7 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     if (B == 0 || check_only) return DMPNN_OK;
     unsigned char* ws = static_cast<unsigned char*>(h.ws);
     const int t_out = (int)h.dims[Ln];                                  // width of the output layer
-    const int nc = h.loss == DMPNN_LOSS_CE ? h.n_classes : ((h.loss == DMPNN_LOSS_MVE || h.loss == DMPNN_LOSS_QUANTILE) ? 2 : (h.loss == DMPNN_LOSS_EVIDENTIAL ? 4 : 1));   // outputs per task
+    const int nc = (h.loss == DMPNN_LOSS_CE || h.loss == DMPNN_LOSS_DIRICHLET) ? h.n_classes : ((h.loss == DMPNN_LOSS_MVE || h.loss == DMPNN_LOSS_QUANTILE) ? 2 : (h.loss == DMPNN_LOSS_EVIDENTIAL ? 4 : 1));   // outputs per task
     const int t = t_out / nc;                                           // tasks (= columns of `targets`)
 
     // ---- forward ----
@@ -1730,7 +1797,7 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     float* gP = reinterpret_cast<float*>(ws + L.gP);
     if (!out_all) {
         LossArgs q{h.preds, t_out, h.targets, t, h.weights, h.task_weights, h.lt_mask, h.gt_mask, want_grad ? gP : nullptr, t_out, h.loss_out, B, t, h.loss, nc,
-                   h.evid_v_kl, h.evid_eps, h.quantile_alpha};
+                   h.evid_v_kl, h.evid_eps, h.quantile_alpha, h.loss == DMPNN_LOSS_DIRICHLET ? (float)std::lgamma((double)nc) : 0.f};
         DMPNN_CHECK_ARG(h.loss_out != nullptr, "head: targets without loss_out");
         hipLaunchKernelGGL(k_loss, dim3(1), dim3(1024), 0, s, q);
         DMPNN_CHECK_LAUNCH("k_loss");
@@ -1829,7 +1896,7 @@ int transform_per_task(int transform, int n_classes) {
     return transform == DMPNN_PT_SOFTMAX ? n_classes : (transform == DMPNN_PT_EVIDENTIAL ? 4 : ((transform == DMPNN_PT_MVE || transform == DMPNN_PT_QUANTILE) ? 2 : 1));
 }
 int loss_per_task(const dmpnn_head_args& h) {
-    return h.loss == DMPNN_LOSS_CE ? h.n_classes : (h.loss == DMPNN_LOSS_EVIDENTIAL ? 4 : ((h.loss == DMPNN_LOSS_MVE || h.loss == DMPNN_LOSS_QUANTILE) ? 2 : 1));
+    return (h.loss == DMPNN_LOSS_CE || h.loss == DMPNN_LOSS_DIRICHLET) ? h.n_classes : (h.loss == DMPNN_LOSS_EVIDENTIAL ? 4 : ((h.loss == DMPNN_LOSS_MVE || h.loss == DMPNN_LOSS_QUANTILE) ? 2 : 1));
 }
 // hidden layer l < n_layers - 1 as a contraction call: tau(A W_l^T + b_l) into C
 dmpnn_gemm_args predict_layer(const dmpnn_head_args& h, int l, int64_t M, const float* A, int64_t lda, float* C) {
@@ -1882,7 +1949,7 @@ int predict_check(const dmpnn_predict_args* pp) {
     DMPNN_CHECK_ARG(p.transform != DMPNN_PT_EVIDENTIAL || n_out % 4 == 0, "predict_head: the evidential transform needs an output layer 4 n_tasks wide (got %lld)",
                     (long long)n_out);
     if (h.targets) {
-        DMPNN_CHECK_ARG(h.loss >= DMPNN_LOSS_MSE && h.loss <= DMPNN_LOSS_QUANTILE, "head: unknown criterion %d", h.loss);
+        DMPNN_CHECK_ARG(h.loss >= DMPNN_LOSS_MSE && h.loss <= DMPNN_LOSS_DIRICHLET, "head: unknown criterion %d", h.loss);
         DMPNN_CHECK_ARG(loss_per_task(h) == transform_per_task(p.transform, h.n_classes),
                         "predict_head: the criterion (%d) and the transform (%d) disagree on the outputs per task (%d against %d)", (int)h.loss, (int)p.transform,
                         loss_per_task(h), transform_per_task(p.transform, h.n_classes));
@@ -1963,7 +2030,7 @@ int predict_core(const dmpnn_predict_args& p, const dmpnn_head_args& h, const fl
     if (!h.targets) return DMPNN_OK;
     const int t = n_out / per;
     LossArgs lq{h.preds, n_out, h.targets, t, h.weights, h.task_weights, h.lt_mask, h.gt_mask, nullptr, n_out, h.loss_out, B, t, h.loss, per,
-                h.evid_v_kl, h.evid_eps, h.quantile_alpha};
+                h.evid_v_kl, h.evid_eps, h.quantile_alpha, h.loss == DMPNN_LOSS_DIRICHLET ? (float)std::lgamma((double)per) : 0.f};
     hipLaunchKernelGGL(k_loss, dim3(1), dim3(1024), 0, s, lq);
     DMPNN_CHECK_LAUNCH("k_loss");
     return DMPNN_OK;

@@ -30,7 +30,7 @@ from .data import merge_components
 from .optim import CLIP_MODES, FlatAdam
 
 __all__ = ["MSE", "MAE", "BCE", "CE", "MVE", "Evidential", "Quantile", "RegressionFFN", "BinaryClassificationFFN", "MulticlassClassificationFFN", "MveFFN", "EvidentialFFN", "QuantileFFN",
-           "MPNN", "MulticomponentMPNN", "FusedTrainer", "masked_loss"]
+           "Dirichlet", "BinaryDirichletFFN", "MulticlassDirichletFFN", "MPNN", "MulticomponentMPNN", "FusedTrainer", "masked_loss"]
 
 
 def masked_loss(preds: Tensor, targets: Tensor, weights: Optional[Tensor] = None, task_weights: Optional[Tensor] = None,
@@ -42,8 +42,18 @@ def masked_loss(preds: Tensor, targets: Tensor, weights: Optional[Tensor] = None
     targets = targets.nan_to_num(nan=0.0)
     w = torch.ones(targets.shape[0], dtype=torch.float, device=targets.device) if weights is None else weights
     tw = 1.0 if task_weights is None else task_weights.view(1, -1)
-    if kind in ("bce", "ce", "mve", "evidential", "quantile"):
+    if kind in ("bce", "ce", "mve", "evidential", "quantile", "dirichlet"):
         lt_mask = gt_mask = None     # (only the Bounded* criteria apply the masks: metrics.py:157-177)
+    if kind == "dirichlet":          # preds [b, t, c] = alpha (the Dirichlet predictors' train_step), targets [b, t] class indices (DirichletLoss)
+        y = torch.nn.functional.one_hot(targets.long(), preds.shape[-1]).to(preds.dtype)
+        S = preds.sum(-1, keepdim=True)
+        p = preds / S
+        L_mse = ((y - p) ** 2).sum(-1) + (p * (1 - p) / (S + 1)).sum(-1)
+        a_t = y + (1 - y) * preds    # (1 at the true class: the KL term leaves its evidence alone)
+        S_t = a_t.sum(-1, keepdim=True)
+        L_kl = (torch.lgamma(S_t).squeeze(-1) - torch.lgamma(a_t).sum(-1) - math.lgamma(preds.shape[-1])
+                + ((a_t - 1) * (torch.digamma(a_t) - torch.digamma(S_t))).sum(-1))
+        return ((L_mse + v_kl * L_kl) * w.view(-1, 1) * tw * mask).sum() / mask.sum()
     if kind in ("mve", "evidential", "quantile"):   # preds [b, t, 2 | 4]: what MveFFN / EvidentialFFN / QuantileFFN.train_step stack (predictors.py:173-232)
         if kind == "mve":               # MVELoss, metrics.py:203-219
             mean, var = torch.unbind(preds, dim=-1)
@@ -255,6 +265,51 @@ class BinaryClassificationFFN(RegressionFFN):
         return self.ffn(Z)
 
 
+class Dirichlet(MSE):
+    """``chemprop.nn.metrics.DirichletLoss``: ``preds [b, t, c]`` = the Dirichlet parameters ``alpha`` against class indices — the
+    expected squared error under ``Dir(alpha)`` plus ``v_kl`` times ``KL(Dir(alpha~) || Dir(1))``; no bounds."""
+
+    kind = "dirichlet"
+
+    def __init__(self, task_weights=1.0, v_kl: float = 0.2):
+        super().__init__(task_weights)
+        self.v_kl = v_kl
+
+
+class BinaryDirichletFFN(RegressionFFN):
+    """``chemprop.nn.predictors.BinaryDirichletFFN``: an MLP ``2 n_tasks`` wide, column ``2 j + k`` the evidence of class ``k`` of task
+    ``j``; ``train_step`` hands ``alpha = softplus + 1`` as ``[b, t, 2]`` to ``DirichletLoss``, ``forward`` predicts
+    ``(p_1, 2 / S) [b, t, 2]``: the probability of class 1 and the uncertainty."""
+
+    n_targets = 2
+    _default_criterion = Dirichlet
+
+    def train_step(self, Z: Tensor) -> Tensor:
+        return (torch.nn.functional.softplus(self.ffn(Z)) + 1).reshape(Z.shape[0], -1, 2)
+
+    def forward(self, Z: Tensor) -> Tensor:
+        alpha = self.train_step(Z)
+        S = alpha.sum(-1)
+        return torch.stack((alpha[..., 1] / S, 2 / S), dim=2)
+
+
+class MulticlassDirichletFFN(MulticlassClassificationFFN):
+    """``chemprop.nn.predictors.MulticlassDirichletFFN``: the multiclass MLP (``n_tasks * n_classes`` wide); ``train_step`` hands
+    ``alpha = softplus + 1`` as ``[b, t, c]`` to ``DirichletLoss``, ``forward`` predicts ``alpha / sum(alpha) [b, t, c]``."""
+
+    def __init__(self, n_classes: int, n_tasks: int = 1, input_dim: int = 300, hidden_dim: int = 300, n_layers: int = 1, dropout: float = 0.0,
+                 activation="relu", criterion: Optional[nn.Module] = None, task_weights: Optional[Tensor] = None):
+        super().__init__(n_classes, n_tasks, input_dim, hidden_dim, n_layers, dropout, activation,
+                         criterion if criterion is not None else Dirichlet(torch.ones(n_tasks) if task_weights is None else task_weights))
+
+    def train_step(self, Z: Tensor) -> Tensor:
+        return (torch.nn.functional.softplus(self.ffn(Z)) + 1).reshape(Z.shape[0], -1, self.n_classes)
+
+    def forward(self, Z: Tensor) -> Tensor:
+        alpha = self.train_step(Z)
+        return alpha / alpha.sum(-1, keepdim=True)
+
+
 class MPNN(nn.Module):
     """``chemprop.models.MPNN`` (``models/model.py:60-146``) without Lightning: the four sub-modules under the reference's
     names and ``fingerprint`` / ``forward``; ``loss(batch)`` is the arithmetic of ``training_step`` (``model.py:148-161``).
@@ -452,6 +507,8 @@ def criterion_kind(crit) -> tuple[Optional[str], bool]:
         return "bce", False
     if "CrossEntropyLoss" in names:   # nn/metrics.py:298-304 (multiclass: logits [b, t, c] against class indices)
         return "ce", False
+    if "DirichletLoss" in names:      # nn/metrics.py (evidential classification: alpha [b, t, c] against class indices)
+        return "dirichlet", False
     for cls, k in (("MSE", "mse"), ("MAE", "mae")):
         if cls in names:
             return k, "BoundedMixin" in names
@@ -484,7 +541,11 @@ class HeadSpec:
     ``attentive=True`` also takes ``AttentiveAggregation`` (this package's mirror, the reference's class or a subclass of it,
     ``nn/agg.py:116-133``) when its ``W`` is an ``nn.Linear(d_h, 1)`` with a bias over the head's input width and the model has one
     component: ``dmpnn_head_args.agg_mode = DMPNN_MOLAGG_ATTENTIVE`` with ``att_W`` / ``att_b``; ``att`` is that layer (``None``
-    otherwise).  The default refuses it like any aggregation that is not sum / mean / norm."""
+    otherwise).  The default refuses it like any aggregation that is not sum / mean / norm.
+
+    A Dirichlet classification head is taken as exactly the pair (``BinaryDirichletFFN`` | ``MulticlassDirichletFFN``, ``DirichletLoss``)
+    — this package's mirrors or the reference's classes, by name: ``kind == "dirichlet"``, ``n_classes`` the predictor's (2 for the
+    binary one), ``n_tasks = n_out / n_classes``, ``v_kl`` handed over as ``evid_v_kl``."""
 
     def __init__(self, model, ffn_dropout: bool = False, attentive: bool = False):
         agg, pred = model.agg, model.predictor
@@ -525,11 +586,20 @@ class HeadSpec:
             raise NotImplementedError("the output transform is the identity while training (predictors.py:166-169)")
         kind, self.bounded = criterion_kind(pred.criterion)
         if kind is None:
-            raise NotImplementedError("MSE / MAE criterion (bounded or not), BCE, cross entropy, MVE, evidential or quantile")
+            raise NotImplementedError("MSE / MAE criterion (bounded or not), BCE, cross entropy, MVE, evidential, quantile or Dirichlet")
+        # evidential classification: exactly the pairs (BinaryDirichletFFN | MulticlassDirichletFFN, DirichletLoss), the predictors told
+        # by MRO name like the other reference classes; the class layout is cross entropy's, the binary head has two classes per task
+        # (its n_targets = 2 says the same thing: for the kernels it is a class dimension, not a chunked one)
+        names = _mro_names(pred)
+        dir_pred = "binary" if "BinaryDirichletFFN" in names else ("multiclass" if "MulticlassDirichletFFN" in names else None)
+        if (kind == "dirichlet") != (dir_pred is not None):
+            raise NotImplementedError("a Dirichlet criterion on a predictor that is neither BinaryDirichletFFN nor MulticlassDirichletFFN"
+                                      if kind == "dirichlet" else f"a Dirichlet predictor ({type(pred).__name__}) with a criterion "
+                                      f"other than DirichletLoss (got {kind})")
         # values per task (predictors.py: n_targets): 1, or — round 6 — the mean-variance / evidential pairs of predictor and criterion
         # (MveFFN + MVELoss: 2, EvidentialFFN + EvidentialLoss: 4, QuantileFFN + QuantileLoss: 2; the predictors' transforms of the
-        # raw outputs live in the criterion kernel); Dirichlet heads train through torch ops
-        self.n_targets = int(getattr(pred, "n_targets", 1))
+        # raw outputs live in the criterion kernel)
+        self.n_targets = 1 if dir_pred == "binary" else int(getattr(pred, "n_targets", 1))
         want_targets = {"mve": 2, "evidential": 4, "quantile": 2}.get(kind, 1)
         want_pred = {"mve": "MveFFN", "evidential": "EvidentialFFN", "quantile": "QuantileFFN"}.get(kind)
         if self.n_targets != want_targets or (want_pred is not None and want_pred not in _mro_names(pred)):
@@ -539,11 +609,11 @@ class HeadSpec:
         self.v_kl, self.eps = float(getattr(pred.criterion, "v_kl", 0.2)), float(getattr(pred.criterion, "eps", 1e-8))
         self.q_alpha = float(getattr(pred.criterion, "alpha", 0.1))
         # multiclass (predictors.py:271-314): the output layer holds n_classes logits per task, the criterion is the cross entropy
-        # over them — every other pairing of a class dimension and a criterion (Dirichlet heads, ...) trains through torch ops
-        self.n_classes = int(getattr(pred, "n_classes", 0) or 0)
-        if (kind == "ce") != (self.n_classes >= 2):
-            raise NotImplementedError("a multiclass predictor (n_classes >= 2) with CrossEntropyLoss, or neither")
-        if kind == "ce" and int(blocks[-1][-1].out_features) % self.n_classes:
+        # over them, or — a Dirichlet head — DirichletLoss; every other pairing of a class dimension and a criterion trains through torch ops
+        self.n_classes = 2 if dir_pred == "binary" else int(getattr(pred, "n_classes", 0) or 0)
+        if (kind in ("ce", "dirichlet")) != (self.n_classes >= 2):
+            raise NotImplementedError("a multiclass predictor (n_classes >= 2) with CrossEntropyLoss or DirichletLoss, or neither")
+        if kind in ("ce", "dirichlet") and int(blocks[-1][-1].out_features) % self.n_classes:
             raise NotImplementedError("the output width must be n_tasks * n_classes")
         self.agg_mode, self.agg_norm = (_lib.MOLAGG_ATTENTIVE if self.att is not None else MODES[mode]), float(getattr(agg, "norm", 1.0))
         self.f_act, self.f_slope, self.kind = f_act, f_slope, kind

@@ -46,6 +46,10 @@ class PredictSpec(HeadSpec):
         super().__init__(model, ffn_dropout=True, attentive=True)
         pred = model.predictor
         names = _mro_names(pred)
+        if "BinaryDirichletFFN" in names or "MulticlassDirichletFFN" in names:
+            # (enum dmpnn_predict_transform has no alpha / sum(alpha): without this the multiclass one — a MulticlassClassificationFFN —
+            #  would be handed to the softmax)
+            raise NotImplementedError(f"a Dirichlet predictor ({type(pred).__name__}): its eval-mode forward runs on the modules")
         self.transform = next((tr for cls, tr in _TRANSFORM_OF if cls in names), None)
         if self.transform is None:
             raise NotImplementedError(f"a predictor of a known class (got {type(pred).__name__})")

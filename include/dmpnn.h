@@ -738,9 +738,18 @@ enum dmpnn_loss { DMPNN_LOSS_MSE = 0, DMPNN_LOSS_MAE = 1,
                                          EvidentialFFN.train_step, predictors.py:193-212): the output layer is [4 n_tasks] wide — mean |
                                          raw v | raw alpha | raw beta, v = softplus, alpha = softplus + 1, beta = softplus;
                                          L = L_nll + evid_v_kl (L_reg - evid_eps) */
-                  DMPNN_LOSS_QUANTILE = 6 /* v14: the interval pinball loss (QuantileLoss, nn/metrics.py:589-610, on QuantileFFN.train_step,
+                  DMPNN_LOSS_QUANTILE = 6, /* v14: the interval pinball loss (QuantileLoss, nn/metrics.py:589-610, on QuantileFFN.train_step,
                                          predictors.py:215-232): the output layer is [2 n_tasks] wide — lower | upper bounds;
-                                         L = pinball(y - lower; alpha / 2) + pinball(y - upper; 1 - alpha / 2), alpha = quantile_alpha */ };
+                                         L = pinball(y - lower; alpha / 2) + pinball(y - upper; 1 - alpha / 2), alpha = quantile_alpha */
+                  DMPNN_LOSS_DIRICHLET = 7 /* v15 growth: evidential classification (DirichletLoss, nn/metrics.py, on BinaryDirichletFFN /
+                                         MulticlassDirichletFFN.train_step, nn/predictors.py): the output layer is [n_tasks * n_classes]
+                                         wide in the layout of DMPNN_LOSS_CE — column j K + k is class k of task j, K = n_classes (>= 2,
+                                         dividing the width; 2 for the binary head) — and `targets` holds class indices c as floats (outside
+                                         [0, K): a NaN loss).  alpha = softplus(raw) + 1, S = sum_k alpha_k, p = alpha / S, y = one_hot(c):
+                                         L_mse = sum_k (y_k - p_k)^2 + sum_k p_k (1 - p_k) / (S + 1);
+                                         alpha~ = y + (1 - y) alpha, S~ = sum_k alpha~_k:
+                                         L_kl = lgamma(S~) - sum_k lgamma(alpha~_k) - lgamma(K) + sum_k (alpha~_k - 1) (psi(alpha~_k) - psi(S~));
+                                         L = L_mse + evid_v_kl L_kl (evid_v_kl: DirichletLoss.v_kl).  No bounds */ };
 typedef struct dmpnn_head_args {
     int64_t n_atoms, n_mols, d_h;           /* rows of H_v, molecules, width of H_v                              */
     const int64_t* batch;                   /* [n_atoms] molecule of every atom, non-decreasing (BatchMolGraph.batch) */
@@ -764,8 +773,9 @@ typedef struct dmpnn_head_args {
     float* gHv; int64_t ldg;                /* out [n_atoms, ldg] dloss / dH_v; NULL: forward (and loss) only       */
     void* ws; size_t ws_bytes;              /* caller-owned scratch, >= dmpnn_head_ws_bytes()                       */
     int64_t* bn_num_batches_tracked;        /* nn.BatchNorm1d's counter: += 1 on device when bn_training (NULL: not kept) — v9 */
-    int32_t n_classes;                      /* v12, DMPNN_LOSS_CE: classes per task (>= 2); the last layer's width is n_tasks * n_classes */
-    float evid_v_kl, evid_eps;              /* v14, DMPNN_LOSS_EVIDENTIAL: EvidentialLoss.v_kl (0.2) and .eps (1e-8)                   */
+    int32_t n_classes;                      /* v12, DMPNN_LOSS_CE (and DMPNN_LOSS_DIRICHLET): classes per task (>= 2); the last layer's width is n_tasks * n_classes */
+    float evid_v_kl, evid_eps;              /* v14, DMPNN_LOSS_EVIDENTIAL: EvidentialLoss.v_kl (0.2) and .eps (1e-8); DMPNN_LOSS_DIRICHLET reads
+                                               evid_v_kl as DirichletLoss.v_kl (0.2) and ignores evid_eps                              */
     float quantile_alpha;                   /* v14, DMPNN_LOSS_QUANTILE: QuantileLoss.alpha (0.1)                                      */
     const float* X_d; int64_t ld_xd;        /* v15 growth: [n_mols, d_xd] molecule descriptors, row stride ld_xd >= d_xd, or NULL (none).
                                                d_xd = dims[0] - d_h: the predictor's input is cat(bn(agg(H_v)), X_d) (models/model.py,
@@ -810,7 +820,7 @@ int dmpnn_head(const dmpnn_head_args* h, const float* Hv, int64_t ldhv, void* st
  * Inference only — each of these is DMPNN_EINVAL before any device work: head.gHv or any head.g* pointer non-NULL; head.bn_training
  * != 0; head.ffn_dropout_p != 0; only one of out_mean / out_scale; an unknown transform; DMPNN_PT_SOFTMAX with head.n_classes < 2 or
  * n_classes not dividing n_out = head.dims[head.n_layers]; DMPNN_PT_MVE / _QUANTILE with n_out % 2 != 0, DMPNN_PT_EVIDENTIAL with
- * n_out % 4 != 0; with head.targets, a head.loss whose outputs per task (cross entropy: n_classes; MVE / quantile: 2; evidential: 4;
+ * n_out % 4 != 0; with head.targets, a head.loss whose outputs per task (cross entropy / Dirichlet: n_classes; MVE / quantile: 2; evidential: 4;
  * else 1) disagree with the transform's (softmax: n_classes; MVE / quantile: 2; evidential: 4; else 1), or no head.loss_out; and
  * whatever dmpnn_head refuses.  A workspace (head.ws) or wsplit that is too small: DMPNN_ENOSPC.  The running statistics and
  * bn_num_batches_tracked are never written.  head.targets != NULL also writes head.loss_out: the criterion on the RAW outputs
