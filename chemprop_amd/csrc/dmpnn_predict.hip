@@ -1,4 +1,5 @@
-// The last launch of the inference head (dmpnn_predict_head, driven from dmpnn_head.hip next to head_run): per molecule row the
+// The last launch of the inference head (dmpnn_predict_head: predict_core in the head's host driver dmpnn_head.hip; the kernels in front of
+// this one — k_agg_bn_fwd_own_bounds, k_head_rows<., 1>, k_loss behind it — are dmpnn_head_kernels.hpp's): per molecule row the
 // predictor's OUTPUT layer, its output transform (nn/predictors.py: the eval-mode forward of the six predictor classes with
 // UnscaleTransform / transform_variance) and every store of the call — the raw outputs, the transformed predictions, the row of the
 // fingerprint — where the module path runs a contraction, two to six elementwise launches and a copy.

@@ -204,8 +204,22 @@ def test_head_attentive_argument_checks_are_codes_before_any_device_work():
     g = _head_args()
     g.ws, g.ws_bytes = DUMMY, sum_bytes                                    # enough for sum / mean / norm, too small for this mode
     assert lib.dmpnn_head(C.byref(g), DUMMY, 8, None) == ENOSPC
+    # (the size it names is this mode's own, never the inner head's — which this workspace would hold)
+    assert f"({sum_bytes} < {att_bytes} bytes)" in lib.dmpnn_last_error_string().decode()
     g.ws = None
     assert lib.dmpnn_head(C.byref(g), DUMMY, 8, None) == ENOSPC
+    # the order of the rules: a call that is wrong in an argument AND has no workspace reports the argument — in either mode, whether
+    # the rule is the attention's own or the head's behind it
+    for mode, spoil, names in ((3, dict(act=_lib.ACT["prelu"]), "activation"), (3, dict(ldg=7), "ldg"), (3, dict(att_b=None), "att_W"),
+                               (0, dict(act=_lib.ACT["prelu"]), "activation"), (0, dict(preds=None), "preds"), (0, dict(n_layers=0), "predictor layers")):
+        g = _head_args(mode=mode)
+        for k, v in spoil.items():
+            setattr(g, k, v)
+        assert g.ws is None and g.ws_bytes == 0
+        assert lib.dmpnn_head(C.byref(g), DUMMY, 8, None) == EINVAL, (mode, spoil)
+        assert names in lib.dmpnn_last_error_string().decode(), (mode, spoil, lib.dmpnn_last_error_string())
+        g = _head_args(mode=mode)   # (the same call, unspoiled: what stops it is the workspace)
+        assert lib.dmpnn_head(C.byref(g), DUMMY, 8, None) == ENOSPC and b"workspace" in lib.dmpnn_last_error_string(), mode
 
 
 def test_abi_mirror_of_the_new_struct_matches_a_c_compiler(tmp_path):

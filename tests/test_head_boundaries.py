@@ -79,7 +79,7 @@ def _build_cases():
                         continue
                     cs.append(_case(form, f"{name}{v}", **kw))
 
-    # molecules per batch: col_quads (256), kFuseAggMols and k_bn_fwd/bwd<REG> (512), kRowsMaxB / kOutAllMaxRows (1 024), row blocks of 16,
+    # molecules per batch: HeadRoute::qpw (256), kFuseAggMols and k_bn_fwd/bwd<REG> (512), kRowsMaxB / kOutAllMaxRows (1 024), row blocks of 16,
     # the row-split weight gradients (2 048)
     B_GROUPS = [(2,), (15, 16, 17), (255, 256, 257), (511, 512, 513), (1009,), (1023, 1024, 1025), (2047, 2048, 2049)]
     sweep(B_GROUPS, "B", lambda v: dict(B=v))

@@ -1,7 +1,7 @@
 """The predictor's dropout (``chemprop train --dropout p``: ``MLP.build``'s shared ``nn.Dropout`` between ``tau`` and every Linear
 layer after the first) on the head kernels and the one-call training step: ``dmpnn_head_args.ffn_dropout_p / ffn_dropout_seed``, a
 hash mask regenerated in the backward pass (``include/dmpnn.h``); the four-launch row form and the chain form of
-``csrc/dmpnn_head.hip``; ``HeadSpec`` / ``FusedTrainer(ffn_dropout=True)``; ``integration.HipMPNN``'s step.
+``csrc/dmpnn_head.hip`` (kernels: ``csrc/dmpnn_head_kernels.hpp``); ``HeadSpec`` / ``FusedTrainer(ffn_dropout=True)``; ``integration.HipMPNN``'s step.
 
 Parity of a stochastic op is parity given its mask: the tests rebuild the head's masks from the seed with the oracle's restatement
 of the hash and replay them in a float64 restatement."""

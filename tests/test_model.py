@@ -676,7 +676,7 @@ def test_module_path_head_is_one_autograd_node(bn, agg, tasks, kind, act, gpu_de
 def test_head_in_row_and_column_kernels_equals_the_nine_launch_chain(n_mols, d_h, hidden, tasks, bn, agg, kind, act, switches, gpu_device, monkeypatch):
     """Round 5: aggregation + batch norm (+ the hidden layer's weight split) as one column kernel, predictor + criterion + their
     backward as two launches over (row block) x (column slice) on the f16 pipe (3-product split), batch norm backward + the broadcast to
-    the atoms (+ the sums over row blocks) as one column kernel (``csrc/dmpnn_head.hip``: ``k_agg_bn_fwd`` / ``k_head_rows<., 1 | 2>`` /
+    the atoms (+ the sums over row blocks) as one column kernel (``csrc/dmpnn_head_kernels.hpp``: ``k_agg_bn_fwd`` / ``k_head_rows<., 1 | 2>`` /
     ``k_bn_agg_bwd``) against the chain of rounds 3-4 (``DMPNN_HEAD=chain``: one exact-fp32 contraction per layer): loss, every
     gradient (the block's included — ``dl/dH_v`` goes through it), batch-norm buffers."""
     from chemprop_amd import synth
