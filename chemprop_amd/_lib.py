@@ -127,7 +127,8 @@ MAX_FFN_LAYERS = 8
 MAX_COMPONENTS = 8   # (DMPNN_MAX_COMPONENTS: blocks side by side in one fingerprint)
 DROP_SITE_VD = 0x8000     # (DMPNN_DROP_SITE_VD: the mask behind the atom-descriptor layer, dmpnn_vd_args.dropout_p)
 DROP_SITE_FFN = 0x10000   # (DMPNN_DROP_SITE_FFN: the predictor's dropout sites are DROP_SITE_FFN + layer)
-LOSS = {"mse": 0, "mae": 1, "bce": 2, "ce": 3, "mve": 4, "evidential": 5, "quantile": 6, "dirichlet": 7}   # enum dmpnn_loss
+LOSS = {"mse": 0, "mae": 1, "bce": 2, "ce": 3, "mve": 4, "evidential": 5, "quantile": 6, "dirichlet": 7, "sid": 8, "wasserstein": 9}   # enum dmpnn_loss
+SPECTRAL_ACT = {"softplus": 0, "exp": 1}   # dmpnn_head_args.spectral_act
 STEP_FORWARD, STEP_BACKWARD, STEP_UPDATE = 1, 2, 4
 
 
@@ -153,6 +154,7 @@ class HeadArgs(C.Structure):
         ("n_components", C.c_int32),
         ("ffn_dropout_p", C.c_float), ("ffn_dropout_seed", C.c_uint64),
         ("att_W", C.c_void_p), ("att_b", C.c_void_p), ("g_att_W", C.c_void_p), ("g_att_b", C.c_void_p),
+        ("spectral_act", C.c_int32), ("spectral_threshold", C.c_float),
     ]
 
 
@@ -173,6 +175,7 @@ class MolAggAttnArgs(C.Structure):
 
 MOLAGG_ATTENTIVE = 3   # (DMPNN_MOLAGG_ATTENTIVE: dmpnn_head_args.agg_mode)
 PREDICT_TRANSFORM = {"none": 0, "unscale": 1, "sigmoid": 2, "softmax": 3, "mve": 4, "evidential": 5, "quantile": 6}   # enum dmpnn_predict_transform
+PT_SPECTRAL = 8   # (DMPNN_PT_SPECTRAL: a value of dmpnn_predict_args.transform beside the enum's — 7 stays unknown)
 PREDICT_MAX_OUT = 64   # (DMPNN_PREDICT_MAX_OUT: output layers up to this width ride in k_predict_tail)
 
 

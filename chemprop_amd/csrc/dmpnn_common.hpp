@@ -448,6 +448,7 @@ struct PredictTail {
     float* raw;                                    // [B, n_out]
     float* preds; int transform, t, nc; const float* mean; const float* scale;
     float* fp; int64_t ld_fp; const float* Z; int64_t ldz; int fp_w;
+    int spectral_act;                              // DMPNN_PT_SPECTRAL: dmpnn_head_args.spectral_act (0 softplus, 1 exp)
 };
 int launch_predict_tail(const PredictTail& q, hipStream_t s);
 

@@ -29,7 +29,11 @@ struct HeadLayout {
     // agg_mode == DMPNN_MOLAGG_ATTENTIVE (behind everything else: the other offsets do not move): the aggregate A [B, d] and its gradient,
     // the batch vector of B one-atom molecules, the bounds table of the real batch, the kept s [n_atoms] | Z [B], the attention's own scratch
     size_t att_A, att_gA, att_idb, att_bounds, att_s, att_Z, att_ws, att_ws_bytes;
+    // the spectral criteria (in front of the attentive part: the inner head's layout stays the front of the outer one): per row the
+    // loss and the count of finite targets, k_spectral_rows to k_spectral_finish
+    size_t spec_loss, spec_cnt;
 };
+inline bool spectral_loss(int loss) { return loss == DMPNN_LOSS_SID || loss == DMPNN_LOSS_WASSERSTEIN; }
 // the shapes the four-launch form takes (training or not is the caller's business): one hidden layer, a handful of outputs
 // (with molecule descriptors the first layer's reduction may be up to kRowsMaxK wide: d_h + d_xd; its data gradient stays d_h wide)
 // components of a multicomponent fingerprint (dmpnn_head_args.n_components: 0 and 1 are one block)
@@ -84,6 +88,10 @@ HeadLayout head_layout(const dmpnn_head_args& h) {
         L.part_stride = (int)(t * N + t + 2);
         L.part = o; o += al256((size_t)L.n_part * L.part_stride * 4);
     }
+    if (spectral_loss(h.loss)) {
+        L.spec_loss = o; o += al256((size_t)B * 4);
+        L.spec_cnt = o; o += al256((size_t)B * 4);
+    }
     if (h.agg_mode == DMPNN_MOLAGG_ATTENTIVE) {
         const int64_t nV = h.n_atoms > 0 ? h.n_atoms : 0;
         L.att_A = o; o += al256((size_t)B * d * 4);
@@ -128,6 +136,11 @@ int loss_per_task(const dmpnn_head_args& h) {
     return (h.loss == DMPNN_LOSS_CE || h.loss == DMPNN_LOSS_DIRICHLET) ? h.n_classes : (h.loss == DMPNN_LOSS_EVIDENTIAL ? 4 : ((h.loss == DMPNN_LOSS_MVE || h.loss == DMPNN_LOSS_QUANTILE) ? 2 : 1));
 }
 
+// the criterion is one this library knows: a value of enum dmpnn_loss — and no class dimension beside the spectral criteria, whose one
+// output per task is a bin of the spectrum (with n_classes set, 8 / 9 name nothing: older callers probe 8 as the first unknown value)
+inline bool known_criterion(const dmpnn_head_args& h) {
+    return h.loss >= DMPNN_LOSS_MSE && h.loss <= DMPNN_LOSS_WASSERSTEIN && !(spectral_loss(h.loss) && h.n_classes != 0);
+}
 // every argument rule of dmpnn_head (head_attentive: its own, then these on the head behind the attention), before the workspace rule
 int head_check(const dmpnn_head_args& h, const float* Hv, int64_t ldhv) {
     DMPNN_CHECK_ARG(h.n_components >= 0 && h.n_components <= DMPNN_MAX_COMPONENTS, "head: n_components (%d) outside 0..%d", (int)h.n_components,
@@ -145,8 +158,13 @@ int head_check(const dmpnn_head_args& h, const float* Hv, int64_t ldhv) {
     DMPNN_CHECK_ARG(!xd || h.ld_xd >= h.dims[0] - d, "head: ld_xd (%lld) < d_xd (%lld)", (long long)h.ld_xd, (long long)(h.dims[0] - d));
     for (int l = 0; l < Ln; ++l) DMPNN_CHECK_ARG(h.W[l] && h.dims[l + 1] > 0, "head: layer %d has no weight / width", l);
     DMPNN_CHECK_ARG(h.act >= DMPNN_ACT_NONE && h.act <= DMPNN_ACT_ELU && h.act != DMPNN_ACT_PRELU, "head: activation %d is not built in", h.act);
-    DMPNN_CHECK_ARG(h.loss >= DMPNN_LOSS_MSE && h.loss <= DMPNN_LOSS_DIRICHLET, "head: unknown criterion %d", h.loss);
+    DMPNN_CHECK_ARG(known_criterion(h), "head: unknown criterion %d (n_classes %d)", h.loss, (int)h.n_classes);
     DMPNN_CHECK_ARG(h.loss <= DMPNN_LOSS_MAE || (!h.lt_mask && !h.gt_mask), "head: only the MSE / MAE criteria have bounds (lt_mask / gt_mask)");
+    if (spectral_loss(h.loss)) {
+        DMPNN_CHECK_ARG(h.spectral_act == 0 || h.spectral_act == 1, "head: unknown spectral_act %d (0 softplus, 1 exp)", (int)h.spectral_act);
+        DMPNN_CHECK_ARG(std::isfinite(h.spectral_threshold) && h.spectral_threshold >= 0.f, "head: spectral_threshold (%g) must be finite and >= 0 (0: none)",
+                        (double)h.spectral_threshold);
+    }
     DMPNN_CHECK_ARG((h.loss != DMPNN_LOSS_MVE && h.loss != DMPNN_LOSS_QUANTILE) || h.dims[Ln] % 2 == 0, "head: the MVE / quantile criteria need an output layer 2 n_tasks wide");
     DMPNN_CHECK_ARG(h.loss != DMPNN_LOSS_QUANTILE || (h.quantile_alpha > 0.f && h.quantile_alpha < 1.f), "head: the quantile criterion needs 0 < quantile_alpha < 1");
     DMPNN_CHECK_ARG(h.loss != DMPNN_LOSS_EVIDENTIAL || h.dims[Ln] % 4 == 0, "head: the evidential criterion needs an output layer 4 n_tasks wide");
@@ -210,7 +228,7 @@ HeadRoute head_route(const dmpnn_head_args& h, const float* Hv, int64_t ldhv, He
     // (4, 1 molecule per thread) up to 256 molecules, (2, 1) up to 512, (2, 2) up to 1 024 (DMPNN_HEAD_QPW=4 | 2: the A/B switch)
     R.qpw = (qpw_env && !strcmp(qpw_env, "4")) ? 4 : ((qpw_env && !strcmp(qpw_env, "2")) ? 2 : (B <= 256 ? 4 : 2));
     R.small_out = Ln >= 1 && Ln <= DMPNN_MAX_FFN_LAYERS && h.dims[Ln] <= kOutMaxTasks;
-    R.out_all = R.small_out && want_grad && h.targets && B <= kOutAllMaxRows && loss_per_task(h) == 1;
+    R.out_all = R.small_out && want_grad && h.targets && B <= kOutAllMaxRows && loss_per_task(h) == 1 && !spectral_loss(h.loss);   // (k_loss's criteria)
     // The ride's own conditions — NOT cols_fused: no alignment terms.  (with descriptors and no batch norm the aggregate goes into the fingerprint's
     // rows, not into H; the attentive aggregate needs every atom's logit first; DMPNN_HEAD_AGG=fused | split switches the ride off)
     R.agg_may_ride = h.agg_mode != DMPNN_MOLAGG_ATTENTIVE && B <= kRowsMaxB && h.d_h % 4 == 0 && !chain && (!h.X_d || h.bn_weight) &&
@@ -319,8 +337,19 @@ LossArgs loss_args(const dmpnn_head_args& h, int ldp, int nc, float* gP) {
     return LossArgs{h.preds, ldp, h.targets, t, h.weights, h.task_weights, h.lt_mask, h.gt_mask, gP, ldp, h.loss_out, h.n_mols, t, h.loss, nc,
                     h.evid_v_kl, h.evid_eps, h.quantile_alpha, h.loss == DMPNN_LOSS_DIRICHLET ? (float)std::lgamma((double)nc) : 0.f};
 }
-// the criterion of h.preds into loss_out, its gradient into gP (or NULL): one launch
-int head_criterion(const dmpnn_head_args& h, float* gP, hipStream_t s) {
+// the criterion of h.preds into loss_out, its gradient into gP (or NULL): one launch (the spectral criteria: their own stage, two)
+int head_criterion(const dmpnn_head_args& h, const HeadLayout& L, float* gP, hipStream_t s) {
+    if (spectral_loss(h.loss)) {
+        const int64_t t = h.dims[h.n_layers], n = h.n_mols * t;
+        const SpectralArgs q{h.preds, t, h.targets, t, h.weights, h.task_weights, gP, t, h.loss_out, h.n_mols, (int)t, h.loss, h.spectral_act,
+                             h.spectral_threshold, ws_f(h, L.spec_loss), reinterpret_cast<int*>(ws_at(h, L.spec_cnt))};
+        hipLaunchKernelGGL(k_spectral_rows, dim3((unsigned)h.n_mols), dim3(kSpecCols), 0, s, q);
+        DMPNN_CHECK_LAUNCH("k_spectral_rows");
+        const int64_t blocks = gP ? (n + 4 * kSpecCols - 1) / (4 * kSpecCols) : 1;   // (four elements per thread; without a gradient: the sums alone)
+        hipLaunchKernelGGL(k_spectral_finish, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(kSpecCols), 0, s, q);
+        DMPNN_CHECK_LAUNCH("k_spectral_finish");
+        return DMPNN_OK;
+    }
     const LossArgs q = loss_args(h, (int)h.dims[h.n_layers], loss_per_task(h), gP);
     hipLaunchKernelGGL(k_loss, dim3(1), dim3(1024), 0, s, q);
     DMPNN_CHECK_LAUNCH("k_loss");
@@ -510,7 +539,7 @@ int head_run(const dmpnn_head_args* hp, const float* Hv, int64_t ldhv, void* str
     if (!h.targets) return DMPNN_OK;
     DMPNN_CHECK_ARG(h.loss_out != nullptr, "head: targets without loss_out");
     float* gP = ws_f(h, L.gP);
-    if (!R.out_all) DMPNN_TRY(head_criterion(h, want_grad ? gP : nullptr, static_cast<hipStream_t>(stream)));
+    if (!R.out_all) DMPNN_TRY(head_criterion(h, L, want_grad ? gP : nullptr, static_cast<hipStream_t>(stream)));
     if (!want_grad) return DMPNN_OK;
     HeadGradZ gZ;
     DMPNN_TRY(head_chain_backward(h, L, R, fr, A, gP, defer, &gZ, stream));
@@ -526,9 +555,10 @@ size_t predict_slot_bytes(const dmpnn_head_args& h, const HeadLayout& L, int l) 
     const dmpnn_gemm_args g = ffn_layer(h, l, 1, reinterpret_cast<const float*>(uintptr_t(256)), l == 0 ? ld0 : h.dims[l], nullptr);
     return linear16_ok(g) ? linear16_wsplit_bytes(g.N, g.K1) : 0;
 }
+inline bool known_transform(int t) { return (t >= DMPNN_PT_NONE && t <= DMPNN_PT_QUANTILE) || t == DMPNN_PT_SPECTRAL; }
 bool predict_sizes_ok(const dmpnn_predict_args* p) {
     return p && p->head.n_layers >= 1 && p->head.n_layers <= DMPNN_MAX_FFN_LAYERS && p->head.d_h > 0 && p->head.n_mols >= 0 && p->head.n_components >= 0 &&
-           p->head.n_components <= DMPNN_MAX_COMPONENTS && p->transform >= DMPNN_PT_NONE && p->transform <= DMPNN_PT_QUANTILE;
+           p->head.n_components <= DMPNN_MAX_COMPONENTS && known_transform(p->transform);
 }
 size_t predict_wsplit_total(const dmpnn_head_args& h, const HeadLayout& L) {
     size_t n = 0;
@@ -547,7 +577,9 @@ int predict_check(const dmpnn_predict_args* pp) {
     DMPNN_CHECK_ARG(h.bn_training == 0, "predict_head: inference only — head.bn_training must be 0 (running statistics)");
     DMPNN_CHECK_ARG(h.ffn_dropout_p == 0.f, "predict_head: inference only — head.ffn_dropout_p must be 0 (got %g)", (double)h.ffn_dropout_p);
     DMPNN_CHECK_ARG((p.out_mean == nullptr) == (p.out_scale == nullptr), "predict_head: out_mean and out_scale come together (both or neither)");
-    DMPNN_CHECK_ARG(p.transform >= DMPNN_PT_NONE && p.transform <= DMPNN_PT_QUANTILE, "predict_head: unknown transform %d", (int)p.transform);
+    DMPNN_CHECK_ARG(known_transform(p.transform), "predict_head: unknown transform %d", (int)p.transform);
+    DMPNN_CHECK_ARG(p.transform != DMPNN_PT_SPECTRAL || (!p.out_mean && (h.spectral_act == 0 || h.spectral_act == 1)),
+                    "predict_head: the spectral transform takes no out_mean / out_scale and head.spectral_act 0 (softplus) or 1 (exp), got %d", (int)h.spectral_act);
     DMPNN_CHECK_ARG(h.n_layers >= 1 && h.n_layers <= DMPNN_MAX_FFN_LAYERS, "predict_head: 1..%d predictor layers", DMPNN_MAX_FFN_LAYERS);
     const int64_t n_out = h.dims[h.n_layers];
     DMPNN_CHECK_ARG(n_out > 0 && n_out < (int64_t(1) << 24), "predict_head: bad output width %lld", (long long)n_out);
@@ -558,7 +590,7 @@ int predict_check(const dmpnn_predict_args* pp) {
     DMPNN_CHECK_ARG(p.transform != DMPNN_PT_EVIDENTIAL || n_out % 4 == 0, "predict_head: the evidential transform needs an output layer 4 n_tasks wide (got %lld)",
                     (long long)n_out);
     if (h.targets) {
-        DMPNN_CHECK_ARG(h.loss >= DMPNN_LOSS_MSE && h.loss <= DMPNN_LOSS_DIRICHLET, "head: unknown criterion %d", h.loss);
+        DMPNN_CHECK_ARG(known_criterion(h), "head: unknown criterion %d (n_classes %d)", h.loss, (int)h.n_classes);
         DMPNN_CHECK_ARG(loss_per_task(h) == transform_per_task(p.transform, h.n_classes),
                         "predict_head: the criterion (%d) and the transform (%d) disagree on the outputs per task (%d against %d)", (int)h.loss, (int)p.transform,
                         loss_per_task(h), transform_per_task(p.transform, h.n_classes));
@@ -622,7 +654,7 @@ int predict_core(const dmpnn_predict_args& p, const dmpnn_head_args& h, const fl
     // its own and the launch transforms its rows)
     const int n_out = (int)h.dims[Ln], per = transform_per_task(p.transform, h.n_classes);
     PredictTail q{A, lda, (int)h.dims[Ln - 1], h.W[Ln - 1], h.b[Ln - 1], n_out, B, h.preds, p.preds, p.transform, n_out / per, per, p.out_mean, p.out_scale,
-                  p.fingerprint, p.ld_fp, fr.Z, fr.ldz, (int)h.dims[0]};
+                  p.fingerprint, p.ld_fp, fr.Z, fr.ldz, (int)h.dims[0], h.spectral_act};
     if (n_out > DMPNN_PREDICT_MAX_OUT) {
         dmpnn_gemm_args g = ffn_layer(h, Ln - 1, B, A, lda, h.preds);
         g.act = DMPNN_ACT_NONE;
@@ -631,7 +663,7 @@ int predict_core(const dmpnn_predict_args& p, const dmpnn_head_args& h, const fl
     }
     if (q.W || q.preds || q.fp) DMPNN_TRY(launch_predict_tail(q, s));
     if (!h.targets) return DMPNN_OK;
-    return head_criterion(h, nullptr, s);
+    return head_criterion(h, L, nullptr, s);
 }
 // agg_mode == DMPNN_MOLAGG_ATTENTIVE: the attention forward into the aggregate A, the head as it is on A — B one-atom molecules under SUM,
 // a one-row sum is the row itself, so every form of the head is taken unchanged (pred: the inference head of *pred instead of head_run) — and

@@ -427,6 +427,184 @@ __global__ __launch_bounds__(1024) void k_loss(LossArgs a) {
     }
 }
 
+// ---- the spectral criteria (DMPNN_LOSS_SID / _WASSERSTEIN, dmpnn.h): a grid over molecule rows ---------------------------------
+// A spectrum has hundreds to thousands of tasks and every (molecule, task) pair is coupled to its whole row, so k_loss's one
+// workgroup over all pairs does not fit.  k_spectral_rows: ONE workgroup of kSpecCols threads per molecule row, thread i on column
+// pass * kSpecCols + i (coalesced), the row re-read from memory in every sweep (it is in the CU's cache after the first):
+//     a = softplus(x) | exp(x - max x),  A = sum a,  p = a / A,  c = max(p, thr),  Z = sum m c,  q = c / Z
+//     SID:         L_j = m (q - y) log(q / y);                 G_j = dL/dq_j = tw_j m_j (log(q_j / y_j) + 1 - y_j / q_j)
+//     Wasserstein: D_j = sum_{k <= j} (y_k - q_k), L_j = |D_j|;  G_j = -sum_{k >= j} tw_k m_k sign(D_k)   (masked columns included)
+//     S = sum G q;  dl/dc_j = (G_j - m_j S) / Z;  dl/dp_j = [p_j >= thr] dl/dc_j;  R = sum_k dl/dp_k p_k = (V - S U) / Z with
+//     V = sum_{p >= thr} G p, U = sum_{p >= thr} m p (without a threshold R is analytically 0 and is not formed);
+//     dl/da_j = (dl/dp_j - R) / A;  dl/dx_j = dl/da_j a'(x_j) w_i            (a' = sigmoid(x) | a)
+// Sums: lane shuffles inside a wave, the four waves' totals through LDS in wave order, thread partials in pass order — a fixed order.
+// The running sums of the Wasserstein distance are scans inside a wave (shuffles), a carry across the waves and the passes; the
+// gradient's suffix sums run the same way from the last pass to the first.  The row's loss w_i sum_j tw_j m_j L_j (NaN for a row
+// without a finite target), its count of finite targets and the gradient WITHOUT the grid-wide factor 1 / sum m leave the kernel;
+// k_spectral_finish sums the counts (integers) in every workgroup, the rows' losses in workgroup 0 in a fixed order, and scales the
+// gradient: two launches, no atomics, no host read, bit-identical from call to call.
+constexpr int kSpecCols = 256;                 // columns per pass = threads per workgroup (one molecule row per workgroup)
+constexpr int kSpecWaves = kSpecCols / 64;
+struct SpectralArgs {
+    const float* X; int64_t ldx; const float* T; int64_t ldt; const float* w; const float* tw;
+    float* gP; int64_t ldg; float* out;   // gP (or NULL: the loss alone) rows of ldg; out[0] = loss, out[1] = number of finite targets
+    int64_t B; int t; int kind; int act; float thr;   // act: 0 softplus, 1 exp;  thr: 0 = none
+    float* rowloss; int* cnt;                          // [B] each (workspace): what k_spectral_rows leaves for k_spectral_finish
+};
+// the same sum in every thread of the workgroup; red: kSpecWaves floats of LDS, shared by every call (hence the leading barrier)
+__device__ __forceinline__ float spec_block_sum(float v, float* red) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__device__ __forceinline__ float spec_block_max(float v, float* red) {
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+// one pass of kSpecCols columns: the inclusive prefix sum (REV: suffix sum) of v over the workgroup's threads on top of `carry`, the
+// sum of every pass before (REV: behind) this one, which takes this pass's total
+template <bool REV>
+__device__ __forceinline__ float spec_block_scan(float v, float& carry, float* red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int off = 1; off < 64; off <<= 1) {
+        const float u = REV ? __shfl_down(v, off) : __shfl_up(v, off);
+        if (REV ? lane + off < 64 : lane >= off) v += u;
+    }
+    __syncthreads();
+    if (lane == (REV ? 0 : 63)) red[wave] = v;
+    __syncthreads();
+    float pre = carry, all = carry;
+    for (int k = 0; k < kSpecWaves; ++k) {
+        const int wk = REV ? kSpecWaves - 1 - k : k;   // (the waves in the scan's direction)
+        if (REV ? wk > wave : wk < wave) pre += red[wk];
+        all += red[wk];
+    }
+    carry = all;
+    return v + pre;
+}
+__global__ __launch_bounds__(kSpecCols) void k_spectral_rows(SpectralArgs a) {
+    __shared__ float red[kSpecWaves];
+    __shared__ int redi[kSpecWaves];
+    const int tid = threadIdx.x, t = a.t;
+    const int64_t r = blockIdx.x;
+    const float* __restrict__ x = a.X + r * a.ldx;
+    const float* __restrict__ T = a.T + r * a.ldt;
+    float* g = a.gP ? a.gP + r * a.ldg : nullptr;
+    const bool ex = a.act == 1, sid = a.kind == DMPNN_LOSS_SID;
+    const float thr = a.thr;
+    // exp: the row maximum is subtracted first (the same p in exact arithmetic; finite where exp(x) alone overflows)
+    float mx = 0.f;
+    if (ex) {
+        float m = -INFINITY;
+        for (int j = tid; j < t; j += kSpecCols) m = fmaxf(m, x[j]);
+        mx = spec_block_max(m, red);
+    }
+    auto act = [&](float v) { return ex ? expf(v - mx) : softplus_f(v); };
+    float s0 = 0.f;
+    for (int j = tid; j < t; j += kSpecCols) s0 += act(x[j]);
+    const float A = spec_block_sum(s0, red);
+    float sz = 0.f, su = 0.f;
+    int c = 0;
+    for (int j = tid; j < t; j += kSpecCols) {
+        if (!isfinite(T[j])) continue;
+        const float p = act(x[j]) / A;
+        ++c; sz += fmaxf(p, thr);
+        if (p >= thr) su += p;
+    }
+    const float Z = spec_block_sum(sz, red), U = spec_block_sum(su, red);
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+    if ((tid & 63) == 0) redi[tid >> 6] = c;   // (read behind the barriers of the sums below)
+    // the row's loss; into g the derivative G_j of sum_j tw_j m_j L_j in q_j (SID) or the weighted signs tw_j m_j sign(D_j) (Wasserstein)
+    float sl = 0.f, sS = 0.f, sV = 0.f;
+    if (sid) {
+        for (int j = tid; j < t; j += kSpecCols) {
+            const float y = T[j];
+            float G = 0.f;
+            if (isfinite(y)) {
+                const float p = act(x[j]) / A, q = fmaxf(p, thr) / Z, lr = logf(q / y), twj = a.tw ? a.tw[j] : 1.f;
+                sl += twj * (q * lr + y * logf(y / q));
+                G = twj * (lr + 1.f - y / q);
+                sS += G * q;
+                if (p >= thr) sV += G * p;
+            }
+            if (g) g[j] = G;
+        }
+    } else {
+        const int last = ((t - 1) / kSpecCols) * kSpecCols;
+        float carry = 0.f;
+        for (int j0 = 0; j0 <= last; j0 += kSpecCols) {   // (every thread takes part in every pass's scan)
+            const int j = j0 + tid;
+            const bool in = j < t;
+            const float y = in ? T[j] : 0.f;
+            const bool m = in && isfinite(y);
+            const float q = in ? fmaxf(act(x[j]) / A, thr) / Z : 0.f;
+            const float D = spec_block_scan<false>((m ? y : 0.f) - q, carry, red);
+            if (m) {
+                const float twj = a.tw ? a.tw[j] : 1.f;
+                sl += twj * fabsf(D);
+                if (g) g[j] = twj * (D > 0.f ? 1.f : (D < 0.f ? -1.f : 0.f));
+            } else if (in && g) g[j] = 0.f;
+        }
+        if (g) {   // (uniform) G_j = -sum_{k >= j} of the signs: each thread re-reads what it wrote itself
+            carry = 0.f;
+            for (int j0 = last; j0 >= 0; j0 -= kSpecCols) {
+                const int j = j0 + tid;
+                const bool in = j < t;
+                const float G = -spec_block_scan<true>(in ? g[j] : 0.f, carry, red);
+                if (in) {
+                    const float p = act(x[j]) / A;
+                    sS += G * (fmaxf(p, thr) / Z);
+                    if (p >= thr) sV += G * p;
+                    g[j] = G;
+                }
+            }
+        }
+    }
+    const float SL = spec_block_sum(sl, red);
+    if (tid == 0) {
+        const int n = (redi[0] + redi[1]) + (redi[2] + redi[3]);
+        a.cnt[r] = n;
+        a.rowloss[r] = n > 0 ? (a.w ? a.w[r] : 1.f) * SL : __int_as_float(0x7fc00000);   // (a row without a finite target: NaN, dmpnn.h)
+    }
+    if (!g) return;   // (uniform)
+    const float S = spec_block_sum(sS, red), V = spec_block_sum(sV, red);
+    const float R = thr > 0.f ? (V - S * U) / Z : 0.f, wr = a.w ? a.w[r] : 1.f;
+    for (int j = tid; j < t; j += kSpecCols) {
+        const float xv = x[j], av = act(xv), p = av / A;
+        const float gp = p >= thr ? (g[j] - (isfinite(T[j]) ? S : 0.f)) / Z : 0.f;
+        g[j] = (gp - R) / A * (ex ? av : softplus_d(xv)) * wr;
+    }
+}
+__global__ __launch_bounds__(kSpecCols) void k_spectral_finish(SpectralArgs a) {
+    __shared__ float red[kSpecWaves];
+    __shared__ int redi[kSpecWaves];
+    const int tid = threadIdx.x;
+    int c = 0;
+    for (int64_t i = tid; i < a.B; i += kSpecCols) c += a.cnt[i];
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+    if ((tid & 63) == 0) redi[tid >> 6] = c;
+    __syncthreads();
+    const float M = (float)((redi[0] + redi[1]) + (redi[2] + redi[3]));
+    if (blockIdx.x == 0) {
+        float s = 0.f;
+        for (int64_t i = tid; i < a.B; i += kSpecCols) s += a.rowloss[i];
+        s = spec_block_sum(s, red);
+        if (tid == 0) { a.out[0] = s / M; a.out[1] = M; }   // (no finite target: NaN, like every criterion)
+    }
+    if (!a.gP) return;
+    const float inv = 1.f / M;
+    const int64_t n = a.B * a.t;
+    for (int64_t i = (int64_t)blockIdx.x * kSpecCols + tid; i < n; i += (int64_t)gridDim.x * kSpecCols) {
+        const int64_t r = i / a.t;
+        a.gP[r * a.ldg + (i - r * a.t)] *= inv;
+    }
+}
+
 // ---- the predictor's OUTPUT layer for a handful of tasks (n_tasks <= kOutMaxTasks: the usual regression head) ----------------
 // P = A W^T + b with W [t, K]: t dot products per row — one wave per row, lanes over K (a 16 x 16 MFMA tile would be 1/16 full
 // and the generic contraction kernel spends 17 us on its pipeline for 0.3 MFLOP).

@@ -11,6 +11,8 @@
 // shuffles.  A row's n_out raw values then go through LDS: the transform's groups — softmax over the nc classes of a task, the
 // chunked columns k t + j of the mean-variance / evidential / quantile predictors — gather values that other lanes reduced.
 // n_out > DMPNN_PREDICT_MAX_OUT: the contraction kernels ran the layer; the <false> build reads the raw rows from memory instead.
+// DMPNN_PT_SPECTRAL couples an element to its whole row (p = a / sum_row a): the row's sum, and its maximum for exp, are wave
+// reductions once per row in front of the element loop, in both builds.
 #include "dmpnn_gemm_impl.hpp"   // (gemm::make_rsrc / clamp_bytes / kOOB: the buffer descriptors of every kernel here)
 
 namespace dmpnn {
@@ -98,9 +100,26 @@ __global__ __launch_bounds__(64 * kTailRows) void k_predict_tail(PredictTail q) 
         if constexpr (MATVEC) return xs[wave][c];
         else return q.raw[r * q.n_out + c];
     };
+    // (uniform) DMPNN_PT_SPECTRAL, p = a / sum_row a with a = softplus(x) | exp(x - max_row x): the row's maximum and sum once per row, as
+    // wave reductions in front of the element loop — a spectrum is hundreds of columns wide, not a softmax's handful of classes
+    const bool spectral = q.transform == DMPNN_PT_SPECTRAL && q.preds;
+    float sp_mx = 0.f, sp_sum = 1.f;
+    auto sp_act = [&](float v) { return q.spectral_act == 1 ? expf(v - sp_mx) : softplus_f(v); };
+    if (spectral) {
+        if (q.spectral_act == 1) {
+            float m = -INFINITY;
+            for (int e = lane; e < q.n_out; e += 64) m = fmaxf(m, x(e));
+            for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+            sp_mx = m;
+        }
+        float s = 0.f;
+        for (int e = lane; e < q.n_out; e += 64) s += sp_act(x(e));
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+        sp_sum = s;
+    }
     for (int e = lane; e < q.n_out; e += 64) {
         if constexpr (MATVEC) q.raw[r * q.n_out + e] = x(e);
-        if (q.preds) q.preds[r * q.n_out + e] = tail_transform(q, e, x);
+        if (q.preds) q.preds[r * q.n_out + e] = spectral ? sp_act(x(e)) / sp_sum : tail_transform(q, e, x);
     }
     if (q.fp)
         for (int c = lane; c < q.fp_w; c += 64) q.fp[r * q.ld_fp + c] = q.Z[r * q.ldz + c];

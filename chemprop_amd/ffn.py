@@ -25,10 +25,22 @@ from . import engine
 from .nn import classify_activation, get_activation_function
 
 
+def mlp_blocks(seq: nn.Sequential) -> list:
+    """The MLP's layer blocks: every child but the ``spectral_activation`` a ``SpectralFFN`` appends behind them."""
+    return [m for name, m in seq.named_children() if name != "spectral_activation"]
+
+
 def mlp_forward(seq: nn.Sequential, X: Tensor) -> Tensor:
-    """``MLP.forward`` (= ``nn.Sequential.forward`` over the blocks of ffn.py:49-58) on the kernels."""
+    """``MLP.forward`` (= ``nn.Sequential.forward`` over the blocks of ffn.py:49-58) on the kernels; a ``spectral_activation`` child
+    behind the blocks is applied last, as ``nn.Sequential`` would."""
+    tail = getattr(seq, "spectral_activation", None)
+    if tail is not None:
+        return tail(_mlp_forward(mlp_blocks(seq), seq, X))
+    return _mlp_forward(list(seq), seq, X)
+
+
+def _mlp_forward(blocks: list, seq: nn.Sequential, X: Tensor) -> Tensor:
     engine._require_device(X, "X")
-    blocks = list(seq)
     lin0 = blocks[0][-1]
     if lin0.weight.device != X.device:
         raise RuntimeError(f"module is on {lin0.weight.device} but the input is on {X.device}")
@@ -84,7 +96,7 @@ class MLP(nn.Sequential):
 
     @property
     def output_dim(self) -> int:
-        return self[-1][-1].out_features
+        return mlp_blocks(self)[-1][-1].out_features
 
     def forward(self, X: Tensor) -> Tensor:
         return mlp_forward(self, X)

@@ -24,26 +24,36 @@ from torch import Tensor, nn
 from . import _lib, engine
 from .agg import MODES, Aggregation, NormAggregation, note_batch
 from .distributed import GradSync, force_collective
-from .ffn import MLP
+from .ffn import MLP, mlp_blocks
 from .nn import BondMessagePassing, MulticomponentMessagePassing, classify_activation
 from .data import merge_components
 from .optim import CLIP_MODES, FlatAdam
 
 __all__ = ["MSE", "MAE", "BCE", "CE", "MVE", "Evidential", "Quantile", "RegressionFFN", "BinaryClassificationFFN", "MulticlassClassificationFFN", "MveFFN", "EvidentialFFN", "QuantileFFN",
-           "Dirichlet", "BinaryDirichletFFN", "MulticlassDirichletFFN", "MPNN", "MulticomponentMPNN", "FusedTrainer", "masked_loss"]
+           "Dirichlet", "BinaryDirichletFFN", "MulticlassDirichletFFN", "SID", "Wasserstein", "SpectralFFN", "MPNN", "MulticomponentMPNN", "FusedTrainer", "masked_loss"]
 
 
 def masked_loss(preds: Tensor, targets: Tensor, weights: Optional[Tensor] = None, task_weights: Optional[Tensor] = None,
                 lt_mask: Optional[Tensor] = None, gt_mask: Optional[Tensor] = None, kind: str = "mse", v_kl: float = 0.2, eps: float = 1e-8,
-                alpha: float = 0.1) -> Tensor:
+                alpha: float = 0.1, threshold: Optional[float] = None) -> Tensor:
     """``ChempropMetric.update`` + ``compute`` on one batch (``nn/metrics.py:78-127``) with the masking of
     ``MPNN.training_step`` (``models/model.py:152-156``): torch ops, differentiable — the module path's criterion."""
     mask = targets.isfinite()
     targets = targets.nan_to_num(nan=0.0)
     w = torch.ones(targets.shape[0], dtype=torch.float, device=targets.device) if weights is None else weights
     tw = 1.0 if task_weights is None else task_weights.view(1, -1)
-    if kind in ("bce", "ce", "mve", "evidential", "quantile", "dirichlet"):
+    if kind in ("bce", "ce", "mve", "evidential", "quantile", "dirichlet", "sid", "wasserstein"):
         lt_mask = gt_mask = None     # (only the Bounded* criteria apply the masks: metrics.py:157-177)
+    if kind in ("sid", "wasserstein"):   # preds [b, t] = p (SpectralFFN.train_step): renormalised over the finite targets (include/dmpnn.h)
+        c = preds if threshold is None else preds.clamp(min=threshold)
+        q = c / (c * mask).sum(1, keepdim=True)
+        if kind == "sid":            # (masked q and y filled with 1: a zero term)
+            one = torch.ones_like(q)
+            qm, ym = torch.where(mask, q, one), torch.where(mask, targets, one)
+            L = qm * (qm / ym).log() + ym * (ym / qm).log()
+        else:                        # (the running sum of q includes the masked columns; only y is 0 there)
+            L = (targets.cumsum(1) - q.cumsum(1)).abs()
+        return (L * w.view(-1, 1) * tw * mask).sum() / mask.sum()
     if kind == "dirichlet":          # preds [b, t, c] = alpha (the Dirichlet predictors' train_step), targets [b, t] class indices (DirichletLoss)
         y = torch.nn.functional.one_hot(targets.long(), preds.shape[-1]).to(preds.dtype)
         S = preds.sum(-1, keepdim=True)
@@ -87,8 +97,10 @@ def masked_loss(preds: Tensor, targets: Tensor, weights: Optional[Tensor] = None
 
 def criterion_loss(c, preds: Tensor, targets: Tensor, weights=None, lt_mask=None, gt_mask=None) -> Tensor:
     """:func:`masked_loss` with what the criterion ``c`` carries — this package's or the reference's (``task_weights``, ``v_kl``, ...)."""
+    thr = getattr(c, "threshold", None)
     return masked_loss(preds, targets, weights, getattr(c, "task_weights", None), lt_mask, gt_mask, getattr(c, "kind", "mse"),
-                       float(getattr(c, "v_kl", 0.2)), float(getattr(c, "eps", 1e-8)), float(getattr(c, "alpha", 0.1)))
+                       float(getattr(c, "v_kl", 0.2)), float(getattr(c, "eps", 1e-8)), float(getattr(c, "alpha", 0.1)),
+                       None if thr is None else float(thr))
 
 
 class MSE(nn.Module):
@@ -310,6 +322,67 @@ class MulticlassDirichletFFN(MulticlassClassificationFFN):
         return alpha / alpha.sum(-1, keepdim=True)
 
 
+class SID(MSE):
+    """``chemprop.nn.metrics.SID``: the spectral information divergence of ``preds [b, t]`` = ``p`` (``SpectralFFN``) against target
+    spectra, both renormalised over the finite targets; ``threshold``: a lower clamp of ``p`` (``None``: none); no bounds."""
+
+    kind = "sid"
+
+    def __init__(self, task_weights=1.0, threshold: Optional[float] = None):
+        super().__init__(task_weights)
+        self.threshold = threshold
+
+
+class Wasserstein(SID):
+    """``chemprop.nn.metrics.Wasserstein``: ``|cumsum(y) - cumsum(q)|`` per column, the masked columns' ``q`` inside the running sum."""
+
+    kind = "wasserstein"
+
+
+class _Exp(nn.Module):
+    def forward(self, x: Tensor) -> Tensor:
+        return x.exp()
+
+
+class SpectralFFN(RegressionFFN):
+    """``chemprop.nn.predictors.SpectralFFN``: the MLP ``n_tasks`` wide, then ``a = softplus(x)`` (``spectral_activation="softplus"``) or
+    ``exp(x)`` (``"exp"``) and ``p = a / sum_j a``: a spectrum that sums to 1.  The activation is a child of ``ffn`` named
+    ``spectral_activation``, as in the reference — not a layer of the MLP; ``train_step`` is ``forward``."""
+
+    _default_criterion = SID
+
+    def __init__(self, n_tasks: int = 1, input_dim: int = 300, hidden_dim: int = 300, n_layers: int = 1, dropout: float = 0.0,
+                 activation="relu", criterion: Optional[nn.Module] = None, task_weights: Optional[Tensor] = None,
+                 spectral_activation: str = "softplus"):
+        super().__init__(n_tasks, input_dim, hidden_dim, n_layers, dropout, activation, criterion, task_weights)
+        if spectral_activation not in ("softplus", "exp"):
+            raise ValueError(f'spectral_activation must be "softplus" or "exp", got {spectral_activation!r}')
+        self.hparams.update(spectral_activation=spectral_activation)
+        self.ffn.add_module("spectral_activation", nn.Softplus() if spectral_activation == "softplus" else _Exp())
+
+    def forward(self, Z: Tensor) -> Tensor:
+        Y = self.ffn(Z)   # (mlp_forward runs the spectral_activation child last, as nn.Sequential does)
+        return Y / Y.sum(1, keepdim=True)
+
+    train_step = forward
+
+
+def _predictor_blocks(pred) -> list:
+    """The predictor's MLP blocks: the children of ``ffn`` but for a ``SpectralFFN``'s ``spectral_activation``."""
+    return mlp_blocks(pred.ffn)
+
+
+def spectral_activation_of(pred) -> Optional[str]:
+    """``"softplus" | "exp"`` of a ``SpectralFFN`` (this package's or the reference's, by its ``spectral_activation`` child), ``None``
+    for an activation the kernels do not have."""
+    act = getattr(pred.ffn, "spectral_activation", None)
+    if isinstance(act, nn.Softplus) and act.beta == 1 and act.threshold == 20:
+        return "softplus"
+    if act is not None and type(act).__name__.lstrip("_").lower() == "exp":
+        return "exp"
+    return None
+
+
 class MPNN(nn.Module):
     """``chemprop.models.MPNN`` (``models/model.py:60-146``) without Lightning: the four sub-modules under the reference's
     names and ``fingerprint`` / ``forward``; ``loss(batch)`` is the arithmetic of ``training_step`` (``model.py:148-161``).
@@ -509,6 +582,10 @@ def criterion_kind(crit) -> tuple[Optional[str], bool]:
         return "ce", False
     if "DirichletLoss" in names:      # nn/metrics.py (evidential classification: alpha [b, t, c] against class indices)
         return "dirichlet", False
+    if "Wasserstein" in names:        # nn/metrics.py (spectra: p [b, t] against target spectra)
+        return "wasserstein", False
+    if "SID" in names:
+        return "sid", False
     for cls, k in (("MSE", "mse"), ("MAE", "mae")):
         if cls in names:
             return k, "BoundedMixin" in names
@@ -545,7 +622,12 @@ class HeadSpec:
 
     A Dirichlet classification head is taken as exactly the pair (``BinaryDirichletFFN`` | ``MulticlassDirichletFFN``, ``DirichletLoss``)
     — this package's mirrors or the reference's classes, by name: ``kind == "dirichlet"``, ``n_classes`` the predictor's (2 for the
-    binary one), ``n_tasks = n_out / n_classes``, ``v_kl`` handed over as ``evid_v_kl``."""
+    binary one), ``n_tasks = n_out / n_classes``, ``v_kl`` handed over as ``evid_v_kl``.
+
+    A spectral head is taken as exactly the pair (``SpectralFFN``, ``SID`` | ``Wasserstein``), by name as well: ``kind == "sid" |
+    "wasserstein"``, one output per task; ``spectral_act`` (``"softplus" | "exp"``, read off the ``spectral_activation`` child of
+    ``ffn``, which is not one of ``layers``) and ``spectral_threshold`` (the criterion's ``threshold``, 0.0 for ``None``) travel in
+    ``dmpnn_head_args.spectral_act`` / ``spectral_threshold``."""
 
     def __init__(self, model, ffn_dropout: bool = False, attentive: bool = False):
         agg, pred = model.agg, model.predictor
@@ -564,7 +646,7 @@ class HeadSpec:
             self.att = W
         elif mode is None:
             raise NotImplementedError(f"sum / mean / norm aggregation (got {type(agg).__name__})")
-        blocks = list(pred.ffn)
+        blocks = _predictor_blocks(pred)   # (a SpectralFFN's spectral_activation child is not a layer)
         if len(blocks) > _lib.MAX_FFN_LAYERS:
             raise NotImplementedError(f"at most {_lib.MAX_FFN_LAYERS} predictor layers")
         f_act, f_slope = "none", 0.0
@@ -586,7 +668,7 @@ class HeadSpec:
             raise NotImplementedError("the output transform is the identity while training (predictors.py:166-169)")
         kind, self.bounded = criterion_kind(pred.criterion)
         if kind is None:
-            raise NotImplementedError("MSE / MAE criterion (bounded or not), BCE, cross entropy, MVE, evidential, quantile or Dirichlet")
+            raise NotImplementedError("MSE / MAE criterion (bounded or not), BCE, cross entropy, MVE, evidential, quantile, Dirichlet, SID or Wasserstein")
         # evidential classification: exactly the pairs (BinaryDirichletFFN | MulticlassDirichletFFN, DirichletLoss), the predictors told
         # by MRO name like the other reference classes; the class layout is cross entropy's, the binary head has two classes per task
         # (its n_targets = 2 says the same thing: for the kernels it is a class dimension, not a chunked one)
@@ -596,6 +678,21 @@ class HeadSpec:
             raise NotImplementedError("a Dirichlet criterion on a predictor that is neither BinaryDirichletFFN nor MulticlassDirichletFFN"
                                       if kind == "dirichlet" else f"a Dirichlet predictor ({type(pred).__name__}) with a criterion "
                                       f"other than DirichletLoss (got {kind})")
+        # spectra: exactly the pairs (SpectralFFN, SID | Wasserstein); the activation and the threshold travel in spectral_act / _threshold
+        spectral_pred = "SpectralFFN" in names
+        if (kind in ("sid", "wasserstein")) != spectral_pred:
+            raise NotImplementedError(f"a spectral criterion ({kind}) on a predictor that is not a SpectralFFN" if not spectral_pred else
+                                      f"a SpectralFFN with a criterion other than SID / Wasserstein (got {kind})")
+        self.spectral_act, self.spectral_threshold = None, 0.0
+        if spectral_pred:
+            self.spectral_act = spectral_activation_of(pred)
+            if self.spectral_act is None:
+                raise NotImplementedError(f"a SpectralFFN whose spectral_activation is softplus or exp "
+                                          f"(got {getattr(pred.ffn, 'spectral_activation', None)!r})")
+            thr = getattr(pred.criterion, "threshold", None)
+            self.spectral_threshold = 0.0 if thr is None else float(thr)
+            if not (math.isfinite(self.spectral_threshold) and self.spectral_threshold >= 0):
+                raise NotImplementedError(f"a spectral criterion's threshold is None or a finite number >= 0 (got {thr!r})")
         # values per task (predictors.py: n_targets): 1, or — round 6 — the mean-variance / evidential pairs of predictor and criterion
         # (MveFFN + MVELoss: 2, EvidentialFFN + EvidentialLoss: 4, QuantileFFN + QuantileLoss: 2; the predictors' transforms of the
         # raw outputs live in the criterion kernel)
@@ -717,6 +814,8 @@ class HeadSpec:
         h.loss = _lib.LOSS[self.kind]
         h.n_classes = self.n_classes
         h.evid_v_kl, h.evid_eps, h.quantile_alpha = self.v_kl, self.eps, self.q_alpha
+        if self.spectral_act is not None:
+            h.spectral_act, h.spectral_threshold = _lib.SPECTRAL_ACT[self.spectral_act], self.spectral_threshold
         h.targets = T.data_ptr()
         keep = [] if X_d is None else [X_d]
         if weights is not None:

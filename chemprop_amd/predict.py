@@ -20,7 +20,7 @@ from .model import HeadSpec, _batch_vector_ok, _component_batch, _head_spec_key,
 
 # the predictor classes (this package's mirrors and the reference's, by MRO name: nn/predictors.py) and the output transform their
 # eval-mode forward applies; the specific classes first — every one of them derives from RegressionFFN
-_TRANSFORM_OF = (("MveFFN", "mve"), ("EvidentialFFN", "evidential"), ("QuantileFFN", "quantile"),
+_TRANSFORM_OF = (("SpectralFFN", "spectral"), ("MveFFN", "mve"), ("EvidentialFFN", "evidential"), ("QuantileFFN", "quantile"),
                  ("MulticlassClassificationFFN", "softmax"), ("BinaryClassificationFFN", "sigmoid"), ("RegressionFFN", "unscale"))
 _GROUP = {"mve": 2, "evidential": 4, "quantile": 2}
 
@@ -37,7 +37,7 @@ class PredictResult(NamedTuple):
 
 class PredictSpec(HeadSpec):
     """What ``dmpnn_predict_head`` needs to know of the model: :class:`~chemprop_amd.model.HeadSpec` with the predictor's dropout and
-    attentive aggregation allowed, plus the output transform (``transform``: a key of ``_lib.PREDICT_TRANSFORM``, told from the
+    attentive aggregation allowed, plus the output transform (``transform``: a key of ``_lib.PREDICT_TRANSFORM`` or ``"spectral"``, told from the
     predictor's class) and the ``UnscaleTransform`` behind it (``unscale``: the module, or ``None`` for ``nn.Identity``).  Raises
     ``NotImplementedError`` for what the inference head does not take.  Also holds the per-model workspace and the cached split
     images of the hidden layers' weights."""
@@ -55,6 +55,8 @@ class PredictSpec(HeadSpec):
             raise NotImplementedError(f"a predictor of a known class (got {type(pred).__name__})")
         ot = pred.output_transform
         self.unscale = None
+        if self.transform == "spectral" and not isinstance(ot, nn.Identity):   # (p sums to 1: DMPNN_PT_SPECTRAL takes no mean / scale)
+            raise NotImplementedError("a SpectralFFN with an output transform that is not the identity")
         if not isinstance(ot, nn.Identity):   # (HeadSpec: an UnscaleTransform by name — identity while training, X * scale + mean in eval mode)
             if self.transform in ("sigmoid", "softmax"):
                 raise NotImplementedError("a classification predictor without an UnscaleTransform")
@@ -68,7 +70,7 @@ class PredictSpec(HeadSpec):
         self._sizes: dict = {}
 
     def out_shape(self, n_mols: int) -> tuple:
-        """The shape ``model(...)`` returns in eval mode."""
+        """The shape ``model(...)`` returns in eval mode (a spectral head: ``[n_mols, n_tasks]``, one value per task)."""
         if self.transform == "softmax":
             return (n_mols, self.n_tasks, self.n_classes)
         if self.transform in _GROUP:
@@ -155,7 +157,7 @@ def fused_predict(model, bmg, V_d=None, X_d=None, *, targets: Optional[Tensor] =
     h = p.head
     keep = spec.fill(h, nV, n_mols, d_out, batch, Hv if T is None else T, weights if T is not None else None, lt_mask if T is not None else None,
                      gt_mask if T is not None else None, lambda prm: None, bn_training=False, X_d=Xd)
-    p.transform = _lib.PREDICT_TRANSFORM[spec.transform]
+    p.transform = _lib.PT_SPECTRAL if spec.transform == "spectral" else _lib.PREDICT_TRANSFORM[spec.transform]
     if spec.unscale is not None:
         mean, scale = (t.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous() for t in (spec.unscale.mean, spec.unscale.scale))
         p.out_mean, p.out_scale = mean.data_ptr(), scale.data_ptr()

@@ -59,7 +59,9 @@ extern "C" {
  * dmpnn_molagg_attn_fwd / _bwd / _ws_bytes and dmpnn_head_args.att_W / att_b / g_att_W / g_att_b (zero in an older caller); DMPNN_F_UNDIRECTED_MASK
  * (a flag bit no older caller sets: dropout_p > 0 with DMPNN_F_UNDIRECTED on the per-step general route, DMPNN_EINVAL without it).
  * Added, same version (new entries only; no existing struct or entry changes): dmpnn_backward_inputs / dmpnn_backward_inputs_ws_bytes /
- * dmpnn_bwd_inputs_args (gradients with respect to V, E and V_d on the per-step general route) and dmpnn_src_sum. */
+ * dmpnn_bwd_inputs_args (gradients with respect to V, E and V_d on the per-step general route) and dmpnn_src_sum.
+ * Grown, same version: DMPNN_LOSS_SID / DMPNN_LOSS_WASSERSTEIN and DMPNN_PT_SPECTRAL (new accepted values) with
+ * dmpnn_head_args.spectral_act / spectral_threshold at its end (zero in an older caller: read by the new values alone). */
 #define DMPNN_ABI_VERSION 15
 
 enum dmpnn_status {
@@ -749,7 +751,37 @@ enum dmpnn_loss { DMPNN_LOSS_MSE = 0, DMPNN_LOSS_MAE = 1,
                                          L_mse = sum_k (y_k - p_k)^2 + sum_k p_k (1 - p_k) / (S + 1);
                                          alpha~ = y + (1 - y) alpha, S~ = sum_k alpha~_k:
                                          L_kl = lgamma(S~) - sum_k lgamma(alpha~_k) - lgamma(K) + sum_k (alpha~_k - 1) (psi(alpha~_k) - psi(S~));
-                                         L = L_mse + evid_v_kl L_kl (evid_v_kl: DirichletLoss.v_kl).  No bounds */ };
+                                         L = L_mse + evid_v_kl L_kl (evid_v_kl: DirichletLoss.v_kl).  No bounds */
+                  , DMPNN_LOSS_SID = 8, DMPNN_LOSS_WASSERSTEIN = 9
+                                      /* v15 growth: the spectral criteria (SID / Wasserstein, nn/metrics.py, on SpectralFFN.train_step,
+                                         nn/predictors.py) — see "The spectral criteria" below.  One output per task; preds holds the raw x.
+                                         n_classes != 0 beside them is no criterion this library knows ("unknown criterion":
+                                         DMPNN_EINVAL), bounds masks beside them: DMPNN_EINVAL */ };
+/* The spectral criteria.  These formulas are the contract: they restate chemprop 2.3.1 (nn/predictors.py: SpectralFFN; nn/metrics.py:
+ * SID, Wasserstein, ChempropMetric.update / compute) from memory and were NOT run against that source.
+ *   x [B, t] the MLP's raw output; T [B, t] the targets, m = isfinite(T), y = T where finite, else 0; w [B] row weights, tw [t] task
+ *   weights; thr = spectral_threshold (the criterion's `threshold`; None there = 0 here = no clamp).
+ * Predictor (SpectralFFN.forward, which is also its train_step):
+ *   a = softplus(x) (beta 1, threshold 20) for spectral_act 0, a = exp(x) for spectral_act 1 (spectral_activation="exp");
+ *   p = a / sum_j a_ij, summed over ALL columns.  (The reference appends the activation module to `ffn` as a child named
+ *   spectral_activation; it is not a layer of the MLP.)
+ * Both criteria:  c = max(p, thr) if thr is given, else p;  Z_i = sum_j m_ij c_ij;  q = c / Z_i.
+ *   SID:          L_ij = q log(q / y) + y log(y / q) where m, 0 elsewhere (the reference fills masked q and y with 1).
+ *   Wasserstein:  L_ij = | sum_{k<=j} y_ik - sum_{k<=j} q_ik |.  The running sum of q INCLUDES the masked columns' q; only y is 0
+ *                 there (no masked_fill in that criterion, as recalled).  Consequence: masked columns get a non-zero gradient; in
+ *                 SID without a threshold their gradient is analytically zero (and exactly 0 here).
+ *   Reduction (update + compute):  loss = sum L w_i tw_j m / sum m;  loss_out = [loss, sum m], as for every other criterion.
+ * Declared behaviour at the edges:
+ *   - no finite target anywhere: NaN loss, as for every criterion;
+ *   - a row with no finite target while others have some: loss_out[0] is NaN.  (The reference's Wasserstein loss is NaN there, and its
+ *     SID gradient is NaN there (0 / 0) beside a finite loss: a declared deviation in favour of "never silently wrong");
+ *   - a finite target of 0 in SID: NaN as in the reference (0 log 0); not special-cased;
+ *   - exp: the kernels subtract the row maximum before exponentiating — identical in exact arithmetic for p, and finite where exp(x)
+ *     alone overflows float32;
+ *   - thr: 0 means none (p > 0, so a clamp at 0 is a no-op); the clamp's derivative is 1 for p >= thr, as torch's; negative or
+ *     non-finite: DMPNN_EINVAL.  An unknown spectral_act: DMPNN_EINVAL.
+ * The stage (k_spectral_rows + k_spectral_finish, two launches in place of k_loss's one): a grid over molecule rows, sums and scans in a
+ * fixed order, no floating-point atomics — loss_out and the gradients are bit-identical from call to call. */
 typedef struct dmpnn_head_args {
     int64_t n_atoms, n_mols, d_h;           /* rows of H_v, molecules, width of H_v                              */
     const int64_t* batch;                   /* [n_atoms] molecule of every atom, non-decreasing (BatchMolGraph.batch) */
@@ -801,6 +833,9 @@ typedef struct dmpnn_head_args {
                                                as on a batch of one-atom molecules, dmpnn_molagg_attn_bwd carries its input gradient back
                                                to gHv.  n_components > 1 with it: DMPNN_EINVAL.  Zero in an older caller; ignored in the
                                                other modes.  dmpnn_head_ws_bytes() grows in this mode only */
+    int32_t spectral_act; float spectral_threshold;  /* v15 growth: DMPNN_LOSS_SID / _WASSERSTEIN and DMPNN_PT_SPECTRAL — SpectralFFN's
+                                               activation (0 softplus, 1 exp) and the criterion's threshold (0: none).  Zero in an older
+                                               caller; ignored by every other criterion and transform */
 } dmpnn_head_args;
 size_t dmpnn_head_ws_bytes(const dmpnn_head_args* h);
 int dmpnn_head(const dmpnn_head_args* h, const float* Hv, int64_t ldhv, void* stream);
@@ -812,7 +847,7 @@ int dmpnn_head(const dmpnn_head_args* h, const float* Hv, int64_t ldhv, void* st
  * kernel k_head_rows<., 1>, 16 molecules x 64 columns per workgroup, where the reduction width is whole quads up to 512; k_rows16
  * otherwise; a layer whose shape dmpnn_linear16_ok refuses — odd widths, unaligned rows — runs as dmpnn_linear_fwd), then ONE launch
  * (k_predict_tail) for the output layer, the predictor's output
- * transform and every store, and k_loss when targets are given.  The usual model (sum / mean / norm aggregation, batch norm, one hidden
+ * transform and every store, and k_loss when targets are given (the spectral criteria: their stage of two launches).  The usual model (sum / mean / norm aggregation, batch norm, one hidden
  * layer, <= DMPNN_PREDICT_MAX_OUT outputs, <= 1 024 molecules, widths in whole quads) with a ready split: three launches, four with
  * targets (dmpnn_last_launch_count()).  Output layers wider than DMPNN_PREDICT_MAX_OUT run on the contraction kernels and
  * k_predict_tail transforms their rows.
@@ -831,7 +866,8 @@ int dmpnn_head(const dmpnn_head_args* h, const float* Hv, int64_t ldhv, void* st
  * threshold 20):  NONE p[j] = x[j];  UNSCALE p[j] = x[j] s + m;  SIGMOID p[j] = 1 / (1 + exp(-x[j]));  SOFTMAX p[j][k] =
  * softmax_k(x[j nc + k]) (the maximum subtracted first);  MVE p[j] = (x[j] s + m, softplus(x[t+j]) s^2);  EVIDENTIAL p[j] = (x[j] s
  * + m, softplus(x[t+j]), softplus(x[2t+j]) + 1, softplus(x[3t+j]) s^2);  QUANTILE lo = x[j] s + m, up = x[t+j] s + m: p[j] = ((lo +
- * up) / 2, up - lo).  These are the eval-mode forward of nn/predictors.py with UnscaleTransform / transform_variance.
+ * up) / 2, up - lo);  SPECTRAL p[j] = a(x[j]) / sum_k a(x[k]) (below the enum).  These are the eval-mode forward of nn/predictors.py with
+ * UnscaleTransform / transform_variance.
  *
  * wsplit: the f16 split images of the hidden layers' weights, one slot per layer l < n_layers - 1 in layer order, each
  * dmpnn_linear16_wsplit_bytes(dims[l+1], dims[l]) long — 0 for a layer that runs as dmpnn_linear_fwd — kept by the caller between
@@ -841,6 +877,11 @@ int dmpnn_head(const dmpnn_head_args* h, const float* Hv, int64_t ldhv, void* st
  * struct. */
 enum dmpnn_predict_transform { DMPNN_PT_NONE = 0, DMPNN_PT_UNSCALE, DMPNN_PT_SIGMOID, DMPNN_PT_SOFTMAX,
                                DMPNN_PT_MVE, DMPNN_PT_EVIDENTIAL, DMPNN_PT_QUANTILE };
+#define DMPNN_PT_SPECTRAL 8
+/* DMPNN_PT_SPECTRAL (v15 growth; a further value of dmpnn_predict_args.transform beside the enumerators, which stay as they were —
+ * 7 stays an unknown transform): SpectralFFN.forward — preds [n_mols, n_tasks] = p = a / sum_row a, a = softplus(x) | exp(x - max_row x)
+ * by head.spectral_act ("The spectral criteria" above); the row's sum (and maximum) once per row.  With out_mean / out_scale, or an
+ * unknown head.spectral_act: DMPNN_EINVAL. */
 #define DMPNN_PREDICT_MAX_OUT 64
 typedef struct dmpnn_predict_args {
     dmpnn_head_args head;          /* the model behind the block, as dmpnn_head reads it. head.preds = the RAW outputs
