@@ -42,7 +42,7 @@ EXPORTS = [
     "dmpnn_predict_head_ws_bytes", "dmpnn_predict_head_wsplit_bytes", "dmpnn_predict_head",
 ]
 
-ACT = {"none": 0, "relu": 1, "leakyrelu": 2, "prelu": 3, "tanh": 4, "elu": 5}
+ACT = {"none": 0, "relu": 1, "leakyrelu": 2, "prelu": 3, "tanh": 4, "elu": 5, "selu": 6}
 F_UNDIRECTED = 1
 F_FUSED = 2
 F_MEGA = 4

@@ -296,7 +296,7 @@ size_t dmpnn_forward_wsplit_bytes(const dmpnn_fwd_args* a) {
 // one bit per element of H0 and of every kept H^(t): 256 words of 8 bytes per tile (64 per wave, RT_E WN 4 <= 60 of them used)
 static bool keep_bits_apply(const dmpnn_fwd_args& a) {
     const unsigned need = DMPNN_F_TILE_PLAN | DMPNN_F_KEEP | DMPNN_F_MEGA | DMPNN_F_SPLIT16 | DMPNN_F_FUSED;
-    return (a.flags & need) == need && (a.act == DMPNN_ACT_NONE || a.act == DMPNN_ACT_RELU || a.act == DMPNN_ACT_LEAKYRELU) &&
+    return (a.flags & need) == need && (a.act == DMPNN_ACT_NONE || act_is_relu_class(a.act)) &&
            !(a.dropout_p > 0.f) && !a.W_d && a.n_atoms > 0 && a.n_edges > 0;
 }
 size_t dmpnn_forward_keep_bits_bytes(const dmpnn_fwd_args* a) {
@@ -374,8 +374,8 @@ int dmpnn_train_route(const dmpnn_fwd_args* a, int64_t n_mols, int32_t have, int
     memset(out, 0, sizeof(*out));
     const int64_t nV = a->n_atoms, nE = a->n_edges, h = a->d_h;
     const bool undirected = (a->flags & DMPNN_F_UNDIRECTED) != 0, atom = (a->flags & DMPNN_F_ATOM) != 0;
-    const bool relu_class = a->act == DMPNN_ACT_RELU || a->act == DMPNN_ACT_LEAKYRELU;
-    const bool builtin = a->act == DMPNN_ACT_NONE || relu_class || a->act == DMPNN_ACT_TANH || a->act == DMPNN_ACT_ELU;   // (not PReLU: its slope trains)
+    const bool relu_class = act_is_relu_class(a->act);
+    const bool builtin = a->act == DMPNN_ACT_NONE || relu_class || act_is_smooth(a->act);   // (not PReLU: its slope trains)
     // ---- which plan ----
     bool tiles = !undirected && !a->W_d && builtin && max_level >= 2 && arith == 0 && nE > 0 && nV > 0 && oversize != 1;
     if (a->dropout_p > 0.f && !relu_class) tiles = false;           // (the mask is recovered from the sign of the kept tensors)
@@ -484,7 +484,7 @@ static int rows_dropout_check(const dmpnn_fwd_args& a) {
     // (undirected: only on request — the backward then regenerates the mask behind the reverse-edge average, DMPNN_F_UNDIRECTED_MASK)
     DMPNN_CHECK_ARG(!(a.flags & DMPNN_F_UNDIRECTED) || (a.flags & DMPNN_F_UNDIRECTED_MASK), "%s: directed messages only (no DMPNN_F_UNDIRECTED)", who);
     DMPNN_CHECK_ARG(!a.W_d, "%s: no W_d (the reference's second dropout behind W_d has no mask site)", who);
-    DMPNN_CHECK_ARG(a.act != DMPNN_ACT_PRELU, "%s: activation none / relu / leakyrelu / tanh / elu (not PReLU)", who);
+    DMPNN_CHECK_ARG(a.act != DMPNN_ACT_PRELU, "%s: activation none / relu / leakyrelu / tanh / elu / selu (not PReLU)", who);
     DMPNN_CHECK_ARG(a.d_h <= 1024, "%s: d_h <= 1024 (the hash key is row * 1024 + col; got %lld)", who, (long long)a.d_h);
     if (a.depth > 1 && a.n_edges > 0) {
         DMPNN_CHECK_ARG(a.Ms && a.Hs, "%s: missing Ms / Hs workspace", who);
@@ -506,7 +506,7 @@ int dmpnn_forward(const dmpnn_fwd_args* a, void* stream) {
     const int64_t nV = a->n_atoms, nE = a->n_edges, h = a->d_h, dv = a->d_v, de = a->d_e;
     DMPNN_CHECK_ARG(a->plan, "forward: null plan");
     DMPNN_CHECK_ARG(h > 0 && dv > 0 && de >= 0 && a->d_vd >= 0 && a->depth >= 1, "forward: bad dimensions");
-    DMPNN_CHECK_ARG(a->act >= DMPNN_ACT_RELU && a->act <= DMPNN_ACT_ELU,
+    DMPNN_CHECK_ARG(a->act >= DMPNN_ACT_RELU && a->act <= DMPNN_ACT_SELU,
                     "forward: activation %d is not built in (chain the row kernels instead)", a->act);
     DMPNN_CHECK_ARG(a->act != DMPNN_ACT_PRELU || a->act_slope_ptr, "forward: PReLU needs act_slope_ptr");
     DMPNN_CHECK_ARG(a->W_i && a->W_h && a->W_o && a->b_o, "forward: null weight");
@@ -555,7 +555,7 @@ int dmpnn_forward(const dmpnn_fwd_args* a, void* stream) {
         // ... or the training forward of the per-step general route on the f16 pipe: the mask in the row kernels' epilogue
         const bool rows_train = !fused && (a->flags & DMPNN_F_SPLIT16) && (a->flags & DMPNN_F_KEEP);
         if (rows_train) DMPNN_TRY(rows_dropout_check(*a));
-        DMPNN_CHECK_ARG(rows_train || lean_train || (tile_train && !has_vd && (a->act == DMPNN_ACT_RELU || a->act == DMPNN_ACT_LEAKYRELU)),
+        DMPNN_CHECK_ARG(rows_train || lean_train || (tile_train && !has_vd && act_is_relu_class(a->act)),
                         "forward: dropout inside the kernels needs the training forward of the tile kernel (DMPNN_F_MEGA | DMPNN_F_SPLIT16 | "
                         "DMPNN_F_KEEP) or the lean training forward of the per-step fused route (DMPNN_F_FUSED | DMPNN_F_SPLIT16 | DMPNN_F_KEEP "
                         "with keep_bits; d_h <= 320, d_h %% 4 == 0, even d_v / d_e, depth 2 .. %d, a full plan), a ReLU-class activation and "

@@ -922,7 +922,7 @@ int backward_impl(const dmpnn_bwd_args* b, void* stream, const ExtraWgrad* extra
     const bool atom = (f.flags & DMPNN_F_ATOM) != 0;
     const int64_t de_i = atom ? 0 : de, de_h = atom ? de : 0;
     DMPNN_CHECK_ARG(f.plan && h > 0 && dv > 0 && T >= 1, "backward: bad forward description");
-    DMPNN_CHECK_ARG(f.act >= DMPNN_ACT_RELU && f.act <= DMPNN_ACT_ELU && f.act != DMPNN_ACT_PRELU,
+    DMPNN_CHECK_ARG(f.act >= DMPNN_ACT_RELU && f.act <= DMPNN_ACT_SELU && f.act != DMPNN_ACT_PRELU,
                     "backward: activation %d has no fused backward (use the row kernels)", f.act);
     DMPNN_CHECK_ARG(!(f.flags & DMPNN_F_UNDIRECTED_MASK) ||
                     ((f.flags & DMPNN_F_UNDIRECTED) && !(f.flags & (DMPNN_F_FUSED | DMPNN_F_MEGA | DMPNN_F_TILE_PLAN | DMPNN_F_ATOM))),

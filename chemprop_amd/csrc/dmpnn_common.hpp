@@ -156,13 +156,28 @@ __device__ __forceinline__ void warm_kernargs() {
 }
 
 // ---- activations ----------------------------------------------------------------------------
+// The two sets the kernels choose their paths by.  Smooth: tau needs a transcendental and tau' is read from the OUTPUT as a function
+// of its value (no sign bit, no slope).  ReLU class: compare + select, tau' is 1 or a constant by the output's sign.  (None and PReLU
+// are in neither: a site that wants "compare + select applies" says !act_is_smooth.)
+__host__ __device__ constexpr bool act_is_smooth(int act) { return act == DMPNN_ACT_TANH || act == DMPNN_ACT_ELU || act == DMPNN_ACT_SELU; }
+__host__ __device__ constexpr bool act_is_relu_class(int act) { return act == DMPNN_ACT_RELU || act == DMPNN_ACT_LEAKYRELU; }
+// SELU = lambda ELU_alpha (torch's constants, include/dmpnn.h); kSeluLA = lambda alpha: -kSeluLA is its limit at -inf
+constexpr float kSeluAlpha = 1.6732632423543772848170429916717f, kSeluLambda = 1.0507009873554804934193349852946f;
+constexpr float kSeluLA = (float)(1.6732632423543772848170429916717 * 1.0507009873554804934193349852946);
+// ELU and SELU through ONE expm1f call site: pos z : neg expm1(z) with (pos, neg) = (1, 1) or (lambda, lambda alpha) — the products by
+// 1 are exact, so ELU's values are what `z > 0 ? z : expm1f(z)` gives
+__device__ __forceinline__ float apply_elu_class(float z, int act) {
+    const bool selu = act == DMPNN_ACT_SELU;
+    return z > 0.f ? (selu ? kSeluLambda : 1.f) * z : (selu ? kSeluLA : 1.f) * expm1f(z);
+}
 __device__ __forceinline__ float apply_act(float z, int act, float slope) {
     switch (act) {
         case DMPNN_ACT_RELU: return z < 0.f ? 0.f : z;
         case DMPNN_ACT_LEAKYRELU:
         case DMPNN_ACT_PRELU: return z > 0.f ? z : slope * z;
         case DMPNN_ACT_TANH: return tanhf(z);
-        case DMPNN_ACT_ELU: return z > 0.f ? z : expm1f(z);
+        case DMPNN_ACT_ELU:
+        case DMPNN_ACT_SELU: return apply_elu_class(z, act);
         default: return z;
     }
 }
@@ -170,10 +185,10 @@ __device__ __forceinline__ float apply_act(float z, int act, float slope) {
 // tens of KB, and a workgroup that runs its code once pays for code size in instruction fetches (the tile kernels:
 // 27 % of their cycles).  ReLU-class activations are a compare + select in line.
 __device__ __noinline__ float apply_act_slow(float z, int act) {
-    return act == DMPNN_ACT_TANH ? tanhf(z) : (z > 0.f ? z : expm1f(z));
+    return act == DMPNN_ACT_TANH ? tanhf(z) : apply_elu_class(z, act);
 }
 __device__ __forceinline__ float apply_act_small(float z, int act, float slope) {
-    if (act == DMPNN_ACT_TANH || act == DMPNN_ACT_ELU) return apply_act_slow(z, act);
+    if (act_is_smooth(act)) return apply_act_slow(z, act);
     const float neg = act == DMPNN_ACT_NONE ? 1.f : (act == DMPNN_ACT_RELU ? 0.f : slope);
     return (z > 0.f ? z : neg * z) + 0.f;
 }
@@ -191,6 +206,7 @@ __device__ __forceinline__ float act_grad_from_out(float y, int act, float slope
         case DMPNN_ACT_LEAKYRELU: return y > 0.f ? 1.f : slope;  // slope > 0: sign(y) == sign(z)
         case DMPNN_ACT_TANH: return 1.f - y * y;
         case DMPNN_ACT_ELU: return y > 0.f ? 1.f : y + 1.f;
+        case DMPNN_ACT_SELU: return y > 0.f ? kSeluLambda : y + kSeluLA;  // y = lambda alpha (e^z - 1): tau' = lambda alpha e^z (z = 0: lambda alpha)
         default: return 1.f;
     }
 }

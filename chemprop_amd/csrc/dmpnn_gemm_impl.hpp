@@ -471,7 +471,7 @@ __global__ __launch_bounds__(kThreads) void k_gemm(GemmK g) {
 
     const float slope = g.slope_ptr ? *g.slope_ptr : g.slope;
     const bool poison = g.poison_flags && (g.poison_flags[0] & g.poison_mask);
-    if (g.act == DMPNN_ACT_TANH || g.act == DMPNN_ACT_ELU) {
+    if (act_is_smooth(g.act)) {
         epilogue_rows<RT, WN, G, EPI, false>(g, Ct, rs, nrows, col0, tid, cadd_pref, slope, 0.f, poison);
     } else {
         const float neg_slope = g.act == DMPNN_ACT_NONE ? 1.f : (g.act == DMPNN_ACT_RELU ? 0.f : slope);

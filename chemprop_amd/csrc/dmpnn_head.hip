@@ -157,7 +157,7 @@ int head_check(const dmpnn_head_args& h, const float* Hv, int64_t ldhv) {
                                                            : "head: dims[0] == d_h (times n_components) without X_d");
     DMPNN_CHECK_ARG(!xd || h.ld_xd >= h.dims[0] - d, "head: ld_xd (%lld) < d_xd (%lld)", (long long)h.ld_xd, (long long)(h.dims[0] - d));
     for (int l = 0; l < Ln; ++l) DMPNN_CHECK_ARG(h.W[l] && h.dims[l + 1] > 0, "head: layer %d has no weight / width", l);
-    DMPNN_CHECK_ARG(h.act >= DMPNN_ACT_NONE && h.act <= DMPNN_ACT_ELU && h.act != DMPNN_ACT_PRELU, "head: activation %d is not built in", h.act);
+    DMPNN_CHECK_ARG(h.act >= DMPNN_ACT_NONE && h.act <= DMPNN_ACT_SELU && h.act != DMPNN_ACT_PRELU, "head: activation %d is not built in", h.act);
     DMPNN_CHECK_ARG(known_criterion(h), "head: unknown criterion %d (n_classes %d)", h.loss, (int)h.n_classes);
     DMPNN_CHECK_ARG(h.loss <= DMPNN_LOSS_MAE || (!h.lt_mask && !h.gt_mask), "head: only the MSE / MAE criteria have bounds (lt_mask / gt_mask)");
     if (spectral_loss(h.loss)) {

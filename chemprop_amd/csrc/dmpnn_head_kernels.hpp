@@ -24,7 +24,7 @@ struct FfnDrop {
     // d(layer input) / d(pre-activation) at an element whose masked value is x = mask tau(pre) scale: scale tau'(pre) where kept, 0 where
     // dropped.  ReLU class: tau' from the sign of x; tanh / ELU: from tau(pre) = x (1 - p)
     __device__ __forceinline__ float act_grad(int64_t r, int c, float x, int act, float slope) const {
-        const bool smooth = act == DMPNN_ACT_TANH || act == DMPNN_ACT_ELU;
+        const bool smooth = act_is_smooth(act);
         return keep(r, c) ? scale * act_grad_from_out(smooth ? x * unscale : x, act, slope) : 0.f;
     }
 };
@@ -1456,7 +1456,7 @@ __global__ __launch_bounds__(256) void k_head_rows(RowsArgs a) {
         // what leaves for memory is the slice's: columns [64 cs, 64 cs + 64)
         // (the 16 rows of a column in registers, dl/dP as 16-byte rows: straight-line code — a loop with the activation's switch inside
         //  waited for every LDS round trip, 6 us)
-        const bool simple_act = a.act != DMPNN_ACT_TANH && a.act != DMPNN_ACT_ELU;
+        const bool simple_act = !act_is_smooth(a.act);
         const float neg = a.act == DMPNN_ACT_NONE ? 1.f : (a.act == DMPNN_ACT_RELU ? 0.f : a.slope);   // tau' for y <= 0 (ReLU class)
         float4 gp4[16];
 #pragma unroll

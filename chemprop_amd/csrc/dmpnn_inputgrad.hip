@@ -408,7 +408,7 @@ int dmpnn_backward_inputs(const dmpnn_bwd_inputs_args* a, void* stream) {
                     "backward_inputs: input gradients are provided on the per-step general route, bond messages (a kept forward without "
                     "DMPNN_F_FUSED / DMPNN_F_MEGA / DMPNN_F_TILE_PLAN / DMPNN_F_ATOM)");
     DMPNN_CHECK_ARG(f.act != DMPNN_ACT_PRELU, "backward_inputs: PReLU has no fused backward (use the row kernels)");
-    DMPNN_CHECK_ARG(f.act >= DMPNN_ACT_RELU && f.act <= DMPNN_ACT_ELU, "backward_inputs: activation %d has no fused backward (use the row kernels)", f.act);
+    DMPNN_CHECK_ARG(f.act >= DMPNN_ACT_RELU && f.act <= DMPNN_ACT_SELU, "backward_inputs: activation %d has no fused backward (use the row kernels)", f.act);
     DMPNN_CHECK_ARG(f.plan && f.d_h > 0 && f.d_v > 0 && f.d_e >= 0 && f.depth >= 1 && f.n_atoms >= 0 && f.n_edges >= 0 && f.ldh >= f.d_h,
                     "backward_inputs: bad forward description");
     DMPNN_CHECK_ARG(f.W_i && f.W_o && (f.depth < 2 || f.n_edges == 0 || f.W_h), "backward_inputs: null weights");

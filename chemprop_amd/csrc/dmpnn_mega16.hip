@@ -210,7 +210,7 @@ int launch_mega16_forward(const dmpnn_fwd_args& a, float* out, int64_t ldout, hi
     g.edge_index = reinterpret_cast<const long long*>(a.edge_index);
     g.rev64 = reinterpret_cast<const long long*>(a.rev_edge_index);
     const int n_tiles = (a.n_tiles_launch > 0 && a.n_tiles_launch < L.max_mtiles) ? (int)a.n_tiles_launch : (int)L.max_mtiles;
-    const bool sa = !(a.act == DMPNN_ACT_TANH || a.act == DMPNN_ACT_ELU), kp = (a.flags & DMPNN_F_KEEP) != 0;
+    const bool sa = !act_is_smooth(a.act), kp = (a.flags & DMPNN_F_KEEP) != 0;
     const int wn = a.d_h <= 64 ? 1 : (a.d_h <= 128 ? 2 : 5);
     if (a.flags & DMPNN_F_STORE16) {   // (validated by dmpnn_forward: inference, bond messages) every product on the hi halves alone
         if (wn == 1) return sa ? mega16::launch_mega16<1, true, false, 4, true>(G, n_tiles, s) : mega16::launch_mega16<1, false, false, 4, true>(G, n_tiles, s);

@@ -124,7 +124,7 @@ __global__ __launch_bounds__(kThreads) void k_mpnn_tile(MegaK g) {
     }
     const float slope = g.slope_ptr ? *g.slope_ptr : g.slope;
     const float neg_slope = g.act == DMPNN_ACT_NONE ? 1.f : (g.act == DMPNN_ACT_RELU ? 0.f : slope);
-    const bool simple_act = !(g.act == DMPNN_ACT_TANH || g.act == DMPNN_ACT_ELU);
+    const bool simple_act = !act_is_smooth(g.act);
     auto tau = [&](float z) -> float {
         if (simple_act) return (z > 0.f ? z : neg_slope * z) + 0.f;
         return apply_act(z, g.act, slope);

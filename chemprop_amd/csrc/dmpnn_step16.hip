@@ -44,12 +44,12 @@ static bool x_path_shapes(const dmpnn_fwd_args& a) {
 bool fused16_lean_shapes(const dmpnn_fwd_args& a, bool on_demand) {
     const unsigned need = DMPNN_F_FUSED | DMPNN_F_SPLIT16;
     if ((a.flags & need) != need || (a.flags & (DMPNN_F_MEGA | DMPNN_F_UNDIRECTED | DMPNN_F_STORE16 | DMPNN_F_ATOM))) return false;
-    if (!(a.act == DMPNN_ACT_NONE || a.act == DMPNN_ACT_RELU || a.act == DMPNN_ACT_LEAKYRELU)) return false;
+    if (!(a.act == DMPNN_ACT_NONE || act_is_relu_class(a.act))) return false;
     // (depth <= kWProdMaxJobs: the backward pass of this route forms every weight gradient as ONE launch of at most that many product
     //  jobs per matrix, dmpnn_backward.hip — a deeper block keeps the fp32 tensors and trains on the fused16 route as before)
     if (a.dropout_p != 0.f) {
         if (!on_demand || !(a.dropout_p > 0.f && a.dropout_p < 1.f)) return false;
-        if (!(a.act == DMPNN_ACT_RELU || a.act == DMPNN_ACT_LEAKYRELU)) return false;
+        if (!act_is_relu_class(a.act)) return false;
     }
     if (a.W_d || a.depth < 2 || a.depth > kWProdMaxJobs || a.n_edges <= 0 || a.n_atoms <= 0) return false;
     // (ldh == d_h: the backward step kernels read T as contiguous rows of d_h floats — k_bstep16's message mode fetches a tile's rows

@@ -414,7 +414,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_step16(Step16K g) {
     // rows) go through ONE row-major pass over the tile instead: no transcendental code unrolled 60 times (code size is
     // latency for a workgroup that runs its code once).
     const bool zpre = g.Zpre != nullptr;
-    const bool tpass = zpre || g.act == DMPNN_ACT_TANH || g.act == DMPNN_ACT_ELU;
+    const bool tpass = zpre || act_is_smooth(g.act);
     const float neg = tpass ? 1.f : (g.act == DMPNN_ACT_NONE ? 1.f : (g.act == DMPNN_ACT_RELU ? 0.f : slope));
 #pragma unroll
     for (int ct = 0; ct < WN; ++ct) {

@@ -349,8 +349,8 @@ def rows_dropout_refusal(d_v: int, d_e: int, d_h: int, depth: int, act: str, has
     ``atom``: an atom block (``DMPNN_F_ATOM``) — its update contraction reads ``[M || ME]``, so ``d_e`` must be even as well.
     ``undirected_dropout=True``: the caller asks for the mask behind the reverse-edge average (``DMPNN_F_UNDIRECTED_MASK``) — then
     ``undirected`` is no reason (a bond block only)."""
-    if act not in ("none", "relu", "leakyrelu", "tanh", "elu"):
-        return f"activation {act!r} (none / relu / leakyrelu / tanh / elu: PReLU's slope trains, a custom module runs between the kernels)"
+    if act not in ("none", "relu", "leakyrelu", "tanh", "elu", "selu"):
+        return f"activation {act!r} (none / relu / leakyrelu / tanh / elu / selu: PReLU's slope trains, a custom module runs between the kernels)"
     if has_vd:
         return "a W_d layer (d_vd > 0)"
     if undirected and not (undirected_dropout and not atom):
@@ -936,7 +936,7 @@ def forward(plan: GraphPlan, V: Tensor, E: Tensor, W_i: Tensor, W_h: Tensor, W_o
     lean training forward of the per-step fused route under its own shapes (molecules beyond the tile; ``st.route`` stays
     ``"fused16/lean"``, the same mask for the same seed), or, on demand as well (``route="general"``, ``mfma="split16"``,
     ``keep``), the row kernels of the per-step general route on the f16 pipe (any molecule size, ``d_h <= 1024``, depth >= 1, relu /
-    leakyrelu / tanh / elu, no ``W_d``, directed — or ``undirected`` with ``undirected_dropout=True``, which sets
+    leakyrelu / tanh / elu / selu, no ``W_d``, directed — or ``undirected`` with ``undirected_dropout=True``, which sets
     ``DMPNN_F_UNDIRECTED_MASK`` (``backward`` reads it from the forward's flags) —: :func:`rows_dropout_refusal`; ``st.route`` stays
     ``"general16"``); raises
     :class:`RouteUnavailable` when this batch takes another route (the caller then runs its own ``nn.Dropout`` between the row

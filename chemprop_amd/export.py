@@ -59,7 +59,7 @@ def traced_forward(mp, bmg, V_d: Optional[Tensor] = None) -> Tensor:
     act, slope, slope_t = classify_activation(mp.tau)
     if act == "custom" or (mp.training and mp.dropout.p > 0):
         raise NotImplementedError("chemprop_amd: torch.export / torch.compile of the message passing needs a built-in activation "
-                                  "(relu, leakyrelu, prelu, tanh, elu) and no active dropout")
+                                  "(relu, leakyrelu, prelu, tanh, elu, selu) and no active dropout")
     has_vd = mp.W_d is not None and V_d is not None
     if V_d is not None:
         V_d = mp.V_d_transform(V_d)

@@ -539,7 +539,7 @@ def fused_block(mp, rows_dropout: bool = False, vd_dropout: bool = False, atom_m
         #  row kernels of the per-step general route for every built-in one: dmpnn_fwd_args.dropout_p; a dropout module that is not
         #  exactly nn.Dropout has its own semantics and stays on the module path)
         raise NotImplementedError("FusedTrainer: dropout inside the block needs nn.Dropout and a ReLU / LeakyReLU activation"
-                                  + ("" if rows_dropout else " (rows_dropout=True also takes tanh / elu, on the row kernels)"))
+                                  + ("" if rows_dropout else " (rows_dropout=True also takes tanh / elu / selu, on the row kernels)"))
     return act, slope
 
 
@@ -979,7 +979,7 @@ class FusedTrainer:
     ``last_head_dropout_seed``); otherwise the head gets ``p = 0``.  The default refuses such a predictor.
 
     ``rows_dropout=True`` gives block dropout a third home behind the tile kernels and the lean step kernels: the row kernels of the
-    per-step general route on the f16 pipe (``route == "general16"``; ``d_h <= 1024``, depth >= 1, relu / leakyrelu / tanh / elu — what
+    per-step general route on the f16 pipe (``route == "general16"``; ``d_h <= 1024``, depth >= 1, relu / leakyrelu / tanh / elu / selu — what
     ``engine.rows_dropout_refusal`` takes), the same hash mask and the same one seed per step.  The default refuses what the first two
     homes do not take.
 

@@ -63,6 +63,8 @@ def classify_activation(tau: nn.Module) -> tuple[str, float, Optional[Tensor]]:
         return "tanh", 0.0, None
     if type(tau) is nn.ELU and tau.alpha == 1.0:
         return "elu", 0.0, None
+    if type(tau) is nn.SELU:   # (no parameters: torch's alpha / lambda are the kernels' constants)
+        return "selu", 0.0, None
     return "custom", 0.0, None
 
 

@@ -61,7 +61,8 @@ extern "C" {
  * Added, same version (new entries only; no existing struct or entry changes): dmpnn_backward_inputs / dmpnn_backward_inputs_ws_bytes /
  * dmpnn_bwd_inputs_args (gradients with respect to V, E and V_d on the per-step general route) and dmpnn_src_sum.
  * Grown, same version: DMPNN_LOSS_SID / DMPNN_LOSS_WASSERSTEIN and DMPNN_PT_SPECTRAL (new accepted values) with
- * dmpnn_head_args.spectral_act / spectral_threshold at its end (zero in an older caller: read by the new values alone). */
+ * dmpnn_head_args.spectral_act / spectral_threshold at its end (zero in an older caller: read by the new values alone).
+ * Grown, same version: DMPNN_ACT_SELU (a new accepted value of every `act` that took DMPNN_ACT_ELU; no struct changes). */
 #define DMPNN_ABI_VERSION 15
 
 enum dmpnn_status {
@@ -79,7 +80,9 @@ enum dmpnn_activation {
     DMPNN_ACT_LEAKYRELU = 2, /* slope = act_slope (chemprop uses 0.1, nn/utils.py:47)            */
     DMPNN_ACT_PRELU = 3,     /* slope read on device from *act_slope_ptr (single learnable scalar) */
     DMPNN_ACT_TANH = 4,
-    DMPNN_ACT_ELU = 5        /* alpha = 1                                                         */
+    DMPNN_ACT_ELU = 5,       /* alpha = 1                                                         */
+    DMPNN_ACT_SELU = 6       /* lambda (z > 0 ? z : alpha expm1(z)), torch's constants:
+                                alpha = 1.6732632423543772848170429916717, lambda = 1.0507009873554804934193349852946 */
 };
 
 enum dmpnn_flags {
@@ -409,11 +412,11 @@ typedef struct dmpnn_fwd_args {
      * (dmpnn_forward_route / dmpnn_train_route) never choose this form for dropout_p > 0: the caller asks for it.
      * The third home: the training forward of the per-step GENERAL route on the f16 pipe (DMPNN_F_SPLIT16 | DMPNN_F_KEEP without
      * DMPNN_F_FUSED) — any molecule size, d_h <= 1024 (the hash key is row * 1024 + col), depth >= 1 (depth 1: the finalize site
-     * only), activation none / relu / leakyrelu / tanh / elu, directed (or, the fourth admitted case, DMPNN_F_UNDIRECTED with
+     * only), activation none / relu / leakyrelu / tanh / elu / selu, directed (or, the fourth admitted case, DMPNN_F_UNDIRECTED with
      * DMPNN_F_UNDIRECTED_MASK: the same mask sites, behind the reverse-edge average in dmpnn_backward), no W_d, and an update and a finalize contraction that
      * dmpnn_linear16_ok takes (they run on the row kernel k_rows16, whose epilogue applies the mask; the hash row is the output row:
      * the edge tensors of this route are in the caller's edge order).  The kept H^(t) and the output are post-dropout;
-     * dmpnn_backward regenerates the mask from the hash for EVERY activation (for tanh / elu / none a zero does not say "dropped")
+     * dmpnn_backward regenerates the mask from the hash for EVERY activation (for tanh / elu / selu / none a zero does not say "dropped")
      * and uses m / (1 - p) * tau'(y (1 - p)).  The route rules never choose a route for dropout_p > 0 here either: the caller asks.
      * Any other route / activation with dropout_p != 0: DMPNN_EINVAL (the caller runs its own dropout between the row kernels). */
     float dropout_p; uint64_t dropout_seed;
