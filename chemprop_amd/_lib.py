@@ -127,7 +127,7 @@ MAX_FFN_LAYERS = 8
 MAX_COMPONENTS = 8   # (DMPNN_MAX_COMPONENTS: blocks side by side in one fingerprint)
 DROP_SITE_VD = 0x8000     # (DMPNN_DROP_SITE_VD: the mask behind the atom-descriptor layer, dmpnn_vd_args.dropout_p)
 DROP_SITE_FFN = 0x10000   # (DMPNN_DROP_SITE_FFN: the predictor's dropout sites are DROP_SITE_FFN + layer)
-LOSS = {"mse": 0, "mae": 1, "bce": 2, "ce": 3, "mve": 4, "evidential": 5, "quantile": 6, "dirichlet": 7, "sid": 8, "wasserstein": 9}   # enum dmpnn_loss
+LOSS = {"mse": 0, "mae": 1, "bce": 2, "ce": 3, "mve": 4, "evidential": 5, "quantile": 6, "dirichlet": 7, "sid": 8, "wasserstein": 9, "mcc": 11}   # enum dmpnn_loss (10 names nothing)
 SPECTRAL_ACT = {"softplus": 0, "exp": 1}   # dmpnn_head_args.spectral_act
 STEP_FORWARD, STEP_BACKWARD, STEP_UPDATE = 1, 2, 4
 

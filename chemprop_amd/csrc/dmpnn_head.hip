@@ -32,12 +32,20 @@ struct HeadLayout {
     // the spectral criteria (in front of the attentive part: the inner head's layout stays the front of the outer one): per row the
     // loss and the count of finite targets, k_spectral_rows to k_spectral_finish
     size_t spec_loss, spec_cnt;
+    // the binary MCC criterion (in front of the attentive part as well): per block of kMccRows molecule rows the four sums of every task
+    // [n_blocks][4][t] and per (row block, column block) the count of finite targets, k_mcc_cols to k_mcc_finish
+    size_t mcc_part, mcc_cnt;
+    int mcc_blocks, mcc_cb;
 };
 inline bool spectral_loss(int loss) { return loss == DMPNN_LOSS_SID || loss == DMPNN_LOSS_WASSERSTEIN; }
+// the criteria that run as a stage of their own (head_criterion) and not in k_loss — so not inside k_out_all's launch either
+inline bool staged_loss(int loss) { return spectral_loss(loss) || loss == DMPNN_LOSS_MCC; }
 // the shapes the four-launch form takes (training or not is the caller's business): one hidden layer, a handful of outputs
 // (with molecule descriptors the first layer's reduction may be up to kRowsMaxK wide: d_h + d_xd; its data gradient stays d_h wide)
 // components of a multicomponent fingerprint (dmpnn_head_args.n_components: 0 and 1 are one block)
 inline int64_t head_ncomp(const dmpnn_head_args& h) { return h.n_components > 1 ? h.n_components : 1; }
+// (loss <= DMPNN_LOSS_BCE: k_head_rows evaluates the per-element criteria MSE / MAE / BCE itself — which keeps DMPNN_LOSS_MCC, a
+//  reduction down the columns, out of this form as it keeps the spectral criteria out)
 bool rows_shape(const dmpnn_head_args& h) {
     return h.n_layers == 2 && h.dims[2] <= kOutMaxTasks && h.dims[2] >= 1 && h.loss <= DMPNN_LOSS_BCE && h.n_mols <= kRowsMaxB &&
            h.dims[0] <= (h.X_d ? kRowsMaxK : kRowsMaxWidth) && head_ncomp(h) * h.d_h <= kRowsMaxWidth && h.dims[1] <= kRowsMaxWidth && h.dims[0] % 4 == 0;
@@ -92,6 +100,13 @@ HeadLayout head_layout(const dmpnn_head_args& h) {
         L.spec_loss = o; o += al256((size_t)B * 4);
         L.spec_cnt = o; o += al256((size_t)B * 4);
     }
+    if (h.loss == DMPNN_LOSS_MCC) {
+        const int64_t tc = t > 0 ? t : 0;
+        L.mcc_blocks = (int)(B > kMccRows ? (B + kMccRows - 1) / kMccRows : 1);
+        L.mcc_cb = (int)(tc > kMccThreads ? (tc + kMccThreads - 1) / kMccThreads : 1);
+        L.mcc_part = o; o += al256((size_t)L.mcc_blocks * tc * 4 * 4);
+        L.mcc_cnt = o; o += al256((size_t)L.mcc_blocks * L.mcc_cb * 4);
+    }
     if (h.agg_mode == DMPNN_MOLAGG_ATTENTIVE) {
         const int64_t nV = h.n_atoms > 0 ? h.n_atoms : 0;
         L.att_A = o; o += al256((size_t)B * d * 4);
@@ -138,7 +153,9 @@ int loss_per_task(const dmpnn_head_args& h) {
 
 // the criterion is one this library knows: a value of enum dmpnn_loss — and no class dimension beside the spectral criteria, whose one
 // output per task is a bin of the spectrum (with n_classes set, 8 / 9 name nothing: older callers probe 8 as the first unknown value)
+// DMPNN_LOSS_MCC = 11 likewise; 10 names nothing (probed as the first unknown value since the spectral criteria)
 inline bool known_criterion(const dmpnn_head_args& h) {
+    if (h.loss == DMPNN_LOSS_MCC) return h.n_classes == 0;
     return h.loss >= DMPNN_LOSS_MSE && h.loss <= DMPNN_LOSS_WASSERSTEIN && !(spectral_loss(h.loss) && h.n_classes != 0);
 }
 // every argument rule of dmpnn_head (head_attentive: its own, then these on the head behind the attention), before the workspace rule
@@ -228,7 +245,7 @@ HeadRoute head_route(const dmpnn_head_args& h, const float* Hv, int64_t ldhv, He
     // (4, 1 molecule per thread) up to 256 molecules, (2, 1) up to 512, (2, 2) up to 1 024 (DMPNN_HEAD_QPW=4 | 2: the A/B switch)
     R.qpw = (qpw_env && !strcmp(qpw_env, "4")) ? 4 : ((qpw_env && !strcmp(qpw_env, "2")) ? 2 : (B <= 256 ? 4 : 2));
     R.small_out = Ln >= 1 && Ln <= DMPNN_MAX_FFN_LAYERS && h.dims[Ln] <= kOutMaxTasks;
-    R.out_all = R.small_out && want_grad && h.targets && B <= kOutAllMaxRows && loss_per_task(h) == 1 && !spectral_loss(h.loss);   // (k_loss's criteria)
+    R.out_all = R.small_out && want_grad && h.targets && B <= kOutAllMaxRows && loss_per_task(h) == 1 && !staged_loss(h.loss);   // (k_loss's criteria)
     // The ride's own conditions — NOT cols_fused: no alignment terms.  (with descriptors and no batch norm the aggregate goes into the fingerprint's
     // rows, not into H; the attentive aggregate needs every atom's logit first; DMPNN_HEAD_AGG=fused | split switches the ride off)
     R.agg_may_ride = h.agg_mode != DMPNN_MOLAGG_ATTENTIVE && B <= kRowsMaxB && h.d_h % 4 == 0 && !chain && (!h.X_d || h.bn_weight) &&
@@ -337,8 +354,23 @@ LossArgs loss_args(const dmpnn_head_args& h, int ldp, int nc, float* gP) {
     return LossArgs{h.preds, ldp, h.targets, t, h.weights, h.task_weights, h.lt_mask, h.gt_mask, gP, ldp, h.loss_out, h.n_mols, t, h.loss, nc,
                     h.evid_v_kl, h.evid_eps, h.quantile_alpha, h.loss == DMPNN_LOSS_DIRICHLET ? (float)std::lgamma((double)nc) : 0.f};
 }
-// the criterion of h.preds into loss_out, its gradient into gP (or NULL): one launch (the spectral criteria: their own stage, two)
+// the criterion of h.preds into loss_out, its gradient into gP (or NULL): one launch (the spectral criteria and binary MCC: their own
+// stages, two launches each)
 int head_criterion(const dmpnn_head_args& h, const HeadLayout& L, float* gP, hipStream_t s) {
+    if (h.loss == DMPNN_LOSS_MCC) {
+        const int64_t t = h.dims[h.n_layers];
+        int lgC = 0;
+        while ((1 << lgC) < kMccThreads && (1 << lgC) < t) ++lgC;   // (C: the smallest power of two >= min(t, kMccThreads))
+        const MccArgs q{h.preds, t, h.targets, t, h.weights, h.task_weights, gP, t, h.loss_out, h.n_mols, (int)t, lgC, L.mcc_blocks, L.mcc_cb,
+                        ws_f(h, L.mcc_part), reinterpret_cast<int*>(ws_at(h, L.mcc_cnt))};
+        hipLaunchKernelGGL(k_mcc_cols, dim3((unsigned)((int64_t)L.mcc_blocks * L.mcc_cb)), dim3(kMccThreads), 0, s, q);
+        DMPNN_CHECK_LAUNCH("k_mcc_cols");
+        // (without a gradient: the sums alone, one workgroup; with one: a workgroup per row block up to kMccFinishMaxBlocks)
+        const int fin = gP ? (L.mcc_blocks > kMccFinishMaxBlocks ? kMccFinishMaxBlocks : L.mcc_blocks) : 1;
+        hipLaunchKernelGGL(k_mcc_finish, dim3((unsigned)fin), dim3(kMccThreads), 0, s, q);
+        DMPNN_CHECK_LAUNCH("k_mcc_finish");
+        return DMPNN_OK;
+    }
     if (spectral_loss(h.loss)) {
         const int64_t t = h.dims[h.n_layers], n = h.n_mols * t;
         const SpectralArgs q{h.preds, t, h.targets, t, h.weights, h.task_weights, gP, t, h.loss_out, h.n_mols, (int)t, h.loss, h.spectral_act,

@@ -605,6 +605,154 @@ __global__ __launch_bounds__(kSpecCols) void k_spectral_finish(SpectralArgs a) {
     }
 }
 
+// ---- the binary MCC criterion (DMPNN_LOSS_MCC, dmpnn.h): a column reduction over blocks of molecule rows -------------------------
+// The loss of one (molecule, task) pair depends on four batch-wide sums of its task's column, so no gradient can be written before
+// a grid-wide reduction down the columns: two launches.
+//   k_mcc_cols:   workgroup rb n_cb + cb takes the kMccRows molecule rows of row block rb and the kMccThreads task columns of column
+//                 block cb and leaves TP, FP, TN, FN of its rows per task in part[rb][.][j], its count of finite targets in
+//                 cnt[rb n_cb + cb].
+//   k_mcc_finish: per column block the blocks' partials per task in block order (double), MCC_j and the two gradient coefficients
+//                 per task (double: N = TP TN - FP FN cancels), then dl/dx for the row blocks the workgroup owns (gP == NULL: one
+//                 workgroup, the loss alone); workgroup 0 writes out[0] = 1 - sum_j tw_j MCC_j / t and out[1] = sum m.
+// Threads to (row, task): C = 2^lgC = the smallest power of two >= min(t, kMccThreads); thread i is on column i % C of the column
+// block and on the rows i / C, i / C + kMccThreads / C, ... of the row block.  X and T are row-major with t columns: for t <= 64 a wave
+// reads 64 / C whole rows, which lie one behind the other in memory (t = 12: 48 consecutive floats, 16 lanes idle), for t in the
+// hundreds 64 consecutive columns of one row.  Threads on the same column: the lanes C apart of a wave (xor shuffles down to C), then
+// the waves through LDS in wave order — a fixed order; no atomics; bit-identical from call to call.
+constexpr int kMccRows = 128;                  // molecule rows one k_mcc_cols workgroup takes
+constexpr int kMccThreads = 256;               // threads per workgroup = task columns per column block
+constexpr int kMccFinishMaxBlocks = 128;       // workgroups of k_mcc_finish (each one adds up every row block's partials)
+struct MccArgs {
+    const float* X; int64_t ldx; const float* T; int64_t ldt; const float* w; const float* tw;
+    float* gP; int64_t ldg; float* out;   // gP (or NULL: the loss alone) rows of ldg; out[0] = loss, out[1] = number of finite targets
+    int64_t B; int t; int lgC;            // C = 1 << lgC
+    int n_blocks, n_cb;                   // row blocks of kMccRows rows, column blocks of kMccThreads columns
+    float* part; int* cnt;                // [n_blocks][4][t] (TP, FP, TN, FN), [n_blocks n_cb] (workspace)
+};
+// p = sigmoid(x) and q = 1 - p = sigmoid(-x), neither by a subtraction from 1
+__device__ __forceinline__ void sigmoid_pair(float x, float& p, float& q) {
+    const float e = expf(-fabsf(x)), r = 1.f / (1.f + e), s = e * r;
+    p = x >= 0.f ? r : s;
+    q = x >= 0.f ? s : r;
+}
+// v[k] of the threads on one column (tid % C) summed: into thread `column` (tid < C); red: NV * kMccThreads values of LDS
+template <class V, int NV>
+__device__ __forceinline__ void mcc_col_reduce(V (&v)[NV], int C, V* red) {
+    const int tid = threadIdx.x;
+    for (int off = 32; off >= C; off >>= 1) {   // (uniform; C < 64: the lanes of a wave on the same column)
+#pragma unroll
+        for (int k = 0; k < NV; ++k) v[k] += __shfl_xor(v[k], off);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NV; ++k) red[k * kMccThreads + tid] = v[k];
+    __syncthreads();
+    if (tid < C) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            V s = 0;
+            for (int wv = 0; wv < kMccThreads / 64; ++wv) {   // (the waves that hold this column, in wave order)
+                const int idx = wv * 64 + (tid & 63);
+                if ((idx & (C - 1)) == tid) s += red[k * kMccThreads + idx];
+            }
+            v[k] = s;
+        }
+    }
+}
+__global__ __launch_bounds__(kMccThreads) void k_mcc_cols(MccArgs a) {
+    __shared__ float red[4 * kMccThreads];
+    __shared__ int redi[kMccThreads / 64];
+    const int tid = threadIdx.x, t = a.t, C = 1 << a.lgC, c = tid & (C - 1), rl = tid >> a.lgC, RL = kMccThreads >> a.lgC;
+    const int64_t rb = blockIdx.x / a.n_cb;   // (workgroup rb n_cb + cb)
+    const int cb = (int)(blockIdx.x - rb * a.n_cb), j = cb * kMccThreads + c;
+    const int64_t r0 = rb * kMccRows, r1 = r0 + kMccRows < a.B ? r0 + kMccRows : a.B;
+    const bool valid = j < t;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    int n = 0;
+    if (valid)
+        for (int64_t r = r0 + rl; r < r1; r += RL) {
+            const float y = a.T[r * a.ldt + j];
+            if (!isfinite(y)) continue;
+            ++n;
+            float p, q;
+            sigmoid_pair(a.X[r * a.ldx + j], p, q);
+            const float wy = (a.w ? a.w[r] : 1.f) * y, wn = (a.w ? a.w[r] : 1.f) * (1.f - y);
+            v[0] += wy * p; v[1] += wn * p; v[2] += wn * q; v[3] += wy * q;
+        }
+    mcc_col_reduce<float, 4>(v, C, red);
+    if (tid < C && valid) {
+        float* o = a.part + rb * 4 * t + j;
+        o[0] = v[0]; o[t] = v[1]; o[2 * (int64_t)t] = v[2]; o[3 * (int64_t)t] = v[3];
+    }
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
+    if ((tid & 63) == 0) redi[tid >> 6] = n;
+    __syncthreads();
+    if (tid == 0) a.cnt[blockIdx.x] = (redi[0] + redi[1]) + (redi[2] + redi[3]);
+}
+__global__ __launch_bounds__(kMccThreads) void k_mcc_finish(MccArgs a) {
+    __shared__ double red[4 * kMccThreads];
+    __shared__ float coef[2 * kMccThreads];
+    __shared__ int redi[kMccThreads / 64];
+    const int tid = threadIdx.x, t = a.t, C = 1 << a.lgC, c = tid & (C - 1), rl = tid >> a.lgC, RL = kMccThreads >> a.lgC;
+    double lsum = 0.0;   // (workgroup 0, threads < C: sum over this thread's columns of tw_j MCC_j)
+    for (int cb = 0; cb < a.n_cb; ++cb) {
+        const int j = cb * kMccThreads + c;
+        const bool valid = j < t;
+        double v[4] = {0.0, 0.0, 0.0, 0.0};
+        if (valid)
+            for (int blk = rl; blk < a.n_blocks; blk += RL) {
+                const float* p = a.part + (int64_t)blk * 4 * t + j;
+                v[0] += p[0]; v[1] += p[t]; v[2] += p[2 * (int64_t)t]; v[3] += p[3 * (int64_t)t];
+            }
+        mcc_col_reduce<double, 4>(v, C, red);
+        if (tid < C) {   // (tid == c)
+            float al = 0.f, be = 0.f;
+            if (valid) {
+                const double TP = v[0], FP = v[1], TN = v[2], FN = v[3];
+                const double A = TP + FP, Bq = TP + FN, Cq = TN + FP, E = TN + FN, N = TP * TN - FP * FN;
+                const double iS = 1.0 / sqrt(A * Bq * Cq * E + 1e-8), mcc = N * iS, hN = 0.5 * mcc * iS * iS;   // hN = N / (2 S^3)
+                // g(dN, dD) = dN / S - N dD / (2 S^3); one class absent: N and the present class's dN, dD are exactly 0
+                const double alpha = (TN * iS - hN * (Bq * Cq * E + A * Cq * E)) - (-FP * iS - hN * (A * Cq * E + A * Bq * Cq));
+                const double beta = (-FN * iS - hN * (Bq * Cq * E + A * Bq * E)) - (TP * iS - hN * (A * Bq * E + A * Bq * Cq));
+                const double twj = a.tw ? (double)a.tw[j] : 1.0, sc = -twj / (double)t;
+                al = (float)(sc * alpha); be = (float)(sc * beta);
+                if (blockIdx.x == 0) lsum += twj * mcc;
+            }
+            coef[tid] = al; coef[kMccThreads + tid] = be;
+        }
+        __syncthreads();
+        if (a.gP && valid) {
+            const float al = coef[c], be = coef[kMccThreads + c];
+            for (int64_t rb = blockIdx.x; rb < a.n_blocks; rb += gridDim.x) {
+                const int64_t r0 = rb * kMccRows, r1 = r0 + kMccRows < a.B ? r0 + kMccRows : a.B;
+                for (int64_t r = r0 + rl; r < r1; r += RL) {
+                    const float y = a.T[r * a.ldt + j];
+                    float g = 0.f;   // (no finite target: exactly 0)
+                    if (isfinite(y)) {
+                        float p, q;
+                        sigmoid_pair(a.X[r * a.ldx + j], p, q);
+                        g = (a.w ? a.w[r] : 1.f) * (y * al + (1.f - y) * be) * (p * q);
+                    }
+                    a.gP[r * a.ldg + j] = g;
+                }
+            }
+        }
+        // (coef is written again behind the two barriers of the next pass's mcc_col_reduce)
+    }
+    if (blockIdx.x != 0) return;
+    for (int off = 32; off > 0; off >>= 1) lsum += __shfl_xor(lsum, off);
+    int n = 0;
+    for (int64_t i = tid; i < (int64_t)a.n_blocks * a.n_cb; i += kMccThreads) n += a.cnt[i];
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
+    __syncthreads();
+    if ((tid & 63) == 0) { red[tid >> 6] = lsum; redi[tid >> 6] = n; }
+    __syncthreads();
+    if (tid == 0) {
+        a.out[0] = (float)(1.0 - ((red[0] + red[1]) + (red[2] + red[3])) / (double)t);   // (no finite target: 1, dmpnn.h)
+        a.out[1] = (float)((redi[0] + redi[1]) + (redi[2] + redi[3]));
+    }
+}
+
 // ---- the predictor's OUTPUT layer for a handful of tasks (n_tasks <= kOutMaxTasks: the usual regression head) ----------------
 // P = A W^T + b with W [t, K]: t dot products per row — one wave per row, lanes over K (a 16 x 16 MFMA tile would be 1/16 full
 // and the generic contraction kernel spends 17 us on its pipeline for 0.3 MFLOP).

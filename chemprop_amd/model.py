@@ -30,7 +30,7 @@ from .data import merge_components
 from .optim import CLIP_MODES, FlatAdam
 
 __all__ = ["MSE", "MAE", "BCE", "CE", "MVE", "Evidential", "Quantile", "RegressionFFN", "BinaryClassificationFFN", "MulticlassClassificationFFN", "MveFFN", "EvidentialFFN", "QuantileFFN",
-           "Dirichlet", "BinaryDirichletFFN", "MulticlassDirichletFFN", "SID", "Wasserstein", "SpectralFFN", "MPNN", "MulticomponentMPNN", "FusedTrainer", "masked_loss"]
+           "Dirichlet", "BinaryDirichletFFN", "MulticlassDirichletFFN", "SID", "Wasserstein", "SpectralFFN", "BinaryMCC", "MPNN", "MulticomponentMPNN", "FusedTrainer", "masked_loss"]
 
 
 def masked_loss(preds: Tensor, targets: Tensor, weights: Optional[Tensor] = None, task_weights: Optional[Tensor] = None,
@@ -42,8 +42,15 @@ def masked_loss(preds: Tensor, targets: Tensor, weights: Optional[Tensor] = None
     targets = targets.nan_to_num(nan=0.0)
     w = torch.ones(targets.shape[0], dtype=torch.float, device=targets.device) if weights is None else weights
     tw = 1.0 if task_weights is None else task_weights.view(1, -1)
-    if kind in ("bce", "ce", "mve", "evidential", "quantile", "dirichlet", "sid", "wasserstein"):
+    if kind in ("bce", "ce", "mve", "evidential", "quantile", "dirichlet", "sid", "wasserstein", "mcc"):
         lt_mask = gt_mask = None     # (only the Bounded* criteria apply the masks: metrics.py:157-177)
+    if kind == "mcc":                # preds [b, t] logits (BinaryClassificationFFN.train_step): BinaryMCCLoss as include/dmpnn.h restates it
+        a = w.view(-1, 1) * mask     # (the sigmoid always; 1 - p as sigmoid(-x); the mean over ALL tasks: no finite target anywhere is loss 1)
+        p, q = preds.sigmoid(), (-preds).sigmoid()
+        TP, FP = (a * targets * p).sum(0), (a * (1 - targets) * p).sum(0)
+        TN, FN = (a * (1 - targets) * q).sum(0), (a * targets * q).sum(0)
+        mcc = (TP * TN - FP * FN) / ((TP + FP) * (TP + FN) * (TN + FP) * (TN + FN) + 1e-8).sqrt()
+        return 1 - (mcc * tw).sum() / targets.shape[1]
     if kind in ("sid", "wasserstein"):   # preds [b, t] = p (SpectralFFN.train_step): renormalised over the finite targets (include/dmpnn.h)
         c = preds if threshold is None else preds.clamp(min=threshold)
         q = c / (c * mask).sum(1, keepdim=True)
@@ -339,6 +346,14 @@ class Wasserstein(SID):
     kind = "wasserstein"
 
 
+class BinaryMCC(MSE):
+    """``chemprop.nn.metrics.BinaryMCCLoss``: one minus the mean over the tasks of the soft Matthews correlation of ``sigmoid(preds)``
+    (``preds [b, t]``: the LOGITS of ``BinaryClassificationFFN.train_step``) against 0 / 1 targets, the four confusion sums taken over
+    the whole batch per task; no bounds.  The contract and its declared deviations: ``include/dmpnn.h``."""
+
+    kind = "mcc"
+
+
 class _Exp(nn.Module):
     def forward(self, x: Tensor) -> Tensor:
         return x.exp()
@@ -576,6 +591,10 @@ def criterion_kind(crit) -> tuple[Optional[str], bool]:
         return "evidential", False
     if "QuantileLoss" in names and "PointQuantileLoss" not in names:   # nn/metrics.py:589-610 (the interval form; the point form takes one value per task)
         return "quantile", False
+    if "MulticlassMCCLoss" in names:  # nn/metrics.py (reaches the logits through argmax and sum softmax alone: a zero gradient — torch ops)
+        return None, False
+    if "BinaryMCCLoss" in names:      # nn/metrics.py (binary classification on logits, --loss-function mcc)
+        return "mcc", False
     if "BCELoss" in names:       # nn/metrics.py:292-295 (binary classification: chemprop's second task type)
         return "bce", False
     if "CrossEntropyLoss" in names:   # nn/metrics.py:298-304 (multiclass: logits [b, t, c] against class indices)
@@ -627,7 +646,10 @@ class HeadSpec:
     A spectral head is taken as exactly the pair (``SpectralFFN``, ``SID`` | ``Wasserstein``), by name as well: ``kind == "sid" |
     "wasserstein"``, one output per task; ``spectral_act`` (``"softplus" | "exp"``, read off the ``spectral_activation`` child of
     ``ffn``, which is not one of ``layers``) and ``spectral_threshold`` (the criterion's ``threshold``, 0.0 for ``None``) travel in
-    ``dmpnn_head_args.spectral_act`` / ``spectral_threshold``."""
+    ``dmpnn_head_args.spectral_act`` / ``spectral_threshold``.
+
+    A binary MCC head is taken as exactly the pair (``BinaryClassificationFFN``, ``BinaryMCCLoss``), by name: ``kind == "mcc"``,
+    ``n_classes == 0``, one output per task; any other predictor with it, and ``MulticlassMCCLoss``, are refused."""
 
     def __init__(self, model, ffn_dropout: bool = False, attentive: bool = False):
         agg, pred = model.agg, model.predictor
@@ -667,8 +689,12 @@ class HeadSpec:
         if not (isinstance(pred.output_transform, nn.Identity) or "UnscaleTransform" in _mro_names(pred.output_transform)):
             raise NotImplementedError("the output transform is the identity while training (predictors.py:166-169)")
         kind, self.bounded = criterion_kind(pred.criterion)
+        if "MulticlassMCCLoss" in _mro_names(pred.criterion):
+            raise NotImplementedError("MulticlassMCCLoss stays on torch ops: it reaches the logits through argmax counts and sum(softmax) "
+                                      "alone, so its gradient is zero and a kernel for it would train nothing (binary MCC is built in)")
         if kind is None:
-            raise NotImplementedError("MSE / MAE criterion (bounded or not), BCE, cross entropy, MVE, evidential, quantile, Dirichlet, SID or Wasserstein")
+            raise NotImplementedError("MSE / MAE criterion (bounded or not), BCE, cross entropy, MVE, evidential, quantile, Dirichlet, SID, "
+                                      "Wasserstein or binary MCC")
         # evidential classification: exactly the pairs (BinaryDirichletFFN | MulticlassDirichletFFN, DirichletLoss), the predictors told
         # by MRO name like the other reference classes; the class layout is cross entropy's, the binary head has two classes per task
         # (its n_targets = 2 says the same thing: for the kernels it is a class dimension, not a chunked one)
@@ -683,6 +709,9 @@ class HeadSpec:
         if (kind in ("sid", "wasserstein")) != spectral_pred:
             raise NotImplementedError(f"a spectral criterion ({kind}) on a predictor that is not a SpectralFFN" if not spectral_pred else
                                       f"a SpectralFFN with a criterion other than SID / Wasserstein (got {kind})")
+        # binary MCC: exactly the pair (BinaryClassificationFFN, BinaryMCCLoss) — logits in, one output per task, no class dimension
+        if kind == "mcc" and "BinaryClassificationFFN" not in names:
+            raise NotImplementedError(f"a binary MCC criterion on a predictor that is not a BinaryClassificationFFN (got {type(pred).__name__})")
         self.spectral_act, self.spectral_threshold = None, 0.0
         if spectral_pred:
             self.spectral_act = spectral_activation_of(pred)

@@ -62,7 +62,9 @@ extern "C" {
  * dmpnn_bwd_inputs_args (gradients with respect to V, E and V_d on the per-step general route) and dmpnn_src_sum.
  * Grown, same version: DMPNN_LOSS_SID / DMPNN_LOSS_WASSERSTEIN and DMPNN_PT_SPECTRAL (new accepted values) with
  * dmpnn_head_args.spectral_act / spectral_threshold at its end (zero in an older caller: read by the new values alone).
- * Grown, same version: DMPNN_ACT_SELU (a new accepted value of every `act` that took DMPNN_ACT_ELU; no struct changes). */
+ * Grown, same version: DMPNN_ACT_SELU (a new accepted value of every `act` that took DMPNN_ACT_ELU; no struct changes).
+ * Grown, same version: DMPNN_LOSS_MCC = 11 (a new accepted value of dmpnn_head_args.loss; 10 stays unknown; no struct changes;
+ * dmpnn_head_ws_bytes() grows with that value only). */
 #define DMPNN_ABI_VERSION 15
 
 enum dmpnn_status {
@@ -759,7 +761,13 @@ enum dmpnn_loss { DMPNN_LOSS_MSE = 0, DMPNN_LOSS_MAE = 1,
                                       /* v15 growth: the spectral criteria (SID / Wasserstein, nn/metrics.py, on SpectralFFN.train_step,
                                          nn/predictors.py) — see "The spectral criteria" below.  One output per task; preds holds the raw x.
                                          n_classes != 0 beside them is no criterion this library knows ("unknown criterion":
-                                         DMPNN_EINVAL), bounds masks beside them: DMPNN_EINVAL */ };
+                                         DMPNN_EINVAL), bounds masks beside them: DMPNN_EINVAL */
+                  , DMPNN_LOSS_MCC = 11
+                                      /* v15 growth: the binary Matthews-correlation criterion (BinaryMCCLoss, nn/metrics.py, on
+                                         BinaryClassificationFFN.train_step) — see "The binary MCC criterion" below.  One output per task;
+                                         preds holds the raw logits.  10 stays a value this library does not know (older callers probe it
+                                         as the first unknown criterion), and so does 11 with n_classes != 0 ("unknown criterion":
+                                         DMPNN_EINVAL); bounds masks beside it: DMPNN_EINVAL.  No struct field: the 1e-8 is a constant */ };
 /* The spectral criteria.  These formulas are the contract: they restate chemprop 2.3.1 (nn/predictors.py: SpectralFFN; nn/metrics.py:
  * SID, Wasserstein, ChempropMetric.update / compute) from memory and were NOT run against that source.
  *   x [B, t] the MLP's raw output; T [B, t] the targets, m = isfinite(T), y = T where finite, else 0; w [B] row weights, tw [t] task
@@ -785,6 +793,34 @@ enum dmpnn_loss { DMPNN_LOSS_MSE = 0, DMPNN_LOSS_MAE = 1,
  *     non-finite: DMPNN_EINVAL.  An unknown spectral_act: DMPNN_EINVAL.
  * The stage (k_spectral_rows + k_spectral_finish, two launches in place of k_loss's one): a grid over molecule rows, sums and scans in a
  * fixed order, no floating-point atomics — loss_out and the gradients are bit-identical from call to call. */
+/* The binary MCC criterion (DMPNN_LOSS_MCC).  These formulas are the contract: they restate chemprop 2.3.1 (nn/metrics.py: BinaryMCCLoss,
+ * on the logits BinaryClassificationFFN.train_step hands over) and were NOT run against that source.
+ *   x [B, t] the output layer's raw logits; T [B, t] the targets, m = isfinite(T), y = T where finite, else 0 (used as the float it
+ *   is; 0 / 1 are expected, as for DMPNN_LOSS_BCE); w [B] row weights, tw [t] task weights (1 where NULL).
+ *   p = sigmoid(x),  a_ij = w_i m_ij, and per task j, over ALL molecules of the batch:
+ *     TP_j = sum_i a y p        FP_j = sum_i a (1 - y) p        TN_j = sum_i a (1 - y) (1 - p)        FN_j = sum_i a y (1 - p)
+ *     D_j = (TP + FP) (TP + FN) (TN + FP) (TN + FN),   MCC_j = (TP TN - FP FN) / sqrt(D_j + 1e-8)
+ *   loss = 1 - (1 / t) sum_j tw_j MCC_j;   loss_out = [loss, sum m].
+ * The gradient, two coefficients per task:  S = sqrt(D + 1e-8), N = TP TN - FP FN, A = TP + FP, Bq = TP + FN, C = TN + FP, E = TN + FN,
+ *   g(dN, dD) = dN / S - N dD / (2 S^3),
+ *   alpha_j = g(TN, Bq C E + A C E) - g(-FP, A C E + A Bq C)        (d/dTP - d/dFN)
+ *   beta_j  = g(-FN, Bq C E + A Bq E) - g(TP, A Bq E + A Bq C)      (d/dFP - d/dTN)
+ *   dloss/dx_ij = -(tw_j / t) a_ij (y_ij alpha_j + (1 - y_ij) beta_j) p_ij (1 - p_ij).
+ * Declared deviations and behaviour at the edges:
+ *   - the reference applies the sigmoid only when some prediction lies outside [0, 1] (a test on the data); here it is always applied:
+ *     the predictor's train_step hands over logits;
+ *   - the mean runs over all t tasks: a task without a finite target has MCC_j = 0 and a gradient of exactly 0; a batch without any
+ *     finite target has loss 1.0 — NOT the NaN of the sum / count criteria — and loss_out[1] = 0;
+ *   - a task whose finite targets are all of one class (0 or 1) has MCC_j = 0 and a gradient of exactly 0, not merely a small one (N and
+ *     the dN, dD of the class that is present vanish exactly in the form above; the other coefficient meets a factor y or 1 - y of 0);
+ *   - rows of weight 0 take no part; no lt_mask / gt_mask (DMPNN_EINVAL), as for every criterion but MSE / MAE;
+ *   - several devices: every rank forms the sums over its own shard, as the reference's training loss does.
+ * The stage (k_mcc_cols + k_mcc_finish, two launches in place of k_loss's one): k_mcc_cols, a grid over blocks of molecule rows (and of
+ * 256 task columns), leaves each block's four sums per task in the workspace; k_mcc_finish adds the blocks' sums per task in block order
+ * (in double), forms MCC_j, alpha_j, beta_j and writes dloss/dx (gP == NULL inside the library: the loss alone, what dmpnn_predict_head
+ * takes with targets); workgroup 0 writes loss_out.  Any B >= 1, any t >= 1; no atomics, no order that depends on scheduling — loss_out
+ * and the gradients are bit-identical from call to call.  The four-launch row form and the one-launch output-layer-plus-criterion form
+ * are not taken with it.  dmpnn_predict_head: with DMPNN_PT_SIGMOID. */
 typedef struct dmpnn_head_args {
     int64_t n_atoms, n_mols, d_h;           /* rows of H_v, molecules, width of H_v                              */
     const int64_t* batch;                   /* [n_atoms] molecule of every atom, non-decreasing (BatchMolGraph.batch) */
@@ -850,7 +886,7 @@ int dmpnn_head(const dmpnn_head_args* h, const float* Hv, int64_t ldhv, void* st
  * kernel k_head_rows<., 1>, 16 molecules x 64 columns per workgroup, where the reduction width is whole quads up to 512; k_rows16
  * otherwise; a layer whose shape dmpnn_linear16_ok refuses — odd widths, unaligned rows — runs as dmpnn_linear_fwd), then ONE launch
  * (k_predict_tail) for the output layer, the predictor's output
- * transform and every store, and k_loss when targets are given (the spectral criteria: their stage of two launches).  The usual model (sum / mean / norm aggregation, batch norm, one hidden
+ * transform and every store, and k_loss when targets are given (the spectral criteria and binary MCC: their stages of two launches).  The usual model (sum / mean / norm aggregation, batch norm, one hidden
  * layer, <= DMPNN_PREDICT_MAX_OUT outputs, <= 1 024 molecules, widths in whole quads) with a ready split: three launches, four with
  * targets (dmpnn_last_launch_count()).  Output layers wider than DMPNN_PREDICT_MAX_OUT run on the contraction kernels and
  * k_predict_tail transforms their rows.
