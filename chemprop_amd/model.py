@@ -27,7 +27,7 @@ from .distributed import GradSync, force_collective
 from .ffn import MLP, mlp_blocks
 from .nn import BondMessagePassing, MulticomponentMessagePassing, classify_activation
 from .data import merge_components
-from .optim import CLIP_MODES, FlatAdam
+from .optim import CLIP_MODES, FlatAdam, bias_corrections
 
 __all__ = ["MSE", "MAE", "BCE", "CE", "MVE", "Evidential", "Quantile", "RegressionFFN", "BinaryClassificationFFN", "MulticlassClassificationFFN", "MveFFN", "EvidentialFFN", "QuantileFFN",
            "Dirichlet", "BinaryDirichletFFN", "MulticlassDirichletFFN", "SID", "Wasserstein", "SpectralFFN", "BinaryMCC", "MPNN", "MulticomponentMPNN", "FusedTrainer", "masked_loss"]
@@ -1235,7 +1235,7 @@ class FusedTrainer:
         b1, b2 = opt.betas
         s.p, s.g, s.m, s.v, s.n_params = opt.flat.data_ptr(), self.sync.flat.data_ptr(), opt.m.data_ptr(), opt.v.data_ptr(), opt.flat.numel()
         s.lr, s.beta1, s.beta2, s.eps, s.weight_decay = float(opt.lr if lr is None else lr), b1, b2, opt.eps, opt.weight_decay
-        s.bias_corr1, s.sqrt_bias_corr2, s.grad_scale = 1.0 - b1 ** k, math.sqrt(1.0 - b2 ** k), 1.0
+        (s.bias_corr1, s.sqrt_bias_corr2), s.grad_scale = bias_corrections(opt.betas, k), 1.0   # (from the betas as float32: optim.py)
         if clip is not None:
             s.clip_val, s.clip_mode, s.clip_ws = clip[0], CLIP_MODES[clip[1]], opt.clip_ws.data_ptr()
         return k

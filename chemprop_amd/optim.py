@@ -20,9 +20,19 @@ import torch
 from . import _lib, engine
 from .distributed import GradSync
 
-__all__ = ["FlatAdam", "CLIP_MODES"]
+__all__ = ["FlatAdam", "CLIP_MODES", "bias_corrections"]
 
 CLIP_MODES = {"norm": 0, "value": 1}   # enum dmpnn_clip_mode
+
+
+def bias_corrections(betas: tuple, step: int) -> tuple:
+    """``(1 - beta1^step, sqrt(1 - beta2^step))`` of Adam's step ``step`` (1-based), formed from the betas AS THE KERNEL HOLDS THEM:
+    ``k_adam`` receives them as float32 and forms ``1.f - beta`` itself — for 0.999 that is 0.99998713e-3, 1.3e-5 off 1e-3.  A bias
+    correction from the double 0.999 then leaves ``v / (1 - beta2^step)`` that far off ``g^2`` at step 1, and the update 6e-6 off
+    ``torch.optim.Adam``'s wherever ``eps`` does not dominate: invisible on a weight matrix, 3e-6 of a scalar parameter near 1e-3
+    (``tests/test_step_combinations_gpu.py``).  With both sides on the float32 betas the moments' weights sum to 1 again."""
+    b1, b2 = (float(C.c_float(b).value) for b in betas)
+    return 1.0 - b1 ** step, math.sqrt(1.0 - b2 ** step)
 
 
 class FlatAdam:
@@ -85,14 +95,13 @@ class FlatAdam:
             self.clip_grad(*clip)
         self.steps += 1
         b1, b2 = self.betas
-        bc1 = 1.0 - b1 ** self.steps
-        bc2 = 1.0 - b2 ** self.steps
+        bc1, sqrt_bc2 = bias_corrections(self.betas, self.steps)
         scale = self._grad_scale()
         with engine._OnDevice(self._dev):
             _lib.check(_lib.load().dmpnn_adam_step(
                 self.flat.data_ptr(), s.flat.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.flat.numel(),
                 C.c_float(self.lr if lr is None else float(lr)), C.c_float(b1), C.c_float(b2), C.c_float(self.eps),
-                C.c_float(self.weight_decay), C.c_float(bc1), C.c_float(math.sqrt(bc2)), C.c_float(scale), None,
+                C.c_float(self.weight_decay), C.c_float(bc1), C.c_float(sqrt_bc2), C.c_float(scale), None,
                 engine._stream_ptr(self._dev)), "dmpnn_adam_step")
         for p in s.params:  # (the engine's weight caches key on the autograd version)
             torch.autograd.graph.increment_version(p)
