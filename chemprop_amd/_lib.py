@@ -176,6 +176,7 @@ class MolAggAttnArgs(C.Structure):
 MOLAGG_ATTENTIVE = 3   # (DMPNN_MOLAGG_ATTENTIVE: dmpnn_head_args.agg_mode)
 PREDICT_TRANSFORM = {"none": 0, "unscale": 1, "sigmoid": 2, "softmax": 3, "mve": 4, "evidential": 5, "quantile": 6}   # enum dmpnn_predict_transform
 PT_SPECTRAL = 8   # (DMPNN_PT_SPECTRAL: a value of dmpnn_predict_args.transform beside the enum's — 7 stays unknown)
+PT_DIRICHLET_BINARY, PT_DIRICHLET_MULTICLASS = 10, 11   # (DMPNN_PT_DIRICHLET_BINARY / _MULTICLASS, beside the enum's as well — 9 stays unknown)
 PREDICT_MAX_OUT = 64   # (DMPNN_PREDICT_MAX_OUT: output layers up to this width ride in k_predict_tail)
 
 

@@ -145,6 +145,7 @@ inline float* ws_f(const dmpnn_head_args& h, size_t off) { return reinterpret_ca
 
 // outputs per task of an output transform and of a criterion
 int transform_per_task(int transform, int n_classes) {
+    if (transform == DMPNN_PT_DIRICHLET_BINARY || transform == DMPNN_PT_DIRICHLET_MULTICLASS) return n_classes;
     return transform == DMPNN_PT_SOFTMAX ? n_classes : (transform == DMPNN_PT_EVIDENTIAL ? 4 : ((transform == DMPNN_PT_MVE || transform == DMPNN_PT_QUANTILE) ? 2 : 1));
 }
 int loss_per_task(const dmpnn_head_args& h) {
@@ -587,7 +588,9 @@ size_t predict_slot_bytes(const dmpnn_head_args& h, const HeadLayout& L, int l) 
     const dmpnn_gemm_args g = ffn_layer(h, l, 1, reinterpret_cast<const float*>(uintptr_t(256)), l == 0 ? ld0 : h.dims[l], nullptr);
     return linear16_ok(g) ? linear16_wsplit_bytes(g.N, g.K1) : 0;
 }
-inline bool known_transform(int t) { return (t >= DMPNN_PT_NONE && t <= DMPNN_PT_QUANTILE) || t == DMPNN_PT_SPECTRAL; }
+inline bool known_transform(int t) {
+    return (t >= DMPNN_PT_NONE && t <= DMPNN_PT_QUANTILE) || t == DMPNN_PT_SPECTRAL || t == DMPNN_PT_DIRICHLET_BINARY || t == DMPNN_PT_DIRICHLET_MULTICLASS;
+}
 bool predict_sizes_ok(const dmpnn_predict_args* p) {
     return p && p->head.n_layers >= 1 && p->head.n_layers <= DMPNN_MAX_FFN_LAYERS && p->head.d_h > 0 && p->head.n_mols >= 0 && p->head.n_components >= 0 &&
            p->head.n_components <= DMPNN_MAX_COMPONENTS && known_transform(p->transform);
@@ -621,6 +624,15 @@ int predict_check(const dmpnn_predict_args* pp) {
                     "predict_head: the MVE / quantile transforms need an output layer 2 n_tasks wide (got %lld)", (long long)n_out);
     DMPNN_CHECK_ARG(p.transform != DMPNN_PT_EVIDENTIAL || n_out % 4 == 0, "predict_head: the evidential transform needs an output layer 4 n_tasks wide (got %lld)",
                     (long long)n_out);
+    // (k_predict_tail reads x(2 j + 1) and x(c0 + k) without a bounds test: these two rules keep it inside the row)
+    DMPNN_CHECK_ARG(p.transform != DMPNN_PT_DIRICHLET_BINARY || (h.n_classes == 2 && n_out % 2 == 0),
+                    "predict_head: the binary Dirichlet transform needs head.n_classes == 2 and an output layer 2 n_tasks wide (%d, %lld)", (int)h.n_classes,
+                    (long long)n_out);
+    DMPNN_CHECK_ARG(p.transform != DMPNN_PT_DIRICHLET_MULTICLASS || (h.n_classes >= 2 && n_out % h.n_classes == 0),
+                    "predict_head: the multiclass Dirichlet transform needs head.n_classes >= 2 dividing the output width (%d, %lld)", (int)h.n_classes,
+                    (long long)n_out);
+    DMPNN_CHECK_ARG((p.transform != DMPNN_PT_DIRICHLET_BINARY && p.transform != DMPNN_PT_DIRICHLET_MULTICLASS) || !p.out_mean,
+                    "predict_head: the Dirichlet transforms take no out_mean / out_scale (probabilities are not unscaled)");
     if (h.targets) {
         DMPNN_CHECK_ARG(known_criterion(h), "head: unknown criterion %d (n_classes %d)", h.loss, (int)h.n_classes);
         DMPNN_CHECK_ARG(loss_per_task(h) == transform_per_task(p.transform, h.n_classes),

@@ -13,6 +13,8 @@
 // n_out > DMPNN_PREDICT_MAX_OUT: the contraction kernels ran the layer; the <false> build reads the raw rows from memory instead.
 // DMPNN_PT_SPECTRAL couples an element to its whole row (p = a / sum_row a): the row's sum, and its maximum for exp, are wave
 // reductions once per row in front of the element loop, in both builds.
+// DMPNN_PT_DIRICHLET_BINARY / _MULTICLASS (BinaryDirichletFFN / MulticlassDirichletFFN.forward): alpha = softplus(x) + 1 over a task's
+// classes, gathered like the softmax's — (alpha_1 / S, 2 / S) per task with S = alpha_0 + alpha_1, and alpha_k / sum_k alpha_k.
 #include "dmpnn_gemm_impl.hpp"   // (gemm::make_rsrc / clamp_bytes / kOOB: the buffer descriptors of every kernel here)
 
 namespace dmpnn {
@@ -58,6 +60,18 @@ __device__ __forceinline__ float tail_transform(const PredictTail& q, int e, X x
             const int j = e >> 1;
             const float s = sc(j), m = mn(j), lo = x(j) * s + m, up = x(t + j) * s + m;
             return (e & 1) ? up - lo : (lo + up) / 2.f;
+        }
+        // the Dirichlet heads, alpha(c) = softplus(x(c)) + 1 — dirichlet_loss's alphas (predict_check keeps 2 j + 1 and c0 + k inside the row)
+        case DMPNN_PT_DIRICHLET_BINARY: {   // BinaryDirichletFFN.forward: (p_1, 2 / S) per task, column 2 j + k the evidence of class k
+            const int j = e >> 1;
+            const float a1 = softplus_f(x(2 * j + 1)) + 1.f, S = (softplus_f(x(2 * j)) + 1.f) + a1;
+            return (e & 1) ? 2.f / S : a1 / S;
+        }
+        case DMPNN_PT_DIRICHLET_MULTICLASS: {   // MulticlassDirichletFFN.forward: alpha / sum over the task's classes
+            const int c0 = (e / q.nc) * q.nc;
+            float S = 0.f;
+            for (int k = 0; k < q.nc; ++k) S += softplus_f(x(c0 + k)) + 1.f;
+            return (softplus_f(x(e)) + 1.f) / S;
         }
         default: return x(e);
     }

@@ -5,7 +5,10 @@ on torch, one :class:`~chemprop_amd.nn.HipMLP` call per predictor layer and two 
 ``validation_step`` then forms the fingerprint a second time for ``val_loss``.  :func:`fused_predict` keeps the block's forward as
 it is and hands everything behind it — aggregation, eval-mode batch norm, ``X_d``, the predictor, its output transform, and the
 criterion on the raw outputs when targets are given — to the library in one call: three launches for the usual model, four with
-targets.  :meth:`chemprop_amd.model.MPNN.predict` is the entry a caller uses; it falls back to the modules where this returns ``None``.
+targets.  The evidential-classification heads (``BinaryDirichletFFN`` / ``MulticlassDirichletFFN`` with ``DirichletLoss``) are taken
+too: ``alpha = softplus + 1`` and ``alpha / sum(alpha)`` — the binary head's ``(p_1, 2 / S)`` — are a transform of the last launch, and
+``loss`` is the Dirichlet criterion on the raw outputs.  :meth:`chemprop_amd.model.MPNN.predict` is the entry a caller uses; it falls
+back to the modules where this returns ``None``.
 """
 from __future__ import annotations
 
@@ -23,6 +26,9 @@ from .model import HeadSpec, _batch_vector_ok, _component_batch, _head_spec_key,
 _TRANSFORM_OF = (("SpectralFFN", "spectral"), ("MveFFN", "mve"), ("EvidentialFFN", "evidential"), ("QuantileFFN", "quantile"),
                  ("MulticlassClassificationFFN", "softmax"), ("BinaryClassificationFFN", "sigmoid"), ("RegressionFFN", "unscale"))
 _GROUP = {"mve": 2, "evidential": 4, "quantile": 2}
+# the evidential-classification predictors (PredictSpec(model, dirichlet=True)) and the transform values beside the enum's
+_DIRICHLET_OF = (("BinaryDirichletFFN", "dirichlet_binary"), ("MulticlassDirichletFFN", "dirichlet_multiclass"))
+_BESIDE_ENUM = {"spectral": _lib.PT_SPECTRAL, "dirichlet_binary": _lib.PT_DIRICHLET_BINARY, "dirichlet_multiclass": _lib.PT_DIRICHLET_MULTICLASS}
 
 
 class PredictResult(NamedTuple):
@@ -37,23 +43,33 @@ class PredictResult(NamedTuple):
 
 class PredictSpec(HeadSpec):
     """What ``dmpnn_predict_head`` needs to know of the model: :class:`~chemprop_amd.model.HeadSpec` with the predictor's dropout and
-    attentive aggregation allowed, plus the output transform (``transform``: a key of ``_lib.PREDICT_TRANSFORM`` or ``"spectral"``, told from the
-    predictor's class) and the ``UnscaleTransform`` behind it (``unscale``: the module, or ``None`` for ``nn.Identity``).  Raises
-    ``NotImplementedError`` for what the inference head does not take.  Also holds the per-model workspace and the cached split
-    images of the hidden layers' weights."""
+    attentive aggregation allowed, plus the output transform (``transform``: a key of ``_lib.PREDICT_TRANSFORM``, ``"spectral"``,
+    ``"dirichlet_binary"`` or ``"dirichlet_multiclass"``, told from the predictor's class) and the ``UnscaleTransform`` behind it
+    (``unscale``: the module, or ``None`` for ``nn.Identity``).  Raises ``NotImplementedError`` for what the inference head does not
+    take.  ``dirichlet=True`` also takes the two pairs ``HeadSpec`` takes for training — (``BinaryDirichletFFN`` |
+    ``MulticlassDirichletFFN``, ``DirichletLoss``), mirrors or reference classes by MRO name — with an identity output transform:
+    ``DMPNN_PT_DIRICHLET_BINARY`` (``(p_1, 2 / S) [n, t, 2]``) / ``_MULTICLASS`` (``alpha / sum alpha [n, t, n_classes]``); the default
+    refuses them, as :func:`predict_spec` does (:func:`fused_predict` opts in).  Also holds the per-model workspace and the cached
+    split images of the hidden layers' weights."""
 
-    def __init__(self, model):
+    def __init__(self, model, dirichlet: bool = False):
         super().__init__(model, ffn_dropout=True, attentive=True)
         pred = model.predictor
         names = _mro_names(pred)
-        if "BinaryDirichletFFN" in names or "MulticlassDirichletFFN" in names:
-            # (enum dmpnn_predict_transform has no alpha / sum(alpha): without this the multiclass one — a MulticlassClassificationFFN —
+        ot = pred.output_transform
+        dir_pred = next((tr for cls, tr in _DIRICHLET_OF if cls in names), None)
+        if dir_pred is not None and not dirichlet:
+            # (the opt-in idiom of HeadSpec's attentive= / ffn_dropout=; without this the multiclass one — a MulticlassClassificationFFN —
             #  would be handed to the softmax)
             raise NotImplementedError(f"a Dirichlet predictor ({type(pred).__name__}): its eval-mode forward runs on the modules")
-        self.transform = next((tr for cls, tr in _TRANSFORM_OF if cls in names), None)
+        if dir_pred is not None:   # (HeadSpec took the pair: kind == "dirichlet", n_classes 2 | the predictor's)
+            if not isinstance(ot, nn.Identity):   # (probabilities and an uncertainty: DMPNN_PT_DIRICHLET_* take no mean / scale)
+                raise NotImplementedError("a Dirichlet predictor with an output transform that is not the identity")
+            self.transform = dir_pred
+        else:
+            self.transform = next((tr for cls, tr in _TRANSFORM_OF if cls in names), None)
         if self.transform is None:
             raise NotImplementedError(f"a predictor of a known class (got {type(pred).__name__})")
-        ot = pred.output_transform
         self.unscale = None
         if self.transform == "spectral" and not isinstance(ot, nn.Identity):   # (p sums to 1: DMPNN_PT_SPECTRAL takes no mean / scale)
             raise NotImplementedError("a SpectralFFN with an output transform that is not the identity")
@@ -71,7 +87,7 @@ class PredictSpec(HeadSpec):
 
     def out_shape(self, n_mols: int) -> tuple:
         """The shape ``model(...)`` returns in eval mode (a spectral head: ``[n_mols, n_tasks]``, one value per task)."""
-        if self.transform == "softmax":
+        if self.transform in ("softmax", "dirichlet_binary", "dirichlet_multiclass"):   # (the binary Dirichlet head: n_classes == 2)
             return (n_mols, self.n_tasks, self.n_classes)
         if self.transform in _GROUP:
             return (n_mols, self.n_tasks, _GROUP[self.transform])
@@ -82,18 +98,23 @@ class PredictSpec(HeadSpec):
         return tuple((lin.weight.data_ptr(), lin.weight._version) for lin in self.layers[:-1])
 
 
-def predict_spec(model) -> Optional[PredictSpec]:
-    """The model's :class:`PredictSpec`, cached on the model under the identities ``head_loss`` keys its own cache on; ``None``: refused."""
-    key = _head_spec_key(model)
-    cached = model.__dict__.get("_dmpnn_predict_spec")
+def predict_spec(model, dirichlet: bool = False) -> Optional[PredictSpec]:
+    """The model's :class:`PredictSpec` (``dirichlet``: its opt-in), cached on the model under the identities ``head_loss`` keys its
+    own cache on — one slot per value of ``dirichlet``: the default's refusal of a Dirichlet model does not answer the opt-in question
+    (any other model has ONE spec, workspace and set of split images, whichever way it is asked for); ``None``: refused."""
+    key, flag = _head_spec_key(model), bool(dirichlet)
+    slots = model.__dict__.setdefault("_dmpnn_predict_spec", {})
+    cached = slots.get(flag)
     if cached is not None and cached[0] == key:
         spec = cached[1]
     else:
         try:
-            spec = PredictSpec(model)
+            spec = PredictSpec(model, dirichlet=flag)
         except NotImplementedError as e:
             spec = str(e)
-        model.__dict__["_dmpnn_predict_spec"] = (key, spec)
+        slots[flag] = (key, spec)
+        if not any(cls in _mro_names(model.predictor) for cls, _ in _DIRICHLET_OF):   # (the flag asks nothing of this model: one answer)
+            slots[not flag] = (key, spec)
     return None if isinstance(spec, str) else spec
 
 
@@ -113,8 +134,8 @@ def fused_predict(model, bmg, V_d=None, X_d=None, *, targets: Optional[Tensor] =
     is on, the inputs are not on the device, a batch vector is not what the kernels read, or ``X_d`` / ``targets`` / ``weights``
     are missing or misshapen.  The workspace and the split images of the hidden weights are kept per model: calls on one model belong
     on one stream.  An in-place change of a hidden weight through ``.data`` does not advance its version: clear
-    ``model.__dict__["_dmpnn_predict_spec"]`` after one."""
-    spec = predict_spec(model)
+    ``model.__dict__["_dmpnn_predict_spec"]`` after one.  A Dirichlet model is asked for with ``PredictSpec``'s ``dirichlet=True``."""
+    spec = predict_spec(model, dirichlet=True)
     if spec is None or model.training or torch.is_grad_enabled():
         return None
     is_list = isinstance(bmg, (list, tuple))
@@ -157,7 +178,7 @@ def fused_predict(model, bmg, V_d=None, X_d=None, *, targets: Optional[Tensor] =
     h = p.head
     keep = spec.fill(h, nV, n_mols, d_out, batch, Hv if T is None else T, weights if T is not None else None, lt_mask if T is not None else None,
                      gt_mask if T is not None else None, lambda prm: None, bn_training=False, X_d=Xd)
-    p.transform = _lib.PT_SPECTRAL if spec.transform == "spectral" else _lib.PREDICT_TRANSFORM[spec.transform]
+    p.transform = _BESIDE_ENUM[spec.transform] if spec.transform in _BESIDE_ENUM else _lib.PREDICT_TRANSFORM[spec.transform]
     if spec.unscale is not None:
         mean, scale = (t.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous() for t in (spec.unscale.mean, spec.unscale.scale))
         p.out_mean, p.out_scale = mean.data_ptr(), scale.data_ptr()

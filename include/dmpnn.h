@@ -64,7 +64,9 @@ extern "C" {
  * dmpnn_head_args.spectral_act / spectral_threshold at its end (zero in an older caller: read by the new values alone).
  * Grown, same version: DMPNN_ACT_SELU (a new accepted value of every `act` that took DMPNN_ACT_ELU; no struct changes).
  * Grown, same version: DMPNN_LOSS_MCC = 11 (a new accepted value of dmpnn_head_args.loss; 10 stays unknown; no struct changes;
- * dmpnn_head_ws_bytes() grows with that value only). */
+ * dmpnn_head_ws_bytes() grows with that value only).
+ * Grown, same version: DMPNN_PT_DIRICHLET_BINARY = 10 / DMPNN_PT_DIRICHLET_MULTICLASS = 11 (new accepted values of
+ * dmpnn_predict_args.transform; 7 and 9 stay unknown; no struct changes). */
 #define DMPNN_ABI_VERSION 15
 
 enum dmpnn_status {
@@ -894,8 +896,10 @@ int dmpnn_head(const dmpnn_head_args* h, const float* Hv, int64_t ldhv, void* st
  * Inference only — each of these is DMPNN_EINVAL before any device work: head.gHv or any head.g* pointer non-NULL; head.bn_training
  * != 0; head.ffn_dropout_p != 0; only one of out_mean / out_scale; an unknown transform; DMPNN_PT_SOFTMAX with head.n_classes < 2 or
  * n_classes not dividing n_out = head.dims[head.n_layers]; DMPNN_PT_MVE / _QUANTILE with n_out % 2 != 0, DMPNN_PT_EVIDENTIAL with
- * n_out % 4 != 0; with head.targets, a head.loss whose outputs per task (cross entropy / Dirichlet: n_classes; MVE / quantile: 2; evidential: 4;
- * else 1) disagree with the transform's (softmax: n_classes; MVE / quantile: 2; evidential: 4; else 1), or no head.loss_out; and
+ * n_out % 4 != 0; DMPNN_PT_DIRICHLET_BINARY with head.n_classes != 2 or an odd n_out, DMPNN_PT_DIRICHLET_MULTICLASS with head.n_classes < 2
+ * or n_classes not dividing n_out, either of the two with out_mean / out_scale; with head.targets, a head.loss whose outputs per task
+ * (cross entropy / Dirichlet: n_classes; MVE / quantile: 2; evidential: 4; else 1) disagree with the transform's (softmax and the two
+ * Dirichlet transforms: n_classes; MVE / quantile: 2; evidential: 4; else 1), or no head.loss_out; and
  * whatever dmpnn_head refuses.  A workspace (head.ws) or wsplit that is too small: DMPNN_ENOSPC.  The running statistics and
  * bn_num_batches_tracked are never written.  head.targets != NULL also writes head.loss_out: the criterion on the RAW outputs
  * (chemprop's val_loss), k_loss's arithmetic unchanged.  n_components > 1 and DMPNN_MOLAGG_ATTENTIVE are taken as dmpnn_head takes
@@ -905,7 +909,9 @@ int dmpnn_head(const dmpnn_head_args* h, const float* Hv, int64_t ldhv, void* st
  * threshold 20):  NONE p[j] = x[j];  UNSCALE p[j] = x[j] s + m;  SIGMOID p[j] = 1 / (1 + exp(-x[j]));  SOFTMAX p[j][k] =
  * softmax_k(x[j nc + k]) (the maximum subtracted first);  MVE p[j] = (x[j] s + m, softplus(x[t+j]) s^2);  EVIDENTIAL p[j] = (x[j] s
  * + m, softplus(x[t+j]), softplus(x[2t+j]) + 1, softplus(x[3t+j]) s^2);  QUANTILE lo = x[j] s + m, up = x[t+j] s + m: p[j] = ((lo +
- * up) / 2, up - lo);  SPECTRAL p[j] = a(x[j]) / sum_k a(x[k]) (below the enum).  These are the eval-mode forward of nn/predictors.py with
+ * up) / 2, up - lo);  SPECTRAL p[j] = a(x[j]) / sum_k a(x[k]) (below the enum);  with alpha[c] = softplus(x[c]) + 1 (the alphas of
+ * DMPNN_LOSS_DIRICHLET):  DIRICHLET_BINARY S = alpha[2j] + alpha[2j+1]: p[j] = (alpha[2j+1] / S, 2 / S);  DIRICHLET_MULTICLASS p[j][k] =
+ * alpha[j nc + k] / sum_m alpha[j nc + m] (both below the enum).  These are the eval-mode forward of nn/predictors.py with
  * UnscaleTransform / transform_variance.
  *
  * wsplit: the f16 split images of the hidden layers' weights, one slot per layer l < n_layers - 1 in layer order, each
@@ -921,6 +927,16 @@ enum dmpnn_predict_transform { DMPNN_PT_NONE = 0, DMPNN_PT_UNSCALE, DMPNN_PT_SIG
  * 7 stays an unknown transform): SpectralFFN.forward — preds [n_mols, n_tasks] = p = a / sum_row a, a = softplus(x) | exp(x - max_row x)
  * by head.spectral_act ("The spectral criteria" above); the row's sum (and maximum) once per row.  With out_mean / out_scale, or an
  * unknown head.spectral_act: DMPNN_EINVAL. */
+#define DMPNN_PT_DIRICHLET_BINARY 10
+#define DMPNN_PT_DIRICHLET_MULTICLASS 11
+/* DMPNN_PT_DIRICHLET_BINARY / _MULTICLASS (v15 growth; further values of dmpnn_predict_args.transform — 7 and 9 stay unknown transforms):
+ * the eval-mode forward of the evidential-classification predictors on alpha[c] = softplus(x[c]) + 1, the alphas DMPNN_LOSS_DIRICHLET forms.
+ * BINARY — BinaryDirichletFFN: raw column 2 j + k is the evidence of class k of task j, head.n_classes == 2 and an even n_out; preds
+ * [n_mols, n_tasks, 2] = (alpha[2j+1] / S, 2 / S) with S = alpha[2j] + alpha[2j+1]: the probability of class 1 and the uncertainty.
+ * MULTICLASS — MulticlassDirichletFFN: cross entropy's layout, head.n_classes >= 2 dividing n_out; preds [n_mols, n_tasks, n_classes] =
+ * alpha[j nc + k] / sum_m alpha[j nc + m].  Both count n_classes outputs per task (head.targets: with DMPNN_LOSS_DIRICHLET).  Any other
+ * n_classes / n_out, or out_mean / out_scale with either: DMPNN_EINVAL before any device work — the kernel gathers a task's columns
+ * without a bounds test of its own. */
 #define DMPNN_PREDICT_MAX_OUT 64
 typedef struct dmpnn_predict_args {
     dmpnn_head_args head;          /* the model behind the block, as dmpnn_head reads it. head.preds = the RAW outputs
