@@ -21,7 +21,7 @@ INCLUDE = os.path.join(_ROOT, "include")
 # DMPNN_LIB: an alternative build of the same sources (kernel experiments: scripts/build_variant.py), same ABI
 LIB_PATH = os.environ.get("DMPNN_LIB") or os.path.join(_HERE, "libdmpnn_gfx950.so")
 SOURCES = ["dmpnn_abi.hip", "dmpnn_prepare.hip", "dmpnn_segment.hip", "dmpnn_gemm.hip", "dmpnn_gemm_p1.hip",
-           "dmpnn_gemm_p2.hip", "dmpnn_gemm_p3.hip", "dmpnn_gemm_p4.hip", "dmpnn_gemm_s1.hip", "dmpnn_rows16_drop.hip", "dmpnn_mega.hip", "dmpnn_mega16.hip", "dmpnn_mega16_lp.hip", "dmpnn_mega16_bwd.hip", "dmpnn_rows16.hip", "dmpnn_step16.hip", "dmpnn_bstep16.hip", "dmpnn_backward.hip", "dmpnn_molagg.hip", "dmpnn_collate.hip", "dmpnn_tiles_large.hip", "dmpnn_optim.hip", "dmpnn_wgrad16.hip", "dmpnn_head.hip", "dmpnn_vd.hip", "dmpnn_attn.hip", "dmpnn_inputgrad.hip", "dmpnn_predict.hip"]
+           "dmpnn_gemm_p2.hip", "dmpnn_gemm_p3.hip", "dmpnn_gemm_p4.hip", "dmpnn_gemm_s1.hip", "dmpnn_rows16_drop.hip", "dmpnn_mega.hip", "dmpnn_mega16.hip", "dmpnn_mega16_lp.hip", "dmpnn_mega16_bwd.hip", "dmpnn_rows16.hip", "dmpnn_step16.hip", "dmpnn_bstep16.hip", "dmpnn_backward.hip", "dmpnn_molagg.hip", "dmpnn_collate.hip", "dmpnn_tiles_large.hip", "dmpnn_optim.hip", "dmpnn_wgrad16.hip", "dmpnn_head.hip", "dmpnn_vd.hip", "dmpnn_attn.hip", "dmpnn_inputgrad.hip", "dmpnn_predict.hip", "dmpnn_metrics.hip"]
 HEADERS = ["dmpnn_common.hpp", "dmpnn_spill_impl.hpp", "dmpnn_gemm_impl.hpp", "dmpnn_mega_impl.hpp", "dmpnn_mega16_impl.hpp", "dmpnn_mega16_bwd_impl.hpp", "dmpnn_rows16_impl.hpp", "dmpnn_seg16.hpp", "dmpnn_step16_impl.hpp", "dmpnn_head_kernels.hpp"]
 ABI_VERSION = 15
 PLAN_NOFFSETS = 15
@@ -40,6 +40,7 @@ EXPORTS = [
     "dmpnn_molagg_attn_ws_bytes", "dmpnn_molagg_attn_fwd", "dmpnn_molagg_attn_bwd",
     "dmpnn_backward_inputs", "dmpnn_backward_inputs_ws_bytes", "dmpnn_src_sum",
     "dmpnn_predict_head_ws_bytes", "dmpnn_predict_head_wsplit_bytes", "dmpnn_predict_head",
+    "dmpnn_metric_stats_doubles", "dmpnn_metric_stats_ws_bytes", "dmpnn_metric_stats", "dmpnn_validate_head_ws_bytes", "dmpnn_validate_head",
 ]
 
 ACT = {"none": 0, "relu": 1, "leakyrelu": 2, "prelu": 3, "tanh": 4, "elu": 5, "selu": 6}
@@ -192,6 +193,35 @@ class PredictArgs(C.Structure):
     ]
 
 
+METRIC = {"none": 0, "regression": 1, "binary": 2, "multiclass": 3}   # enum dmpnn_metric_kind
+METRIC_MAX_CLASSES = 16   # (DMPNN_METRIC_MAX_CLASSES)
+METRIC_HEADER = 4         # (DMPNN_METRIC_HEADER: doubles in front of the tasks)
+
+
+class MetricArgs(C.Structure):
+    """``dmpnn_metric_args``: one batch's per-task sums into the epoch's statistics (``dmpnn_metric_stats``)."""
+    _fields_ = [
+        ("kind", C.c_int32), ("n_mols", C.c_int64), ("n_tasks", C.c_int64),
+        ("n_classes", C.c_int32), ("group", C.c_int32), ("threshold", C.c_float),
+        ("preds", C.c_void_p), ("ld_p", C.c_int64),
+        ("targets", C.c_void_p), ("ld_t", C.c_int64),
+        ("lt_mask", C.c_void_p), ("gt_mask", C.c_void_p),
+        ("loss", C.c_void_p),
+        ("stats", C.c_void_p), ("stats_bytes", C.c_size_t),
+        ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+    ]
+
+
+class ValidateArgs(C.Structure):
+    """``dmpnn_validate_args``: the inference head, then the metric stage on its predictions (``dmpnn_validate_head``)."""
+    _fields_ = [
+        ("predict", PredictArgs),
+        ("metric_kind", C.c_int32), ("threshold", C.c_float),
+        ("metric_targets", C.c_void_p), ("ld_mt", C.c_int64),
+        ("stats", C.c_void_p), ("stats_bytes", C.c_size_t),
+    ]
+
+
 class TrainRouteInfo(C.Structure):
     _fields_ = [("plan_kind", C.c_int32), ("route", C.c_int32), ("keep_rows", C.c_int32), ("keep_bits", C.c_int32), ("lean", C.c_int32)]
 
@@ -250,7 +280,7 @@ def _stale() -> bool:
 
 
 # sources whose kernels must not spill: compiled with the resource remarks on, a kernel with scratch fails the build
-NO_SCRATCH = ("dmpnn_predict.hip",)
+NO_SCRATCH = ("dmpnn_predict.hip", "dmpnn_metrics.hip")
 
 
 def _check_no_scratch(src: str, remarks: str, verbose: bool) -> None:
@@ -386,7 +416,8 @@ def load() -> C.CDLL:
     size_t_fns = ("dmpnn_plan_bytes", "dmpnn_backward_ws_bytes", "dmpnn_linear_wgrad_ws_bytes", "dmpnn_forward_wsplit_bytes", "dmpnn_forward_spill_bytes",
                   "dmpnn_forward_keep_bits_bytes",
                   "dmpnn_molagg_ws_bytes", "dmpnn_linear16_wsplit_bytes", "dmpnn_head_ws_bytes", "dmpnn_clip_grad_ws_bytes", "dmpnn_forward_h0_bytes", "dmpnn_vd_ws_bytes",
-                  "dmpnn_molagg_attn_ws_bytes", "dmpnn_backward_inputs_ws_bytes", "dmpnn_predict_head_ws_bytes", "dmpnn_predict_head_wsplit_bytes")
+                  "dmpnn_molagg_attn_ws_bytes", "dmpnn_backward_inputs_ws_bytes", "dmpnn_predict_head_ws_bytes", "dmpnn_predict_head_wsplit_bytes",
+                  "dmpnn_metric_stats_doubles", "dmpnn_metric_stats_ws_bytes", "dmpnn_validate_head_ws_bytes")
     lib.dmpnn_linear16_wsplit_bytes.argtypes = [C.c_int64, C.c_int64]
     lib.dmpnn_linear16_ok.argtypes = [C.POINTER(GemmArgs)]
     lib.dmpnn_linear16_fwd.argtypes = [C.POINTER(GemmArgs), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
@@ -439,6 +470,11 @@ def load() -> C.CDLL:
     lib.dmpnn_predict_head_ws_bytes.argtypes = [C.POINTER(PredictArgs)]
     lib.dmpnn_predict_head_wsplit_bytes.argtypes = [C.POINTER(PredictArgs)]
     lib.dmpnn_predict_head.argtypes = [C.POINTER(PredictArgs), C.c_void_p, C.c_int64, C.c_void_p]
+    lib.dmpnn_metric_stats_doubles.argtypes = [C.c_int32, C.c_int64, C.c_int32]
+    lib.dmpnn_metric_stats_ws_bytes.argtypes = [C.POINTER(MetricArgs)]
+    lib.dmpnn_metric_stats.argtypes = [C.POINTER(MetricArgs), C.c_void_p]
+    lib.dmpnn_validate_head_ws_bytes.argtypes = [C.POINTER(ValidateArgs)]
+    lib.dmpnn_validate_head.argtypes = [C.POINTER(ValidateArgs), C.c_void_p, C.c_int64, C.c_void_p]
     lib.dmpnn_split_row_floats.argtypes = [C.c_int64]
     lib.dmpnn_split_row_floats.restype = C.c_int64
     lib.dmpnn_debug_timestamps.argtypes = [C.c_void_p]

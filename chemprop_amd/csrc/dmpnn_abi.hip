@@ -797,4 +797,18 @@ int dmpnn_forward(const dmpnn_fwd_args* a, void* stream) {
     return DMPNN_OK;
 }
 
+// the metric stage on its own, over any preds (dmpnn_metrics.hip; dmpnn_validate_head runs it behind the inference head)
+size_t dmpnn_metric_stats_doubles(int32_t kind, int64_t n_tasks, int32_t n_classes) {
+    const int per = metric_per_task(kind, n_classes);
+    if (per < 0 || n_tasks < 0 || n_tasks >= (int64_t(1) << 24)) return 0;
+    return DMPNN_METRIC_HEADER + (size_t)n_tasks * (size_t)per;
+}
+size_t dmpnn_metric_stats_ws_bytes(const dmpnn_metric_args* a) { return a ? metric_ws_bytes(*a) : 0; }
+int dmpnn_metric_stats(const dmpnn_metric_args* a, void* stream) {
+    DMPNN_CHECK_ARG(a != nullptr, "metric_stats: null args");
+    DMPNN_TRY(metric_check(*a));   // (every refusal in front of the count's reset: dmpnn_last_launch_count() stays as it was)
+    reset_launch_count();
+    return launch_metric_stats(*a, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -468,6 +468,13 @@ struct PredictTail {
 };
 int launch_predict_tail(const PredictTail& q, hipStream_t s);
 
+// The metric stage behind the inference head (dmpnn_metrics.hip; dmpnn.h "Epoch metric statistics"): a batch's per-task sums added
+// into the caller's double buffer — k_metric_cols | k_metric_confusion into the workspace's partials, then k_metric_finish.
+int metric_per_task(int kind, int n_classes);               // doubles per task (NONE: 0); -1: an unknown kind / n_classes out of range
+size_t metric_ws_bytes(const dmpnn_metric_args& a);         // the partials [n_row_blocks][n_tasks per_task] doubles
+int metric_check(const dmpnn_metric_args& a);               // every rule of dmpnn_metric_stats, no device work
+int launch_metric_stats(const dmpnn_metric_args& a, hipStream_t s);   // (checked arguments) n_mols == 0: nothing
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // The leading dimensions of a contraction call against the widths they carry (the C entries dmpnn_linear_fwd / dmpnn_linear16_fwd,

@@ -902,3 +902,71 @@ int dmpnn_predict_head(const dmpnn_predict_args* p, const float* Hv, int64_t ldh
 }
 
 }  // extern "C"
+
+// ---- one validation step: the inference head, then the metric stage (dmpnn_metrics.hip) on its preds ---------------------------------
+namespace {
+// the transforms that feed a metric kind (dmpnn.h); NONE goes behind every transform
+bool metric_kind_fits(int kind, int transform) {
+    switch (kind) {
+        case DMPNN_METRIC_NONE: return true;
+        case DMPNN_METRIC_REGRESSION:
+            return transform == DMPNN_PT_NONE || transform == DMPNN_PT_UNSCALE || transform == DMPNN_PT_MVE || transform == DMPNN_PT_EVIDENTIAL ||
+                   transform == DMPNN_PT_QUANTILE;
+        case DMPNN_METRIC_BINARY: return transform == DMPNN_PT_SIGMOID || transform == DMPNN_PT_DIRICHLET_BINARY;
+        case DMPNN_METRIC_MULTICLASS: return transform == DMPNN_PT_SOFTMAX || transform == DMPNN_PT_DIRICHLET_MULTICLASS;
+        default: return false;
+    }
+}
+// every rule of dmpnn_validate_head that is its own, and the stage's arguments into *m: the partials behind the head's layout in head.ws
+int validate_check(const dmpnn_validate_args* vp, dmpnn_metric_args* m) {
+    DMPNN_CHECK_ARG(vp != nullptr, "validate_head: null args");
+    const dmpnn_validate_args& v = *vp;
+    const dmpnn_predict_args& p = v.predict;
+    const dmpnn_head_args& h = p.head;
+    DMPNN_TRY(predict_check(&p));
+    DMPNN_CHECK_ARG(predict_sizes_ok(&p), "validate_head: bad sizes (d_h, n_mols, n_components)");
+    DMPNN_CHECK_ARG(h.targets && h.loss_out && p.preds, "validate_head: head.targets, head.loss_out and predict.preds are required");
+    DMPNN_CHECK_ARG(v.metric_kind >= DMPNN_METRIC_NONE && v.metric_kind <= DMPNN_METRIC_MULTICLASS, "validate_head: unknown metric_kind %d", (int)v.metric_kind);
+    DMPNN_CHECK_ARG(metric_kind_fits(v.metric_kind, p.transform), "validate_head: metric_kind %d does not go with transform %d (outputs per task, or a spectral head)",
+                    (int)v.metric_kind, (int)p.transform);
+    const int per = transform_per_task(p.transform, h.n_classes);
+    const int64_t n_out = h.dims[h.n_layers], t = n_out / per;
+    memset(m, 0, sizeof(*m));
+    m->kind = v.metric_kind; m->n_mols = h.n_mols; m->n_tasks = t; m->n_classes = h.n_classes; m->group = per; m->threshold = v.threshold;
+    m->preds = p.preds; m->ld_p = n_out;
+    m->targets = v.metric_targets ? v.metric_targets : h.targets; m->ld_t = v.metric_targets ? v.ld_mt : t;
+    m->lt_mask = h.lt_mask; m->gt_mask = h.gt_mask;
+    m->loss = h.loss_out; m->stats = v.stats; m->stats_bytes = v.stats_bytes;
+    // the stage's argument rules first (a stand-in for its workspace: that rule is the next one, on head.ws as a whole)
+    m->ws = m; m->ws_bytes = ~size_t(0);
+    DMPNN_TRY(metric_check(*m));
+    const size_t front = head_layout(h).total, need = front + metric_ws_bytes(*m);
+    if (!h.ws || h.ws_bytes < need) {
+        set_error("validate_head: workspace missing or too small (%zu < %zu bytes)", h.ws_bytes, need);
+        return DMPNN_ENOSPC;
+    }
+    m->ws = static_cast<unsigned char*>(h.ws) + front; m->ws_bytes = h.ws_bytes - front;
+    return DMPNN_OK;
+}
+}  // namespace
+
+extern "C" {
+
+size_t dmpnn_validate_head_ws_bytes(const dmpnn_validate_args* v) {
+    if (!v || !predict_sizes_ok(&v->predict)) return 0;
+    const dmpnn_head_args& h = v->predict.head;
+    const int per = transform_per_task(v->predict.transform, h.n_classes);
+    if (per < 1) return 0;
+    dmpnn_metric_args m{};
+    m.kind = v->metric_kind; m.n_mols = h.n_mols; m.n_tasks = h.dims[h.n_layers] / per; m.n_classes = h.n_classes;
+    return head_layout(h).total + metric_ws_bytes(m);
+}
+int dmpnn_validate_head(const dmpnn_validate_args* v, const float* Hv, int64_t ldhv, void* stream) {
+    dmpnn_metric_args m;
+    DMPNN_TRY(validate_check(v, &m));   // (every refusal of its own in front of the count's reset: dmpnn_last_launch_count() stays as it was)
+    reset_launch_count();
+    DMPNN_TRY(predict_core(v->predict, v->predict.head, Hv, ldhv, stream, HeadPre{false, false}));
+    return launch_metric_stats(m, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

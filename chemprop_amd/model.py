@@ -456,6 +456,33 @@ class MPNN(nn.Module):
             r = fused_predict(self, bmg, V_d, X_d)
             return self(bmg, V_d, X_d) if r is None else r.preds
 
+    def validate(self, bmg, targets: Tensor, stats, V_d: Optional[Tensor] = None, X_d: Optional[Tensor] = None, *,
+                 metric_targets: Optional[Tensor] = None, weights: Optional[Tensor] = None, lt_mask: Optional[Tensor] = None,
+                 gt_mask: Optional[Tensor] = None, fingerprint: bool = False):
+        """One validation step without autograd: the predictions, the criterion on the raw outputs (``val_loss``) and the batch's
+        metric sums added into ``stats`` (a :class:`~chemprop_amd.metrics.MetricStats`: :meth:`MetricStats.for_model`).  In eval mode
+        everything behind the block is ONE C call (:func:`chemprop_amd.predict.fused_validate`) where the inference head takes this
+        model and these inputs; otherwise the fingerprint is formed once, ``preds = predictor(Z)``, the loss is the criterion on
+        ``predictor.train_step(Z)`` and ``stats.update`` adds the sums.  ``metric_targets``: what the metrics compare the predictions
+        with where that is not ``targets`` (unscaled against scaled).  The bounds reach the statistics where they reach the criterion
+        (:func:`criterion_kind`).  Returns a :class:`~chemprop_amd.predict.PredictResult` (on the module path ``raw`` is
+        ``train_step``'s tensor as the predictor shapes it)."""
+        from .predict import PredictResult, fused_validate
+
+        with torch.no_grad():
+            r = fused_validate(self, bmg, V_d, X_d, targets=targets, stats=stats, metric_targets=metric_targets, weights=weights,
+                               lt_mask=lt_mask, gt_mask=gt_mask, fingerprint=fingerprint)
+            if r is not None:
+                return r
+            Z = self.fingerprint(bmg, V_d, X_d)
+            preds, raw = self.predictor(Z), self.predictor.train_step(Z)
+            l = criterion_loss(self.criterion, raw, targets, weights, lt_mask, gt_mask)
+            loss = torch.stack((l.float(), targets.isfinite().sum().float()))
+            bounded = criterion_kind(self.criterion)[1]
+            stats.update(preds, targets if metric_targets is None else metric_targets, lt_mask if bounded else None,
+                         gt_mask if bounded else None, loss=loss)
+            return PredictResult(preds, raw, Z if fingerprint else None, loss)
+
 
 class MulticomponentMPNN(MPNN):
     """``chemprop.models.MulticomponentMPNN`` (``models/multi.py``): a :class:`~chemprop_amd.nn.MulticomponentMessagePassing` block,

@@ -29,6 +29,9 @@ _GROUP = {"mve": 2, "evidential": 4, "quantile": 2}
 # the evidential-classification predictors (PredictSpec(model, dirichlet=True)) and the transform values beside the enum's
 _DIRICHLET_OF = (("BinaryDirichletFFN", "dirichlet_binary"), ("MulticlassDirichletFFN", "dirichlet_multiclass"))
 _BESIDE_ENUM = {"spectral": _lib.PT_SPECTRAL, "dirichlet_binary": _lib.PT_DIRICHLET_BINARY, "dirichlet_multiclass": _lib.PT_DIRICHLET_MULTICLASS}
+# the metric statistics a transform's predictions feed (chemprop_amd.metrics: a key of _lib.METRIC)
+_METRIC_OF = {"none": "regression", "unscale": "regression", "mve": "regression", "evidential": "regression", "quantile": "regression",
+              "sigmoid": "binary", "dirichlet_binary": "binary", "softmax": "multiclass", "dirichlet_multiclass": "multiclass", "spectral": "none"}
 
 
 class PredictResult(NamedTuple):
@@ -124,17 +127,14 @@ def _grown(buf: Optional[Tensor], nbytes: int, dev) -> Tensor:
     return buf
 
 
-def fused_predict(model, bmg, V_d=None, X_d=None, *, targets: Optional[Tensor] = None, weights: Optional[Tensor] = None,
-                  lt_mask: Optional[Tensor] = None, gt_mask: Optional[Tensor] = None, fingerprint: bool = False) -> Optional[PredictResult]:
-    """``model(bmg, V_d, X_d)`` in eval mode: ``model.message_passing`` as it is, then ONE ``dmpnn_predict_head`` call for everything
-    behind it.  ``targets`` (with ``weights`` / ``lt_mask`` / ``gt_mask``): also the criterion on the raw outputs, chemprop's
-    ``val_loss``.  ``fingerprint=True``: also the predictor's input.  A multicomponent model takes lists, as its ``forward`` does.
+class _HeadCall:
+    """One call behind the block, filled but for the workspace: what :func:`fused_predict` and :func:`fused_validate` share."""
+    __slots__ = ("spec", "dev", "p", "Hv", "n_mols", "size_key", "wkey", "result", "keep")
 
-    ``None`` — the caller takes the module path — when the model is refused (:class:`PredictSpec`), is in training mode, grad mode
-    is on, the inputs are not on the device, a batch vector is not what the kernels read, or ``X_d`` / ``targets`` / ``weights``
-    are missing or misshapen.  The workspace and the split images of the hidden weights are kept per model: calls on one model belong
-    on one stream.  An in-place change of a hidden weight through ``.data`` does not advance its version: clear
-    ``model.__dict__["_dmpnn_predict_spec"]`` after one.  A Dirichlet model is asked for with ``PredictSpec``'s ``dirichlet=True``."""
+
+def _fill_call(model, bmg, V_d, X_d, p, targets, weights, lt_mask, gt_mask, fingerprint: bool) -> Optional[_HeadCall]:
+    """The gates of :func:`fused_predict`, the block's forward and ``p`` (a ``_lib.PredictArgs``) filled from the model and the inputs,
+    with fresh outputs; ``None``: the caller takes the module path."""
     spec = predict_spec(model, dirichlet=True)
     if spec is None or model.training or torch.is_grad_enabled():
         return None
@@ -173,8 +173,6 @@ def fused_predict(model, bmg, V_d=None, X_d=None, *, targets: Optional[Tensor] =
     if spec.n_components * d_out + spec.d_xd != int(spec.layers[0].in_features):
         return None
 
-    lib = _lib.load()
-    p = _lib.PredictArgs()
     h = p.head
     keep = spec.fill(h, nV, n_mols, d_out, batch, Hv if T is None else T, weights if T is not None else None, lt_mask if T is not None else None,
                      gt_mask if T is not None else None, lambda prm: None, bn_training=False, X_d=Xd)
@@ -192,26 +190,94 @@ def fused_predict(model, bmg, V_d=None, X_d=None, *, targets: Optional[Tensor] =
     else:
         loss = torch.empty(2, dtype=torch.float32, device=dev)
         h.loss_out = loss.data_ptr()
+        keep.append(T)
     if fingerprint:
         fp = torch.empty(n_mols, int(h.dims[0]), dtype=torch.float32, device=dev)
         p.fingerprint, p.ld_fp = fp.data_ptr(), fp.stride(0)
-    size_key = (nV if spec.att is not None else 0, n_mols, d_out, Xd is not None)
-    sizes = spec._sizes.get(size_key)
+    c = _HeadCall()
+    keep.append(batch)
+    c.spec, c.dev, c.p, c.Hv, c.n_mols, c.keep = spec, dev, p, Hv, n_mols, keep
+    c.size_key = (nV if spec.att is not None else 0, n_mols, d_out, Xd is not None)
+    c.wkey = (spec.hidden_key(), d_out, Xd is not None)
+    c.result = PredictResult(preds, raw, fp, loss)
+    return c
+
+
+def _run_call(c: _HeadCall, entry, arg, what: str, ws_bytes, size_tag: tuple = ()) -> PredictResult:
+    """The per-model workspace and split images behind ``c.p``, then ``entry(arg, H_v, ld, stream)``; ``ws_bytes()``: what the entry
+    asks of ``head.ws`` (cached per shape under ``c.size_key + size_tag``)."""
+    spec, p, dev, lib = c.spec, c.p, c.dev, _lib.load()
+    h = p.head
+    key = c.size_key + size_tag
+    sizes = spec._sizes.get(key)
     if sizes is None:
         if len(spec._sizes) > 256:
             spec._sizes.clear()
-        sizes = spec._sizes[size_key] = (int(lib.dmpnn_predict_head_ws_bytes(C.byref(p))), int(lib.dmpnn_predict_head_wsplit_bytes(C.byref(p))))
+        sizes = spec._sizes[key] = (int(ws_bytes()), int(lib.dmpnn_predict_head_wsplit_bytes(C.byref(p))))
     spec._ws = _grown(spec._ws, sizes[0], dev)
     h.ws, h.ws_bytes = spec._ws.data_ptr(), spec._ws.numel()
-    wkey = (spec.hidden_key(), d_out, Xd is not None)
     if sizes[1]:
         if spec._wsplit is None or spec._wsplit.device != dev or spec._wsplit.numel() < sizes[1]:
             spec._wsplit, spec._wsplit_key = _grown(None, sizes[1], dev), None
         p.wsplit, p.wsplit_bytes = spec._wsplit.data_ptr(), spec._wsplit.numel()
-        p.wsplit_ready = 1 if spec._wsplit_key == wkey else 0
+        p.wsplit_ready = 1 if spec._wsplit_key == c.wkey else 0
     with engine._OnDevice(dev):
-        _lib.check(lib.dmpnn_predict_head(C.byref(p), Hv.data_ptr(), Hv.stride(0), engine._stream_ptr(dev)), "dmpnn_predict_head")
+        _lib.check(entry(C.byref(arg), c.Hv.data_ptr(), c.Hv.stride(0), engine._stream_ptr(dev)), what)
     if sizes[1]:
-        spec._wsplit_key = wkey
-    del keep
-    return PredictResult(preds, raw, fp, loss)
+        spec._wsplit_key = c.wkey
+    c.keep = None
+    return c.result
+
+
+def fused_predict(model, bmg, V_d=None, X_d=None, *, targets: Optional[Tensor] = None, weights: Optional[Tensor] = None,
+                  lt_mask: Optional[Tensor] = None, gt_mask: Optional[Tensor] = None, fingerprint: bool = False) -> Optional[PredictResult]:
+    """``model(bmg, V_d, X_d)`` in eval mode: ``model.message_passing`` as it is, then ONE ``dmpnn_predict_head`` call for everything
+    behind it.  ``targets`` (with ``weights`` / ``lt_mask`` / ``gt_mask``): also the criterion on the raw outputs, chemprop's
+    ``val_loss``.  ``fingerprint=True``: also the predictor's input.  A multicomponent model takes lists, as its ``forward`` does.
+
+    ``None`` — the caller takes the module path — when the model is refused (:class:`PredictSpec`), is in training mode, grad mode
+    is on, the inputs are not on the device, a batch vector is not what the kernels read, or ``X_d`` / ``targets`` / ``weights``
+    are missing or misshapen.  The workspace and the split images of the hidden weights are kept per model: calls on one model belong
+    on one stream.  An in-place change of a hidden weight through ``.data`` does not advance its version: clear
+    ``model.__dict__["_dmpnn_predict_spec"]`` after one.  A Dirichlet model is asked for with ``PredictSpec``'s ``dirichlet=True``."""
+    p = _lib.PredictArgs()
+    c = _fill_call(model, bmg, V_d, X_d, p, targets, weights, lt_mask, gt_mask, fingerprint)
+    if c is None:
+        return None
+    lib = _lib.load()
+    return _run_call(c, lib.dmpnn_predict_head, p, "dmpnn_predict_head", lambda: lib.dmpnn_predict_head_ws_bytes(C.byref(p)))
+
+
+def fused_validate(model, bmg, V_d=None, X_d=None, *, targets: Tensor, stats, metric_targets: Optional[Tensor] = None,
+                   weights: Optional[Tensor] = None, lt_mask: Optional[Tensor] = None, gt_mask: Optional[Tensor] = None,
+                   fingerprint: bool = False) -> Optional[PredictResult]:
+    """One validation step behind the block as ONE ``dmpnn_validate_head`` call: :func:`fused_predict` with ``targets`` — the same
+    kernels, the same bits — and, behind it, the batch's metric sums added into ``stats`` (a
+    :class:`~chemprop_amd.metrics.MetricStats` on the model's device; at most two launches more).  ``metric_targets``: the targets the
+    metrics compare the predictions with where they differ from the criterion's (unscaled against scaled).  The bounds reach the
+    statistics where they reach the criterion (a bounded MSE / MAE).
+
+    ``None`` under :func:`fused_predict`'s conditions, for ``stats`` on another device and for misshapen ``metric_targets``;
+    ``ValueError`` for ``stats`` of another kind or shape than the model's (:meth:`MetricStats.for_model`)."""
+    if targets is None:
+        raise ValueError("fused_validate: a validation step has targets")
+    v = _lib.ValidateArgs()
+    c = _fill_call(model, bmg, V_d, X_d, v.predict, targets, weights, lt_mask, gt_mask, fingerprint)
+    if c is None or stats.device != c.dev:
+        return None
+    kind = _METRIC_OF[c.spec.transform]
+    fits = (kind, c.spec.n_tasks, c.spec.n_classes if kind == "multiclass" else 0)
+    if fits != (stats.kind, stats.n_tasks, stats.n_classes if kind == "multiclass" else 0):
+        raise ValueError(f"fused_validate: stats of kind / tasks / classes {(stats.kind, stats.n_tasks, stats.n_classes)}, the model's are {fits}")
+    if metric_targets is not None:
+        M = metric_targets if metric_targets.dtype == torch.float32 else metric_targets.float()
+        if M.device != c.dev or M.dim() != 2 or tuple(M.shape) != (c.n_mols, stats.n_tasks):
+            return None
+        if M.stride(1) != 1 or M.stride(0) < stats.n_tasks:
+            M = M.contiguous()
+        v.metric_targets, v.ld_mt = M.data_ptr(), max(int(M.stride(0)), stats.n_tasks)
+        c.keep.append(M)
+    v.metric_kind, v.threshold = _lib.METRIC[stats.kind], stats.threshold
+    v.stats, v.stats_bytes = stats.stats.data_ptr(), stats.stats.numel() * 8
+    lib = _lib.load()
+    return _run_call(c, lib.dmpnn_validate_head, v, "dmpnn_validate_head", lambda: lib.dmpnn_validate_head_ws_bytes(C.byref(v)), ("validate", stats.kind))

@@ -952,6 +952,76 @@ size_t dmpnn_predict_head_ws_bytes(const dmpnn_predict_args* p);
 size_t dmpnn_predict_head_wsplit_bytes(const dmpnn_predict_args* p);
 int    dmpnn_predict_head(const dmpnn_predict_args* p, const float* Hv, int64_t ldhv, void* stream);
 
+/* Epoch metric statistics (v15 growth: new entry points, every existing struct and call as it was).  Every metric a validation epoch
+ * reports — MSE / RMSE / MAE / R2 and their bounded forms, binary accuracy / F1 / MCC, multiclass accuracy / MCC, the epoch's val_loss —
+ * is a function of a few per-task SUMS over the (molecule, task) pairs with a finite target, and sums add across batches.  This stage
+ * adds one batch's sums into a persistent device buffer `stats` of doubles; the epoch ends with ONE copy of it to the host.
+ *
+ * stats = header[4] | task 0 | task 1 | ... (dmpnn_metric_stats_doubles() doubles; the caller zeroes it at the start of an epoch):
+ *   header: [0] += loss[0] loss[1] and [1] += loss[1] — `loss` is the [loss, n_finite] pair a criterion wrote on the same stream
+ *           (dmpnn_predict_head's loss_out), read by the stage's last launch; skipped when loss == NULL or loss[1] is not > 0, so the
+ *           epoch's val_loss = stats[0] / stats[1] is the count-weighted mean over batches; [2] += 1 (calls); [3] += n_mols.
+ *   DMPNN_METRIC_NONE: the header alone.
+ *   DMPNN_METRIC_REGRESSION, 8 doubles per task: with m = target finite, e = p - t (p and t converted to double first), e_b = e but 0
+ *           where (lt_mask and p < t) or (gt_mask and p > t) — BoundedMixin (nn/metrics.py:157-163), restated — the sums over m of
+ *           1, e^2, |e|, t, t^2, e_b^2, |e_b|, and one reserved slot that is written as 0.  p = preds[i][j group]: element 0 of task
+ *           j's group (group 1: plain / unscaled, 2: MVE / quantile, 4: evidential).
+ *   DMPNN_METRIC_BINARY, 8 doubles per task: n, TP, FP, TN, FN and three reserved slots (written as 0).  Predicted class: p > threshold
+ *           (strictly: torchmetrics' convention, restated); positive target: t > 0.5.  p = preds[i][j group] (group 1: sigmoid; 2:
+ *           DMPNN_PT_DIRICHLET_BINARY, whose column 0 is p_1).
+ *   DMPNN_METRIC_MULTICLASS, n_classes^2 doubles per task: the confusion counts [target class][argmax_k preds[i][j n_classes + k]];
+ *           argmax takes the lowest index among equal maxima; a finite target is truncated to int, one outside [0, n_classes) is
+ *           skipped like a NaN one.  2 <= n_classes <= DMPNN_METRIC_MAX_CLASSES, group is ignored.
+ * Declared deviation — restated from chemprop 2.3.1 and not run against it: the statistics are UNWEIGHTED (validation and test run
+ * with unit weights in the reference); head.weights and task_weights go into val_loss only.
+ *
+ * Two launches at most: a column reduction (row blocks of 128 molecules x column blocks of tasks; each leaves its partial sums in ws
+ * [n_row_blocks][n_tasks per_task] doubles) and a finish that adds the partials in block order in double — exactly one thread performs
+ * stats[k] += batch_sum for each slot, no floating-point atomics: the buffer after a call is bitwise reproducible for the same inputs
+ * and the same starting contents.  DMPNN_METRIC_NONE is the finish alone.  n_mols == 0 launches nothing and leaves stats as it was.
+ * DMPNN_EINVAL before any device work: an unknown kind; n_mols or n_tasks < 0; n_classes outside 2..DMPNN_METRIC_MAX_CLASSES
+ * (multiclass); group outside {1, 2, 4}; a threshold that is not finite (binary); NULL preds / targets (kind != NONE) or stats; ld_p
+ * below n_tasks group (multiclass: n_tasks n_classes) or ld_t below n_tasks; stats not 8-byte aligned; stats_bytes below 8
+ * dmpnn_metric_stats_doubles().  DMPNN_ENOSPC: ws missing (where bytes are needed) or below dmpnn_metric_stats_ws_bytes(). */
+enum dmpnn_metric_kind { DMPNN_METRIC_NONE = 0, DMPNN_METRIC_REGRESSION, DMPNN_METRIC_BINARY, DMPNN_METRIC_MULTICLASS };
+#define DMPNN_METRIC_MAX_CLASSES 16
+#define DMPNN_METRIC_HEADER 4              /* doubles in front of the tasks */
+typedef struct dmpnn_metric_args {
+    int32_t kind;                          /* enum dmpnn_metric_kind */
+    int64_t n_mols, n_tasks;
+    int32_t n_classes, group;              /* multiclass: classes per task; regression / binary: preds elements per task (1 | 2 | 4) */
+    float threshold;                       /* binary: predicted class = p > threshold */
+    const float* preds; int64_t ld_p;      /* [n_mols, n_tasks, group | n_classes], rows of ld_p floats */
+    const float* targets; int64_t ld_t;    /* [n_mols, n_tasks], NaN = missing, rows of ld_t floats */
+    const unsigned char* lt_mask; const unsigned char* gt_mask;   /* regression: [n_mols, n_tasks] bytes or NULL */
+    const float* loss;                     /* device [loss, n_finite] of this batch or NULL */
+    double* stats; size_t stats_bytes;     /* device, in / out */
+    void* ws; size_t ws_bytes;             /* the row blocks' partials */
+} dmpnn_metric_args;
+size_t dmpnn_metric_stats_doubles(int32_t kind, int64_t n_tasks, int32_t n_classes);   /* 0: an unknown kind / bad sizes */
+size_t dmpnn_metric_stats_ws_bytes(const dmpnn_metric_args* a);
+int    dmpnn_metric_stats(const dmpnn_metric_args* a, void* stream);
+
+/* One validation step behind the block as one call: predict_core exactly as dmpnn_predict_head runs it (same kernels, same bits), then
+ * the stage above on predict.preds with loss = predict.head.loss_out — dmpnn_predict_head's launches plus at most two.  The stage's
+ * partials live behind the head's layout in predict.head.ws: dmpnn_validate_head_ws_bytes() = dmpnn_predict_head_ws_bytes() + the
+ * stage's.  n_tasks = n_out / (the transform's outputs per task), group = those outputs, n_classes = predict.head.n_classes; the
+ * bounds are predict.head.lt_mask / gt_mask.  DMPNN_EINVAL before any device work (dmpnn_last_launch_count() as it was): whatever
+ * dmpnn_predict_head refuses; no predict.head.targets, predict.head.loss_out or predict.preds; a kind the transform does not feed —
+ * REGRESSION wants NONE / UNSCALE / MVE / EVIDENTIAL / QUANTILE, BINARY wants SIGMOID / DIRICHLET_BINARY, MULTICLASS wants SOFTMAX /
+ * DIRICHLET_MULTICLASS with 2 <= n_classes <= DMPNN_METRIC_MAX_CLASSES, DMPNN_PT_SPECTRAL takes DMPNN_METRIC_NONE alone; ld_mt below
+ * n_tasks; stats_bytes too small.  A workspace that is too small: DMPNN_ENOSPC.  n_mols == 0 launches nothing. */
+typedef struct dmpnn_validate_args {
+    dmpnn_predict_args predict;            /* as dmpnn_predict_head reads it */
+    int32_t metric_kind;                   /* enum dmpnn_metric_kind */
+    float threshold;                       /* DMPNN_METRIC_BINARY */
+    const float* metric_targets; int64_t ld_mt;   /* [n_mols, n_tasks] the targets the metrics compare with, or NULL: predict.head.targets
+                                              (a caller whose criterion's targets are scaled while the metrics' are not) */
+    double* stats; size_t stats_bytes;
+} dmpnn_validate_args;
+size_t dmpnn_validate_head_ws_bytes(const dmpnn_validate_args* v);
+int    dmpnn_validate_head(const dmpnn_validate_args* v, const float* Hv, int64_t ldhv, void* stream);
+
 /* One training step of models/model.py:148-161 with torch.optim.Adam (model.py:208-231), every kernel enqueued by ONE call:
  * K0 (dmpnn_prepare_with_batch into bwd.f.plan unless plan_ready) -> dmpnn_forward(&bwd.f) (DMPNN_F_KEEP) -> dmpnn_head on
  * bwd.f.out (head.gHv must be bwd.gout) -> dmpnn_backward(&bwd) -> dmpnn_adam_step over the flat buffers (n_params == 0: no
