@@ -423,9 +423,10 @@ def hip_mpnn_class():
                 if self.training:
                     # everything behind the block as ONE autograd node on the head kernels where they implement this model
                     # (chemprop_amd.model.head_loss: aggregation, batch norm, descriptors, predictor, criterion + their backward in one call)
-                    from .model import criterion_kind, head_loss
+                    from .heads import criterion_bounded
+                    from .model import head_loss
 
-                    bounded = criterion_kind(self.criterion)[1]
+                    bounded = criterion_bounded(self.criterion)
                     loss = head_loss(self, self.message_passing(bmg, V_d), [b.batch for b in bmg] if multi else bmg.batch, n_batch, targets, weights,
                                      lt_mask if bounded else None, gt_mask if bounded else None,
                                      X_d=None if X_d is None else self.X_d_transform(X_d))

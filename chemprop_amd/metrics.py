@@ -28,6 +28,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from .heads import predictor_row
 
 KINDS = tuple(_lib.METRIC)
 HEADER = _lib.METRIC_HEADER
@@ -46,17 +47,12 @@ def per_task(kind: str, n_classes: int = 0) -> int:
 
 def kind_of_model(model) -> tuple:
     """``(kind, n_tasks, n_classes)`` of a model's predictor, told from its class (this package's mirrors and the reference's, by MRO
-    name — the table :class:`~chemprop_amd.predict.PredictSpec` reads its transform from)."""
-    from .model import _mro_names
-    from .predict import _DIRICHLET_OF, _METRIC_OF, _TRANSFORM_OF
-
+    name — its row of ``heads.PREDICTORS``, which :class:`~chemprop_amd.predict.PredictSpec` reads its transform from)."""
     pred = model.predictor
-    names = _mro_names(pred)
-    tr = next((t for cls, t in _DIRICHLET_OF if cls in names), None) or next((t for cls, t in _TRANSFORM_OF if cls in names), None)
-    if tr is None:
+    row = predictor_row(pred)
+    if row is None:
         raise NotImplementedError(f"a predictor of a known class (got {type(pred).__name__})")
-    kind = _METRIC_OF[tr]
-    return kind, int(pred.n_tasks), int(pred.n_classes) if kind == "multiclass" else 0
+    return row.metric, int(pred.n_tasks), int(pred.n_classes) if row.metric == "multiclass" else 0
 
 
 def _zero_safe(num: np.ndarray, den: np.ndarray) -> np.ndarray:

@@ -24,381 +24,17 @@ from torch import Tensor, nn
 from . import _lib, engine
 from .agg import MODES, Aggregation, NormAggregation, note_batch
 from .distributed import GradSync, force_collective
-from .ffn import MLP, mlp_blocks
+from .ffn import mlp_blocks
+from .heads import (BCE, CE, CRITERIA, CRITERION, MAE, MSE, MVE, NOT_BUILT_IN, ONE_VALUE_PER_TASK, SID, UNKNOWN_CRITERION,  # noqa: F401
+                    BinaryClassificationFFN, BinaryDirichletFFN, BinaryMCC, Dirichlet, Evidential, EvidentialFFN, MulticlassClassificationFFN,
+                    MulticlassDirichletFFN, MveFFN, Quantile, QuantileFFN, RegressionFFN, SpectralFFN, Wasserstein, _mro_names,
+                    criterion_bounded, criterion_kind, criterion_loss, masked_loss, predictor_row, spectral_activation_of)
 from .nn import BondMessagePassing, MulticomponentMessagePassing, classify_activation
 from .data import merge_components
 from .optim import CLIP_MODES, FlatAdam, bias_corrections
 
 __all__ = ["MSE", "MAE", "BCE", "CE", "MVE", "Evidential", "Quantile", "RegressionFFN", "BinaryClassificationFFN", "MulticlassClassificationFFN", "MveFFN", "EvidentialFFN", "QuantileFFN",
            "Dirichlet", "BinaryDirichletFFN", "MulticlassDirichletFFN", "SID", "Wasserstein", "SpectralFFN", "BinaryMCC", "MPNN", "MulticomponentMPNN", "FusedTrainer", "masked_loss"]
-
-
-def masked_loss(preds: Tensor, targets: Tensor, weights: Optional[Tensor] = None, task_weights: Optional[Tensor] = None,
-                lt_mask: Optional[Tensor] = None, gt_mask: Optional[Tensor] = None, kind: str = "mse", v_kl: float = 0.2, eps: float = 1e-8,
-                alpha: float = 0.1, threshold: Optional[float] = None) -> Tensor:
-    """``ChempropMetric.update`` + ``compute`` on one batch (``nn/metrics.py:78-127``) with the masking of
-    ``MPNN.training_step`` (``models/model.py:152-156``): torch ops, differentiable — the module path's criterion."""
-    mask = targets.isfinite()
-    targets = targets.nan_to_num(nan=0.0)
-    w = torch.ones(targets.shape[0], dtype=torch.float, device=targets.device) if weights is None else weights
-    tw = 1.0 if task_weights is None else task_weights.view(1, -1)
-    if kind in ("bce", "ce", "mve", "evidential", "quantile", "dirichlet", "sid", "wasserstein", "mcc"):
-        lt_mask = gt_mask = None     # (only the Bounded* criteria apply the masks: metrics.py:157-177)
-    if kind == "mcc":                # preds [b, t] logits (BinaryClassificationFFN.train_step): BinaryMCCLoss as include/dmpnn.h restates it
-        a = w.view(-1, 1) * mask     # (the sigmoid always; 1 - p as sigmoid(-x); the mean over ALL tasks: no finite target anywhere is loss 1)
-        p, q = preds.sigmoid(), (-preds).sigmoid()
-        TP, FP = (a * targets * p).sum(0), (a * (1 - targets) * p).sum(0)
-        TN, FN = (a * (1 - targets) * q).sum(0), (a * targets * q).sum(0)
-        mcc = (TP * TN - FP * FN) / ((TP + FP) * (TP + FN) * (TN + FP) * (TN + FN) + 1e-8).sqrt()
-        return 1 - (mcc * tw).sum() / targets.shape[1]
-    if kind in ("sid", "wasserstein"):   # preds [b, t] = p (SpectralFFN.train_step): renormalised over the finite targets (include/dmpnn.h)
-        c = preds if threshold is None else preds.clamp(min=threshold)
-        q = c / (c * mask).sum(1, keepdim=True)
-        if kind == "sid":            # (masked q and y filled with 1: a zero term)
-            one = torch.ones_like(q)
-            qm, ym = torch.where(mask, q, one), torch.where(mask, targets, one)
-            L = qm * (qm / ym).log() + ym * (ym / qm).log()
-        else:                        # (the running sum of q includes the masked columns; only y is 0 there)
-            L = (targets.cumsum(1) - q.cumsum(1)).abs()
-        return (L * w.view(-1, 1) * tw * mask).sum() / mask.sum()
-    if kind == "dirichlet":          # preds [b, t, c] = alpha (the Dirichlet predictors' train_step), targets [b, t] class indices (DirichletLoss)
-        y = torch.nn.functional.one_hot(targets.long(), preds.shape[-1]).to(preds.dtype)
-        S = preds.sum(-1, keepdim=True)
-        p = preds / S
-        L_mse = ((y - p) ** 2).sum(-1) + (p * (1 - p) / (S + 1)).sum(-1)
-        a_t = y + (1 - y) * preds    # (1 at the true class: the KL term leaves its evidence alone)
-        S_t = a_t.sum(-1, keepdim=True)
-        L_kl = (torch.lgamma(S_t).squeeze(-1) - torch.lgamma(a_t).sum(-1) - math.lgamma(preds.shape[-1])
-                + ((a_t - 1) * (torch.digamma(a_t) - torch.digamma(S_t))).sum(-1))
-        return ((L_mse + v_kl * L_kl) * w.view(-1, 1) * tw * mask).sum() / mask.sum()
-    if kind in ("mve", "evidential", "quantile"):   # preds [b, t, 2 | 4]: what MveFFN / EvidentialFFN / QuantileFFN.train_step stack (predictors.py:173-232)
-        if kind == "mve":               # MVELoss, metrics.py:203-219
-            mean, var = torch.unbind(preds, dim=-1)
-            L = (mean - targets) ** 2 / (2 * var) + (2 * torch.pi * var).log() / 2
-        elif kind == "quantile":        # QuantileLoss, metrics.py:589-610
-            mean, interval = torch.unbind(preds, dim=-1)
-            bounds = torch.tensor([-0.5, 0.5], device=preds.device).view(-1, 1, 1)
-            tau = torch.tensor([[alpha / 2, 1 - alpha / 2], [alpha / 2 - 1, -alpha / 2]], device=preds.device).view(2, 2, 1, 1)
-            L = (tau * (targets - (mean + bounds * interval))).amax(0).sum(0)
-        else:                           # EvidentialLoss, metrics.py:222-262
-            mean, v, alpha, beta = torch.unbind(preds, dim=-1)
-            residuals = targets - mean
-            two_b_lambda = 2 * beta * (1 + v)
-            L_nll = (0.5 * (torch.pi / v).log() - alpha * two_b_lambda.log() + (alpha + 0.5) * torch.log(v * residuals**2 + two_b_lambda)
-                     + torch.lgamma(alpha) - torch.lgamma(alpha + 0.5))
-            L = L_nll + v_kl * ((2 * v + alpha) * residuals.abs() - eps)
-        return (L * w.view(-1, 1) * tw * mask).sum() / mask.sum()
-    if kind == "ce":                 # preds [b, t, c] logits, targets [b, t] class indices (metrics.py:298-304)
-        L = torch.nn.functional.cross_entropy(preds.transpose(1, 2), targets.long(), reduction="none")
-        return (L * w.view(-1, 1) * tw * mask).sum() / mask.sum()
-    if lt_mask is not None:
-        preds = torch.where((preds < targets) & lt_mask, targets, preds)
-    if gt_mask is not None:
-        preds = torch.where((preds > targets) & gt_mask, targets, preds)
-    if kind == "bce":     # nn/metrics.py:292-295 (on logits: the classification predictor's train_step, predictors.py:246-247)
-        L = torch.nn.functional.binary_cross_entropy_with_logits(preds, targets, reduction="none")
-    else:
-        L = (preds - targets).abs() if kind == "mae" else torch.nn.functional.mse_loss(preds, targets, reduction="none")
-    return (L * w.view(-1, 1) * tw * mask).sum() / mask.sum()
-
-
-def criterion_loss(c, preds: Tensor, targets: Tensor, weights=None, lt_mask=None, gt_mask=None) -> Tensor:
-    """:func:`masked_loss` with what the criterion ``c`` carries — this package's or the reference's (``task_weights``, ``v_kl``, ...)."""
-    thr = getattr(c, "threshold", None)
-    return masked_loss(preds, targets, weights, getattr(c, "task_weights", None), lt_mask, gt_mask, getattr(c, "kind", "mse"),
-                       float(getattr(c, "v_kl", 0.2)), float(getattr(c, "eps", 1e-8)), float(getattr(c, "alpha", 0.1)),
-                       None if thr is None else float(thr))
-
-
-class MSE(nn.Module):
-    """The criterion's state (``nn/metrics.py:60-76``: a ``task_weights`` buffer of shape ``[1, t]``) and its batch value; only the
-    kinds ``mse`` / ``mae`` apply ``lt_mask`` / ``gt_mask`` (:func:`masked_loss`)."""
-
-    kind = "mse"
-
-    def __init__(self, task_weights=1.0):
-        super().__init__()
-        self.register_buffer("task_weights", torch.as_tensor(task_weights, dtype=torch.float).view(1, -1))
-
-    def forward(self, preds, targets, mask=None, weights=None, lt_mask=None, gt_mask=None):
-        t = targets if mask is None else torch.where(mask, targets, torch.full_like(targets, float("nan")))
-        return criterion_loss(self, preds, t, weights, lt_mask, gt_mask)
-
-
-class MAE(MSE):
-    kind = "mae"
-
-
-class BCE(MSE):
-    """``chemprop.nn.metrics.BCELoss`` (``metrics.py:292-295``): binary cross entropy on LOGITS; no bounds."""
-
-    kind = "bce"
-
-
-class RegressionFFN(nn.Module):
-    """``chemprop.nn.predictors.RegressionFFN`` (``predictors.py:101-169``): ``ffn = MLP.build(input_dim, n_tasks, hidden_dim,
-    n_layers, dropout, activation)``, criterion MSE, identity output transform while training."""
-
-    n_targets = 1   # (values per task, ``predictors.py:132``: the MLP is ``n_tasks * n_targets`` wide)
-    _default_criterion = MSE
-
-    def __init__(self, n_tasks: int = 1, input_dim: int = 300, hidden_dim: int = 300, n_layers: int = 1, dropout: float = 0.0,
-                 activation="relu", criterion: Optional[nn.Module] = None, task_weights: Optional[Tensor] = None):
-        super().__init__()
-        self.hparams = dict(n_tasks=n_tasks, input_dim=input_dim, hidden_dim=hidden_dim, n_layers=n_layers, dropout=dropout,
-                            activation=activation, cls=self.__class__)
-        self.ffn = MLP.build(input_dim, n_tasks * self.n_targets, hidden_dim, n_layers, dropout, activation)
-        self.criterion = criterion if criterion is not None else self._default_criterion(torch.ones(n_tasks) if task_weights is None else task_weights)
-        self.output_transform = nn.Identity()
-
-    @property
-    def input_dim(self) -> int:
-        return self.ffn.input_dim
-
-    @property
-    def output_dim(self) -> int:
-        return self.ffn.output_dim
-
-    @property
-    def n_tasks(self) -> int:
-        return self.output_dim // self.n_targets
-
-    def forward(self, Z: Tensor) -> Tensor:
-        return self.output_transform(self.ffn(Z))
-
-    train_step = forward
-
-
-class CE(MSE):
-    """``chemprop.nn.metrics.CrossEntropyLoss`` (``metrics.py:298-304``): ``preds [b, t, c]`` logits against class indices; no bounds."""
-
-    kind = "ce"
-
-
-class MVE(MSE):
-    """``chemprop.nn.metrics.MVELoss`` (``metrics.py:203-219``): ``preds [b, t, 2]`` = (mean, variance); no bounds."""
-
-    kind = "mve"
-
-
-class Evidential(MSE):
-    """``chemprop.nn.metrics.EvidentialLoss`` (``metrics.py:222-262``): ``preds [b, t, 4]`` = (mean, v, alpha, beta); no bounds."""
-
-    kind = "evidential"
-
-    def __init__(self, task_weights=1.0, v_kl: float = 0.2, eps: float = 1e-8):
-        super().__init__(task_weights)
-        self.v_kl, self.eps = v_kl, eps
-
-
-class Quantile(MSE):
-    """``chemprop.nn.metrics.QuantileLoss`` (``metrics.py:589-610``): ``preds [b, t, 2]`` = (mean, interval); no bounds."""
-
-    kind = "quantile"
-
-    def __init__(self, task_weights=1.0, alpha: float = 0.1):
-        super().__init__(task_weights)
-        self.alpha = alpha
-        # (the reference's buffers, metrics.py:594-600: the state dicts match)
-        self.register_buffer("bounds", torch.tensor([-1 / 2, 1 / 2]).view(-1, 1, 1))
-        self.register_buffer("tau", torch.tensor([[alpha / 2, 1 - alpha / 2], [alpha / 2 - 1, -alpha / 2]]).view(2, 2, 1, 1))
-
-
-class MveFFN(RegressionFFN):
-    """``chemprop.nn.predictors.MveFFN`` (``predictors.py:173-190``): an MLP ``2 n_tasks`` wide, chunked into means and raw variances
-    (``softplus``), stacked ``[b, t, 2]``; ``train_step`` is ``forward``.  (The output transform is the identity here, as the
-    reference's ``UnscaleTransform`` is while training.)"""
-
-    n_targets = 2
-    _default_criterion = MVE
-
-    def forward(self, Z: Tensor) -> Tensor:
-        mean, var = torch.chunk(self.ffn(Z), 2, 1)
-        return torch.stack((mean, torch.nn.functional.softplus(var)), dim=2)
-
-    train_step = forward
-
-
-class EvidentialFFN(RegressionFFN):
-    """``chemprop.nn.predictors.EvidentialFFN`` (``predictors.py:193-212``): ``4 n_tasks`` wide — mean | v | alpha | beta,
-    ``v = softplus``, ``alpha = softplus + 1``, ``beta = softplus``, stacked ``[b, t, 4]``."""
-
-    n_targets = 4
-    _default_criterion = Evidential
-
-    def forward(self, Z: Tensor) -> Tensor:
-        sp = torch.nn.functional.softplus
-        mean, v, alpha, beta = torch.chunk(self.ffn(Z), 4, 1)
-        return torch.stack((mean, sp(v), sp(alpha) + 1, sp(beta)), dim=2)
-
-    train_step = forward
-
-
-class QuantileFFN(RegressionFFN):
-    """``chemprop.nn.predictors.QuantileFFN`` (``predictors.py:215-232``): ``2 n_tasks`` wide — lower | upper bounds, stacked as
-    ``(mean, interval) [b, t, 2]``."""
-
-    n_targets = 2
-    _default_criterion = Quantile
-
-    def forward(self, Z: Tensor) -> Tensor:
-        lower, upper = torch.chunk(self.ffn(Z), 2, 1)
-        return torch.stack(((lower + upper) / 2, upper - lower), dim=2)
-
-    train_step = forward
-
-
-class MulticlassClassificationFFN(RegressionFFN):
-    """``chemprop.nn.predictors.MulticlassClassificationFFN`` (``predictors.py:271-314``): an MLP ``n_tasks * n_classes`` wide;
-    ``forward`` predicts class probabilities ``[b, t, c]`` (softmax), ``train_step`` hands the logits ``[b, t, c]`` to ``CrossEntropyLoss``."""
-
-    def __init__(self, n_classes: int, n_tasks: int = 1, input_dim: int = 300, hidden_dim: int = 300, n_layers: int = 1, dropout: float = 0.0,
-                 activation="relu", criterion: Optional[nn.Module] = None, task_weights: Optional[Tensor] = None):
-        super().__init__(n_tasks * n_classes, input_dim, hidden_dim, n_layers, dropout, activation,
-                         criterion if criterion is not None else CE(torch.ones(n_tasks) if task_weights is None else task_weights))
-        self.n_classes = n_classes
-        # (predictors.py:271-314 records n_tasks AND n_classes; the base class saw their product — `cls(**hparams)` must rebuild this width)
-        self.hparams.update(n_tasks=n_tasks, n_classes=n_classes)
-
-    @property
-    def n_tasks(self) -> int:
-        return self.output_dim // (self.n_targets * self.n_classes)
-
-    def forward(self, Z: Tensor) -> Tensor:
-        return self.ffn(Z).reshape(Z.shape[0], -1, self.n_classes).softmax(-1)
-
-    def train_step(self, Z: Tensor) -> Tensor:
-        return self.ffn(Z).reshape(Z.shape[0], -1, self.n_classes)
-
-
-class BinaryClassificationFFN(RegressionFFN):
-    """``chemprop.nn.predictors.BinaryClassificationFFN`` (``predictors.py:235-247``): the same MLP; ``forward`` predicts
-    probabilities (``sigmoid``), ``train_step`` hands the raw logits to ``BCELoss``."""
-
-    _default_criterion = BCE
-
-    def forward(self, Z: Tensor) -> Tensor:
-        return self.ffn(Z).sigmoid()
-
-    def train_step(self, Z: Tensor) -> Tensor:
-        return self.ffn(Z)
-
-
-class Dirichlet(MSE):
-    """``chemprop.nn.metrics.DirichletLoss``: ``preds [b, t, c]`` = the Dirichlet parameters ``alpha`` against class indices — the
-    expected squared error under ``Dir(alpha)`` plus ``v_kl`` times ``KL(Dir(alpha~) || Dir(1))``; no bounds."""
-
-    kind = "dirichlet"
-
-    def __init__(self, task_weights=1.0, v_kl: float = 0.2):
-        super().__init__(task_weights)
-        self.v_kl = v_kl
-
-
-class BinaryDirichletFFN(RegressionFFN):
-    """``chemprop.nn.predictors.BinaryDirichletFFN``: an MLP ``2 n_tasks`` wide, column ``2 j + k`` the evidence of class ``k`` of task
-    ``j``; ``train_step`` hands ``alpha = softplus + 1`` as ``[b, t, 2]`` to ``DirichletLoss``, ``forward`` predicts
-    ``(p_1, 2 / S) [b, t, 2]``: the probability of class 1 and the uncertainty.  :meth:`MPNN.predict` on an eval-mode model runs that
-    ``forward`` inside the one-call inference head (``DMPNN_PT_DIRICHLET_BINARY``: :func:`chemprop_amd.predict.fused_predict`)."""
-
-    n_targets = 2
-    _default_criterion = Dirichlet
-
-    def train_step(self, Z: Tensor) -> Tensor:
-        return (torch.nn.functional.softplus(self.ffn(Z)) + 1).reshape(Z.shape[0], -1, 2)
-
-    def forward(self, Z: Tensor) -> Tensor:
-        alpha = self.train_step(Z)
-        S = alpha.sum(-1)
-        return torch.stack((alpha[..., 1] / S, 2 / S), dim=2)
-
-
-class MulticlassDirichletFFN(MulticlassClassificationFFN):
-    """``chemprop.nn.predictors.MulticlassDirichletFFN``: the multiclass MLP (``n_tasks * n_classes`` wide); ``train_step`` hands
-    ``alpha = softplus + 1`` as ``[b, t, c]`` to ``DirichletLoss``, ``forward`` predicts ``alpha / sum(alpha) [b, t, c]``.
-    :meth:`MPNN.predict` on an eval-mode model runs that ``forward`` inside the one-call inference head
-    (``DMPNN_PT_DIRICHLET_MULTICLASS``: :func:`chemprop_amd.predict.fused_predict`)."""
-
-    def __init__(self, n_classes: int, n_tasks: int = 1, input_dim: int = 300, hidden_dim: int = 300, n_layers: int = 1, dropout: float = 0.0,
-                 activation="relu", criterion: Optional[nn.Module] = None, task_weights: Optional[Tensor] = None):
-        super().__init__(n_classes, n_tasks, input_dim, hidden_dim, n_layers, dropout, activation,
-                         criterion if criterion is not None else Dirichlet(torch.ones(n_tasks) if task_weights is None else task_weights))
-
-    def train_step(self, Z: Tensor) -> Tensor:
-        return (torch.nn.functional.softplus(self.ffn(Z)) + 1).reshape(Z.shape[0], -1, self.n_classes)
-
-    def forward(self, Z: Tensor) -> Tensor:
-        alpha = self.train_step(Z)
-        return alpha / alpha.sum(-1, keepdim=True)
-
-
-class SID(MSE):
-    """``chemprop.nn.metrics.SID``: the spectral information divergence of ``preds [b, t]`` = ``p`` (``SpectralFFN``) against target
-    spectra, both renormalised over the finite targets; ``threshold``: a lower clamp of ``p`` (``None``: none); no bounds."""
-
-    kind = "sid"
-
-    def __init__(self, task_weights=1.0, threshold: Optional[float] = None):
-        super().__init__(task_weights)
-        self.threshold = threshold
-
-
-class Wasserstein(SID):
-    """``chemprop.nn.metrics.Wasserstein``: ``|cumsum(y) - cumsum(q)|`` per column, the masked columns' ``q`` inside the running sum."""
-
-    kind = "wasserstein"
-
-
-class BinaryMCC(MSE):
-    """``chemprop.nn.metrics.BinaryMCCLoss``: one minus the mean over the tasks of the soft Matthews correlation of ``sigmoid(preds)``
-    (``preds [b, t]``: the LOGITS of ``BinaryClassificationFFN.train_step``) against 0 / 1 targets, the four confusion sums taken over
-    the whole batch per task; no bounds.  The contract and its declared deviations: ``include/dmpnn.h``."""
-
-    kind = "mcc"
-
-
-class _Exp(nn.Module):
-    def forward(self, x: Tensor) -> Tensor:
-        return x.exp()
-
-
-class SpectralFFN(RegressionFFN):
-    """``chemprop.nn.predictors.SpectralFFN``: the MLP ``n_tasks`` wide, then ``a = softplus(x)`` (``spectral_activation="softplus"``) or
-    ``exp(x)`` (``"exp"``) and ``p = a / sum_j a``: a spectrum that sums to 1.  The activation is a child of ``ffn`` named
-    ``spectral_activation``, as in the reference — not a layer of the MLP; ``train_step`` is ``forward``."""
-
-    _default_criterion = SID
-
-    def __init__(self, n_tasks: int = 1, input_dim: int = 300, hidden_dim: int = 300, n_layers: int = 1, dropout: float = 0.0,
-                 activation="relu", criterion: Optional[nn.Module] = None, task_weights: Optional[Tensor] = None,
-                 spectral_activation: str = "softplus"):
-        super().__init__(n_tasks, input_dim, hidden_dim, n_layers, dropout, activation, criterion, task_weights)
-        if spectral_activation not in ("softplus", "exp"):
-            raise ValueError(f'spectral_activation must be "softplus" or "exp", got {spectral_activation!r}')
-        self.hparams.update(spectral_activation=spectral_activation)
-        self.ffn.add_module("spectral_activation", nn.Softplus() if spectral_activation == "softplus" else _Exp())
-
-    def forward(self, Z: Tensor) -> Tensor:
-        Y = self.ffn(Z)   # (mlp_forward runs the spectral_activation child last, as nn.Sequential does)
-        return Y / Y.sum(1, keepdim=True)
-
-    train_step = forward
-
-
-def _predictor_blocks(pred) -> list:
-    """The predictor's MLP blocks: the children of ``ffn`` but for a ``SpectralFFN``'s ``spectral_activation``."""
-    return mlp_blocks(pred.ffn)
-
-
-def spectral_activation_of(pred) -> Optional[str]:
-    """``"softplus" | "exp"`` of a ``SpectralFFN`` (this package's or the reference's, by its ``spectral_activation`` child), ``None``
-    for an activation the kernels do not have."""
-    act = getattr(pred.ffn, "spectral_activation", None)
-    if isinstance(act, nn.Softplus) and act.beta == 1 and act.threshold == 20:
-        return "softplus"
-    if act is not None and type(act).__name__.lstrip("_").lower() == "exp":
-        return "exp"
-    return None
 
 
 class MPNN(nn.Module):
@@ -465,7 +101,7 @@ class MPNN(nn.Module):
         model and these inputs; otherwise the fingerprint is formed once, ``preds = predictor(Z)``, the loss is the criterion on
         ``predictor.train_step(Z)`` and ``stats.update`` adds the sums.  ``metric_targets``: what the metrics compare the predictions
         with where that is not ``targets`` (unscaled against scaled).  The bounds reach the statistics where they reach the criterion
-        (:func:`criterion_kind`).  Returns a :class:`~chemprop_amd.predict.PredictResult` (on the module path ``raw`` is
+        (:func:`~chemprop_amd.heads.criterion_bounded`).  Returns a :class:`~chemprop_amd.predict.PredictResult` (on the module path ``raw`` is
         ``train_step``'s tensor as the predictor shapes it)."""
         from .predict import PredictResult, fused_validate
 
@@ -478,7 +114,7 @@ class MPNN(nn.Module):
             preds, raw = self.predictor(Z), self.predictor.train_step(Z)
             l = criterion_loss(self.criterion, raw, targets, weights, lt_mask, gt_mask)
             loss = torch.stack((l.float(), targets.isfinite().sum().float()))
-            bounded = criterion_kind(self.criterion)[1]
+            bounded = criterion_bounded(self.criterion)
             stats.update(preds, targets if metric_targets is None else metric_targets, lt_mask if bounded else None,
                          gt_mask if bounded else None, loss=loss)
             return PredictResult(preds, raw, Z if fingerprint else None, loss)
@@ -588,10 +224,6 @@ def fused_block(mp, rows_dropout: bool = False, vd_dropout: bool = False, atom_m
     return act, slope
 
 
-def _mro_names(obj) -> set:
-    return {c.__name__ for c in type(obj).__mro__}
-
-
 def aggregation_mode(agg) -> Optional[str]:
     """``"sum" | "mean" | "norm"`` for this package's aggregations (``.mode``) and for the reference's own classes / their HIP
     subclasses (``chemprop/nn/agg.py:66-113``, told by class name); ``None`` for anything else (attentive, custom)."""
@@ -603,42 +235,6 @@ def aggregation_mode(agg) -> Optional[str]:
         if cls in names:
             return m
     return None
-
-
-def criterion_kind(crit) -> tuple[Optional[str], bool]:
-    """``(kind, bounded)``: ``"mse" | "mae"`` and whether the criterion applies ``lt_mask`` / ``gt_mask``.  This package's criteria
-    carry ``.kind`` (bounded iff masks are handed over); the reference's are told by class name — ``MSE`` / ``MAE`` ignore the masks
-    (``nn/metrics.py:139-150``), ``BoundedMSE`` / ``BoundedMAE`` apply them (``:158-177``); RMSE, MVE, ... are not built in."""
-    kind = getattr(crit, "kind", None)
-    if kind in _lib.LOSS:
-        return kind, kind in ("mse", "mae")
-    names = _mro_names(crit)
-    if "RMSE" in names:
-        return None, False
-    if "MVELoss" in names:            # nn/metrics.py:203-219
-        return "mve", False
-    if "EvidentialLoss" in names:     # nn/metrics.py:222-262
-        return "evidential", False
-    if "QuantileLoss" in names and "PointQuantileLoss" not in names:   # nn/metrics.py:589-610 (the interval form; the point form takes one value per task)
-        return "quantile", False
-    if "MulticlassMCCLoss" in names:  # nn/metrics.py (reaches the logits through argmax and sum softmax alone: a zero gradient — torch ops)
-        return None, False
-    if "BinaryMCCLoss" in names:      # nn/metrics.py (binary classification on logits, --loss-function mcc)
-        return "mcc", False
-    if "BCELoss" in names:       # nn/metrics.py:292-295 (binary classification: chemprop's second task type)
-        return "bce", False
-    if "CrossEntropyLoss" in names:   # nn/metrics.py:298-304 (multiclass: logits [b, t, c] against class indices)
-        return "ce", False
-    if "DirichletLoss" in names:      # nn/metrics.py (evidential classification: alpha [b, t, c] against class indices)
-        return "dirichlet", False
-    if "Wasserstein" in names:        # nn/metrics.py (spectra: p [b, t] against target spectra)
-        return "wasserstein", False
-    if "SID" in names:
-        return "sid", False
-    for cls, k in (("MSE", "mse"), ("MAE", "mae")):
-        if cls in names:
-            return k, "BoundedMixin" in names
-    return None, False
 
 
 def _batch_vector_ok(batch: Optional[Tensor], n_atoms: int, dev) -> bool:
@@ -669,17 +265,10 @@ class HeadSpec:
     component: ``dmpnn_head_args.agg_mode = DMPNN_MOLAGG_ATTENTIVE`` with ``att_W`` / ``att_b``; ``att`` is that layer (``None``
     otherwise).  The default refuses it like any aggregation that is not sum / mean / norm.
 
-    A Dirichlet classification head is taken as exactly the pair (``BinaryDirichletFFN`` | ``MulticlassDirichletFFN``, ``DirichletLoss``)
-    — this package's mirrors or the reference's classes, by name: ``kind == "dirichlet"``, ``n_classes`` the predictor's (2 for the
-    binary one), ``n_tasks = n_out / n_classes``, ``v_kl`` handed over as ``evid_v_kl``.
-
-    A spectral head is taken as exactly the pair (``SpectralFFN``, ``SID`` | ``Wasserstein``), by name as well: ``kind == "sid" |
-    "wasserstein"``, one output per task; ``spectral_act`` (``"softplus" | "exp"``, read off the ``spectral_activation`` child of
-    ``ffn``, which is not one of ``layers``) and ``spectral_threshold`` (the criterion's ``threshold``, 0.0 for ``None``) travel in
-    ``dmpnn_head_args.spectral_act`` / ``spectral_threshold``.
-
-    A binary MCC head is taken as exactly the pair (``BinaryClassificationFFN``, ``BinaryMCCLoss``), by name: ``kind == "mcc"``,
-    ``n_classes == 0``, one output per task; any other predictor with it, and ``MulticlassMCCLoss``, are refused."""
+    Which predictor meets which criterion is the tables' word (``heads.CRITERIA`` / ``PREDICTORS``, the reference's classes by MRO name).
+    A Dirichlet head: ``n_classes`` the predictor's (2 for the binary one), ``v_kl`` handed over as ``evid_v_kl``.  A spectral head:
+    ``spectral_act`` (``"softplus" | "exp"``, off ``ffn.spectral_activation``, which is not one of ``layers``) and ``spectral_threshold``
+    (the criterion's ``threshold``, 0.0 for ``None``) travel in ``dmpnn_head_args``."""
 
     def __init__(self, model, ffn_dropout: bool = False, attentive: bool = False):
         agg, pred = model.agg, model.predictor
@@ -698,7 +287,7 @@ class HeadSpec:
             self.att = W
         elif mode is None:
             raise NotImplementedError(f"sum / mean / norm aggregation (got {type(agg).__name__})")
-        blocks = _predictor_blocks(pred)   # (a SpectralFFN's spectral_activation child is not a layer)
+        blocks = mlp_blocks(pred.ffn)   # (a SpectralFFN's spectral_activation child is not a layer)
         if len(blocks) > _lib.MAX_FFN_LAYERS:
             raise NotImplementedError(f"at most {_lib.MAX_FFN_LAYERS} predictor layers")
         f_act, f_slope = "none", 0.0
@@ -718,58 +307,37 @@ class HeadSpec:
         # (the reference's UnscaleTransform IS the identity in training mode, transforms.py:45-50: what a scaled regression run carries)
         if not (isinstance(pred.output_transform, nn.Identity) or "UnscaleTransform" in _mro_names(pred.output_transform)):
             raise NotImplementedError("the output transform is the identity while training (predictors.py:166-169)")
-        kind, self.bounded = criterion_kind(pred.criterion)
-        if "MulticlassMCCLoss" in _mro_names(pred.criterion):
-            raise NotImplementedError("MulticlassMCCLoss stays on torch ops: it reaches the logits through argmax counts and sum(softmax) "
-                                      "alone, so its gradient is zero and a kernel for it would train nothing (binary MCC is built in)")
+        kind, self.bounded = criterion_kind(pred.criterion)   # (the criterion's row and the predictor's, held against each other)
         if kind is None:
-            raise NotImplementedError("MSE / MAE criterion (bounded or not), BCE, cross entropy, MVE, evidential, quantile, Dirichlet, SID, "
-                                      "Wasserstein or binary MCC")
-        # evidential classification: exactly the pairs (BinaryDirichletFFN | MulticlassDirichletFFN, DirichletLoss), the predictors told
-        # by MRO name like the other reference classes; the class layout is cross entropy's, the binary head has two classes per task
-        # (its n_targets = 2 says the same thing: for the kernels it is a class dimension, not a chunked one)
-        names = _mro_names(pred)
-        dir_pred = "binary" if "BinaryDirichletFFN" in names else ("multiclass" if "MulticlassDirichletFFN" in names else None)
-        if (kind == "dirichlet") != (dir_pred is not None):
-            raise NotImplementedError("a Dirichlet criterion on a predictor that is neither BinaryDirichletFFN nor MulticlassDirichletFFN"
-                                      if kind == "dirichlet" else f"a Dirichlet predictor ({type(pred).__name__}) with a criterion "
-                                      f"other than DirichletLoss (got {kind})")
-        # spectra: exactly the pairs (SpectralFFN, SID | Wasserstein); the activation and the threshold travel in spectral_act / _threshold
-        spectral_pred = "SpectralFFN" in names
-        if (kind in ("sid", "wasserstein")) != spectral_pred:
-            raise NotImplementedError(f"a spectral criterion ({kind}) on a predictor that is not a SpectralFFN" if not spectral_pred else
-                                      f"a SpectralFFN with a criterion other than SID / Wasserstein (got {kind})")
-        # binary MCC: exactly the pair (BinaryClassificationFFN, BinaryMCCLoss) — logits in, one output per task, no class dimension
-        if kind == "mcc" and "BinaryClassificationFFN" not in names:
-            raise NotImplementedError(f"a binary MCC criterion on a predictor that is not a BinaryClassificationFFN (got {type(pred).__name__})")
+            raise NotImplementedError(next((why for n, why in NOT_BUILT_IN.items() if n in _mro_names(pred.criterion)), UNKNOWN_CRITERION))
+        crit, row = CRITERION[kind], predictor_row(pred)
+        name, fmt = getattr(row, "name", None), dict(kind=kind, cls=type(pred).__name__)
+        for c in CRITERIA:   # predictors that take one criterion alone: a Dirichlet head, then (table order) a SpectralFFN
+            if c.alone and (crit.predictors == c.predictors) != (name in c.predictors):
+                raise NotImplementedError((c.alone if name in c.predictors else crit.refusal).format(**fmt))
         self.spectral_act, self.spectral_threshold = None, 0.0
-        if spectral_pred:
+        if row is not None and row.transform == "spectral":
             self.spectral_act = spectral_activation_of(pred)
             if self.spectral_act is None:
-                raise NotImplementedError(f"a SpectralFFN whose spectral_activation is softplus or exp "
-                                          f"(got {getattr(pred.ffn, 'spectral_activation', None)!r})")
+                raise NotImplementedError(f"a SpectralFFN whose spectral_activation is softplus or exp (got {getattr(pred.ffn, 'spectral_activation', None)!r})")
             thr = getattr(pred.criterion, "threshold", None)
             self.spectral_threshold = 0.0 if thr is None else float(thr)
             if not (math.isfinite(self.spectral_threshold) and self.spectral_threshold >= 0):
                 raise NotImplementedError(f"a spectral criterion's threshold is None or a finite number >= 0 (got {thr!r})")
-        # values per task (predictors.py: n_targets): 1, or — round 6 — the mean-variance / evidential pairs of predictor and criterion
-        # (MveFFN + MVELoss: 2, EvidentialFFN + EvidentialLoss: 4, QuantileFFN + QuantileLoss: 2; the predictors' transforms of the
-        # raw outputs live in the criterion kernel)
-        self.n_targets = 1 if dir_pred == "binary" else int(getattr(pred, "n_targets", 1))
-        want_targets = {"mve": 2, "evidential": 4, "quantile": 2}.get(kind, 1)
-        want_pred = {"mve": "MveFFN", "evidential": "EvidentialFFN", "quantile": "QuantileFFN"}.get(kind)
-        if self.n_targets != want_targets or (want_pred is not None and want_pred not in _mro_names(pred)):
-            raise NotImplementedError("one value per task, or MveFFN with MVELoss / EvidentialFFN with EvidentialLoss / QuantileFFN with QuantileLoss")
-        if want_targets > 1 and int(blocks[-1][-1].out_features) % want_targets:
+        # a criterion with predictors of its own (binary MCC, MVE / evidential / quantile); the binary Dirichlet head's two values are classes
+        if crit.predictors is not None and name not in crit.predictors:
+            raise NotImplementedError(crit.refusal.format(**fmt))
+        two_classes = row is not None and row.classes == 2
+        self.n_targets = 1 if two_classes else int(getattr(pred, "n_targets", 1))
+        if self.n_targets != crit.values:
+            raise NotImplementedError(ONE_VALUE_PER_TASK)
+        if crit.values > 1 and int(blocks[-1][-1].out_features) % crit.values:
             raise NotImplementedError("the output width must be n_tasks * n_targets")
-        self.v_kl, self.eps = float(getattr(pred.criterion, "v_kl", 0.2)), float(getattr(pred.criterion, "eps", 1e-8))
-        self.q_alpha = float(getattr(pred.criterion, "alpha", 0.1))
-        # multiclass (predictors.py:271-314): the output layer holds n_classes logits per task, the criterion is the cross entropy
-        # over them, or — a Dirichlet head — DirichletLoss; every other pairing of a class dimension and a criterion trains through torch ops
-        self.n_classes = 2 if dir_pred == "binary" else int(getattr(pred, "n_classes", 0) or 0)
-        if (kind in ("ce", "dirichlet")) != (self.n_classes >= 2):
+        self.v_kl, self.eps, self.q_alpha = (float(getattr(pred.criterion, n, d)) for n, d in (("v_kl", 0.2), ("eps", 1e-8), ("alpha", 0.1)))
+        self.n_classes = 2 if two_classes else int(getattr(pred, "n_classes", 0) or 0)
+        if crit.classes != (self.n_classes >= 2):
             raise NotImplementedError("a multiclass predictor (n_classes >= 2) with CrossEntropyLoss or DirichletLoss, or neither")
-        if kind in ("ce", "dirichlet") and int(blocks[-1][-1].out_features) % self.n_classes:
+        if crit.classes and int(blocks[-1][-1].out_features) % self.n_classes:
             raise NotImplementedError("the output width must be n_tasks * n_classes")
         self.agg_mode, self.agg_norm = (_lib.MOLAGG_ATTENTIVE if self.att is not None else MODES[mode]), float(getattr(agg, "norm", 1.0))
         self.f_act, self.f_slope, self.kind = f_act, f_slope, kind

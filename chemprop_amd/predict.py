@@ -19,19 +19,8 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib, engine
-from .model import HeadSpec, _batch_vector_ok, _component_batch, _head_spec_key, _mro_names
-
-# the predictor classes (this package's mirrors and the reference's, by MRO name: nn/predictors.py) and the output transform their
-# eval-mode forward applies; the specific classes first — every one of them derives from RegressionFFN
-_TRANSFORM_OF = (("SpectralFFN", "spectral"), ("MveFFN", "mve"), ("EvidentialFFN", "evidential"), ("QuantileFFN", "quantile"),
-                 ("MulticlassClassificationFFN", "softmax"), ("BinaryClassificationFFN", "sigmoid"), ("RegressionFFN", "unscale"))
-_GROUP = {"mve": 2, "evidential": 4, "quantile": 2}
-# the evidential-classification predictors (PredictSpec(model, dirichlet=True)) and the transform values beside the enum's
-_DIRICHLET_OF = (("BinaryDirichletFFN", "dirichlet_binary"), ("MulticlassDirichletFFN", "dirichlet_multiclass"))
-_BESIDE_ENUM = {"spectral": _lib.PT_SPECTRAL, "dirichlet_binary": _lib.PT_DIRICHLET_BINARY, "dirichlet_multiclass": _lib.PT_DIRICHLET_MULTICLASS}
-# the metric statistics a transform's predictions feed (chemprop_amd.metrics: a key of _lib.METRIC)
-_METRIC_OF = {"none": "regression", "unscale": "regression", "mve": "regression", "evidential": "regression", "quantile": "regression",
-              "sigmoid": "binary", "dirichlet_binary": "binary", "softmax": "multiclass", "dirichlet_multiclass": "multiclass", "spectral": "none"}
+from .heads import predictor_row
+from .model import HeadSpec, _batch_vector_ok, _component_batch, _head_spec_key
 
 
 class PredictResult(NamedTuple):
@@ -46,39 +35,27 @@ class PredictResult(NamedTuple):
 
 class PredictSpec(HeadSpec):
     """What ``dmpnn_predict_head`` needs to know of the model: :class:`~chemprop_amd.model.HeadSpec` with the predictor's dropout and
-    attentive aggregation allowed, plus the output transform (``transform``: a key of ``_lib.PREDICT_TRANSFORM``, ``"spectral"``,
-    ``"dirichlet_binary"`` or ``"dirichlet_multiclass"``, told from the predictor's class) and the ``UnscaleTransform`` behind it
-    (``unscale``: the module, or ``None`` for ``nn.Identity``).  Raises ``NotImplementedError`` for what the inference head does not
-    take.  ``dirichlet=True`` also takes the two pairs ``HeadSpec`` takes for training — (``BinaryDirichletFFN`` |
-    ``MulticlassDirichletFFN``, ``DirichletLoss``), mirrors or reference classes by MRO name — with an identity output transform:
+    attentive aggregation allowed, plus the predictor's row of ``heads.PREDICTORS`` (``transform``: a key of ``_lib.PREDICT_TRANSFORM``,
+    ``"spectral"``, ``"dirichlet_binary"`` or ``"dirichlet_multiclass"``; ``code``: the library's value for it) and the ``UnscaleTransform``
+    behind it (``unscale``: the module, or ``None`` for ``nn.Identity``).  Raises ``NotImplementedError`` for what the inference head
+    does not take.  ``dirichlet=True`` also takes the Dirichlet pairs ``HeadSpec`` takes for training, with an identity output transform:
     ``DMPNN_PT_DIRICHLET_BINARY`` (``(p_1, 2 / S) [n, t, 2]``) / ``_MULTICLASS`` (``alpha / sum alpha [n, t, n_classes]``); the default
     refuses them, as :func:`predict_spec` does (:func:`fused_predict` opts in).  Also holds the per-model workspace and the cached
     split images of the hidden layers' weights."""
 
     def __init__(self, model, dirichlet: bool = False):
         super().__init__(model, ffn_dropout=True, attentive=True)
-        pred = model.predictor
-        names = _mro_names(pred)
-        ot = pred.output_transform
-        dir_pred = next((tr for cls, tr in _DIRICHLET_OF if cls in names), None)
-        if dir_pred is not None and not dirichlet:
-            # (the opt-in idiom of HeadSpec's attentive= / ffn_dropout=; without this the multiclass one — a MulticlassClassificationFFN —
-            #  would be handed to the softmax)
-            raise NotImplementedError(f"a Dirichlet predictor ({type(pred).__name__}): its eval-mode forward runs on the modules")
-        if dir_pred is not None:   # (HeadSpec took the pair: kind == "dirichlet", n_classes 2 | the predictor's)
-            if not isinstance(ot, nn.Identity):   # (probabilities and an uncertainty: DMPNN_PT_DIRICHLET_* take no mean / scale)
-                raise NotImplementedError("a Dirichlet predictor with an output transform that is not the identity")
-            self.transform = dir_pred
-        else:
-            self.transform = next((tr for cls, tr in _TRANSFORM_OF if cls in names), None)
-        if self.transform is None:
+        pred, ot = model.predictor, model.predictor.output_transform
+        row = predictor_row(pred)
+        if row is None:
             raise NotImplementedError(f"a predictor of a known class (got {type(pred).__name__})")
-        self.unscale = None
-        if self.transform == "spectral" and not isinstance(ot, nn.Identity):   # (p sums to 1: DMPNN_PT_SPECTRAL takes no mean / scale)
-            raise NotImplementedError("a SpectralFFN with an output transform that is not the identity")
+        if row.opt_in and not dirichlet:   # (the opt-in idiom of HeadSpec's attentive= / ffn_dropout=; HeadSpec took the pair)
+            raise NotImplementedError(f"a Dirichlet predictor ({type(pred).__name__}): its eval-mode forward runs on the modules")
+        self.transform, self.code, self.metric, self.unscale = row.transform, row.code, row.metric, None
+        self.group = self.n_classes if row.classes else row.values if row.values > 1 else 0   # (the predictions' last dimension; 0: none)
         if not isinstance(ot, nn.Identity):   # (HeadSpec: an UnscaleTransform by name — identity while training, X * scale + mean in eval mode)
-            if self.transform in ("sigmoid", "softmax"):
-                raise NotImplementedError("a classification predictor without an UnscaleTransform")
+            if row.no_unscale is not None:    # (probabilities, an uncertainty, a spectrum that sums to 1: no mean / scale)
+                raise NotImplementedError(row.no_unscale)
             mean, scale = getattr(ot, "mean", None), getattr(ot, "scale", None)
             if not (torch.is_tensor(mean) and torch.is_tensor(scale) and mean.numel() == self.n_tasks and scale.numel() == self.n_tasks):
                 raise NotImplementedError(f"an UnscaleTransform with {self.n_tasks} means and scales (one per task)")
@@ -90,11 +67,7 @@ class PredictSpec(HeadSpec):
 
     def out_shape(self, n_mols: int) -> tuple:
         """The shape ``model(...)`` returns in eval mode (a spectral head: ``[n_mols, n_tasks]``, one value per task)."""
-        if self.transform in ("softmax", "dirichlet_binary", "dirichlet_multiclass"):   # (the binary Dirichlet head: n_classes == 2)
-            return (n_mols, self.n_tasks, self.n_classes)
-        if self.transform in _GROUP:
-            return (n_mols, self.n_tasks, _GROUP[self.transform])
-        return (n_mols, self.n_tasks)
+        return (n_mols, self.n_tasks) + ((self.group,) if self.group else ())
 
     def hidden_key(self) -> tuple:
         """Identity and version of every hidden layer's weight: the split images are current while this does not change."""
@@ -116,7 +89,7 @@ def predict_spec(model, dirichlet: bool = False) -> Optional[PredictSpec]:
         except NotImplementedError as e:
             spec = str(e)
         slots[flag] = (key, spec)
-        if not any(cls in _mro_names(model.predictor) for cls, _ in _DIRICHLET_OF):   # (the flag asks nothing of this model: one answer)
+        if not getattr(predictor_row(model.predictor), "opt_in", False):   # (the flag asks nothing of this model: one answer)
             slots[not flag] = (key, spec)
     return None if isinstance(spec, str) else spec
 
@@ -176,7 +149,7 @@ def _fill_call(model, bmg, V_d, X_d, p, targets, weights, lt_mask, gt_mask, fing
     h = p.head
     keep = spec.fill(h, nV, n_mols, d_out, batch, Hv if T is None else T, weights if T is not None else None, lt_mask if T is not None else None,
                      gt_mask if T is not None else None, lambda prm: None, bn_training=False, X_d=Xd)
-    p.transform = _BESIDE_ENUM[spec.transform] if spec.transform in _BESIDE_ENUM else _lib.PREDICT_TRANSFORM[spec.transform]
+    p.transform = spec.code
     if spec.unscale is not None:
         mean, scale = (t.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous() for t in (spec.unscale.mean, spec.unscale.scale))
         p.out_mean, p.out_scale = mean.data_ptr(), scale.data_ptr()
@@ -265,7 +238,7 @@ def fused_validate(model, bmg, V_d=None, X_d=None, *, targets: Tensor, stats, me
     c = _fill_call(model, bmg, V_d, X_d, v.predict, targets, weights, lt_mask, gt_mask, fingerprint)
     if c is None or stats.device != c.dev:
         return None
-    kind = _METRIC_OF[c.spec.transform]
+    kind = c.spec.metric
     fits = (kind, c.spec.n_tasks, c.spec.n_classes if kind == "multiclass" else 0)
     if fits != (stats.kind, stats.n_tasks, stats.n_classes if kind == "multiclass" else 0):
         raise ValueError(f"fused_validate: stats of kind / tasks / classes {(stats.kind, stats.n_tasks, stats.n_classes)}, the model's are {fits}")
