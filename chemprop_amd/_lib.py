@@ -21,7 +21,7 @@ INCLUDE = os.path.join(_ROOT, "include")
 # DMPNN_LIB: an alternative build of the same sources (kernel experiments: scripts/build_variant.py), same ABI
 LIB_PATH = os.environ.get("DMPNN_LIB") or os.path.join(_HERE, "libdmpnn_gfx950.so")
 SOURCES = ["dmpnn_abi.hip", "dmpnn_prepare.hip", "dmpnn_segment.hip", "dmpnn_gemm.hip", "dmpnn_gemm_p1.hip",
-           "dmpnn_gemm_p2.hip", "dmpnn_gemm_p3.hip", "dmpnn_gemm_p4.hip", "dmpnn_gemm_s1.hip", "dmpnn_rows16_drop.hip", "dmpnn_mega.hip", "dmpnn_mega16.hip", "dmpnn_mega16_lp.hip", "dmpnn_mega16_bwd.hip", "dmpnn_rows16.hip", "dmpnn_step16.hip", "dmpnn_bstep16.hip", "dmpnn_backward.hip", "dmpnn_molagg.hip", "dmpnn_collate.hip", "dmpnn_tiles_large.hip", "dmpnn_optim.hip", "dmpnn_wgrad16.hip", "dmpnn_head.hip", "dmpnn_vd.hip", "dmpnn_attn.hip", "dmpnn_inputgrad.hip", "dmpnn_predict.hip", "dmpnn_metrics.hip"]
+           "dmpnn_gemm_p2.hip", "dmpnn_gemm_p3.hip", "dmpnn_gemm_p4.hip", "dmpnn_gemm_s1.hip", "dmpnn_rows16_drop.hip", "dmpnn_mega.hip", "dmpnn_mega16.hip", "dmpnn_mega16_lp.hip", "dmpnn_mega16_bwd.hip", "dmpnn_rows16.hip", "dmpnn_step16.hip", "dmpnn_bstep16.hip", "dmpnn_backward.hip", "dmpnn_molagg.hip", "dmpnn_collate.hip", "dmpnn_tiles_large.hip", "dmpnn_optim.hip", "dmpnn_wgrad16.hip", "dmpnn_head.hip", "dmpnn_vd.hip", "dmpnn_attn.hip", "dmpnn_inputgrad.hip", "dmpnn_predict.hip", "dmpnn_metrics.hip", "dmpnn_rank.hip"]
 HEADERS = ["dmpnn_common.hpp", "dmpnn_spill_impl.hpp", "dmpnn_gemm_impl.hpp", "dmpnn_mega_impl.hpp", "dmpnn_mega16_impl.hpp", "dmpnn_mega16_bwd_impl.hpp", "dmpnn_rows16_impl.hpp", "dmpnn_seg16.hpp", "dmpnn_step16_impl.hpp", "dmpnn_head_kernels.hpp"]
 ABI_VERSION = 15
 PLAN_NOFFSETS = 15
@@ -41,6 +41,7 @@ EXPORTS = [
     "dmpnn_backward_inputs", "dmpnn_backward_inputs_ws_bytes", "dmpnn_src_sum",
     "dmpnn_predict_head_ws_bytes", "dmpnn_predict_head_wsplit_bytes", "dmpnn_predict_head",
     "dmpnn_metric_stats_doubles", "dmpnn_metric_stats_ws_bytes", "dmpnn_metric_stats", "dmpnn_validate_head_ws_bytes", "dmpnn_validate_head",
+    "dmpnn_rank_append", "dmpnn_validate_head_ranked_ws_bytes", "dmpnn_validate_head_ranked", "dmpnn_rank_metrics_ws_bytes", "dmpnn_rank_metrics",
 ]
 
 ACT = {"none": 0, "relu": 1, "leakyrelu": 2, "prelu": 3, "tanh": 4, "elu": 5, "selu": 6}
@@ -222,6 +223,41 @@ class ValidateArgs(C.Structure):
     ]
 
 
+RANK_MAX_ROWS = 262144   # (DMPNN_RANK_MAX_ROWS: keys ranked together)
+RANK_TILE = 2048         # (DMPNN_RANK_TILE: pairs k_rank_pairs stages through LDS at a time)
+RANK_OUT = 8             # (DMPNN_RANK_OUT: doubles per row of dmpnn_rank_metrics' out)
+
+
+class RankAppendArgs(C.Structure):
+    """``dmpnn_rank_append_args``: one batch's (key, label) rows into the epoch's rank buffer (``dmpnn_rank_append``)."""
+    _fields_ = [
+        ("n_mols", C.c_int64), ("n_tasks", C.c_int64), ("group", C.c_int32),
+        ("preds", C.c_void_p), ("ld_p", C.c_int64),
+        ("targets", C.c_void_p), ("ld_t", C.c_int64),
+        ("keys", C.c_void_p), ("labels", C.c_void_p),
+        ("capacity", C.c_int64), ("row0", C.c_int64),
+    ]
+
+
+class ValidateRankArgs(C.Structure):
+    """``dmpnn_validate_rank_args``: ``dmpnn_validate_head``, then the append (``dmpnn_validate_head_ranked``)."""
+    _fields_ = [
+        ("validate", ValidateArgs),
+        ("keys", C.c_void_p), ("labels", C.c_void_p),
+        ("capacity", C.c_int64), ("row0", C.c_int64),
+    ]
+
+
+class RankArgs(C.Structure):
+    """``dmpnn_rank_args``: the epoch's ROC-AUC / PRC-AUC from the rank buffer (``dmpnn_rank_metrics``)."""
+    _fields_ = [
+        ("keys", C.c_void_p), ("labels", C.c_void_p),
+        ("rows", C.c_int64), ("n_tasks", C.c_int64), ("pooled", C.c_int32),
+        ("out", C.c_void_p),
+        ("ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+    ]
+
+
 class TrainRouteInfo(C.Structure):
     _fields_ = [("plan_kind", C.c_int32), ("route", C.c_int32), ("keep_rows", C.c_int32), ("keep_bits", C.c_int32), ("lean", C.c_int32)]
 
@@ -280,7 +316,7 @@ def _stale() -> bool:
 
 
 # sources whose kernels must not spill: compiled with the resource remarks on, a kernel with scratch fails the build
-NO_SCRATCH = ("dmpnn_predict.hip", "dmpnn_metrics.hip")
+NO_SCRATCH = ("dmpnn_predict.hip", "dmpnn_metrics.hip", "dmpnn_rank.hip")
 
 
 def _check_no_scratch(src: str, remarks: str, verbose: bool) -> None:
@@ -417,7 +453,8 @@ def load() -> C.CDLL:
                   "dmpnn_forward_keep_bits_bytes",
                   "dmpnn_molagg_ws_bytes", "dmpnn_linear16_wsplit_bytes", "dmpnn_head_ws_bytes", "dmpnn_clip_grad_ws_bytes", "dmpnn_forward_h0_bytes", "dmpnn_vd_ws_bytes",
                   "dmpnn_molagg_attn_ws_bytes", "dmpnn_backward_inputs_ws_bytes", "dmpnn_predict_head_ws_bytes", "dmpnn_predict_head_wsplit_bytes",
-                  "dmpnn_metric_stats_doubles", "dmpnn_metric_stats_ws_bytes", "dmpnn_validate_head_ws_bytes")
+                  "dmpnn_metric_stats_doubles", "dmpnn_metric_stats_ws_bytes", "dmpnn_validate_head_ws_bytes",
+                  "dmpnn_validate_head_ranked_ws_bytes", "dmpnn_rank_metrics_ws_bytes")
     lib.dmpnn_linear16_wsplit_bytes.argtypes = [C.c_int64, C.c_int64]
     lib.dmpnn_linear16_ok.argtypes = [C.POINTER(GemmArgs)]
     lib.dmpnn_linear16_fwd.argtypes = [C.POINTER(GemmArgs), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
@@ -475,6 +512,11 @@ def load() -> C.CDLL:
     lib.dmpnn_metric_stats.argtypes = [C.POINTER(MetricArgs), C.c_void_p]
     lib.dmpnn_validate_head_ws_bytes.argtypes = [C.POINTER(ValidateArgs)]
     lib.dmpnn_validate_head.argtypes = [C.POINTER(ValidateArgs), C.c_void_p, C.c_int64, C.c_void_p]
+    lib.dmpnn_rank_append.argtypes = [C.POINTER(RankAppendArgs), C.c_void_p]
+    lib.dmpnn_validate_head_ranked_ws_bytes.argtypes = [C.POINTER(ValidateRankArgs)]
+    lib.dmpnn_validate_head_ranked.argtypes = [C.POINTER(ValidateRankArgs), C.c_void_p, C.c_int64, C.c_void_p]
+    lib.dmpnn_rank_metrics_ws_bytes.argtypes = [C.POINTER(RankArgs)]
+    lib.dmpnn_rank_metrics.argtypes = [C.POINTER(RankArgs), C.c_void_p]
     lib.dmpnn_split_row_floats.argtypes = [C.c_int64]
     lib.dmpnn_split_row_floats.restype = C.c_int64
     lib.dmpnn_debug_timestamps.argtypes = [C.c_void_p]

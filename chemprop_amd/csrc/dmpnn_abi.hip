@@ -811,4 +811,19 @@ int dmpnn_metric_stats(const dmpnn_metric_args* a, void* stream) {
     return launch_metric_stats(*a, static_cast<hipStream_t>(stream));
 }
 
+// the epoch's rank metrics (dmpnn_rank.hip; dmpnn_validate_head_ranked runs the append behind the validation step)
+int dmpnn_rank_append(const dmpnn_rank_append_args* a, void* stream) {
+    DMPNN_CHECK_ARG(a != nullptr, "rank_append: null args");
+    DMPNN_TRY(rank_append_check(*a));   // (every refusal in front of the count's reset)
+    reset_launch_count();
+    return launch_rank_append(*a, static_cast<hipStream_t>(stream));
+}
+size_t dmpnn_rank_metrics_ws_bytes(const dmpnn_rank_args* a) { return a ? rank_ws_bytes(*a) : 0; }
+int dmpnn_rank_metrics(const dmpnn_rank_args* a, void* stream) {
+    DMPNN_CHECK_ARG(a != nullptr, "rank_metrics: null args");
+    DMPNN_TRY(rank_check(*a));
+    reset_launch_count();
+    return launch_rank_metrics(*a, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -475,6 +475,14 @@ size_t metric_ws_bytes(const dmpnn_metric_args& a);         // the partials [n_r
 int metric_check(const dmpnn_metric_args& a);               // every rule of dmpnn_metric_stats, no device work
 int launch_metric_stats(const dmpnn_metric_args& a, hipStream_t s);   // (checked arguments) n_mols == 0: nothing
 
+// Epoch rank metrics (dmpnn_rank.hip; dmpnn.h "Epoch rank metrics"): k_rank_append behind a validation step, k_rank_pairs and
+// k_rank_finish at the epoch's end.
+int rank_append_check(const dmpnn_rank_append_args& a);     // every rule of dmpnn_rank_append, no device work
+int launch_rank_append(const dmpnn_rank_append_args& a, hipStream_t s);   // (checked arguments) no element: nothing
+size_t rank_ws_bytes(const dmpnn_rank_args& a);             // the workgroups' partials, per task and pooled
+int rank_check(const dmpnn_rank_args& a);                   // every rule of dmpnn_rank_metrics, no device work
+int launch_rank_metrics(const dmpnn_rank_args& a, hipStream_t s);   // (checked arguments) rows == 0: no launch
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // The leading dimensions of a contraction call against the widths they carry (the C entries dmpnn_linear_fwd / dmpnn_linear16_fwd,

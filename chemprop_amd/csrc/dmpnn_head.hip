@@ -969,4 +969,23 @@ int dmpnn_validate_head(const dmpnn_validate_args* v, const float* Hv, int64_t l
     return launch_metric_stats(m, static_cast<hipStream_t>(stream));
 }
 
+// the same step, then the batch's (key, label) rows into the epoch's rank buffer (dmpnn_rank.hip): one launch more
+size_t dmpnn_validate_head_ranked_ws_bytes(const dmpnn_validate_rank_args* r) { return r ? dmpnn_validate_head_ws_bytes(&r->validate) : 0; }
+int dmpnn_validate_head_ranked(const dmpnn_validate_rank_args* r, const float* Hv, int64_t ldhv, void* stream) {
+    DMPNN_CHECK_ARG(r != nullptr, "validate_head_ranked: null args");
+    const dmpnn_validate_args& v = r->validate;
+    dmpnn_metric_args m;
+    DMPNN_TRY(validate_check(&v, &m));
+    DMPNN_CHECK_ARG(v.metric_kind == DMPNN_METRIC_BINARY, "validate_head_ranked: metric_kind %d — ranks are kept for DMPNN_METRIC_BINARY alone", (int)v.metric_kind);
+    dmpnn_rank_append_args ap{};
+    ap.n_mols = m.n_mols; ap.n_tasks = m.n_tasks; ap.group = m.group;
+    ap.preds = m.preds; ap.ld_p = m.ld_p; ap.targets = m.targets; ap.ld_t = m.ld_t;
+    ap.keys = r->keys; ap.labels = r->labels; ap.capacity = r->capacity; ap.row0 = r->row0;
+    DMPNN_TRY(rank_append_check(ap));
+    reset_launch_count();
+    DMPNN_TRY(predict_core(v.predict, v.predict.head, Hv, ldhv, stream, HeadPre{false, false}));
+    DMPNN_TRY(launch_metric_stats(m, static_cast<hipStream_t>(stream)));
+    return launch_rank_append(ap, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

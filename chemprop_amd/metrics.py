@@ -16,6 +16,9 @@ Layout (``stats``, float64): ``[sum loss * n_finite, sum n_finite, calls, molecu
 
 Declared deviation — restated from chemprop 2.3.1 and not run against it: the statistics are UNWEIGHTED (validation and test run with
 unit weights in the reference); ``weights`` and the criterion's ``task_weights`` go into ``val_loss`` only.
+
+ROC-AUC and PRC-AUC are functions of ranks, not of sums: :class:`RankStats` (below) keeps the epoch's (score, label) pairs on the
+device and ranks them there at the epoch's end.
 """
 from __future__ import annotations
 
@@ -263,4 +266,195 @@ class MetricStats:
             per["n"] = tot
             for name in ("accuracy", "multiclass-mcc"):
                 out[name] = float(per[name].mean())
+        return out
+
+
+# ---- the epoch's rank metrics: ROC-AUC and PRC-AUC of a binary head ---------------------------------------------------------------------
+RANK_MAX_ROWS = _lib.RANK_MAX_ROWS
+
+
+def rank_keys(scores: Tensor, targets: Tensor) -> tuple:
+    """``(keys, labels)`` of float32 ``scores`` / ``targets`` of one shape — ``k_rank_append``'s rules restated on torch ops.  ``keys``
+    (int32 holding the uint32 bits): the order-preserving image of the score — ``-0.0`` becomes ``+0.0``, then sign bit set ``->
+    ~bits``, else ``bits | 0x80000000`` — and 0 where the pair is not ranked.  ``labels`` (uint8): 0 negative, 1 positive (``t > 0.5``),
+    2 the target is NaN / infinite, 3 the target is finite and the score is not (counted as ``n_skipped``).  Integer tests on the bits
+    throughout: no denormal mode can merge or split ties."""
+    b = scores.detach().float().contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    T = targets.detach().float()
+    t_ok = T.isfinite()
+    p_ok = (b & 0x7F800000) != 0x7F800000
+    b = torch.where((b & 0x7FFFFFFF) == 0, torch.zeros_like(b), b)
+    key = torch.where((b & 0x80000000) != 0, b ^ 0xFFFFFFFF, b | 0x80000000)
+    ranked = t_ok & p_ok
+    key = torch.where(ranked, key, torch.zeros_like(key))
+    lab = torch.where(ranked, (T > 0.5).to(torch.uint8), torch.where(t_ok, torch.full_like(T, 3, dtype=torch.uint8), torch.full_like(T, 2, dtype=torch.uint8)))
+    key = torch.where(key >= 1 << 31, key - (1 << 32), key).to(torch.int32)   # (the same 32 bits in int32)
+    return key, lab
+
+
+def rank_column(keys: np.ndarray, labels: np.ndarray) -> np.ndarray:
+    """``dmpnn_rank_metrics``' 8 doubles of ONE column, restated in float64 numpy: ``n_pos, n_neg, n_skipped, n_thresholds, U2, roc,
+    prc, 0``.  The five counts of every distinct key come from one sort of the distinct keys (the device counts all pairs; the
+    integers are the same, the PRC sum is added in key order, not row order)."""
+    keys, labels = np.asarray(keys).reshape(-1).view(np.uint32), np.asarray(labels).reshape(-1)
+    out = np.zeros(8)
+    ranked = labels < 2
+    out[2] = float((labels == 3).sum())
+    k, pos = keys[ranked], labels[ranked] == 1
+    P, N = int(pos.sum()), int((~pos).sum())
+    out[0], out[1] = P, N
+    out[5] = out[6] = np.nan
+    if k.size == 0:
+        return out
+    u, inv = np.unique(k, return_inverse=True)
+    ep = np.bincount(inv, weights=pos, minlength=u.size).astype(np.int64)
+    en = np.bincount(inv, minlength=u.size).astype(np.int64) - ep
+    gp = ep[::-1].cumsum()[::-1] - ep      # positives / negatives with a strictly greater key
+    gn = en[::-1].cumsum()[::-1] - en
+    U2 = int((en * (2 * gp + ep)).sum())
+    out[3], out[4] = u.size, U2
+    if P > 0 and N > 0:
+        above = (gp + gn).astype(np.float64)
+        p_i = (gp + ep) / (above + ep + en)
+        p_prev = np.where(above > 0, gp / np.where(above > 0, above, 1.0), 1.0)
+        out[5] = U2 / (2.0 * P * N)
+        out[6] = float((ep * (p_i + p_prev) * 0.5).sum()) / P
+    return out
+
+
+class RankStats:
+    """The epoch's rank buffer of one binary model — ``keys`` (int32 holding ``uint32`` bits) and ``labels`` (uint8), ``[capacity,
+    n_tasks]`` on ``device`` — and ``rows``, the molecules appended so far, counted on the host (``include/dmpnn.h``, "Epoch rank
+    metrics").  ROC-AUC and PRC-AUC need every (score, label) pair of the epoch, not sums: the pairs stay on the device, and
+    :meth:`compute` ranks them there by an all-pairs count and copies ``8 (n_tasks + 1)`` doubles to the host.
+
+    ``update`` appends one batch: on device tensors it is ``dmpnn_rank_append`` (one launch), on CPU tensors :func:`rank_keys`.
+    ``merge`` appends another buffer's used rows — unlike sums, ranks need every rank's rows: under ``--devices N`` this is what an
+    ``all_gather`` of the buffers feeds.
+
+    Declared deviations — restated from chemprop 2.3.1 (``BinaryAUROC`` / ``BinaryAUPRC``) and not run against it: unweighted; ``roc`` /
+    ``prc`` are per-task values averaged over the tasks that have both classes, where the reference pools all tasks' pairs into one
+    curve — that pooling is offered beside them as ``roc-pooled`` / ``prc-pooled``; a column without positives or without negatives
+    gives NaN, not the reference's warning-and-zero; a pair whose target is finite and whose prediction is not is left out and counted
+    (``n_skipped``) where the reference would rank it.  At most ``RANK_MAX_ROWS`` keys are ranked together (the cost is quadratic)."""
+
+    def __init__(self, n_tasks: int, capacity: int, device="cpu"):
+        self.n_tasks, self.capacity = int(n_tasks), int(capacity)
+        if self.n_tasks < 1 or self.capacity < 0:
+            raise ValueError(f"n_tasks >= 1 and capacity >= 0 (got {n_tasks}, {capacity})")
+        self.keys = torch.zeros(self.capacity, self.n_tasks, dtype=torch.int32, device=device)
+        self.labels = torch.full((self.capacity, self.n_tasks), 2, dtype=torch.uint8, device=device)
+        self.rows = 0
+        self._ws: Optional[Tensor] = None
+
+    @classmethod
+    def for_model(cls, model, capacity: int, device=None) -> "RankStats":
+        """The buffer that fits ``model``'s binary predictor (a sigmoid or a binary Dirichlet head) and ``capacity`` molecules — the
+        validation set's size — on the device of its parameters; ``NotImplementedError`` for every other predictor."""
+        pred = model.predictor
+        row = predictor_row(pred)
+        if row is None or row.metric != "binary":
+            raise NotImplementedError(f"rank metrics take a binary classification predictor (got {type(pred).__name__})")
+        dev = device if device is not None else next(model.parameters()).device
+        return cls(int(pred.n_tasks), capacity, dev)
+
+    @property
+    def device(self):
+        return self.keys.device
+
+    def reset(self) -> None:
+        self.rows = 0
+
+    def fits(self, n: int) -> bool:
+        return self.rows + int(n) <= self.capacity
+
+    def merge(self, other: "RankStats") -> None:
+        if other.n_tasks != self.n_tasks:
+            raise ValueError("merge: a buffer of another number of tasks")
+        if not self.fits(other.rows):
+            raise ValueError(f"merge: {other.rows} rows do not fit ({self.rows} of {self.capacity} used)")
+        dev = self.keys.device
+        self.keys[self.rows:self.rows + other.rows] = other.keys[:other.rows].to(dev)
+        self.labels[self.rows:self.rows + other.rows] = other.labels[:other.rows].to(dev)
+        self.rows += other.rows
+
+    def update(self, preds: Tensor, targets: Tensor) -> None:
+        """Append one batch: ``preds`` as the model returns them in eval mode (``[n, t]`` or ``[n, t, k]`` with ``k`` 1 or 2: element 0
+        of a task's group is the score), ``targets [n, t]`` (NaN: missing).  ``ValueError`` when the batch does not fit or lives on
+        another device."""
+        n, t, dev = int(targets.shape[0]), self.n_tasks, targets.device
+        if dev != self.keys.device or preds.device != dev:
+            raise ValueError(f"this buffer lives on {self.keys.device}, the batch on {preds.device} / {dev}")
+        if targets.dim() != 2 or int(targets.shape[1]) != t or int(preds.shape[0]) != n:
+            raise ValueError(f"targets must be [n, {t}] with one row of preds each, got {tuple(targets.shape)} / {tuple(preds.shape)}")
+        if not self.fits(n):
+            raise ValueError(f"a batch of {n} rows does not fit ({self.rows} of {self.capacity} used)")
+        if n == 0:
+            return
+        P, T = preds.detach().float().reshape(n, t, -1), targets.detach().float()
+        group = int(P.shape[2])
+        if group not in (1, 2):
+            raise ValueError(f"preds must hold 1 or 2 values per task, got {tuple(preds.shape)}")
+        if dev.type == "cuda":
+            from . import engine
+
+            lib = _lib.load()
+            rows = lambda X: X if n > 1 and X.stride(1) == 1 and X.stride(0) >= X.shape[1] else X.contiguous()   # (views into wider tables stay views)
+            P2, T = rows(P.reshape(n, -1)), rows(T)
+            a = _lib.RankAppendArgs()
+            a.n_mols, a.n_tasks, a.group = n, t, group
+            a.preds, a.ld_p, a.targets, a.ld_t = P2.data_ptr(), int(P2.stride(0)), T.data_ptr(), int(T.stride(0))
+            a.keys, a.labels, a.capacity, a.row0 = self.keys.data_ptr(), self.labels.data_ptr(), self.capacity, self.rows
+            with engine._OnDevice(dev):
+                _lib.check(lib.dmpnn_rank_append(C.byref(a), engine._stream_ptr(dev)), "dmpnn_rank_append")
+            del P2, T
+        else:
+            k, l = rank_keys(P[:, :, 0], T)
+            self.keys[self.rows:self.rows + n], self.labels[self.rows:self.rows + n] = k, l
+        self.rows += n
+
+    def _out(self, pooled: bool) -> np.ndarray:
+        """``dmpnn_rank_metrics``' ``out`` on the host, ``[n_tasks + pooled, 8]``."""
+        t, n, dev = self.n_tasks, self.rows, self.keys.device
+        if dev.type != "cuda":
+            K, L = self.keys[:n].numpy(), self.labels[:n].numpy()
+            cols = [rank_column(K[:, j], L[:, j]) for j in range(t)]
+            if pooled:
+                cols.append(rank_column(K, L))
+            return np.stack(cols)
+        from . import engine
+
+        lib = _lib.load()
+        out = torch.empty(t + int(pooled), _lib.RANK_OUT, dtype=torch.float64, device=dev)
+        a = _lib.RankArgs()
+        a.keys, a.labels, a.rows, a.n_tasks, a.pooled, a.out = self.keys.data_ptr(), self.labels.data_ptr(), n, t, int(pooled), out.data_ptr()
+        nb = int(lib.dmpnn_rank_metrics_ws_bytes(C.byref(a)))
+        if nb:
+            if self._ws is None or self._ws.device != dev or self._ws.numel() < nb:
+                self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            a.ws, a.ws_bytes = self._ws.data_ptr(), self._ws.numel()
+        with engine._OnDevice(dev):
+            _lib.check(lib.dmpnn_rank_metrics(C.byref(a), engine._stream_ptr(dev)), "dmpnn_rank_metrics")
+        return out.cpu().numpy()   # (the ONE copy)
+
+    def compute(self, pooled: bool = True) -> dict:
+        """``roc`` / ``prc``: the mean of the per-task values over the tasks that have both classes (NaN if none); with ``pooled``
+        also ``roc-pooled`` / ``prc-pooled``, all tasks' pairs ranked as one column (the reference's pooling); ``per_task``: arrays
+        ``roc, prc, n_pos, n_neg, n_thresholds, n_skipped``.  On the device ONE ``dmpnn_rank_metrics`` call and one copy of ``8
+        (n_tasks + pooled)`` doubles; on CPU buffers :func:`rank_column`.  ``ValueError`` when more than ``RANK_MAX_ROWS`` keys would
+        be ranked together (beyond it for the pooled column alone: ``pooled=False``)."""
+        together = self.rows * (self.n_tasks if pooled else 1)
+        if together > RANK_MAX_ROWS:
+            raise ValueError(f"{together} keys would be ranked together, the cap is RANK_MAX_ROWS = {RANK_MAX_ROWS}"
+                             + (" (pooled=False ranks each task alone)" if pooled and self.rows <= RANK_MAX_ROWS else ""))
+        A = self._out(bool(pooled))
+        t = self.n_tasks
+        per = dict(roc=A[:t, 5].copy(), prc=A[:t, 6].copy(), n_pos=A[:t, 0].copy(), n_neg=A[:t, 1].copy(), n_thresholds=A[:t, 3].copy(),
+                   n_skipped=A[:t, 2].copy(), U2=A[:t, 4].copy())
+        ok = (per["n_pos"] > 0) & (per["n_neg"] > 0)
+        out = {"roc": float(per["roc"][ok].mean()) if ok.any() else float("nan"),
+               "prc": float(per["prc"][ok].mean()) if ok.any() else float("nan"), "n_mols": self.rows, "per_task": per}
+        if pooled:
+            out["roc-pooled"], out["prc-pooled"] = float(A[t, 5]), float(A[t, 6])
+            out["pooled"] = dict(n_pos=A[t, 0], n_neg=A[t, 1], n_thresholds=A[t, 3], n_skipped=A[t, 2], U2=A[t, 4])
         return out

@@ -223,21 +223,31 @@ def fused_predict(model, bmg, V_d=None, X_d=None, *, targets: Optional[Tensor] =
 
 def fused_validate(model, bmg, V_d=None, X_d=None, *, targets: Tensor, stats, metric_targets: Optional[Tensor] = None,
                    weights: Optional[Tensor] = None, lt_mask: Optional[Tensor] = None, gt_mask: Optional[Tensor] = None,
-                   fingerprint: bool = False) -> Optional[PredictResult]:
+                   fingerprint: bool = False, ranks=None) -> Optional[PredictResult]:
     """One validation step behind the block as ONE ``dmpnn_validate_head`` call: :func:`fused_predict` with ``targets`` — the same
     kernels, the same bits — and, behind it, the batch's metric sums added into ``stats`` (a
     :class:`~chemprop_amd.metrics.MetricStats` on the model's device; at most two launches more).  ``metric_targets``: the targets the
     metrics compare the predictions with where they differ from the criterion's (unscaled against scaled).  The bounds reach the
     statistics where they reach the criterion (a bounded MSE / MAE).
 
-    ``None`` under :func:`fused_predict`'s conditions, for ``stats`` on another device and for misshapen ``metric_targets``;
-    ``ValueError`` for ``stats`` of another kind or shape than the model's (:meth:`MetricStats.for_model`)."""
+    ``ranks`` (a :class:`~chemprop_amd.metrics.RankStats` on the model's device, binary heads): the call is
+    ``dmpnn_validate_head_ranked`` — the same step and one launch more, which appends the batch's (score, label) rows to the epoch's
+    rank buffer at ``ranks.rows``; the counter advances only after the call has returned 0.
+
+    ``None`` under :func:`fused_predict`'s conditions, for ``stats`` / ``ranks`` on another device and for misshapen ``metric_targets``;
+    ``ValueError`` for ``stats`` of another kind or shape than the model's (:meth:`MetricStats.for_model`), for ``ranks`` of another
+    number of tasks and — before anything is launched — for a batch that does not fit ``ranks``."""
     if targets is None:
         raise ValueError("fused_validate: a validation step has targets")
-    v = _lib.ValidateArgs()
+    if ranks is not None and not ranks.fits(int(targets.shape[0])):
+        raise ValueError(f"fused_validate: a batch of {int(targets.shape[0])} rows does not fit ranks ({ranks.rows} of {ranks.capacity} used)")
+    vr = _lib.ValidateRankArgs() if ranks is not None else None
+    v = vr.validate if ranks is not None else _lib.ValidateArgs()
     c = _fill_call(model, bmg, V_d, X_d, v.predict, targets, weights, lt_mask, gt_mask, fingerprint)
-    if c is None or stats.device != c.dev:
+    if c is None or stats.device != c.dev or (ranks is not None and ranks.device != c.dev):
         return None
+    if ranks is not None and ranks.n_tasks != c.spec.n_tasks:
+        raise ValueError(f"fused_validate: ranks of {ranks.n_tasks} tasks, the model has {c.spec.n_tasks}")
     kind = c.spec.metric
     fits = (kind, c.spec.n_tasks, c.spec.n_classes if kind == "multiclass" else 0)
     if fits != (stats.kind, stats.n_tasks, stats.n_classes if kind == "multiclass" else 0):
@@ -253,4 +263,10 @@ def fused_validate(model, bmg, V_d=None, X_d=None, *, targets: Tensor, stats, me
     v.metric_kind, v.threshold = _lib.METRIC[stats.kind], stats.threshold
     v.stats, v.stats_bytes = stats.stats.data_ptr(), stats.stats.numel() * 8
     lib = _lib.load()
-    return _run_call(c, lib.dmpnn_validate_head, v, "dmpnn_validate_head", lambda: lib.dmpnn_validate_head_ws_bytes(C.byref(v)), ("validate", stats.kind))
+    if ranks is None:
+        return _run_call(c, lib.dmpnn_validate_head, v, "dmpnn_validate_head", lambda: lib.dmpnn_validate_head_ws_bytes(C.byref(v)), ("validate", stats.kind))
+    vr.keys, vr.labels, vr.capacity, vr.row0 = ranks.keys.data_ptr(), ranks.labels.data_ptr(), ranks.capacity, ranks.rows
+    r = _run_call(c, lib.dmpnn_validate_head_ranked, vr, "dmpnn_validate_head_ranked", lambda: lib.dmpnn_validate_head_ranked_ws_bytes(C.byref(vr)),
+                  ("validate", stats.kind))
+    ranks.rows += c.n_mols
+    return r

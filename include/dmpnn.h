@@ -1022,6 +1022,83 @@ typedef struct dmpnn_validate_args {
 size_t dmpnn_validate_head_ws_bytes(const dmpnn_validate_args* v);
 int    dmpnn_validate_head(const dmpnn_validate_args* v, const float* Hv, int64_t ldhv, void* stream);
 
+/* Epoch rank metrics (v15 growth: new entry points and structs, every existing struct and call as it was).  ROC-AUC and PRC-AUC of a
+ * binary head are functions of RANKS, not of sums, so the epoch keeps every (score, label) pair — on the device, in a buffer the
+ * caller owns — and the epoch ends with one all-pairs count and one copy of 8 (n_tasks + pooled) doubles.  No sort, no atomics of any
+ * kind, a fixed order of additions: `out` is bitwise reproducible.
+ *
+ * The buffer: keys uint32 [capacity, n_tasks] and labels uint8 [capacity, n_tasks], contiguous, leading dimension n_tasks.  Row r is
+ * the r-th molecule appended this epoch; the caller counts the rows on the host (every batch's n_mols is known there).
+ *   key    the order-preserving uint32 image of the float32 score: -0.0 becomes +0.0, then sign bit set -> ~bits, else bits |
+ *          0x80000000.  Compares are integer compares: flushing denormals can neither merge nor split ties.  A finite score never
+ *          maps to 0; key 0 is "not ranked".
+ *   label  0 negative, 1 positive (t > 0.5, DMPNN_METRIC_BINARY's rule); not ranked, with key 0: 2 where the target is NaN or not
+ *          finite, 3 where the target is finite and the prediction is not — counted per task as n_skipped (a declared deviation: the
+ *          reference would rank the garbage).
+ * For one column, over its ranked elements, with s the score, for element i and all elements j (j = i included in the "equal" counts):
+ *   gp_i, gn_i  positives / negatives with s_j > s_i;   ep_i, en_i  positives / negatives with s_j == s_i;
+ *   first_i     no j < i (row order) has s_j == s_i: one representative per distinct threshold.
+ *   ROC-AUC = U2 / (2 P N), U2 = sum over negative i of (2 gp_i + ep_i) — an integer, twice the Mann-Whitney count with ties counted
+ *             half: the trapezoid under torchmetrics' BinaryAUROC(thresholds=None) curve.
+ *   PRC-AUC = (1 / P) sum over i with first_i of ep_i (P_i + Pprev_i) / 2, P_i = (gp_i + ep_i) / (gp_i + ep_i + gn_i + en_i), Pprev_i =
+ *             gp_i / (gp_i + gn_i), or 1 where nothing is strictly greater (the curve's appended point, recall 0 and precision 1):
+ *             chemprop 2.3.1's BinaryAUPRC — auc(recall, precision) over BinaryPrecisionRecallCurve, trapezoid, no truncation.
+ * Declared deviations — restated from chemprop 2.3.1 and not run against it: unweighted; a column without positives or without
+ * negatives gives NaN for both (the reference warns and returns 0); n_skipped above.  The cost is quadratic in the keys ranked
+ * together, bounded by DMPNN_RANK_MAX_ROWS (which also keeps the uint32 counters safe). */
+#define DMPNN_RANK_MAX_ROWS 262144         /* keys ranked together (one column; the pooled column: rows n_tasks) */
+#define DMPNN_RANK_TILE 2048               /* (key, label) pairs k_rank_pairs stages through LDS at a time */
+#define DMPNN_RANK_OUT 8                   /* doubles per row of `out` */
+
+/* One launch (k_rank_append, one thread per (molecule, task)): rows [row0, row0 + n_mols) of the buffer from preds [n_mols, n_tasks
+ * group] (the score is element 0 of the task's group; group 1: sigmoid, 2: DMPNN_PT_DIRICHLET_BINARY, whose column 0 is p_1) and
+ * targets [n_mols, n_tasks].  DMPNN_EINVAL before any device work: NULL pointers, negative sizes, group outside {1, 2}, ld_p below
+ * n_tasks group or ld_t below n_tasks, n_mols n_tasks beyond one launch (2^31).  DMPNN_ENOSPC before any device work: row0 + n_mols >
+ * capacity.  n_mols == 0 (or n_tasks == 0) launches nothing. */
+typedef struct dmpnn_rank_append_args {
+    int64_t n_mols, n_tasks;
+    int32_t group;                         /* preds elements per task: 1 | 2 */
+    const float* preds; int64_t ld_p;      /* rows of ld_p floats */
+    const float* targets; int64_t ld_t;    /* NaN = missing, rows of ld_t floats */
+    uint32_t* keys; unsigned char* labels; /* the epoch's buffer */
+    int64_t capacity, row0;                /* rows the buffer holds; the first row this call writes */
+} dmpnn_rank_append_args;
+int    dmpnn_rank_append(const dmpnn_rank_append_args* a, void* stream);
+
+/* dmpnn_validate_head exactly as it runs (same kernels, same bits in preds / raw / loss / stats), then the append launch on
+ * predict.preds and metric_targets (predict.head.targets where that is NULL): dmpnn_validate_head's launches plus one.  It takes
+ * metric_kind == DMPNN_METRIC_BINARY only.  DMPNN_EINVAL before any device work (dmpnn_last_launch_count() as it was): whatever
+ * dmpnn_validate_head refuses, another metric_kind, NULL keys / labels, negative capacity / row0; DMPNN_ENOSPC: a workspace that is
+ * too small (dmpnn_validate_head_ranked_ws_bytes() = dmpnn_validate_head_ws_bytes(): the append needs none) or row0 + n_mols >
+ * capacity. */
+typedef struct dmpnn_validate_rank_args {
+    dmpnn_validate_args validate;          /* as dmpnn_validate_head reads it */
+    uint32_t* keys; unsigned char* labels;
+    int64_t capacity, row0;
+} dmpnn_validate_rank_args;
+size_t dmpnn_validate_head_ranked_ws_bytes(const dmpnn_validate_rank_args* r);
+int    dmpnn_validate_head_ranked(const dmpnn_validate_rank_args* r, const float* Hv, int64_t ldhv, void* stream);
+
+/* The epoch's end: out = double [n_tasks + pooled][8] = n_pos, n_neg, n_skipped, n_thresholds, U2, roc, prc, 0 per task column — counts
+ * and U2 exact integers held in doubles, roc = U2 / (2 P N) (one division of exact integers), prc as above, both NaN where P == 0 or
+ * N == 0.  pooled = 1 adds a last row that ranks all rows n_tasks pairs as ONE column (ClassificationMixin.update flattens
+ * preds[mask] over tasks: the reference's pooling) — the same kernels on the contiguous buffer read as [rows n_tasks, 1]; its
+ * n_skipped is the sum over tasks.  k_rank_pairs (one workgroup per 256 rows i and task; the column's j staged through LDS in tiles
+ * of DMPNN_RANK_TILE; one partial per workgroup into ws) and k_rank_finish (one thread per column, the partials in block order): two
+ * launches for the per-task rows, two more for the pooled row; rows == 0 launches nothing and leaves zeros for the counts and NaN
+ * for roc / prc.  DMPNN_EINVAL before any device work: NULL keys / labels / out, out or ws not 8-byte aligned, rows < 0, n_tasks
+ * outside [1, 65535], pooled outside {0, 1}, more than DMPNN_RANK_MAX_ROWS keys ranked together (rows, and rows n_tasks with pooled: a
+ * caller above it passes pooled = 0).  DMPNN_ENOSPC: ws missing or below dmpnn_rank_metrics_ws_bytes(). */
+typedef struct dmpnn_rank_args {
+    const uint32_t* keys; const unsigned char* labels;
+    int64_t rows, n_tasks;
+    int32_t pooled;                        /* 0 | 1 */
+    double* out;                           /* device, [n_tasks + pooled][DMPNN_RANK_OUT] */
+    void* ws; size_t ws_bytes;             /* the workgroups' partials */
+} dmpnn_rank_args;
+size_t dmpnn_rank_metrics_ws_bytes(const dmpnn_rank_args* a);
+int    dmpnn_rank_metrics(const dmpnn_rank_args* a, void* stream);
+
 /* One training step of models/model.py:148-161 with torch.optim.Adam (model.py:208-231), every kernel enqueued by ONE call:
  * K0 (dmpnn_prepare_with_batch into bwd.f.plan unless plan_ready) -> dmpnn_forward(&bwd.f) (DMPNN_F_KEEP) -> dmpnn_head on
  * bwd.f.out (head.gHv must be bwd.gout) -> dmpnn_backward(&bwd) -> dmpnn_adam_step over the flat buffers (n_params == 0: no
