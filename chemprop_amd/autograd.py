@@ -19,6 +19,9 @@ from torch import Tensor
 from . import engine
 
 
+_FUSED_ARGS = ("W_i", "b_i", "W_h", "b_h", "W_o", "b_o", "W_d", "b_d")   # the tensors behind FusedMP.apply's options, in its order
+
+
 def _params(mp):
     g = lambda lin, n: None if lin is None else getattr(lin, n)
     return dict(W_i=mp.W_i.weight, b_i=mp.W_i.bias, W_h=mp.W_h.weight, b_h=mp.W_h.bias,
@@ -59,10 +62,10 @@ def mp_forward(mp, plan: engine.GraphPlan, V: Tensor, E: Tensor, V_d: Optional[T
     # other than PReLU with inactive dropout; everything else takes the rows route below, where every row Function has a data gradient
     in_grad = input_grad_wanted(V, E, V_d if has_vd else None)
     if in_grad and act not in ("custom", "prelu") and not drop_active:
-        from .backward import FusedMP
+        from .backward import FusedMP, FusedOptions
 
-        return FusedMP.apply(mp, plan, V, E, V_d if has_vd else None, act, slope, (slope_t, 0, None, False, False, "general"),
-                             *[p[k] for k in ("W_i", "b_i", "W_h", "b_h", "W_o", "b_o", "W_d", "b_d")])
+        return FusedMP.apply(mp, plan, V, E, V_d if has_vd else None, act, slope, FusedOptions(slope_t=slope_t, max_level=0, route="general"),
+                             *[p[k] for k in _FUSED_ARGS])
     # (the dropout scale of the backward pass lives in the backward TILE kernel, which only runs when a gradient of W_i or W_h is
     #  wanted: a block with both frozen — W_o alone trainable — keeps the rows route)
     edge_grad = any(t is not None and t.requires_grad for t in (p["W_i"], p["b_i"], p["W_h"], p["b_h"]))
@@ -72,22 +75,22 @@ def mp_forward(mp, plan: engine.GraphPlan, V: Tensor, E: Tensor, V_d: Optional[T
         # one draw from torch's CPU generator (so torch.manual_seed fixes the run); a batch that takes another route falls
         # through to the rows route below, where the block's own nn.Dropout runs between the kernels (as does any module that is not
         # exactly nn.Dropout: a subclass has its own semantics)
-        from .backward import FusedMP
-
         seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
         try:
-            return FusedMP.apply(mp, plan, V, E, None, act, slope, (slope_t, max_level, (float(mp.dropout.p), seed)),
-                                 *[p[k] for k in ("W_i", "b_i", "W_h", "b_h", "W_o", "b_o", "W_d", "b_d")])
+            from .backward import FusedMP, FusedOptions
+
+            return FusedMP.apply(mp, plan, V, E, None, act, slope,
+                                 FusedOptions(slope_t=slope_t, max_level=max_level, dropout=(float(mp.dropout.p), seed)), *[p[k] for k in _FUSED_ARGS])
         except engine.RouteUnavailable:
             pass
     use_rows = act == "custom" or drop_active or (act == "prelu" and grad) or in_grad
 
     if not use_rows:
         if grad:
-            from .backward import FusedMP
+            from .backward import FusedMP, FusedOptions
 
-            return FusedMP.apply(mp, plan, V, E, V_d if has_vd else None, act, slope, (slope_t, max_level),
-                                 *[p[k] for k in ("W_i", "b_i", "W_h", "b_h", "W_o", "b_o", "W_d", "b_d")])
+            return FusedMP.apply(mp, plan, V, E, V_d if has_vd else None, act, slope, FusedOptions(slope_t=slope_t, max_level=max_level),
+                                 *[p[k] for k in _FUSED_ARGS])
         out, st = engine.forward(plan, V, E, p["W_i"], p["W_h"], p["W_o"], p["b_o"], p["b_i"], p["b_h"],
                                  p["W_d"] if has_vd else None, p["b_d"] if has_vd else None,
                                  V_d if has_vd else None, depth=mp.depth, act=act, slope=slope,
@@ -96,27 +99,72 @@ def mp_forward(mp, plan: engine.GraphPlan, V: Tensor, E: Tensor, V_d: Optional[T
         mp.__dict__["_dmpnn_last"] = st  # (nn.py builds the replay state of the steady inference path from it)
         return out
 
-    # ---- rows route: kernels for every contraction / segment op, torch modules in between ----
+    from .nn import _Block
+
+    return rows_forward(_Block(mp), plan, V, E, V_d, grad=grad, in_grad=in_grad)[0]
+
+
+def _direct_linear(A1, W, b, A2=None, gather=None, n_rows=None, Cadd=None, plan=None):
+    return engine.linear(A1, W, b, A2=A2, gather1=gather, n_rows=n_rows, Cadd=Cadd)
+
+
+def edge_readout(blk, linear_fn, E: Tensor, H: Tensor, E_d: Optional[Tensor]) -> Tensor:
+    """``edge_finalize`` of the mol-atom-bond blocks (mol_atom_bond.py:221-264) on the last edge states ``H``."""
+    H_e = blk.dropout(blk.tau(linear_fn(E, blk.W_eo.weight, blk.W_eo.bias, A2=H)))
+    if E_d is not None:
+        H_e = blk.dropout(linear_fn(H_e, blk.W_ed.weight, blk.W_ed.bias, A2=E_d))
+    return H_e
+
+
+def rows_forward(blk, plan: engine.GraphPlan, V: Tensor, E: Tensor, V_d: Optional[Tensor] = None, E_d: Optional[Tensor] = None, *,
+                 grad: bool, in_grad: bool) -> tuple:
+    """The rows route of every block (``blk``: ``nn._Block``) -> ``(H_v | None, H_e | None)``: a row kernel for every contraction /
+    segment operation, the block's own ``tau`` / dropout MODULES between them (base.py:135-141,180-194; mixins.py:8-30;
+    mol_atom_bond.py:174-264).  Bond messages ``M = message(H)``, atom messages ``M = [(segsum_dst H)[src] || (segsum_dst E)[src]]``
+    — the second half constant over the loop, formed once, through its Functions when ``E`` requires grad.
+
+    ``grad``: chain the autograd Functions of ``backward.py``; ``False`` calls the engine directly (the bond forward without a
+    gradient to record; the atom and mol-atom-bond forwards always pass ``True``).  ``in_grad``: an input requires grad — the first
+    contraction then carries the plan, for the gradient of the gathered ``V``."""
     if grad:
-        from .backward import linear_fn, message_fn, aggregate_fn
+        from .backward import aggregate_fn, gather_src_fn, linear_fn, message_fn
     else:
-        linear_fn = lambda A1, W, b, A2=None, gather=None, n_rows=None, Cadd=None, plan=None: engine.linear(
-            A1, W, b, A2=A2, gather1=gather, n_rows=n_rows, Cadd=Cadd)
-        message_fn = lambda plan_, H: engine.message(plan_, H)
-        aggregate_fn = lambda plan_, H: engine.aggregate(plan_, H)
-    tau, drop = mp.tau, mp.dropout
-    rev = None
-    H0 = linear_fn(V, p["W_i"], p["b_i"], A2=E, gather=plan.src32, n_rows=plan.n_edges, plan=plan if in_grad else None)
+        assert not blk.atom, "rows_forward(grad=False) serves bond messages only (no direct form of the source gather)"
+        linear_fn, message_fn, aggregate_fn = _direct_linear, engine.message, engine.aggregate
+    tau, drop, W_i, W_h = blk.tau, blk.dropout, blk.W_i, blk.W_h
+    nE = plan.n_edges
+    H0 = linear_fn(V, W_i.weight, W_i.bias, A2=None if blk.atom else E, gather=plan.src32, n_rows=nE, plan=plan if in_grad else None)
     H = tau(H0)
-    for _ in range(1, mp.depth):
-        if mp.undirected:
+    # (behind tau(H0) for every caller; the mol-atom-bond forward used to enqueue these two kernels in front of it: they depend on
+    #  E alone, and the outputs are bit-identical)
+    if blk.atom and blk.depth > 1 and nE:
+        if torch.is_grad_enabled() and E.requires_grad:
+            ME = gather_src_fn(plan, aggregate_fn(plan, E))                     # (the same two kernels, with their transposes)
+        else:
+            with torch.no_grad():
+                ME = engine.gather_rows(engine.aggregate(plan, E), plan.src32)      # [E, d_e], constant over the loop
+    # a batch without edges: the atom and the mol-atom-bond chains skip the W_h contraction, the bond block's runs it on no rows — each
+    # as before.  (A backward pass through either form is refused on such a batch, by dmpnn_linear_wgrad: the recorded table holds that.)
+    skip_empty = (blk.atom or blk.mab) and not nE
+    rev = None
+    for _ in range(1, blk.depth):
+        if blk.undirected:
             if rev is None:
                 rev = plan.rev64
             H = (H + H[rev]) / 2
-        M = message_fn(plan, H)
-        H = drop(tau(linear_fn(M, p["W_h"], p["b_h"], Cadd=H0)))
-    Mv = aggregate_fn(plan, H)
-    Hv = drop(tau(linear_fn(V, p["W_o"], p["b_o"], A2=Mv)))
-    if has_vd:
-        Hv = drop(linear_fn(Hv, p["W_d"], p["b_d"], A2=V_d))
-    return Hv
+        if skip_empty:
+            H = drop(tau(H0))
+        elif blk.atom:
+            MH = gather_src_fn(plan, aggregate_fn(plan, H))
+            H = drop(tau(linear_fn(MH, W_h.weight, W_h.bias, A2=ME, Cadd=H0)))
+        else:
+            H = drop(tau(linear_fn(message_fn(plan, H), W_h.weight, W_h.bias, Cadd=H0)))
+    H_v = H_e = None
+    if blk.want_v:
+        Mv = aggregate_fn(plan, H)
+        H_v = drop(tau(linear_fn(V, blk.W_o.weight, blk.W_o.bias, A2=Mv)))
+        if V_d is not None and blk.W_d is not None:
+            H_v = drop(linear_fn(H_v, blk.W_d.weight, blk.W_d.bias, A2=V_d))
+    if blk.want_e:
+        H_e = edge_readout(blk, linear_fn, E, H, E_d)
+    return H_v, H_e

@@ -7,7 +7,7 @@ through the block).  Gradients are produced by the K6 HIP kernels; torch only ro
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 from torch import Tensor
@@ -17,18 +17,26 @@ from . import engine
 _PARAM_ORDER = ("W_i", "b_i", "W_h", "b_h", "W_o", "b_o", "W_d", "b_d")
 
 
+class FusedOptions(NamedTuple):
+    """What a :class:`FusedMP` forward is asked for beside its tensors (ONE positional argument of ``apply``: the positions of the
+    tensors, hence the ``needs_input_grad`` indices of the backward pass, do not depend on it)."""
+
+    slope_t: Optional[Tensor]            # the PReLU weight (the kernels read it on the device), else None
+    max_level: int                       # cap on the route: 2 tile kernel, 1 per-step fused, 0 general
+    dropout: Optional[tuple] = None      # (p, seed): active dropout inside the tile kernels
+    atom: bool = False                   # atom messages on the tile kernels (DMPNN_F_ATOM)
+    # the mol-atom-bond blocks (mab.py): the kept H^(depth-1) is a second OUTPUT, for the edge read-out — in the caller's edge order —
+    # and its gradient a second input of the backward tile kernel (dmpnn_bwd_args.g_edge); tile-kernel forwards only, depth >= 2
+    want_edge: bool = False
+    # a demanded route (autograd.mp_forward: "general" when V, E or V_d requires grad — the route whose backward pass also returns
+    # the input gradients, dmpnn_backward_inputs)
+    route: Optional[str] = None
+
+
 class FusedMP(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mp, plan, V, E, V_d, act, slope, slope_and_route, W_i, b_i, W_h, b_h, W_o, b_o, W_d, b_d):
-        slope_t, max_level = slope_and_route[0], slope_and_route[1]
-        dropout = slope_and_route[2] if len(slope_and_route) > 2 else None
-        atom = bool(slope_and_route[3]) if len(slope_and_route) > 3 else False   # AtomMessagePassing on the tile kernels (DMPNN_F_ATOM)
-        # the mol-atom-bond blocks (mab.py): the kept H^(depth-1) is a second OUTPUT, for the edge read-out — in the caller's edge order —
-        # and its gradient a second input of the backward tile kernel (dmpnn_bwd_args.g_edge); tile-kernel forwards only, depth >= 2
-        want_edge = bool(slope_and_route[4]) if len(slope_and_route) > 4 else False
-        # a demanded route (autograd.mp_forward: "general" when V, E or V_d requires grad — the route whose backward pass also returns
-        # the input gradients, dmpnn_backward_inputs)
-        route = slope_and_route[5] if len(slope_and_route) > 5 else None
+    def forward(ctx, mp, plan, V, E, V_d, act, slope, opts: FusedOptions, W_i, b_i, W_h, b_h, W_o, b_o, W_d, b_d):
+        slope_t, max_level, dropout, atom, want_edge, route = opts
         has_vd = V_d is not None and W_d is not None
         out, st = engine.forward(plan, V, E, W_i, W_h, W_o, b_o, b_i, b_h, W_d if has_vd else None,
                                  b_d if has_vd else None, V_d if has_vd else None, depth=mp.depth, act=act,

@@ -28,8 +28,10 @@ import torch
 from torch import Tensor, nn
 
 from . import engine
-from .nn import (DEFAULT_ATOM_FDIM, DEFAULT_BOND_FDIM, DEFAULT_HIDDEN_DIM, InvalidShapeError, _HParams,
-                 classify_activation, get_activation_function)
+from .autograd import edge_readout, rows_forward
+from .backward import linear_fn
+from .nn import (DEFAULT_ATOM_FDIM, DEFAULT_BOND_FDIM, DEFAULT_HIDDEN_DIM, _batch_facts, _Block, _check_descriptors, _HParams, _route,
+                 _tile_training_attempt, batch_oversize, classify_activation, get_activation_function)
 
 
 class _MABMessagePassingBase(nn.Module):
@@ -106,20 +108,6 @@ class MABAtomMessagePassing(_MABMessagePassingBase):
         return W_i, W_h, W_vo, W_vd, W_eo, W_ed
 
 
-def _check_descriptors(name: str, X: Optional[Tensor], transform, W_x, W_o, n_rows: int):
-    """The reference applies the transform, then lets ``cat`` + ``Linear`` raise on a bad shape and converts that
-    RuntimeError into InvalidShapeError (mol_atom_bond.py:208-217,250-262).  Same outcome, checked up front; a
-    descriptor tensor given to a block built without ``d_vd`` / ``d_ed`` fails there with an AttributeError-turned
-    TypeError ('NoneType' is not callable) — here it is the same InvalidShapeError."""
-    if X is None:
-        return None
-    X = transform(X)
-    d = (W_x.in_features - W_o.out_features) if (W_x is not None and W_o is not None) else None
-    if d is None or X.dim() != 2 or X.shape[0] != n_rows or X.shape[1] != d:
-        raise InvalidShapeError(name, X.shape, [n_rows, d if d is not None else 0])
-    return X
-
-
 def _tile_route_ok(mp, bmg, V_d, E_d) -> bool:
     if mp.atom_messages or mp.W_vo is None or mp.depth < 2 or torch.is_grad_enabled() and (
             any(p.requires_grad for p in mp.parameters())):
@@ -154,41 +142,32 @@ def _tile_train_ok(mp, bmg, V_d) -> bool:
         return getattr(bmg, "oversize", None) is not True
     # atom messages: such a molecule is NaN on these training routes, forward and every gradient (the generic path knows bond messages
     # only, dmpnn_mega16_impl.hpp) — the host must KNOW, not guess: counted on the device for a foreign batch (round-4 ADVICE)
-    from .nn import batch_oversize
-
     return batch_oversize(bmg, len(bmg) if hasattr(bmg, "__len__") else 0) is False
 
 
 def mab_forward(mp, bmg, V_d: Optional[Tensor] = None, E_d: Optional[Tensor] = None):
     """``_MABMessagePassingBase.forward`` (mol_atom_bond.py:266-282) -> ``(H_v | None, H_e | None)``."""
-    from .backward import aggregate_fn, gather_src_fn, linear_fn, message_fn
-
-    bmg = mp.graph_transform(bmg)
-    engine._require_device(bmg.V, "bmg.V")
-    if mp.W_i.weight.device != bmg.V.device:
-        raise RuntimeError(f"module is on {mp.W_i.weight.device} but the batch is on {bmg.V.device}")
-    n_atoms, n_edges = int(bmg.V.shape[0]), int(bmg.E.shape[0])
-    want_v, want_e = mp.return_vertex_embeddings, mp.return_edge_embeddings
-    V_d = _check_descriptors("V_d", V_d, mp.V_d_transform, mp.W_vd, mp.W_vo, n_atoms) if want_v else None
+    blk = _Block(mp, mab=True)
+    facts = _batch_facts(mp, bmg)   # (this forward does not note the batch for the aggregation behind it: it never has)
+    bmg, n_edges = facts.bmg, facts.n_edges
+    want_v, want_e = blk.want_v, blk.want_e
+    V_d = _check_descriptors("V_d", V_d, mp.V_d_transform, mp.W_vd, mp.W_vo, facts.n_atoms) if want_v else None
     E_d = _check_descriptors("E_d", E_d, mp.E_d_transform, mp.W_ed, mp.W_eo, n_edges) if want_e else None
+    # (unlike the bond and atom blocks, whose rows route returns input gradients)
     for name, t in (("bmg.V", bmg.V), ("bmg.E", bmg.E), ("V_d", V_d), ("E_d", E_d)):
         if t is not None and t.requires_grad and torch.is_grad_enabled():
             raise NotImplementedError(f"chemprop_amd: gradient w.r.t. `{name}` is not provided by the engine "
                                       "(the reference never asks for it: features are data)")
     V, E = bmg.V, bmg.E
-    tau, drop = mp.tau, mp.dropout
 
     if _tile_route_ok(mp, bmg, V_d, E_d):
-        from .nn import _route
-
         plan = engine.GraphPlan.from_bmg(bmg)
         act, slope, slope_t = classify_activation(mp.tau)
         has_vd = V_d is not None
         # the same route policy as the bond block (nn.py: _route): the first batches of a module are checked on the plan's
         # verdict — an oversize molecule switches the tile kernel off for the module, an unusual graph takes the general route
-        n_mols = len(bmg) if hasattr(bmg, "__len__") else 0
-        plan.oversize = getattr(bmg, "oversize", None)
-        level = _route(mp, plan, n_mols, getattr(bmg, "batch", None))
+        plan.oversize = facts.oversize
+        level = _route(mp, plan, facts.n_mols, facts.batch)
         if plan.oversize is True:  # (host knowledge of the batching code: per-step routes for this batch)
             level = min(level, 1)
         Hv, st = engine.forward(plan, V, E, mp.W_i.weight, mp.W_h.weight, mp.W_vo.weight, mp.W_vo.bias,
@@ -209,72 +188,13 @@ def mab_forward(mp, bmg, V_d: Optional[Tensor] = None, E_d: Optional[Tensor] = N
     if _tile_train_ok(mp, bmg, V_d):
         # ---- round 4: TRAINING on the tile kernels — the block's forward is ONE launch that keeps what the backward tile kernel reads,
         # the kept H^(depth-1) leaves it as a second output for the edge read-out (a row kernel under autograd) and that read-out's
-        # gradient enters the backward tile kernel beside the vertex one (dmpnn_bwd_args.g_edge).  Both variants (DMPNN_F_ATOM). ----
-        import types
+        # gradient enters the backward tile kernel beside the vertex one (dmpnn_bwd_args.g_edge).  Both variants (DMPNN_F_ATOM).
+        # (a block built with d_vd and called without V_d plans as the block without the layer: vd_outside) ----
+        res, _ = _tile_training_attempt(blk, bmg, facts, V_d, vd_outside=V_d is None)
+        if res is not None:
+            H_v, H = res if want_e else (res, None)
+            return (H_v if want_v else None), (edge_readout(blk, linear_fn, E, H, E_d) if want_e else None)
 
-        from .backward import FusedMP
-        from .nn import _route, _training_plan_kind
-
-        act, slope, slope_t = classify_activation(mp.tau)
-        has_vd = V_d is not None
-        shim = types.SimpleNamespace(undirected=mp.undirected, W_d=mp.W_vd if has_vd else None, tau=mp.tau, training=mp.training, dropout=mp.dropout, depth=mp.depth,
-                                     W_i=mp.W_i, W_h=mp.W_h, W_o=mp.W_vo, _dmpnn_batches_checked=getattr(mp, "_dmpnn_batches_checked", 0),
-                                     _dmpnn_no_mega=getattr(mp, "_dmpnn_no_mega", False))
-        light = _training_plan_kind(shim, bmg)
-        plan = engine.GraphPlan.from_bmg(bmg, light=light, launch="defer" if light == "tiles" else True)
-        n_mols = len(bmg) if hasattr(bmg, "__len__") else 0
-        plan.oversize = getattr(bmg, "oversize", None)
-        if _route(mp, plan, n_mols, getattr(bmg, "batch", None)) >= 2:
-            try:
-                res = FusedMP.apply(mp, plan, V, E, V_d if has_vd else None, act, slope, (slope_t, 2, None, mp.atom_messages, want_e),
-                                    mp.W_i.weight, mp.W_i.bias, mp.W_h.weight, mp.W_h.bias, mp.W_vo.weight, mp.W_vo.bias,
-                                    mp.W_vd.weight if has_vd else None, mp.W_vd.bias if has_vd else None)
-                plan.ensure_launched()
-                H_v, H = res if want_e else (res, None)
-                H_e = None
-                if want_e:
-                    H_e = drop(tau(linear_fn(E, mp.W_eo.weight, mp.W_eo.bias, A2=H)))
-                    if E_d is not None:
-                        H_e = drop(linear_fn(H_e, mp.W_ed.weight, mp.W_ed.bias, A2=E_d))
-                mp.__dict__["_dmpnn_route"] = "mega16/atom" if mp.atom_messages else "mega16"
-                return (H_v if want_v else None), H_e
-            except engine.RouteUnavailable:
-                pass
-        plan.pending = None   # (a deferred K0 that nothing ran: the rows route builds its own full plan)
-
-    # ---- rows route ----
+    # ---- rows route (on a full plan of its own, whatever the attempt above launched: as it always was) ----
     mp.__dict__["_dmpnn_route"] = "rows"
-    plan = engine.GraphPlan.from_bmg(bmg)
-    nE = plan.n_edges
-    rev = None
-    if mp.atom_messages:  # mixins.py:21-30
-        H0 = linear_fn(V, mp.W_i.weight, mp.W_i.bias, gather=plan.src32, n_rows=nE)
-        if mp.depth > 1 and nE:
-            with torch.no_grad():
-                ME = engine.gather_rows(engine.aggregate(plan, E), plan.src32)  # [E, d_e]: constant over the loop
-    else:                 # mixins.py:8-18
-        H0 = linear_fn(V, mp.W_i.weight, mp.W_i.bias, A2=E, gather=plan.src32, n_rows=nE)
-    H = tau(H0)
-    for _ in range(1, mp.depth):
-        if mp.undirected:
-            if rev is None:
-                rev = plan.rev64
-            H = (H + H[rev]) / 2
-        if not nE:
-            H = drop(tau(H0))
-        elif mp.atom_messages:
-            MH = gather_src_fn(plan, aggregate_fn(plan, H))
-            H = drop(tau(linear_fn(MH, mp.W_h.weight, mp.W_h.bias, A2=ME, Cadd=H0)))
-        else:
-            H = drop(tau(linear_fn(message_fn(plan, H), mp.W_h.weight, mp.W_h.bias, Cadd=H0)))
-    H_v = H_e = None
-    if want_v:
-        Mv = aggregate_fn(plan, H)
-        H_v = drop(tau(linear_fn(V, mp.W_vo.weight, mp.W_vo.bias, A2=Mv)))
-        if V_d is not None:
-            H_v = drop(linear_fn(H_v, mp.W_vd.weight, mp.W_vd.bias, A2=V_d))
-    if want_e:
-        H_e = drop(tau(linear_fn(E, mp.W_eo.weight, mp.W_eo.bias, A2=H)))
-        if E_d is not None:
-            H_e = drop(linear_fn(H_e, mp.W_ed.weight, mp.W_ed.bias, A2=E_d))
-    return H_v, H_e
+    return rows_forward(blk, engine.GraphPlan.from_bmg(bmg), V, E, V_d, E_d, grad=True, in_grad=False)

@@ -15,13 +15,13 @@ from __future__ import annotations
 import copy
 import ctypes as _ctypes
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 from torch import Tensor, nn
 
 from . import _lib, engine
-from .autograd import input_grad_plan, input_grad_wanted, mp_forward
+from .autograd import input_grad_plan, input_grad_wanted, mp_forward, rows_forward
 from .data import BatchMolGraph as _OwnBatch
 
 DEFAULT_ATOM_FDIM, DEFAULT_BOND_FDIM = 72, 14  # chemprop/conf.py:8 (v2 featurizers)
@@ -34,6 +34,20 @@ class InvalidShapeError(ValueError):
     def __init__(self, var_name, received, expected):
         super().__init__(f"arg '{var_name}' has incorrect shape! got: `{tuple(received)}`. "
                          f"expected: `{tuple(expected)}`")
+
+
+def _check_descriptors(name: str, X: Optional[Tensor], transform, W_x, W_o, n_rows: int):
+    """The reference applies the transform, then lets ``cat`` + ``Linear`` raise on a bad shape and converts that
+    RuntimeError into InvalidShapeError (base.py:189-192; mol_atom_bond.py:208-217,250-262).  Same outcome, checked up front; a
+    descriptor tensor given to a block built without ``d_vd`` / ``d_ed`` fails there with an AttributeError-turned
+    TypeError ('NoneType' is not callable) — here it is the same InvalidShapeError."""
+    if X is None:
+        return None
+    X = transform(X)
+    d = (W_x.in_features - W_o.out_features) if (W_x is not None and W_o is not None) else None
+    if d is None or X.dim() != 2 or X.shape[0] != n_rows or X.shape[1] != d:
+        raise InvalidShapeError(name, X.shape, [n_rows, d if d is not None else 0])
+    return X
 
 
 def get_activation_function(activation) -> nn.Module:
@@ -135,6 +149,83 @@ class BondMessagePassing(EngineStateMixin, nn.Module):
         return bond_message_passing_forward(self, bmg, V_d)
 
 
+class _Block:
+    """Read-only view of a message-passing block under ONE set of names, whatever its class calls its layers, made by the forward
+    that was called (it knows which block it serves) and read during that forward: ``W_i, W_h, W_o, W_d`` (``W_vo`` / ``W_vd`` of
+    the mol-atom-bond blocks), ``W_eo, W_ed`` (their edge read-out, ``None`` elsewhere), ``want_v`` / ``want_e`` (the read-outs asked
+    for), ``atom`` (atom messages: the mol-atom-bond classes say so themselves, ``atom_messages``), ``depth, undirected, tau,
+    dropout, training``.  What the engine remembers about the module between forwards (``_dmpnn_batches_checked``,
+    ``_dmpnn_no_mega``) is read from the MODULE when asked and written to it (:func:`_remember`) — never a copy.  The planners
+    below (``_training_plan_kind``, ``_tile_plan_ok``, ``_route``) take a view or a module that has the bond block's names already.
+    (Plain slots, filled once: a forwarding ``__getattr__`` cost the atom block's training step 10 us.)"""
+
+    __slots__ = ("module", "mab", "atom", "W_i", "W_h", "W_o", "W_d", "W_eo", "W_ed", "want_v", "want_e", "depth", "undirected", "tau",
+                 "dropout", "training")
+
+    def __init__(self, mp, atom: bool = False, mab: bool = False):
+        self.module = mp
+        self.mab = mab
+        self.atom = bool(mp.atom_messages) if mab else atom
+        self.W_i = mp.W_i
+        self.W_h = mp.W_h
+        self.W_o = mp.W_vo if mab else mp.W_o
+        self.W_d = mp.W_vd if mab else mp.W_d
+        self.W_eo = mp.W_eo if mab else None
+        self.W_ed = mp.W_ed if mab else None
+        self.want_v = bool(mp.return_vertex_embeddings) if mab else True
+        self.want_e = bool(mp.return_edge_embeddings) if mab else False
+        self.depth = mp.depth
+        self.undirected = mp.undirected
+        self.tau = mp.tau
+        self.dropout = mp.dropout
+        self.training = mp.training
+
+    _dmpnn_batches_checked = property(lambda self: getattr(self.module, "_dmpnn_batches_checked", 0))
+    _dmpnn_no_mega = property(lambda self: getattr(self.module, "_dmpnn_no_mega", False))
+
+
+def _remember(mp, name: str, value) -> None:
+    """Set what the engine remembers about a block on the MODULE (``mp``: the module or its view)."""
+    object.__setattr__(mp.module if type(mp) is _Block else mp, name, value)
+
+
+class _BatchFacts(NamedTuple):
+    """What every module-path forward establishes about its batch, once (:func:`_batch_facts`)."""
+
+    bmg: object                  # the batch behind the block's graph_transform
+    n_atoms: int
+    n_edges: int
+    n_mols: int                  # 0: a batch without len()
+    batch: Optional[Tensor]
+    oversize: Optional[bool]     # host knowledge of the batching code (None: bare tensors)
+
+
+def _batch_facts(mp, bmg) -> _BatchFacts:
+    """The head of every module-path forward: the graph transform, the two device refusals, the facts of the batch."""
+    bmg = mp.graph_transform(bmg)  # Identity, or eval-only scaling on a shallow copy (transforms.py:65-74)
+    engine._require_device(bmg.V, "bmg.V")
+    if mp.W_i.weight.device != bmg.V.device:
+        raise RuntimeError(f"module is on {mp.W_i.weight.device} but the batch is on {bmg.V.device}")
+    n_atoms, n_edges = int(bmg.V.shape[0]), int(bmg.E.shape[0])
+    batch = getattr(bmg, "batch", None)
+    return _BatchFacts(bmg, n_atoms, n_edges, len(bmg) if hasattr(bmg, "__len__") else 0, batch, getattr(bmg, "oversize", None))
+
+
+def _tile_plan_available(facts: _BatchFacts) -> bool:
+    """A tile plan at any batch size: the table came with the batch (PackedBatch), or the batch vector is there for the
+    multi-workgroup planner.  (Asked only by the forwards that may build a tile plan for inference.)"""
+    return getattr(facts.bmg, "tiles", None) is not None or (
+        facts.batch is not None and not engine.small_plan_fits(facts.n_atoms, facts.n_edges)
+        and bool(_lib.load().dmpnn_tile_plan_any_size(facts.n_atoms, facts.n_edges)))
+
+
+def _note_batch(facts: _BatchFacts) -> None:
+    if facts.n_mols and facts.batch is not None:
+        from .agg import note_batch
+
+        note_batch(facts.batch, facts.n_mols)
+
+
 def _training_plan_kind(mp, bmg, atom: bool = False, vd_outside: bool = False):
     """``"tiles"`` when a TRAINING forward of ``mp`` on ``bmg`` runs on the tile plan (K0 = the tile table alone, kept tensors in the
     caller's edge order, ``DMPNN_F_TILE_PLAN``), else ``False`` (the full CSR plan).  The SHAPE rule is the library's
@@ -142,7 +233,8 @@ def _training_plan_kind(mp, bmg, atom: bool = False, vd_outside: bool = False):
     library can build from what the batch carries, at most 30 directed edges per molecule); the host adds only what it alone knows:
     the environment switches, an activation / dropout MODULE the kernels cannot stand in for, the validation window of the module's
     first batches, whether a gradient of ``W_i`` or ``W_h`` is wanted at all.  ``vd_outside``: the answer for the block with its
-    ``W_d`` taken out (``FusedTrainer`` runs that layer as a stage of its own behind the block: ``dmpnn_vd_forward``)."""
+    ``W_d`` taken out (``FusedTrainer`` runs that layer as a stage of its own behind the block: ``dmpnn_vd_forward``).  ``mp``: a
+    module with the bond block's attribute names, or a :class:`_Block`."""
     if _lib.opt("DMPNN_GENERAL", "0") == "1" or _lib.opt("DMPNN_TRAIN_PLAN", "tiles") == "full":
         return False
     act = classify_activation(mp.tau)[0]
@@ -257,6 +349,7 @@ def _replay_forward(mp, r: "_Replay", bmg):
         own = None
     small = engine.small_plan_fits(nV, nE)
     lib = _lib.load()
+    # (its own copy of `_tile_plan_available`, on values it has in hand: the shared form would add a call to this path)
     if (n_mols <= 0 or nE > 30 * n_mols or nE == 0 or (tiles is None and not small and not lib.dmpnn_tile_plan_any_size(nV, nE))
             or batch.numel() != nV
             or ei.shape[1] != nE or rev.numel() != nE or getattr(mp, "_dmpnn_no_mega", False)):
@@ -364,22 +457,19 @@ def bond_message_passing_forward(mp, bmg, V_d: Optional[Tensor] = None) -> Tenso
             out = _replay_forward(mp, r, bmg)
             if out is not None:
                 return out
+    # (the stages of `_batch_facts`, `_tile_plan_available` and `_note_batch` written out: this forward is the module-path training step
+    #  the benchmarks time, where the calls and the record cost 3 us of 187 — like `_replay_forward`, it keeps its own lines)
     bmg = mp.graph_transform(bmg)  # Identity, or eval-only scaling on a shallow copy (transforms.py:65-74)
     engine._require_device(bmg.V, "bmg.V")
     if mp.W_i.weight.device != bmg.V.device:
         raise RuntimeError(f"module is on {mp.W_i.weight.device} but the batch is on {bmg.V.device}")
-    n_atoms = int(bmg.V.shape[0])
+    n_atoms, n_edges = int(bmg.V.shape[0]), int(bmg.E.shape[0])
     if V_d is not None:
-        V_d = mp.V_d_transform(V_d)
-        d_vd = (mp.W_d.in_features - mp.W_o.out_features) if mp.W_d is not None else None
-        if mp.W_d is None or V_d.dim() != 2 or V_d.shape[0] != n_atoms or V_d.shape[1] != d_vd:
-            raise InvalidShapeError("V_d", V_d.shape, [n_atoms, d_vd if d_vd is not None else 0])
+        V_d = _check_descriptors("V_d", V_d, mp.V_d_transform, mp.W_d, mp.W_o, n_atoms)
     n_mols = len(bmg) if hasattr(bmg, "__len__") else 0
-    # a tile plan at any batch size: the table came with the batch (PackedBatch), or the batch vector is there for the
-    # multi-workgroup planner
+    batch = getattr(bmg, "batch", None)
     loader_tiles = getattr(bmg, "tiles", None) is not None or (
-        getattr(bmg, "batch", None) is not None and not engine.small_plan_fits(int(bmg.V.shape[0]), int(bmg.E.shape[0]))
-        and bool(_lib.load().dmpnn_tile_plan_any_size(int(bmg.V.shape[0]), int(bmg.E.shape[0]))))
+        batch is not None and not engine.small_plan_fits(n_atoms, n_edges) and bool(_lib.load().dmpnn_tile_plan_any_size(n_atoms, n_edges)))
     oversize = getattr(bmg, "oversize", None)  # host knowledge of the batching code (None: bare tensors)
     if oversize is None and mp.training and mp.dropout.p > 0 and torch.is_grad_enabled():
         # (active dropout lives inside the tile kernels, whose generic path for a molecule beyond the tile has none: such a molecule
@@ -389,7 +479,7 @@ def bond_message_passing_forward(mp, bmg, V_d: Optional[Tensor] = None) -> Tenso
         loader_tiles = False
     # (an inference forward of the fused routes: tile kernel, per-step fused route on the f16 pipe, fp32 fused route)
     light = _light_plan_ok(mp)
-    if light and oversize is not True and _tile_plan_ok(mp, int(bmg.V.shape[0]), int(bmg.E.shape[0]), n_mols, loader_tiles):
+    if light and oversize is not True and _tile_plan_ok(mp, n_atoms, n_edges, n_mols, loader_tiles):
         light = "tiles"
     if not light and torch.is_grad_enabled() and V_d is None:
         # a training forward bound for the tile kernels: the tile plan (DMPNN_F_TILE_PLAN)
@@ -403,13 +493,14 @@ def bond_message_passing_forward(mp, bmg, V_d: Optional[Tensor] = None) -> Tenso
     own = getattr(bmg, "plan_table", None)
     if own is not None and plan.pending is not None and not torch.is_grad_enabled() and own[0].device == plan.device:
         plan.host_tiles = own  # (an inference forward of our own batch: the deferred K0 takes the table the batch carries)
-    if n_mols and getattr(bmg, "batch", None) is not None:
+    # (the bond forward notes the batch behind its plan, the atom forward in front of any, the mol-atom-bond forward not at all: kept)
+    if n_mols and batch is not None:
         from .agg import note_batch
 
-        note_batch(bmg.batch, n_mols)  # the aggregation that follows (model.py:131) skips its host read of batch.max()
+        note_batch(batch, n_mols)  # the aggregation that follows (model.py:131) skips its host read of batch.max()
     mp.__dict__.pop("_dmpnn_last", None)
     plan.oversize = oversize
-    level = _route(mp, plan, n_mols, getattr(bmg, "batch", None))
+    level = _route(mp, plan, n_mols, batch)
     if oversize is True:
         level = min(level, 1)
     level = min(level, cap)
@@ -505,7 +596,7 @@ def _route(mp, plan, n_mols: int = 0, batch=None) -> int:
     if n_mols > 0 and plan.n_edges > 30 * n_mols:  # average molecule already near the tile: do not try
         no_mega = True
     if mode == "always" or (mode == "first" and seen < _VALIDATE_FIRST_N):
-        object.__setattr__(mp, "_dmpnn_batches_checked", seen + 1)
+        _remember(mp, "_dmpnn_batches_checked", seen + 1)
         hdr = plan.header()
         flags = hdr[0]
         if flags & 7:
@@ -516,18 +607,18 @@ def _route(mp, plan, n_mols: int = 0, batch=None) -> int:
             # module whose first batches already hold some takes the per-step routes (a speed decision; _spill_monitor keeps
             # watching)
             no_mega = True
-            object.__setattr__(mp, "_dmpnn_no_mega", True)
+            _remember(mp, "_dmpnn_no_mega", True)
         if flags & 8:
             # no piece tiles: a molecule larger than a tile switches the tile kernel off for the module — but a batch
             # beyond the single-workgroup plan has none either way, which says nothing about its molecules
             if engine.small_plan_fits(plan.n_atoms, plan.n_edges) or (getattr(plan, "any_size", False) and not plan.tiles_only):
                 # (a full plan with tiles from the batch vector, dmpnn_prepare_with_batch, carries the verdict itself)
-                object.__setattr__(mp, "_dmpnn_no_mega", True)
+                _remember(mp, "_dmpnn_no_mega", True)
             elif batch is not None and not no_mega and _lib.load().dmpnn_tile_plan_any_size(plan.n_atoms, plan.n_edges):
                 # (validated batches only: the multi-workgroup tile planner's verdict on the molecule sizes of this batch)
                 tp = engine.GraphPlan(plan.edge_index, plan.rev_edge_index, plan.n_atoms, light="tiles", batch=batch)
                 if tp.tiles_only and tp.flags() & 8:
-                    object.__setattr__(mp, "_dmpnn_no_mega", True)
+                    _remember(mp, "_dmpnn_no_mega", True)
             return 1
     return 1 if no_mega else 2
 
@@ -573,49 +664,36 @@ class AtomMessagePassing(BondMessagePassing):
 
 def atom_message_passing_forward(mp, bmg, V_d: Optional[Tensor] = None) -> Tensor:
     """``_MessagePassingBase.forward`` (base.py:196-212) with the atom mixin (mixins.py:21-30)."""
-    from .backward import aggregate_fn, gather_src_fn, linear_fn
-
     if V_d is None and not torch.is_grad_enabled():
         r = mp.__dict__.get("_dmpnn_replay")   # the steady inference path of the tile kernel (the bond block's: the argument block carries DMPNN_F_ATOM)
         if r is not None:
             out = _replay_forward(mp, r, bmg)
             if out is not None:
                 return out
-    bmg = mp.graph_transform(bmg)
-    engine._require_device(bmg.V, "bmg.V")
-    if mp.W_i.weight.device != bmg.V.device:
-        raise RuntimeError(f"module is on {mp.W_i.weight.device} but the batch is on {bmg.V.device}")
-    n_atoms = int(bmg.V.shape[0])
-    has_vd = False
-    if V_d is not None:
-        V_d = mp.V_d_transform(V_d)
-        d_vd = (mp.W_d.in_features - mp.W_o.out_features) if mp.W_d is not None else None
-        if mp.W_d is None or V_d.dim() != 2 or V_d.shape[0] != n_atoms or V_d.shape[1] != d_vd:
-            raise InvalidShapeError("V_d", V_d.shape, [n_atoms, d_vd if d_vd is not None else 0])
-        has_vd = True
-    n_mols = len(bmg) if hasattr(bmg, "__len__") else 0
-    if n_mols and getattr(bmg, "batch", None) is not None:
-        from .agg import note_batch
-
-        note_batch(bmg.batch, n_mols)
+    facts = _batch_facts(mp, bmg)
+    bmg, n_mols = facts.bmg, facts.n_mols
+    has_vd = V_d is not None
+    if has_vd:
+        V_d = _check_descriptors("V_d", V_d, mp.V_d_transform, mp.W_d, mp.W_o, facts.n_atoms)
+    _note_batch(facts)   # (in front of any plan: see the bond forward)
     V, E = bmg.V, bmg.E
+    blk = _Block(mp, atom=True)
     # ---- round 3: the whole forward of a tile of molecules in ONE launch (DMPNN_F_ATOM of the tile kernel) — inference, built-in
     # activation, molecules that fit a tile, d_e <= 16.  Everything else: the per-step kernels chained below. ----
     act, slope, slope_t = classify_activation(mp.tau)
     grad = torch.is_grad_enabled() and any(p.requires_grad for p in mp.parameters())
     # V, E or V_d requires grad: the rows route on a full plan (every row Function below has a data gradient), also with the block frozen
     in_grad = input_grad_wanted(V, E, V_d)
+    tile_block = not has_vd and not in_grad and not mp.undirected and not (mp.training and mp.dropout.p > 0) and facts.n_edges > 0
+    d_e = int(E.shape[1])
+    plan = None
     # (an oversize molecule is NaN on the atom variant of the tile kernels — their generic path knows bond messages only — so the
     #  host must KNOW: counted on the device for a foreign batch, batch_oversize)
-    if (not grad and not in_grad and not has_vd and act != "custom" and not mp.undirected and not (mp.training and mp.dropout.p > 0)
-            and 1 <= int(E.shape[1]) <= 16 and int(E.shape[0]) > 0 and batch_oversize(bmg, n_mols) is False):
-        nV_, nE_ = int(V.shape[0]), int(E.shape[0])
-        loader_tiles = getattr(bmg, "tiles", None) is not None or (
-            getattr(bmg, "batch", None) is not None and not engine.small_plan_fits(nV_, nE_) and bool(_lib.load().dmpnn_tile_plan_any_size(nV_, nE_)))
-        light = "tiles" if (_light_plan_ok(mp) and _tile_plan_ok(mp, nV_, nE_, n_mols, loader_tiles)) else False
+    if not grad and tile_block and act != "custom" and 1 <= d_e <= 16 and batch_oversize(bmg, n_mols) is False:
+        light = "tiles" if (_light_plan_ok(mp) and _tile_plan_ok(mp, facts.n_atoms, facts.n_edges, n_mols, _tile_plan_available(facts))) else False
         plan = engine.GraphPlan.from_bmg(bmg, light=light)
-        plan.oversize = getattr(bmg, "oversize", None)
-        if _route(mp, plan, n_mols, getattr(bmg, "batch", None)) >= 2:
+        plan.oversize = facts.oversize
+        if _route(mp, plan, n_mols, facts.batch) >= 2:
             try:
                 out, st = engine.forward(plan, V, E, mp.W_i.weight, mp.W_h.weight, mp.W_o.weight, mp.W_o.bias, mp.W_i.bias, mp.W_h.bias,
                                          depth=mp.depth, act=act, slope=slope, slope_t=slope_t, atom=True,
@@ -627,60 +705,47 @@ def atom_message_passing_forward(mp, bmg, V_d: Optional[Tensor] = None) -> Tenso
             except engine.RouteUnavailable:
                 pass
         if light:
-            plan = engine.GraphPlan.from_bmg(bmg)
-    elif (grad and not has_vd and act not in ("custom", "prelu") and not mp.undirected and not (mp.training and mp.dropout.p > 0)
-          and 2 <= int(E.shape[1]) <= 16 and int(E.shape[1]) % 2 == 0 and int(E.shape[0]) > 0 and batch_oversize(bmg, n_mols) is False
-          and not in_grad):
+            plan = None
+    elif grad and tile_block and act not in ("custom", "prelu") and 2 <= d_e <= 16 and d_e % 2 == 0 and batch_oversize(bmg, n_mols) is False:
         # ---- round 4: TRAINING on the tile kernels (DMPNN_F_ATOM | DMPNN_F_KEEP): one forward launch that keeps what the backward tile
         # kernel and the weight-gradient products read (sign bits or H^(t), M^(t), the bond-feature half of the messages), one autograd
         # node — the bond block's (backward.FusedMP).  Molecules beyond the tile, W_d, active dropout: the chain below. ----
-        from .backward import FusedMP
-
-        light = _training_plan_kind(mp, bmg)
-        plan = engine.GraphPlan.from_bmg(bmg, light=light, launch="defer" if light == "tiles" else True)
-        plan.oversize = getattr(bmg, "oversize", None)
-        if _route(mp, plan, n_mols, getattr(bmg, "batch", None)) >= 2:
-            try:
-                out = FusedMP.apply(mp, plan, V, E, None, act, slope, (slope_t, 2, None, True), mp.W_i.weight, mp.W_i.bias, mp.W_h.weight,
-                                    mp.W_h.bias, mp.W_o.weight, mp.W_o.bias, None, None)
-                plan.ensure_launched()
-                mp.__dict__["_dmpnn_route"] = "mega16/atom"
-                return out
-            except engine.RouteUnavailable:
-                pass
-        if light:
-            plan = engine.GraphPlan.from_bmg(bmg)
-        else:
-            plan.ensure_launched()
-    else:
+        out, plan = _tile_training_attempt(blk, bmg, facts)
+        if out is not None:
+            return out
+    if plan is None:
         plan = engine.GraphPlan.from_bmg(bmg)
     mp.__dict__["_dmpnn_route"] = "rows/atom"
-    tau, drop = mp.tau, mp.dropout
-    nE = plan.n_edges
-    H0 = linear_fn(V, mp.W_i.weight, mp.W_i.bias, gather=plan.src32, n_rows=nE, plan=plan if in_grad else None)
-    H = tau(H0)
-    if mp.depth > 1 and nE:
-        if torch.is_grad_enabled() and E.requires_grad:
-            ME = gather_src_fn(plan, aggregate_fn(plan, E))                     # (the same two kernels, with their transposes)
-        else:
-            with torch.no_grad():
-                ME = engine.gather_rows(engine.aggregate(plan, E), plan.src32)      # [E, d_e], constant over the loop
-    rev = None
-    for _ in range(1, mp.depth):
-        if mp.undirected:
-            if rev is None:
-                rev = plan.rev64
-            H = (H + H[rev]) / 2
-        if nE:
-            MH = gather_src_fn(plan, aggregate_fn(plan, H))
-            H = drop(tau(linear_fn(MH, mp.W_h.weight, mp.W_h.bias, A2=ME, Cadd=H0)))
-        else:
-            H = drop(tau(H0))
-    Mv = aggregate_fn(plan, H)
-    Hv = drop(tau(linear_fn(V, mp.W_o.weight, mp.W_o.bias, A2=Mv)))
-    if has_vd:
-        Hv = drop(linear_fn(Hv, mp.W_d.weight, mp.W_d.bias, A2=V_d))
-    return Hv
+    return rows_forward(blk, plan, V, E, V_d, grad=True, in_grad=in_grad)[0]
+
+
+def _tile_training_attempt(blk: _Block, bmg, facts: _BatchFacts, V_d: Optional[Tensor] = None, vd_outside: bool = False) -> tuple:
+    """A TRAINING forward on the tile kernels for a block whose caller found it eligible (the atom forward, ``mab.mab_forward``): the
+    plan kind, K0 deferred into the forward's own call on a tile plan, the route of this batch, ONE autograd node (``FusedMP``).
+    -> ``(result, None)``, the result being ``H_v`` or — a block with an edge read-out — ``(H_v, H^(depth-1))``; or, where the batch
+    takes another route (``_route`` below 2, ``RouteUnavailable``), ``(None, plan)``: the full plan this attempt launched, for the row
+    chain, else ``None`` — a tile plan is dropped, and a deferred K0 that nothing ran with it: it was never enqueued."""
+    from .backward import FusedMP, FusedOptions
+
+    mp = blk.module
+    act, slope, slope_t = classify_activation(blk.tau)
+    # (asked as for bond messages, whatever the block passes: both callers always have)
+    light = _training_plan_kind(blk, bmg, vd_outside=vd_outside)
+    plan = engine.GraphPlan.from_bmg(bmg, light=light, launch="defer" if light == "tiles" else True)
+    plan.oversize = facts.oversize
+    if _route(blk, plan, facts.n_mols, facts.batch) >= 2:
+        W_d = blk.W_d if V_d is not None else None
+        try:
+            res = FusedMP.apply(mp, plan, bmg.V, bmg.E, V_d, act, slope,
+                                FusedOptions(slope_t=slope_t, max_level=2, atom=blk.atom, want_edge=blk.want_e),
+                                blk.W_i.weight, blk.W_i.bias, blk.W_h.weight, blk.W_h.bias, blk.W_o.weight, blk.W_o.bias,
+                                None if W_d is None else W_d.weight, None if W_d is None else W_d.bias)
+            plan.ensure_launched()
+            mp.__dict__["_dmpnn_route"] = "mega16/atom" if blk.atom else "mega16"
+            return res, None
+        except engine.RouteUnavailable:
+            pass
+    return None, (None if light else plan)
 
 
 class MulticomponentMessagePassing(nn.Module):
